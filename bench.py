@@ -33,11 +33,9 @@ import os
 import sys
 import time
 
-# HIP maps the streams of a process onto 4 hardware queues unless told otherwise; a context of this library runs the BWT stages of a
-# batch on three streams beside torch's, and the stream classes have six lanes with two copy streams each. Eight queues: +1.5 % on
-# the device-resident step, +5 % end to end (profiles/r05_host_layer_sweeps.txt). An application that embeds the library sets the same
-# variable before its first HIP call; the library does not touch the environment of its host process.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# The number of hardware queues HIP maps this process's streams onto is left to the environment: HIP streams share
+# a process's queues, so the three BWT streams and the copy streams run with whatever the machine allows, with less overlap when it
+# allows fewer (profiles/r05_host_layer_sweeps.txt measures the difference).
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -284,6 +282,43 @@ def real_bytes_leg(ctx, torch, np, hipapi, corpus, framing, dev, steps=3, with_c
     return out
 
 
+DUMP_SAMPLE = 4 << 20         # bytes drawn from each output by --dump-outputs: 2 x 16 MiB of float32, under the 64 MB cap
+DUMP_CHUNK = 1 << 20          # --dump-outputs checksums every byte of an output, one (sum, position-weighted sum) pair per chunk
+DUMP_SEED = 20240607
+
+
+def dump_outputs(out_dir, torch, np, d_enc, bits, d_dec, n):
+    """Writes what the last timed step handed its caller -- the encoded stream (d_enc, `bits` bits) and the decoded bytes (d_dec[:n]) --
+    as .npy files under out_dir, so that two builds run with the same arguments can be compared output for output:
+      compressed_bits.npy           float64 [1]          length of the stream in bits
+      compressed_sample.npy         float32 [k]          bytes of the stream at k fixed positions (every byte when it is shorter): the
+                                                         sorted numpy.random.default_rng(DUMP_SEED).choice(length, k, replace=False)
+      compressed_chunk_sums.npy     float64 [chunks, 2]  per 1 MiB of the stream: sum of the bytes, sum of byte * (offset in chunk + 1)
+      decoded_length.npy (bytes), decoded_sample.npy, decoded_chunk_sums.npy: the same for the decoded bytes
+    Every value is an integer below 2^53, exact in float64; the samples are bytes, exact in float32."""
+    os.makedirs(out_dir, exist_ok=True)
+    comp_len = (bits + 7) // 8
+    arrays = {"compressed_bits": np.array([bits], dtype=np.float64), "decoded_length": np.array([n], dtype=np.float64)}
+    for name, buf, length in (("compressed", d_enc, comp_len), ("decoded", d_dec, n)):
+        rng = np.random.default_rng(DUMP_SEED)
+        if length <= DUMP_SAMPLE:
+            idx = np.arange(length, dtype=np.int64)
+        else:
+            idx = np.sort(rng.choice(length, DUMP_SAMPLE, replace=False)).astype(np.int64)
+        sample = buf[torch.from_numpy(idx).to(buf.device)] if length else buf[:0]
+        arrays[name + "_sample"] = sample.cpu().numpy().astype(np.float32)
+        chunks = (length + DUMP_CHUNK - 1) // DUMP_CHUNK
+        padded = torch.zeros(chunks * DUMP_CHUNK, dtype=torch.int64, device=buf.device)
+        padded[:length] = buf[:length]
+        padded = padded.view(chunks, DUMP_CHUNK)
+        weight = torch.arange(1, DUMP_CHUNK + 1, dtype=torch.int64, device=buf.device)
+        sums = torch.stack([padded.sum(dim=1), (padded * weight).sum(dim=1)], dim=1)
+        arrays[name + "_chunk_sums"] = sums.cpu().numpy().astype(np.float64)
+        del padded
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -299,9 +334,15 @@ def main():
     ap.add_argument("--reps", type=int, default=0, help="repetitions of the separate encode / decode / per-kernel timing passes (default: 2..5 by --steps)")
     ap.add_argument("--dist-backend", default="nccl", help="gloo + --share-device: the N-rank code path on a 1-GPU box (developer check)")
     ap.add_argument("--share-device", action="store_true", help="every rank uses cuda:0")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (encoded "
+                    "stream, decoded bytes: seeded samples and per-MiB checksums) as DIR/<name>.npy (rank 0's share)")
     ap.add_argument("--many-blocks", type=int, default=-1, help="copies of the corpus in the many-block sharded job (default: 5 when N > 1, "
                     "off at N = 1; 0 = off): one job of that many corpora back to back, sharded over the ranks by block index")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     import numpy as np
     import torch
@@ -397,6 +438,8 @@ def main():
     if cnt:
         assert state["out_bytes"] == n, "decoded %d of %d bytes" % (state["out_bytes"], n)
         assert torch.equal(d_dec[:n], d_in[:n]), "round trip mismatch"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, np, d_enc, state["bits"], d_dec, n)
     comp_bytes = (state["bits"] + 7) // 8
     if world > 1:
         t = torch.tensor([comp_bytes], dtype=torch.int64, device=dev if args.dist_backend == "nccl" else "cpu")
