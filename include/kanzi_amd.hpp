@@ -258,6 +258,15 @@ protected:
 };
 
 class BWTBlockCodec : public DeviceTransform { public: explicit BWTBlockCodec(Context& ctx) : DeviceTransform(KNZ_T_BWT, &ctx) {} BWTBlockCodec() : DeviceTransform(KNZ_T_BWT, nullptr) {} };
+// transform/BWTS.hpp: bijective BWT, no header (getMaxEncodedLength = n), blocks up to MAX_BLOCK_SIZE
+class BWTS : public DeviceTransform {
+public:
+    static const int MAX_BLOCK_SIZE = 1024 * 1024 * 1024;
+    BWTS() : DeviceTransform(KNZ_T_BWTS, nullptr) {}
+    explicit BWTS(Context& ctx) : DeviceTransform(KNZ_T_BWTS, &ctx) {}
+    bool forward(SliceArray<byte>& src, SliceArray<byte>& dst, int length);
+    bool inverse(SliceArray<byte>& src, SliceArray<byte>& dst, int length);
+};
 class SBRT : public DeviceTransform {
 public:
     static const int MODE_MTF = 1, MODE_RANK = 2, MODE_TIMESTAMP = 3;

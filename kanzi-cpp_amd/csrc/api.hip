@@ -156,7 +156,7 @@ static int count_transforms(uint64_t t, int* tok)
 }
 
 static bool host_stage_id(int t) { return t == KNZ_T_TEXT || t == KNZ_T_UTF; }
-static bool transform_supported(int t) { return t == KNZ_T_NONE || t == KNZ_T_ZRLT || t == KNZ_T_MTFT || t == KNZ_T_BWT || t == KNZ_T_SRT || t == KNZ_T_RLT || t == KNZ_T_LZ || t == KNZ_T_LZX || t == KNZ_T_RANK || t == KNZ_T_TIMESTAMP; }
+static bool transform_supported(int t) { return t == KNZ_T_NONE || t == KNZ_T_ZRLT || t == KNZ_T_MTFT || t == KNZ_T_BWT || t == KNZ_T_BWTS || t == KNZ_T_SRT || t == KNZ_T_RLT || t == KNZ_T_LZ || t == KNZ_T_LZX || t == KNZ_T_RANK || t == KNZ_T_TIMESTAMP; }
 static bool entropy_supported(int e) { return e == KNZ_E_NONE || e == KNZ_E_ANS0 || e == KNZ_E_ANS1 || e == KNZ_E_HUFFMAN || e == KNZ_E_FPAQ; }
 
 static int max_encoded_len(int t, int n)
@@ -587,6 +587,16 @@ static int run_forward_stage(Ctx* c, hipStream_t s, int t, const XfStage& st)
         if (launch_bwt_forward(s, st, sc, bytes, reinterpret_cast<u32*>(c->pinned)) != 0) return fail(c, -1, "BWT forward failed: %s", hipGetErrorString(hipGetLastError()));
         break;
     }
+    case KNZ_T_BWTS: {
+        if (const int parts = bwt_parts_wanted(c, st.nBlocks); parts > 1)
+            return bwt_in_parts(c, s, st, parts, [&](int nb) { return bwts_forward_scratch_bytes(nb, st.maxLen, (size_t)nb * st.maxLen); },
+                                 [](hipStream_t q, const XfStage& h, void* sc, size_t bytes, u32* pin) { return launch_bwts_forward(q, h, sc, bytes, pin); }, "BWTS forward", true);
+        const size_t bytes = bwts_forward_scratch_bytes(st.nBlocks, st.maxLen, (size_t)st.nBlocks * st.maxLen);
+        void* sc;
+        if (int r = ws_get(c, "bwtScratch", bytes, &sc)) return r;
+        if (launch_bwts_forward(s, st, sc, bytes, reinterpret_cast<u32*>(c->pinned)) != 0) return fail(c, -1, "BWTS forward failed: %s", hipGetErrorString(hipGetLastError()));
+        break;
+    }
     default: break;
     }
     return 0;
@@ -637,6 +647,21 @@ static int run_inverse_stage(Ctx* c, hipStream_t s, int t, const XfStage& st, in
         void* sc;
         if (int r = ws_get(c, wsName[k], bytes, &sc)) return r;
         if (launch_bwt_inverse(s, st, sc, bytes, reinterpret_cast<u32*>(c->pinned) + 32768 * k) != 0) return fail(c, -1, "BWT inverse failed: %s", hipGetErrorString(hipGetLastError()));
+        break;
+    }
+    case KNZ_T_BWTS: {
+        // (the inverse reads convergence flags back every round: the parts of a split batch run on helper threads)
+        if (lane < 0) {
+            if (const int parts = bwt_parts_wanted(c, st.nBlocks); parts > 1)
+                return bwt_in_parts(c, s, st, parts, [&](int nb) { return bwts_inverse_scratch_bytes(nb, st.maxLen, (size_t)nb * st.maxLen); },
+                                     [](hipStream_t q, const XfStage& h, void* sc, size_t bytes, u32* pin) { return launch_bwts_inverse(q, h, sc, bytes, pin); }, "BWTS inverse", true);
+        }
+        static const char* const wsName[4] = { "bwtScratch", "bwtScratch2", "bwtScratch3", "bwtScratch4" };
+        const int k = lane < 0 ? 0 : (lane & 3);
+        const size_t bytes = bwts_inverse_scratch_bytes(st.nBlocks, st.maxLen, (size_t)st.nBlocks * st.maxLen);
+        void* sc;
+        if (int r = ws_get(c, wsName[k], bytes, &sc)) return r;
+        if (launch_bwts_inverse(s, st, sc, bytes, reinterpret_cast<u32*>(c->pinned) + 32768 * k) != 0) return fail(c, -1, "BWTS inverse failed: %s", hipGetErrorString(hipGetLastError()));
         break;
     }
     default: break;

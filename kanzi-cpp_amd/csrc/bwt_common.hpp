@@ -1,6 +1,7 @@
 // Shared by the forward (bwt_fwd.hip) and inverse (bwt.hip) BWT block codec kernels.
 #pragma once
 #include "common.hpp"
+#include "stages.hpp"
 
 namespace knz {
 
@@ -34,5 +35,12 @@ __device__ __forceinline__ int find_block(const u32* __restrict__ base, int nBlo
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (base[mid] <= s) lo = mid; else hi = mid; }
     return lo;
 }
+
+// The suffix sort of bwt_fwd.hip without the BWT output (the first step of BWTS, bwts.hip). Sorts every block with 2 <= len <= cap;
+// writes ok[b] = 1 for those blocks and 0 for the others (the caller decides them) and leaves newLen zero. On return (0 or a negative
+// HIP error; the stream is synchronised) SA[base[b] + r] = base[b] + position of the suffix of rank r of block b, for the sorted blocks,
+// base[nBlocks] = total. Both arrays live in `scratch` (bwt_forward_scratch_bytes(nBlocks, maxLen, nBlocks * maxLen) bytes).
+struct BwtSuffixArrays { const u32* SA; const u32* base; u32 total; };
+int bwt_suffix_arrays(hipStream_t s, const XfStage& st, void* scratch, size_t scratchBytes, u32* h_pinned, BwtSuffixArrays* out);
 
 }  // namespace knz

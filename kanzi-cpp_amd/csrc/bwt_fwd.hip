@@ -163,14 +163,15 @@ __device__ __forceinline__ void agg_write(const ClassAgg& A, const FwdView& v, i
 // round 0
 // ------------------------------------------------------------------------------------------------
 // base[b] = sum of active lengths of the blocks before b ; total in base[nBlocks]
-__global__ void k_bwt_bases(BwtView v, u32* __restrict__ base, u8* __restrict__ ok, u32* __restrict__ maxLen)
+// (suffixOnly: the suffix array for BWTS, bwts.hip: every block of at least 2 bytes that fits its destination is sorted)
+__global__ void k_bwt_bases(BwtView v, u32* __restrict__ base, u8* __restrict__ ok, u32* __restrict__ maxLen, int suffixOnly)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     u32 sum = 0, mx = 0;
     for (int b = 0; b < v.nBlocks; b++) {
         base[b] = sum;
         u32 ps;
-        const bool a = bwt_fwd_applies(v.len[b], v.cap[b], &ps);
+        const bool a = suffixOnly ? (v.len[b] >= 2 && v.len[b] <= v.cap[b]) : bwt_fwd_applies(v.len[b], v.cap[b], &ps);
         ok[b] = a ? 1 : 0;
         if (a) { sum += v.len[b]; mx = v.len[b] > mx ? v.len[b] : mx; }
     }
@@ -2486,14 +2487,15 @@ size_t bwt_forward_scratch_bytes(int nBlocks, u32 VS, size_t total)
 #define GRID1(n) dim3((unsigned)(((n) + 255) / 256)), dim3(256), 0, s
 
 // Returns 0 or a negative HIP error. Synchronises the stream (the sizes of the work lists are read back per round).
-int launch_bwt_forward(hipStream_t s, const XfStage& st, void* scratch, size_t scratchBytes, u32* h_pinned)
+// sa == nullptr: the BWT block codec (emits header + BWT bytes). Otherwise the suffix arrays only, left in the scratch (bwt_suffix_arrays).
+static int bwt_forward_run(hipStream_t s, const XfStage& st, void* scratch, size_t scratchBytes, u32* h_pinned, BwtSuffixArrays* sa)
 {
     BwtView bv; bv.src = st.src; bv.dst = st.dst; bv.len = st.len; bv.cap = st.cap; bv.VS = st.maxLen; bv.nBlocks = st.nBlocks;
     const size_t maxTotal = (size_t)st.nBlocks * bv.VS;
     FwdScratch w;
     if (fwd_carve(reinterpret_cast<u8*>(scratch), st.nBlocks, maxTotal, &w, bv.VS) > scratchBytes) return -2;
     const FwdTuning tune = fwd_tuning();
-    { KScope ks_("k_bwt_f_bases"); hipLaunchKernelGGL(k_bwt_bases, dim3(1), dim3(64), 0, s, bv, w.base, st.ok, w.counters + 32); }
+    { KScope ks_("k_bwt_f_bases"); hipLaunchKernelGGL(k_bwt_bases, dim3(1), dim3(64), 0, s, bv, w.base, st.ok, w.counters + 32, sa ? 1 : 0); }
     hipMemsetAsync(st.newLen, 0, sizeof(u32) * st.nBlocks, s);
     { KScope ks_("k_bwt_f_r0_hist");                                // byte histograms: the key length of round 0, later its digit counts
       hipMemsetAsync(w.byteHist, 0, 1024ull * st.nBlocks, s);
@@ -2503,6 +2505,7 @@ int launch_bwt_forward(hipStream_t s, const XfStage& st, void* scratch, size_t s
     if (hipMemcpyAsync(h_pinned + 1, w.counters + 32, 8, hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
     if (hipStreamSynchronize(s) != hipSuccess) return -1;
     const u32 total = h_pinned[0];
+    if (sa) { sa->SA = w.SA; sa->base = w.base; sa->total = total; }
     if (total == 0) return 0;
     FwdView v; v.base = w.base; v.nBlocks = st.nBlocks; v.total = total; v.SA = w.SA; v.ISA = w.ISA; v.K = w.K; v.ISA2 = (w.ISA2 != nullptr && !tune.plainLabels) ? w.ISA2 : (u64*)nullptr; v.round = 0; v.gbits = w.gbits; v.gnew = w.gnew; v.counters = w.counters; v.medStage = w.medStage; v.ovr = nullptr; v.rtbits = nullptr;
     const u32 medSlots = (u32)((size_t)total / 256 + 1);
@@ -2863,9 +2866,20 @@ int launch_bwt_forward(hipStream_t s, const XfStage& st, void* scratch, size_t s
         cur = nxt;
         h <<= 1;
     }
+    if (sa) return hipGetLastError() == hipSuccess ? 0 : -1;
     const dim3 gridB((unsigned)std::min<size_t>(((size_t)bv.VS + 255) / 256, 4096), st.nBlocks);
     { KScope ks_("k_bwt_f_emit"); hipLaunchKernelGGL(k_bwt_f_emit, gridB, dim3(256), 0, s, bv, w.base, st.ok, w.SA, v, st.newLen); }
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_bwt_forward(hipStream_t s, const XfStage& st, void* scratch, size_t scratchBytes, u32* h_pinned)
+{
+    return bwt_forward_run(s, st, scratch, scratchBytes, h_pinned, nullptr);
+}
+
+int bwt_suffix_arrays(hipStream_t s, const XfStage& st, void* scratch, size_t scratchBytes, u32* h_pinned, BwtSuffixArrays* out)
+{
+    return bwt_forward_run(s, st, scratch, scratchBytes, h_pinned, out);
 }
 
 }  // namespace knz

@@ -460,6 +460,28 @@ bool DeviceTransform::inverse(SliceArray<byte>& src, SliceArray<byte>& dst, int 
     return true;
 }
 
+// BWTS.cpp:44-52 / :196-202: a block above MAX_BLOCK_SIZE is not a recoverable error
+static void bwtsCheckSize(int length)
+{
+    if (length > BWTS::MAX_BLOCK_SIZE) {
+        std::stringstream ss;
+        ss << "The max BWTS block size is " << BWTS::MAX_BLOCK_SIZE << ", got " << length;
+        throw std::invalid_argument(ss.str());
+    }
+}
+
+bool BWTS::forward(SliceArray<byte>& src, SliceArray<byte>& dst, int length)
+{
+    bwtsCheckSize(length);
+    return DeviceTransform::forward(src, dst, length);
+}
+
+bool BWTS::inverse(SliceArray<byte>& src, SliceArray<byte>& dst, int length)
+{
+    bwtsCheckSize(length);
+    return DeviceTransform::inverse(src, dst, length);
+}
+
 static int lzTypeFromContext(Context& ctx)
 {
     const int t = ctx.getInt("lz", 3);
@@ -701,7 +723,7 @@ static bool chainIsHostBound(uint64 ttype)
 {
     for (int i = 0; i < 8; i++) {
         const int t = int((ttype >> (42 - 6 * i)) & 63);
-        if (t == KNZ_T_BWT || t == KNZ_T_LZ || t == KNZ_T_LZX || t == KNZ_T_SRT || t == KNZ_T_RANK || t == KNZ_T_TEXT || t == KNZ_T_UTF) return false;
+        if (t == KNZ_T_BWT || t == KNZ_T_BWTS || t == KNZ_T_LZ || t == KNZ_T_LZX || t == KNZ_T_SRT || t == KNZ_T_RANK || t == KNZ_T_TEXT || t == KNZ_T_UTF) return false;
     }
     return true;
 }
@@ -862,6 +884,7 @@ TransformSequence<T>* TransformFactory<T>::newTransform(Context& ctx, uint64 fun
             switch (int(t)) {
             case NONE_TYPE: transforms[nbtr++] = new NullTransform(ctx); break;
             case BWT_TYPE: transforms[nbtr++] = new BWTBlockCodec(ctx); break;
+            case BWTS_TYPE: transforms[nbtr++] = new BWTS(ctx); break;
             case MTFT_TYPE: transforms[nbtr++] = new SBRT(SBRT::MODE_MTF, ctx); break;
             case RANK_TYPE: transforms[nbtr++] = new SBRT(SBRT::MODE_RANK, ctx); break;
             case SRT_TYPE: transforms[nbtr++] = new SRT(ctx); break;
