@@ -9,9 +9,9 @@
 // GPU formulation: prefix doubling with group refinement (Larsson-Sadakane order refinement, made data parallel).
 //   State in HBM: SA[slot] (global position ids), ISA[position] = a label of the position's group (a slot inside the group's range), and
 //   one bit per slot, gbits, set where a group starts. A position is resolved when its group has one member.
-//   Round 0 sorts every block's suffixes on their first 4 symbols with the segmented LSD radix sort of prims.hpp; its first pass reads
+//   Round 0 sorts every block's suffixes on their first 4 or 5 symbols with the segmented LSD radix sort of prims.hpp; its first pass reads
 //   the text. Then:
-//     * the small groups once on the next eight text bytes (k_bwt_f_sort_small_text),
+//     * the small groups once on the next seven text bytes, in the kernel that places round 0 (k_bwt_f_r0_place_text),
 //     * run groups (4 equal symbols) in one round by run length: the runs are sorted, the members follow their runs (k_bwt_f_run_*),
 //   and the doubling rounds, h = 4, 8, 16, ..., refine what is left on the key ISA[p + h] (0 past the block end: "shorter sorts first"):
 //     * small groups (2..256 members) need no list at all: a kernel sweeps the bit map in windows of 2048 slots, finds the groups that
@@ -23,7 +23,8 @@
 //     * large groups go through one global radix sort of (descriptor index, key) pairs.
 //   A round sorts on the labels as they stood when it began (a refined head read beside an unrefined one would order two suffixes that
 //   are still equal): the keys of medium and large groups are gathered by kernels of their own before anything moves; the small groups
-//   read theirs in the kernel that sorts them (k_bwt_f_small_fused, round 6), which the VERSIONED labels make safe (lab_old / lab_set below).
+//   read theirs in the kernel that sorts them (k_bwt_f_small_fused, round 6), which the VERSIONED labels make safe (lab_old / lab_set below);
+//   blocks above 256 MiB keep plain labels and gather the small groups' keys first as well (k_bwt_f_gather_small, k_bwt_f_sort_small).
 #include "common.hpp"
 #include "stages.hpp"
 #include "bwt_common.hpp"
@@ -46,6 +47,8 @@ constexpr u32 SM_G = 256;          // largest "small" group
 // size the global sort of (descriptor, key) pairs is no slower than one workgroup per CU. Stays 8,192.
 constexpr u32 MED_CAP = 8192;
 constexpr u32 SUPER_CAP = 8192;    // largest group the chain round and the periodic-stretch probe take
+constexpr int GATHER_THREADS = 512;        // workgroup of k_bwt_f_gather_desc
+constexpr u32 LARGE_OS_MIN = 1000000;      // members from which the sort of the large groups uses the one-sweep radix passes
 constexpr u32 NO_BIT = 0x7FFFFFFFu;
 
 struct FwdView {
@@ -387,7 +390,7 @@ __global__ __launch_bounds__(256) void k_bwt_f_r0_flags(const u64* __restrict__ 
     }
 }
 
-// per window of 2048 slots: the last group start in it (0 when it has none: slot 0 always starts a group, so 0 is neutral
+// per window of wordsPerWin bit-map words: the last group start in it (0 when it has none: slot 0 always starts a group, so 0 is neutral
 // for the running maximum) and, mirrored for a running minimum from the right, the first one (`total` when none)
 __global__ __launch_bounds__(256) void k_bwt_f_r0_winsum(const u32* __restrict__ gbits, u32 total, u32 nWin, u32* __restrict__ winLast, u32* __restrict__ winFirstRev,
                                                          u32 wordsPerWin)
@@ -469,99 +472,15 @@ __device__ __forceinline__ bool sm_group_of(const SmWindow& W, u32 i, u32& s, u3
     return true;
 }
 
-// Round 0: SA, ISA and the descriptors of the groups that are not small, one workgroup per window of 2048 slots. The group
-// of a slot starts at the last set bit at or before it: found in the window's 64 bit-map words, else in the running
-// maximum over the windows before it (winLastIncl); the length of a group (needed where it starts) ends at the next set bit.
-__global__ __launch_bounds__(256) void k_bwt_f_r0_place(FwdView v, const u32* __restrict__ vals, const u32* __restrict__ winLastIncl,
-                                                        const u32* __restrict__ winFirstInclRev, u32 nWin, uint2* __restrict__ medNext, uint2* __restrict__ largeNext,
-                                                        const u64* __restrict__ keys, int nsym, int pbits, uint2* __restrict__ runList)
-{
-    __shared__ SmWindow W;
-    __shared__ int sBlk;
-    __shared__ ClassAgg A;
-    const int tid = (int)threadIdx.x;
-    const u32 win = blockIdx.x;
-    const u32 slot0 = win * SM_WIN;
-    if (tid == 0) sBlk = find_block(v.base, v.nBlocks, slot0 < v.total ? slot0 : v.total - 1);
-    agg_init(A);
-    int hKind[SM_WIN / 256];
-    u32 hLocal[SM_WIN / 256], hSize[SM_WIN / 256];
-    (void)vals;
-    if (tid < 64) {
-        const u32 w = v.gbits[(slot0 >> 5) + (u32)tid];
-        W.bw[tid] = w;
-        int pm = w ? (tid * 32 + 31 - __clz((int)w)) : -1;
-        u32 sm = w ? (u32)(tid * 32 + __ffs((int)w) - 1) : NO_BIT;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(pm, (unsigned)o, 64);
-            if (tid >= o) pm = t > pm ? t : pm;
-            const u32 u = (u32)__shfl_down((int)sm, (unsigned)o, 64);
-            if (tid + o < 64) sm = u < sm ? u : sm;
-        }
-        int pex = __shfl_up(pm, 1u, 64);
-        if (tid == 0) pex = -1;
-        u32 sex = (u32)__shfl_down((int)sm, 1u, 64);
-        if (tid == 63) sex = NO_BIT;
-        W.prevSet[tid] = pex;
-        W.nextSet[tid] = sex;
-    }
-    __syncthreads();
-    const u32 before = win ? winLastIncl[win - 1] : 0u;
-    const u32 after = (win + 1 < nWin) ? winFirstInclRev[nWin - 2 - win] : v.total;
-    u32 surv = 0;
-#pragma unroll
-    for (int k = 0; k < (int)(SM_WIN / 256); k++) {
-        const u32 i = (u32)tid + 256u * (u32)k;
-        const u32 a = slot0 + i;
-        hKind[k] = -1; hLocal[k] = 0; hSize[k] = 0;
-        if (a >= v.total) continue;
-        const u32 w = i >> 5, bit = i & 31;
-        const u32 lowmask = (bit == 31) ? 0xFFFFFFFFu : ((2u << bit) - 1u);
-        const u32 word = W.bw[w];
-        const u32 m = word & lowmask;
-        const int si = m ? (int)(w * 32 + 31 - (u32)__clz((int)m)) : W.prevSet[w];
-        const u32 hd = (si >= 0) ? slot0 + (u32)si : before;
-        int blk = sBlk;
-        while (a >= v.base[blk + 1]) blk++;
-        const u64 kk = keys[a];
-        const u32 pos = (u32)(kk & ((1ull << pbits) - 1ull));
-        const u32 gp = v.base[blk] + pos;
-        v.SA[a] = gp;
-        lab_set(v, gp, v.base[blk], hd, hd);
-        if (hd == a) {
-            const u32 m2 = word & ~lowmask;
-            const u32 ei = m2 ? (w * 32 + (u32)__ffs((int)m2) - 1) : W.nextSet[w];
-            u32 nxt = (ei != NO_BIT) ? slot0 + ei : after;
-            if (nxt > v.total) nxt = v.total;
-            const u32 size = nxt - a;
-            // a group whose nsym key bytes are one and the same byte (and whose suffixes are at least nsym long) sits inside runs
-            // of that byte: above the small size it is finished by the run-length round instead of log2(run length) doublings
-            bool runGroup = false;
-            if (runList != nullptr && size > SM_G) {
-                const u64 bytes = kk >> pbits;
-                u64 rep = 0;
-                for (int q = 0; q < nsym; q++) rep = (rep << 8) | (bytes & 0xFF);
-                runGroup = (pos + (u32)nsym <= v.base[blk + 1] - v.base[blk]) && bytes == rep;
-            }
-            hSize[k] = size;
-            hKind[k] = agg_note(A, size, runGroup, surv, hLocal[k]);
-        }
-    }
-    if (__ballot(surv != 0) != 0 && (tid & 63) == 0) v.counters[0] = 1;
-    __syncthreads();
-    if (tid == 0) agg_reserve(A, v);
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < (int)(SM_WIN / 256); k++)
-        if (hKind[k] >= 0) agg_write(A, v, hKind[k], hLocal[k], slot0 + (u32)tid + 256u * (u32)k, hSize[k], largeNext, runList);
-}
-
-// Round 0 and the text round in one sweep (the default; knob bwt_no_text_round = 2 runs k_bwt_f_r0_place and k_bwt_f_sort_small_text one
-// after the other instead): windows of SM_TS owned slots that look SM_G slots further, as the small-group kernels do. A slot is placed
-// by the window that owns it -- except the members of a SMALL group (2..SM_G members), which are all placed by the window that owns
-// the group's first slot: that window has their keys in LDS anyway, sorts them on the seven text bytes behind the round-0 symbols
-// before anything is written, and writes position and label ONCE, with the label the text order gives (the separate text round read
-// SA back, and wrote SA and the labels of every member that moved a second time).
+// Round 0 and the text round in one sweep: SA, the labels and the descriptors of the groups that are not small. Windows of SM_TS owned
+// slots that look SM_G slots further, as the small-group kernels do. The group of a slot starts at the last set bit at or before it:
+// found in the window's bit-map words, else in the running maximum over the windows before it (winLastIncl); the length of a group
+// (needed where it starts) ends at the next set bit. A slot is placed by the window that owns it -- except the members of a SMALL group
+// (2..SM_G members), which are all placed by the window that owns the group's first slot: that window has their keys in LDS anyway,
+// sorts them on the seven text bytes behind the round-0 symbols before anything is written, and writes position and label ONCE, with
+// the label the text order gives. Most small groups of round 0 are resolved here and never enter a doubling round: a member pays one
+// random read for seven symbols of depth where a doubling round at h = 4 buys four (a separate text round read SA back, and wrote SA
+// and the labels of every member that moved a second time).
 __global__ __launch_bounds__(256) void k_bwt_f_r0_place_text(BwtView bv, FwdView v, const u32* __restrict__ winLastIncl, const u32* __restrict__ winFirstInclRev, u32 nWin,
                                                              uint2* __restrict__ largeNext, const u64* __restrict__ keys, int nsym, int pbits, uint2* __restrict__ runList)
 {
@@ -739,6 +658,7 @@ __global__ __launch_bounds__(256) void k_bwt_f_gather_small(FwdView v, u32 h, in
     }
 }
 
+// (plain labels only: versioned ones take k_bwt_f_small_fused)
 __global__ __launch_bounds__(256) void k_bwt_f_sort_small(FwdView v, u32* __restrict__ survTile)
 {
     __shared__ SmWindow W;
@@ -747,11 +667,9 @@ __global__ __launch_bounds__(256) void k_bwt_f_sort_small(FwdView v, u32* __rest
     __shared__ u32 sK[SM_WIN];
     __shared__ u32 sNew[64];
     __shared__ u32 sWs[4];
-    __shared__ int sBlk;
     const u32 slot0 = blockIdx.x * SM_TS;
     if (!sm_load_window(v, slot0, W, &sAny)) { if (threadIdx.x == 0 && survTile) survTile[blockIdx.x] = 0; return; }
     if (threadIdx.x < 64) sNew[threadIdx.x] = 0;
-    if (threadIdx.x == 64) sBlk = find_block(v.base, v.nBlocks, slot0 < v.total ? slot0 : v.total - 1);
     u32 gs[SM_WIN / 256], ge[SM_WIN / 256];
     bool act[SM_WIN / 256];
 #pragma unroll
@@ -761,7 +679,6 @@ __global__ __launch_bounds__(256) void k_bwt_f_sort_small(FwdView v, u32* __rest
         if (act[k]) { sSA[i] = v.SA[slot0 + i]; sK[i] = v.K[slot0 + i]; }
     }
     __syncthreads();
-    const int b0 = sBlk;
     u32 surv = 0;
 #pragma unroll
     for (int k = 0; k < (int)(SM_WIN / 256); k++) {
@@ -780,9 +697,7 @@ __global__ __launch_bounds__(256) void k_bwt_f_sort_small(FwdView v, u32* __rest
         const u32 headIdx = gs[k] + less;
         v.SA[slot0 + headIdx + eqBefore] = gp;
         if (less != 0) {
-            u32 bbase = 0;
-            if (v.ISA2) { int b = b0; while (slot0 + i >= v.base[b + 1]) b++; bbase = v.base[b]; }
-            lab_set(v, gp, bbase, slot0 + headIdx, slot0 + gs[k]);             // (a small group's label is its first slot)
+            lab_set(v, gp, 0u, slot0 + headIdx, slot0 + gs[k]);                // (a small group's label is its first slot; plain labels need no block base)
             if (eqBefore == 0) atomicOr(&sNew[headIdx >> 5], 1u << (headIdx & 31));
         }
         if (eq > 1) surv++;
@@ -890,74 +805,6 @@ __global__ __launch_bounds__(256) void k_bwt_f_small_fused(FwdView v, u32 h, u32
     }
     __syncthreads();
     if (threadIdx.x == 0 && survTile) survTile[blockIdx.x] = sWs[0] + sWs[1] + sWs[2] + sWs[3];
-    if (threadIdx.x < 64 && sNew[threadIdx.x]) atomicOr(&v.gnew[(slot0 >> 5) + threadIdx.x], sNew[threadIdx.x]);
-}
-
-// The small groups of round 0 once more, on the EIGHT TEXT BYTES behind the sorted symbols (zero past the block end): the keys come
-// from the text, which nobody changes, so gathering and sorting are one kernel (no key array, no ordering constraint between
-// windows), and a member pays one random read and one label write for eight symbols of depth where a doubling round at h = 4 buys
-// four. Most small groups of round 0 are resolved here and never enter a doubling round; ties (also: a suffix that ends inside the
-// eight bytes against one that continues with zeros) stay groups and go on as usual.
-__global__ __launch_bounds__(256) void k_bwt_f_sort_small_text(BwtView bv, FwdView v, u32 off)
-{
-    __shared__ SmWindow W;
-    __shared__ int sAny;
-    __shared__ int sBlk;
-    __shared__ u32 sSA[SM_WIN];
-    __shared__ u64 sK[SM_WIN];
-    __shared__ u32 sNew[64];
-    const u32 slot0 = blockIdx.x * SM_TS;
-    if (!sm_load_window(v, slot0, W, &sAny)) return;
-    if (threadIdx.x < 64) sNew[threadIdx.x] = 0;
-    if (threadIdx.x == 64) sBlk = find_block(v.base, v.nBlocks, slot0 < v.total ? slot0 : v.total - 1);
-    __syncthreads();
-    const int b0 = sBlk;
-    u32 gs[SM_WIN / 256], ge[SM_WIN / 256];
-    bool act[SM_WIN / 256];
-#pragma unroll
-    for (int k = 0; k < (int)(SM_WIN / 256); k++) {
-        const u32 i = threadIdx.x + 256u * k;
-        act[k] = sm_group_of(W, i, gs[k], ge[k]);
-        if (!act[k]) continue;
-        const u32 slot = slot0 + i;
-        int b = b0;
-        while (slot >= v.base[b + 1]) b++;
-        const u32 bb = v.base[b], n = v.base[b + 1] - bb;
-        const u32 gp = v.SA[slot];
-        const u32 q = gp - bb + off;
-        const u8* t = bv.src[b];
-        const u64 x = text8(t, q, n);
-        sSA[i] = gp;
-        sK[i] = __builtin_bswap64(x);
-    }
-    __syncthreads();
-    u32 surv = 0;
-#pragma unroll
-    for (int k = 0; k < (int)(SM_WIN / 256); k++) {
-        if (!act[k]) continue;
-        const u32 i = threadIdx.x + 256u * k;
-        const u64 ki = sK[i];
-        u32 less = 0, eq = 0, eqBefore = 0;
-        for (u32 j = gs[k]; j < ge[k]; j++) {
-            const u64 kj = sK[j];
-            less += (kj < ki) ? 1u : 0u;
-            const u32 same = (kj == ki) ? 1u : 0u;
-            eq += same;
-            eqBefore += (j < i) ? same : 0u;
-        }
-        const u32 gp = sSA[i];
-        const u32 headIdx = gs[k] + less;
-        v.SA[slot0 + headIdx + eqBefore] = gp;
-        if (less != 0) {
-            int b = b0;
-            while (slot0 + i >= v.base[b + 1]) b++;
-            lab_set(v, gp, v.base[b], slot0 + headIdx, slot0 + gs[k]);
-            if (eqBefore == 0) atomicOr(&sNew[headIdx >> 5], 1u << (headIdx & 31));
-        }
-        if (eq > 1) surv = 1;
-    }
-    if (__ballot(surv != 0) != 0 && (threadIdx.x & 63) == 0) v.counters[0] = 1;
-    __syncthreads();
     if (threadIdx.x < 64 && sNew[threadIdx.x]) atomicOr(&v.gnew[(slot0 >> 5) + threadIdx.x], sNew[threadIdx.x]);
 }
 
@@ -1148,8 +995,7 @@ __global__ __launch_bounds__(256) void k_bwt_f_link_apply(FwdView v, const u32* 
 // The 32 workgroups that run on one XCD (workgroup index mod 8 -- an observed placement, used for speed only) walk through one
 // contiguous eighth of the list side by side, so that a line of ISA fetched for one group is found in that XCD's L2 by the
 // 31 groups next to it, instead of being fetched from memory once per group.
-template <int THREADS>
-__global__ __launch_bounds__(THREADS) void k_bwt_f_gather_desc(FwdView v, const uint2* __restrict__ desc, u32 nDesc, u32 h, uint2* __restrict__ descInfo, int stats)
+__global__ __launch_bounds__(GATHER_THREADS) void k_bwt_f_gather_desc(FwdView v, const uint2* __restrict__ desc, u32 nDesc, u32 h, uint2* __restrict__ descInfo, int stats)
 {
     __shared__ int sBlk;
     const u32 xcd = blockIdx.x & 7, lanesPerXcd = gridDim.x >> 3, slot = blockIdx.x >> 3;      // the grid is a multiple of 8 workgroups
@@ -1166,14 +1012,14 @@ __global__ __launch_bounds__(THREADS) void k_bwt_f_gather_desc(FwdView v, const 
         if (threadIdx.x == 0) { descInfo[g] = make_uint2(bb, lab_old(v, v.SA[d.x], bb)); if (stats) atomicAdd(&v.counters[12], d.y); }
         // eight members per thread at a time: all position loads, then all key loads, then the stores -- two memory
         // latencies per batch instead of two per member
-        for (u32 i0 = 0; i0 < d.y; i0 += 8 * THREADS) {
+        for (u32 i0 = 0; i0 < d.y; i0 += 8 * GATHER_THREADS) {
             u32 gp[8], key[8];
 #pragma unroll
-            for (int k = 0; k < 8; k++) { const u32 i = i0 + (u32)k * THREADS + threadIdx.x; gp[k] = (i < d.y) ? v.SA[d.x + i] : bb; }
+            for (int k = 0; k < 8; k++) { const u32 i = i0 + (u32)k * GATHER_THREADS + threadIdx.x; gp[k] = (i < d.y) ? v.SA[d.x + i] : bb; }
 #pragma unroll
-            for (int k = 0; k < 8; k++) { const u32 i = i0 + (u32)k * THREADS + threadIdx.x; key[k] = (i < d.y) ? gather_key(v, gp[k], off, bb, be) : 0u; }
+            for (int k = 0; k < 8; k++) { const u32 i = i0 + (u32)k * GATHER_THREADS + threadIdx.x; key[k] = (i < d.y) ? gather_key(v, gp[k], off, bb, be) : 0u; }
 #pragma unroll
-            for (int k = 0; k < 8; k++) { const u32 i = i0 + (u32)k * THREADS + threadIdx.x; if (i < d.y) v.K[d.x + i] = key[k]; }
+            for (int k = 0; k < 8; k++) { const u32 i = i0 + (u32)k * GATHER_THREADS + threadIdx.x; if (i < d.y) v.K[d.x + i] = key[k]; }
         }
         __syncthreads();
     }
@@ -1462,7 +1308,7 @@ __global__ __launch_bounds__(THREADS, (THREADS >= 1024 ? 4 : THREADS / 128)) voi
         u32 c = 0;
         for (u32 i = (u32)tid; i < n; i += THREADS) c += (L.oK[i] == m) ? 1u : 0u;
         c = med_block_sum(L, c);
-        if (c < n && 2 * c >= n && n <= SUPER_CAP && superList != nullptr && m == info.y - info.x + 1u) {
+        if (c < n && 2 * c >= n && n <= SUPER_CAP && m == info.y - info.x + 1u) {
             // the majority looks at the group itself (a periodic stretch whose period divides h): k_bwt_f_super finishes it in one round
             if (tid == 0) { const u32 at = atomicAdd(&v.counters[7], 1u); superList[at] = make_uint4(gs, n, info.x, info.y); }
             __syncthreads();
@@ -1885,7 +1731,7 @@ template <class KEY>
 __global__ __launch_bounds__(256) void k_bwt_f_large_place(FwdView v, const uint2* __restrict__ desc, const u32* __restrict__ loff, u32 L, int kbits,
                                                            const KEY* __restrict__ keys, const u32* __restrict__ vals, const u32* __restrict__ head,
                                                            const u32* __restrict__ nextRev, uint2* __restrict__ medNext, uint2* __restrict__ largeNext,
-                                                           const u32* __restrict__ memberR, u32* __restrict__ ovr, u32* __restrict__ rtbits, const u32* __restrict__ lbase)
+                                                           const u32* __restrict__ lbase)
 {
     const u32 j = blockIdx.x * 256 + threadIdx.x;
     u32 surv = 0;
@@ -1905,7 +1751,6 @@ __global__ __launch_bounds__(256) void k_bwt_f_large_place(FwdView v, const uint
         // (a large group's label is its first slot: round 0 and this kernel are the only ones that make large groups)
         if (nh != off) lab_set(v, gp, lbase[di], gs + (nh - off), gs);
         mySlot = gs + (j - off);
-        if (memberR != nullptr) ovr[mySlot] = memberR[j];          // the run round: what the doubling rounds need to look behind the run
         if (nh == j) {
             const u32 nxt = (j + 1 < L) ? nextRev[L - 2 - j] : L;
             setBit = (j != off);
@@ -1924,19 +1769,6 @@ __global__ __launch_bounds__(256) void k_bwt_f_large_place(FwdView v, const uint
     const int lane = (int)(threadIdx.x & 63);
     const u32 s0 = (u32)__shfl((int)mySlot, 0, 64);
     const bool inLine = (j < L) && (mySlot == s0 + (u32)lane);
-    if (rtbits != nullptr) {
-        const unsigned long long rm = __ballot(inLine);
-        if (j < L && !inLine) atomicOr(&rtbits[mySlot >> 5], 1u << (mySlot & 31));
-        if (rm != 0 && lane == 0) {
-            const u32 w0 = s0 >> 5, sh = s0 & 31;
-            const u32 p0 = (u32)(rm << sh);
-            const u32 p1 = sh ? (u32)(rm >> (32 - sh)) : (u32)(rm >> 32);
-            const u32 p2 = sh ? (u32)(rm >> (64 - sh)) : 0u;
-            if (p0) atomicOr(&rtbits[w0], p0);
-            if (p1) atomicOr(&rtbits[w0 + 1], p1);
-            if (p2) atomicOr(&rtbits[w0 + 2], p2);
-        }
-    }
     const unsigned long long mask = __ballot(setBit && inLine);
     if (setBit && !inLine) atomicOr(&v.gnew[mySlot >> 5], 1u << (mySlot & 31));
     if (mask != 0 && lane == 0) {
@@ -2036,14 +1868,14 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_len(BwtView bv, FwdView v, co
             // a run starts here when a run ends right in front (block ends are run ends); it takes part in the run-length round when it
             // is at least nsym long and its byte has a run group
             const bool endBefore = (i == 0) ? ((prevWord >> 31) & 1u) != 0 : ((bw[(i - 1) >> 5] >> ((i - 1) & 31)) & 1u) != 0;
-            if (endBefore && r >= nsym && classTab != nullptr) {
+            if (endBefore && r >= nsym) {
                 int b = sBlk;
                 while (gp >= v.base[b + 1]) b++;
                 start = classTab[(u32)b * 256u + (u32)bv.src[b][gp - v.base[b]]] != 0xFFFFFFFFu;
             }
         }
         const unsigned long long m64 = __ballot(start);
-        if ((tid & 63) == 0 && startBits64 != nullptr) {
+        if ((tid & 63) == 0) {
             startBits64[(pos0 + 256u * (u32)k + (u32)(tid & ~63)) >> 6] = m64;
             startCount[((pos0 + 256u * (u32)k + (u32)(tid & ~63)) >> 5)] = (u32)__popc((u32)m64);
             startCount[((pos0 + 256u * (u32)k + (u32)(tid & ~63)) >> 5) + 1] = (u32)__popc((u32)(m64 >> 32));
@@ -2177,7 +2009,7 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_expand(const u64* __restrict_
     const u32 Rr = (u32)(above ? ((1ull << hbits) - 1ull - hiK) : hiK);
     keys[j] = (ch << kbits) | T;
     vals[j] = sE[k] - Rr;
-    if (Rout != nullptr) Rout[j] = Rr;
+    Rout[j] = Rr;
 }
 
 // ---- the run round's last step without index arrays: where a tie starts among the sorted members is ONE BIT per member (a ballot per
@@ -2246,7 +2078,7 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_place(FwdView v, const uint2*
         mySlot = gs + (j - off);
         v.SA[mySlot] = gp;
         if (nh != off) lab_set(v, gp, lbase[di], gs + (nh - off), gs);      // (the first tie of a group keeps the group's label)
-        if (memberR != nullptr) ovr[mySlot] = memberR[j];
+        ovr[mySlot] = memberR[j];                                            // what the doubling rounds need to look behind the run
         if (nh == j) {
             const u32 m2 = word & ~lowmask;
             const u32 ei = m2 ? (w * 32 + (u32)__ffs((int)m2) - 1) : W.nextSet[w];
@@ -2270,14 +2102,14 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_place(FwdView v, const uint2*
     const unsigned long long hm = __ballot(setBit && inLine), rm = __ballot(inLine);
     if (live && !inLine) {
         if (setBit) atomicOr(&v.gnew[mySlot >> 5], 1u << (mySlot & 31));
-        if (rtbits != nullptr) atomicOr(&rtbits[mySlot >> 5], 1u << (mySlot & 31));
+        atomicOr(&rtbits[mySlot >> 5], 1u << (mySlot & 31));
     }
     if (lane == 0) {
         const u32 w0 = s0 >> 5, sh = s0 & 31;
         for (int which = 0; which < 2; which++) {
             const unsigned long long mask = which ? rm : hm;
             u32* dst = which ? rtbits : v.gnew;
-            if (mask == 0 || dst == nullptr) continue;
+            if (mask == 0) continue;
             const u32 p0 = (u32)(mask << sh);
             const u32 p1 = sh ? (u32)(mask >> (32 - sh)) : (u32)(mask >> 32);
             const u32 p2 = sh ? (u32)(mask >> (64 - sh)) : 0u;
@@ -2365,24 +2197,21 @@ __global__ __launch_bounds__(256) void k_bwt_f_med_compact(uint2* __restrict__ s
     if (d.y) { medNext[prefix[i]] = d; stage[i] = make_uint2(0u, 0u); }
 }
 
-// knobs (tests, tuning): read from the environment once per process, or set through knz_hip_tune()
-struct FwdTuning { int nsym; int noRunRound; int runFallback; int noSuper; int noTextRound; int stats; int noRunOffsets; int noProbe; int link; int gatherWg; int plainLabels; int noFuse; int largeOs; int noPack; };
+// knobs (tests, diagnostics): read from the environment once per process, or set through knz_hip_tune(). Each one forces, at test
+// sizes, a path that some inputs take by themselves (round-0 key length, no run round, the run groups' fall-back, the plain labels of
+// blocks above 256 MiB, the plain keys of blocks above 8 MiB, where the link step starts), or reports (stats).
+struct FwdTuning { int nsym; int noRunRound; int runFallback; int stats; int link; int plainLabels; int noPack; };
 static FwdTuning& fwd_tuning()
 {
     static FwdTuning t = [] {
-        FwdTuning x; x.nsym = 0; x.noRunRound = 0; x.runFallback = 0; x.noSuper = 0; x.noTextRound = 0; x.stats = 0; x.noRunOffsets = 0; x.noProbe = 0; x.link = 1; x.gatherWg = 512; x.plainLabels = 0; x.noFuse = 0; x.largeOs = 1000000; x.noPack = 0;     // link: 0 off, 1 on (from h = 32), n > 1: from h = n
-        if (getenv("KNZ_BWT_NO_PROBE")) x.noProbe = 1;
+        FwdTuning x; x.nsym = 0; x.noRunRound = 0; x.runFallback = 0; x.stats = 0; x.link = 1; x.plainLabels = 0; x.noPack = 0;     // link: 0 off, 1 on (from h = 32), n > 1: from h = n
         if (getenv("KNZ_BWT_PLAIN_LABELS")) x.plainLabels = 1;
-        if (getenv("KNZ_BWT_NO_FUSE")) x.noFuse = 1;
         if (getenv("KNZ_BWT_NO_PACK")) x.noPack = 1;
         if (const char* e = getenv("KNZ_BWT_LINK")) x.link = atoi(e);
-        if (getenv("KNZ_BWT_NO_RUN_OFFSETS")) x.noRunOffsets = 1;
         if (getenv("KNZ_BWT_STATS")) x.stats = 1;
         if (const char* e = getenv("KNZ_BWT_NSYM")) x.nsym = atoi(e);
         if (getenv("KNZ_BWT_NO_RUN_ROUND")) x.noRunRound = 1;
         if (getenv("KNZ_BWT_RUN_FALLBACK")) x.runFallback = 1;
-        if (getenv("KNZ_BWT_NO_SUPER")) x.noSuper = 1;
-        if (const char* e = getenv("KNZ_BWT_NO_TEXT_ROUND")) x.noTextRound = atoi(e);
         return x;
     }();
     return t;
@@ -2394,17 +2223,10 @@ int bwt_forward_tune(const char* key, int value)
     if (!strcmp(key, "bwt_nsym")) t.nsym = value;
     else if (!strcmp(key, "bwt_no_run_round")) t.noRunRound = value;
     else if (!strcmp(key, "bwt_run_fallback")) t.runFallback = value;
-    else if (!strcmp(key, "bwt_no_super")) t.noSuper = value;
-    else if (!strcmp(key, "bwt_no_text_round")) t.noTextRound = value;
     else if (!strcmp(key, "bwt_stats")) t.stats = value;
-    else if (!strcmp(key, "bwt_no_run_offsets")) t.noRunOffsets = value;
-    else if (!strcmp(key, "bwt_no_probe")) t.noProbe = value;
     else if (!strcmp(key, "bwt_link")) t.link = value;
-    else if (!strcmp(key, "bwt_gather_wg")) t.gatherWg = value;
     else if (!strcmp(key, "bwt_plain_labels")) t.plainLabels = value;
-    else if (!strcmp(key, "bwt_no_fuse")) t.noFuse = value;
     else if (!strcmp(key, "bwt_no_pack")) t.noPack = value;      // small groups ranked on plain keys (three counts per pair) also where the packed keys fit
-    else if (!strcmp(key, "bwt_large_os")) t.largeOs = value;
     else return -1;
     return 0;
 }
@@ -2539,8 +2361,6 @@ static int bwt_forward_run(hipStream_t s, const XfStage& st, void* scratch, size
                          && (size_t)bv.VS < (size_t)prims::RS_VAL_MASK;   // 30-bit counts in the look-back words (a 1 GiB block: count + scatter)
     if (oneRead) {                                                // the digits of all passes counted from the text, once
         KScope ks_("k_bwt_f_r0_sort");
-        TextSrc src; src.src = bv.src; src.P = nsym; src.pbits = pbits; src.shift = pbits;
-        (void)src;
         hipLaunchKernelGGL(k_bwt_f_r0_counts, dim3((unsigned)rs.L.nSeg), dim3(256), 0, s, bv, w.base, w.byteHist, nsym, rs.L);
         hipLaunchKernelGGL(prims::k_rs_digit_bases, dim3((unsigned)rs.L.nSeg, (unsigned)nsym), dim3(256), 0, s, rs.L);
     }
@@ -2566,34 +2386,21 @@ static int bwt_forward_run(hipStream_t s, const XfStage& st, void* scratch, size
     hipMemsetAsync(w.counters, 0, 64, s);
     { KScope ks_("k_bwt_f_r0_flags"); hipLaunchKernelGGL(k_bwt_f_r0_flags, dim3((total + 256 * R0F_ROWS - 1) / (256 * R0F_ROWS)), dim3(256), 0, s, sortedKeys, w.base, st.nBlocks, total, nsym, pbits,
                                                          reinterpret_cast<unsigned long long*>(w.gbits)); }
-    // group starts before / after every window of 2048 slots: two scans over ~total/2048 values
-    const u32 nWin = (total + SM_WIN - 1) / SM_WIN;
-    // (windows of SM_TS slots for the fused placement + text round, of SM_WIN slots for the separate kernels)
-    const bool fusedText = tune.noTextRound == 0;
-    const u32 nWinP = fusedText ? (total + SM_TS - 1) / SM_TS : nWin;
-    { KScope ks_("k_bwt_f_r0_winsum"); hipLaunchKernelGGL(k_bwt_f_r0_winsum, GRID1(nWinP), w.gbits, total, nWinP, w.t0, w.t2, fusedText ? SM_TS / 32 : SM_WIN / 32); }
+    // group starts before / after every window of SM_TS slots (the windows of the placement): two scans over ~total/1792 values
+    const u32 nWinP = (total + SM_TS - 1) / SM_TS;
+    { KScope ks_("k_bwt_f_r0_winsum"); hipLaunchKernelGGL(k_bwt_f_r0_winsum, GRID1(nWinP), w.gbits, total, nWinP, w.t0, w.t2, SM_TS / 32); }
     { KScope ks_("k_bwt_f_scan_max"); prims::launch_scan<prims::SCAN_MAX_INCL>(s, w.t0, w.t1, nWinP, nullptr, w.scanTmp); }
     { KScope ks_("k_bwt_f_scan_min"); prims::launch_scan<prims::SCAN_MIN_INCL>(s, w.t2, w.t3, nWinP, nullptr, w.scanTmp); }
     int cur = 0;
     int kbits = 1;
     while ((1ull << kbits) < (u64)bv.VS + 2) kbits++;
     // the run-length round needs descriptor index + (kbits + 1) + kbits bits in one 64-bit key
+    // (2 * kbits + 1 >= 64 needs VS >= 2^31 - 1: no block of an encode, only a per-stage call, knz_hip_transform_forward, with n or dst_cap
+    // that close to 2 GiB)
     const bool runRound = (2 * kbits + 1) < 64 && !tune.noRunRound;
-    const bool runOffsets = !tune.noRunOffsets;
-    if (fusedText) {
-        KScope ks_("k_bwt_f_r0_place");
-        hipLaunchKernelGGL(k_bwt_f_r0_place_text, dim3(nWinP), dim3(256), 0, s, bv, v, w.t1, w.t3, nWinP, w.large[cur], sortedKeys, nsym, pbits, runRound ? w.runList : (uint2*)nullptr);
-        hipLaunchKernelGGL(k_bwt_f_merge_bits, GRID1(total / 32 + 2), w.gbits, w.gnew, total / 32 + 2);
-    } else {
-        KScope ks_("k_bwt_f_r0_place");
-        hipLaunchKernelGGL(k_bwt_f_r0_place, dim3(nWin), dim3(256), 0, s, v, (const u32*)nullptr, w.t1, w.t3, nWin, w.med[cur], w.large[cur],
-                           sortedKeys, nsym, pbits, runRound ? w.runList : (uint2*)nullptr);
-    }
-    if (tune.noTextRound == 2) {
-        const u32 nTiles0 = (total + SM_TS - 1) / SM_TS;
-        { KScope ks_("k_bwt_f_sort_small_text"); hipLaunchKernelGGL(k_bwt_f_sort_small_text, dim3(nTiles0), dim3(256), 0, s, bv, v, (u32)nsym); }
-        { KScope ks_("k_bwt_f_merge_bits"); hipLaunchKernelGGL(k_bwt_f_merge_bits, GRID1(total / 32 + 2), w.gbits, w.gnew, total / 32 + 2); }
-    }
+    { KScope ks_("k_bwt_f_r0_place");
+      hipLaunchKernelGGL(k_bwt_f_r0_place_text, dim3(nWinP), dim3(256), 0, s, bv, v, w.t1, w.t3, nWinP, w.large[cur], sortedKeys, nsym, pbits, runRound ? w.runList : (uint2*)nullptr);
+      hipLaunchKernelGGL(k_bwt_f_merge_bits, GRID1(total / 32 + 2), w.gbits, w.gnew, total / 32 + 2); }
     if (hipMemcpyAsync(h_pinned, w.counters, 64, hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
     if (hipStreamSynchronize(s) != hipSuccess) return -1;
     u32 nRun = h_pinned[4], runElems = h_pinned[5];
@@ -2609,13 +2416,13 @@ static int bwt_forward_run(hipStream_t s, const XfStage& st, void* scratch, size
     // candidates for k_bwt_f_probe among the medium groups of the list just compacted (their number comes back with the counters)
     u32* probeCand = w.medFlags;                                  // (free between two compactions)
     auto probeScan = [&]() {
-        if (tune.noProbe) return;
         KScope ks_("k_bwt_f_probe");
         hipLaunchKernelGGL(k_bwt_f_probe_scan, dim3(256), dim3(256), 0, s, v, w.med[cur], (u32)nsym, v.rtbits, probeCand);
     };
     prims::RsWs rs1 = prims::rs_carve(w.rsMem, maxTotal, st.nBlocks + 1, w.seg2, 1);     // single-segment sorts of the rounds: [0, seg2[1])
     if (nRun) {
         // run lengths of every position (text order), then one sort of the run groups' members on (run length, what follows)
+        const u32 nWin = (total + SM_WIN - 1) / SM_WIN;          // (windows of 2048 positions)
         { KScope ks_("k_bwt_f_run_ends"); hipLaunchKernelGGL(k_bwt_f_run_ends, dim3((total + SM_WIN - 1) / SM_WIN), dim3(256), 0, s, bv, v, reinterpret_cast<u8*>(w.ebits)); }
         { KScope ks_("k_bwt_f_r0_winsum"); hipLaunchKernelGGL(k_bwt_f_r0_winsum, GRID1(nWin), w.ebits, total, nWin, w.t0, w.t2, SM_WIN / 32); }
         { KScope ks_("k_bwt_f_scan_min"); prims::launch_scan<prims::SCAN_MIN_INCL>(s, w.t2, w.t3, nWin, nullptr, w.scanTmp); }
@@ -2667,7 +2474,7 @@ static int bwt_forward_run(hipStream_t s, const XfStage& st, void* scratch, size
           const int r = prims::rs_sort<u64, false>(s, rs1, keysFree, keysFree2, (u32*)nullptr, (u32*)nullptr, (size_t)runElems, 32, 32 + hbits + rbits);
           const u64* sortedM = r ? keysFree2 : keysFree;
           rk = r ? keysFree : keysFree2;
-          hipLaunchKernelGGL(k_bwt_f_run_expand, GRID1(runElems), sortedM, runElems, w.sKey, w.sE, kbits, hbits, rk, rv, runOffsets ? w.valsB : (u32*)nullptr); }
+          hipLaunchKernelGGL(k_bwt_f_run_expand, GRID1(runElems), sortedM, runElems, w.sKey, w.sE, kbits, hbits, rk, rv, w.valsB); }
         {
             // ties among the sorted members as a bit map, heads and sizes per window of 2048 members (the bit map reuses the run-end map,
             // which nobody reads any more)
@@ -2678,10 +2485,10 @@ static int bwt_forward_run(hipStream_t s, const XfStage& st, void* scratch, size
             { KScope ks_("k_bwt_f_scan_max"); prims::launch_scan<prims::SCAN_MAX_INCL>(s, w.t0, w.t1, nWinM, nullptr, w.scanTmp); }
             { KScope ks_("k_bwt_f_scan_min"); prims::launch_scan<prims::SCAN_MIN_INCL>(s, w.t2, w.t3, nWinM, nullptr, w.scanTmp); }
             { KScope ks_("k_bwt_f_large_place");
-              if (runOffsets) hipMemsetAsync(w.rtbits, 0, 4 * w.gbitsWords, s);
+              hipMemsetAsync(w.rtbits, 0, 4 * w.gbitsWords, s);
               hipLaunchKernelGGL(k_bwt_f_run_place, dim3((runElems + 255) / 256), dim3(256), 0, s, v, w.runList, w.loff, runElems, keyBits, rk, rv, mbits, w.t1, w.t3, nWinM, w.large[cur],
-                                 runOffsets ? (const u32*)w.valsB : (const u32*)nullptr, runOffsets ? w.ovr : (u32*)nullptr, runOffsets ? w.rtbits : (u32*)nullptr, w.lbase);
-              if (runOffsets) { v.ovr = w.ovr; v.rtbits = w.rtbits; } }
+                                 w.valsB, w.ovr, w.rtbits, w.lbase);
+              v.ovr = w.ovr; v.rtbits = w.rtbits; }
         }
         { KScope ks_("k_bwt_f_merge_bits"); hipLaunchKernelGGL(k_bwt_f_merge_bits, GRID1(total / 32 + 2), w.gbits, w.gnew, total / 32 + 2); }
         compactMedium(w.med[cur]);
@@ -2698,7 +2505,7 @@ static int bwt_forward_run(hipStream_t s, const XfStage& st, void* scratch, size
         if (hipStreamSynchronize(s) != hipSuccess) return -1;
     }
     u32 surv = h_pinned[0], nMed = h_pinned[1], nLarge = h_pinned[2], largeElems = h_pinned[3];
-    if (const u32 nCand = tune.noProbe ? 0u : h_pinned[14]) {
+    if (const u32 nCand = h_pinned[14]) {
         // Periodic stretches of a period the doubling offsets never meet, by looking at the text (k_bwt_f_probe), before the first round: the
         // groups it takes apart are void in the list (length 0), their parts that are medium groups are appended to it
         if (!v.rtbits) { hipMemsetAsync(w.rtbits, 0, 4 * w.gbitsWords, s); v.ovr = w.ovr; v.rtbits = w.rtbits; }
@@ -2781,16 +2588,12 @@ static int bwt_forward_run(hipStream_t s, const XfStage& st, void* scratch, size
             linkStepUsed = linkStep;
         }
         // -- all keys first (with versioned labels the small groups fetch theirs in the kernel that sorts them: k_bwt_f_small_fused)
-        const bool fused = v.ISA2 != nullptr && !tune.noFuse;
+        const bool fused = v.ISA2 != nullptr;
         if (surv && !fused) { KScope ks_("k_bwt_f_gather_small"); hipLaunchKernelGGL(k_bwt_f_gather_small, dim3(nTiles), dim3(256), 0, s, v, h, tune.stats); }
         if (nMed) {
             // (the list is in slot order: k_bwt_f_med_compact)
             KScope ks_("k_bwt_f_gather_desc");
-            // Threads per workgroup (knob bwt_gather_wg, default 512): a group's keys are three dependent loads, and more, smaller workgroups keep
-            // more groups in flight per CU. Real files 4.13 -> 2.99 ms (512) / 3.16 (256), text 3.26 -> 2.39 / 2.46, the stand-in 2.54 -> 2.56 / 2.71.
-            if (tune.gatherWg == 256) hipLaunchKernelGGL(k_bwt_f_gather_desc<256>, dim3(2048), dim3(256), 0, s, v, w.med[cur], nMed, h, w.descInfo, tune.stats);
-            else if (tune.gatherWg == 1024) hipLaunchKernelGGL(k_bwt_f_gather_desc<1024>, dim3(256), dim3(1024), 0, s, v, w.med[cur], nMed, h, w.descInfo, tune.stats);
-            else hipLaunchKernelGGL(k_bwt_f_gather_desc<512>, dim3(1024), dim3(512), 0, s, v, w.med[cur], nMed, h, w.descInfo, tune.stats);
+            hipLaunchKernelGGL(k_bwt_f_gather_desc, dim3(1024), dim3(GATHER_THREADS), 0, s, v, w.med[cur], nMed, h, w.descInfo, tune.stats);
         }
         int lbits = 0;
         bool small32 = false;
@@ -2813,13 +2616,12 @@ static int bwt_forward_run(hipStream_t s, const XfStage& st, void* scratch, size
         if (nMed) {
             // two workgroup shapes over the same list, each takes the groups of its size class: 256 threads x 8 elements (21 KB of LDS,
             // groups up to 2048) and 512 threads x 16 elements (76 KB: two groups per CU in flight)
-            uint4* sup = tune.noSuper ? (uint4*)nullptr : w.superList;
             { KScope ks_("k_bwt_f_sort_medium");
               const dim3 gridM(std::min<u32>(nMed, 8192));
-              hipLaunchKernelGGL((k_bwt_f_sort_medium<256, 8>), gridM, dim3(256), 0, s, v, w.med[cur], nMed, npass, SM_G, w.med[nxt], w.large[nxt], w.descInfo, sup);
-              hipLaunchKernelGGL((k_bwt_f_sort_medium<512, 16>), gridM, dim3(512), 0, s, v, w.med[cur], nMed, npass, 2048u, w.med[nxt], w.large[nxt], w.descInfo, sup); }
+              hipLaunchKernelGGL((k_bwt_f_sort_medium<256, 8>), gridM, dim3(256), 0, s, v, w.med[cur], nMed, npass, SM_G, w.med[nxt], w.large[nxt], w.descInfo, w.superList);
+              hipLaunchKernelGGL((k_bwt_f_sort_medium<512, 16>), gridM, dim3(512), 0, s, v, w.med[cur], nMed, npass, 2048u, w.med[nxt], w.large[nxt], w.descInfo, w.superList); }
             // groups whose majority looks at the group itself (sort_medium has listed them; the kernel reads the count itself)
-            if (sup) { KScope ks_("k_bwt_f_super"); hipLaunchKernelGGL(k_bwt_f_super, dim3(std::min<u32>(nMed, 512)), dim3(1024), 0, s, v, sup, h, npass, w.med[nxt], w.large[nxt]); }
+            { KScope ks_("k_bwt_f_super"); hipLaunchKernelGGL(k_bwt_f_super, dim3(std::min<u32>(nMed, 512)), dim3(1024), 0, s, v, w.superList, h, npass, w.med[nxt], w.large[nxt]); }
         }
         if (nLarge) {
             u32* k32a = reinterpret_cast<u32*>(lkA); u32* k32b = reinterpret_cast<u32*>(lkB);
@@ -2829,9 +2631,9 @@ static int bwt_forward_run(hipStream_t s, const XfStage& st, void* scratch, size
               prims::rs_launch_layout(s, rs1);
               // (count + scatter passes here: with the many passes of these keys, most of them on constant digits, counting all of
               // them ahead costs more than it saves -- period 3 / 5 / 7 / 768 at 8 MiB: 11.1-17.6 ms against 11.8-18.2)
-              // (knob bwt_large_os: from that many members on the passes are the one-sweep ones; real files' 27 M members in the first round: 4.11 -> 3.94 ms,
+              // (from LARGE_OS_MIN members on the passes are the one-sweep ones; real files' 27 M members in the first round: 4.11 -> 3.94 ms,
               // and counted for every sort they cost the many small ones of periodic data more than they save: 4.11 -> 4.56)
-              const bool os = tune.largeOs != 0 && largeElems >= (u32)tune.largeOs;
+              const bool os = largeElems >= LARGE_OS_MIN;
               r = small32 ? prims::rs_sort<u32, true>(s, rs1, k32a, k32b, w.valsA, w.valsB, (size_t)largeElems, 0, kbits + lbits, os)
                           : prims::rs_sort<u64, true>(s, rs1, lkA, lkB, w.valsA, w.valsB, (size_t)largeElems, 0, kbits + lbits, os); }
             const u32* sk32 = r ? k32b : k32a; const u64* sk64 = r ? lkB : lkA; const u32* sv = r ? w.valsB : w.valsA;
@@ -2841,8 +2643,8 @@ static int bwt_forward_run(hipStream_t s, const XfStage& st, void* scratch, size
             { KScope ks_("k_bwt_f_scan_max"); prims::launch_scan<prims::SCAN_MAX_INCL>(s, w.t0, w.t1, largeElems, nullptr, w.scanTmp); }
             { KScope ks_("k_bwt_f_scan_min"); prims::launch_scan<prims::SCAN_MIN_INCL>(s, w.t2, w.t3, largeElems, nullptr, w.scanTmp); }
             { KScope ks_("k_bwt_f_large_place");
-              if (small32) hipLaunchKernelGGL(k_bwt_f_large_place<u32>, GRID1(largeElems), v, w.large[cur], w.loff, largeElems, kbits, sk32, sv, w.t1, w.t3, w.med[nxt], w.large[nxt], (const u32*)nullptr, (u32*)nullptr, (u32*)nullptr, w.lbase);
-              else hipLaunchKernelGGL(k_bwt_f_large_place<u64>, GRID1(largeElems), v, w.large[cur], w.loff, largeElems, kbits, sk64, sv, w.t1, w.t3, w.med[nxt], w.large[nxt], (const u32*)nullptr, (u32*)nullptr, (u32*)nullptr, w.lbase); }
+              if (small32) hipLaunchKernelGGL(k_bwt_f_large_place<u32>, GRID1(largeElems), v, w.large[cur], w.loff, largeElems, kbits, sk32, sv, w.t1, w.t3, w.med[nxt], w.large[nxt], w.lbase);
+              else hipLaunchKernelGGL(k_bwt_f_large_place<u64>, GRID1(largeElems), v, w.large[cur], w.loff, largeElems, kbits, sk64, sv, w.t1, w.t3, w.med[nxt], w.large[nxt], w.lbase); }
         }
         { KScope ks_("k_bwt_f_merge_bits"); hipLaunchKernelGGL(k_bwt_f_merge_bits, GRID1(total / 32 + 2), w.gbits, w.gnew, total / 32 + 2); }
         compactMedium(w.med[nxt]);

@@ -77,16 +77,13 @@ def test_bwt_forward_kernels_emulated(tmp_path):
         for order in (("0", "1", "2") if i in (2, 5, 6) else ("0", "2")):       # workgroup dispatch order is not defined: forward, reverse, shuffled
             r = subprocess.run([exe, path], capture_output=True, text=True, timeout=900, env=dict(os.environ, HIPEMU_ORDER=order))
             assert r.returncode == 0, (i, order, r.stdout[-2000:] + r.stderr[-2000:])
-        # the same without the run-length round (run groups refined by doubling like any other group), with the run groups
-        # handed back to the ordinary lists (the path taken when a batch has more run groups than the sort key has index bits),
-        # without the "look behind the run" offsets of the groups the run round leaves tied, without the periodic-stretch probe, and
-        # with round-0 placement and text round as two kernels
+        # the same without the run-length round (run groups refined by doubling like any other group), and with the run groups
+        # handed back to the ordinary lists (the path taken when a batch has more run groups than the sort key has index bits)
         if i in (0, 6):                      # (the switches below on the cases with runs, periods and tiny blocks; the two text cases keep the default path)
             continue
-        # (round 6: KNZ_BWT_PLAIN_LABELS = 32-bit labels with separate key kernels, the path of blocks above 256 MiB; KNZ_BWT_NO_FUSE = versioned
-        # labels with the small groups' keys and refinement as two kernels)
-        for var in ("KNZ_BWT_NO_RUN_ROUND", "KNZ_BWT_RUN_FALLBACK", "KNZ_BWT_NO_RUN_OFFSETS", "KNZ_BWT_NO_PROBE", "KNZ_BWT_NO_TEXT_ROUND", "KNZ_BWT_PLAIN_LABELS", "KNZ_BWT_NO_FUSE"):
-            r = subprocess.run([exe, path], capture_output=True, text=True, timeout=900, env=dict(os.environ, **{var: "2" if var == "KNZ_BWT_NO_TEXT_ROUND" else "1"}))
+        # (round 6: KNZ_BWT_PLAIN_LABELS = 32-bit labels with separate key kernels, the path of blocks above 256 MiB)
+        for var in ("KNZ_BWT_NO_RUN_ROUND", "KNZ_BWT_RUN_FALLBACK", "KNZ_BWT_PLAIN_LABELS"):
+            r = subprocess.run([exe, path], capture_output=True, text=True, timeout=900, env=dict(os.environ, **{var: "1"}))
             assert r.returncode == 0, (i, var, r.stdout[-2000:] + r.stderr[-2000:])
 
 
