@@ -267,6 +267,16 @@ public:
     bool forward(SliceArray<byte>& src, SliceArray<byte>& dst, int length);
     bool inverse(SliceArray<byte>& src, SliceArray<byte>& dst, int length);
 };
+// transform/AliasCodec.hpp: PACK, getMaxEncodedLength = n + 1024. forward() reads the Context's "dataType" and writes back what
+// the stage left there (knz_hip_transform_forward_dt), as AliasCodec.cpp:46-72 does.
+class AliasCodec : public DeviceTransform {
+public:
+    AliasCodec() : DeviceTransform(KNZ_T_PACK, nullptr), _ctx(nullptr) {}
+    explicit AliasCodec(Context& ctx) : DeviceTransform(KNZ_T_PACK, &ctx), _ctx(&ctx) {}
+    bool forward(SliceArray<byte>& src, SliceArray<byte>& dst, int length);
+private:
+    Context* _ctx;
+};
 class SBRT : public DeviceTransform {
 public:
     static const int MODE_MTF = 1, MODE_RANK = 2, MODE_TIMESTAMP = 3;

@@ -156,7 +156,7 @@ static int count_transforms(uint64_t t, int* tok)
 }
 
 static bool host_stage_id(int t) { return t == KNZ_T_TEXT || t == KNZ_T_UTF; }
-static bool transform_supported(int t) { return t == KNZ_T_NONE || t == KNZ_T_ZRLT || t == KNZ_T_MTFT || t == KNZ_T_BWT || t == KNZ_T_BWTS || t == KNZ_T_SRT || t == KNZ_T_RLT || t == KNZ_T_LZ || t == KNZ_T_LZX || t == KNZ_T_RANK || t == KNZ_T_TIMESTAMP; }
+static bool transform_supported(int t) { return t == KNZ_T_NONE || t == KNZ_T_ZRLT || t == KNZ_T_MTFT || t == KNZ_T_BWT || t == KNZ_T_BWTS || t == KNZ_T_SRT || t == KNZ_T_RLT || t == KNZ_T_LZ || t == KNZ_T_LZX || t == KNZ_T_RANK || t == KNZ_T_TIMESTAMP || t == KNZ_T_PACK; }
 static bool entropy_supported(int e) { return e == KNZ_E_NONE || e == KNZ_E_ANS0 || e == KNZ_E_ANS1 || e == KNZ_E_HUFFMAN || e == KNZ_E_FPAQ; }
 
 static int max_encoded_len(int t, int n)
@@ -164,6 +164,7 @@ static int max_encoded_len(int t, int n)
     switch (t) {
     case KNZ_T_BWT: return n + 33;
     case KNZ_T_SRT: return n + 1024;
+    case KNZ_T_PACK: return n + 1024;                                                  // AliasCodec.hpp:52-55
     case KNZ_T_RLT: return (n <= 512) ? n + 32 : n;
     case KNZ_T_LZ: case KNZ_T_LZX: return ((n <= 1024) ? n + 16 : n + n / 64) + 2;     // LZCodec.hpp:91-95
     case KNZ_T_UTF: return n + 8192;                                                   // UTFCodec.hpp:54 (a host stage: only its share of the chain's buffer size matters here)
@@ -453,7 +454,7 @@ static int seq_alloc(Ctx* c, int nBlocks, u64 S, bool needAB, size_t scratchU32,
     const size_t nb = (size_t)nBlocks;
     const std::string nSmall = std::string("seqSmall") + sfx, nA = std::string("xfA") + sfx, nB = std::string("xfB") + sfx, nScr = std::string("xfScratch") + sfx;
     // one slab for all small per-block arrays
-    const size_t bytes = nb * (5 * 1 + 4 * 6 + 8 * 4) + 1024;
+    const size_t bytes = nb * (6 * 1 + 4 * 6 + 8 * 4) + 1024;
     if (int r = ws_get(c, nSmall.c_str(), bytes + 256, (void**)&base)) return r;
     size_t off = 0;
     auto take = [&](size_t sz, size_t align) { off = (off + align - 1) & ~(align - 1); u8* p = base + off; off += sz; return p; };
@@ -472,6 +473,7 @@ static int seq_alloc(Ctx* c, int nBlocks, u64 S, bool needAB, size_t scratchU32,
     w->a.active = take(nb, 16);
     w->a.skip = take(nb, 16);
     w->a.ok = take(nb, 16);
+    w->a.dtype = take(nb, 16);
     w->a.bufCap = w->d_capEven;
     w->a.dataCap = w->d_capOdd;
     w->S = S;
@@ -587,6 +589,12 @@ static int run_forward_stage(Ctx* c, hipStream_t s, int t, const XfStage& st)
         if (launch_bwt_forward(s, st, sc, bytes, reinterpret_cast<u32*>(c->pinned)) != 0) return fail(c, -1, "BWT forward failed: %s", hipGetErrorString(hipGetLastError()));
         break;
     }
+    case KNZ_T_PACK: {
+        void* sc;
+        if (int r = ws_get(c, "packScratch", pack_scratch_bytes(st.nBlocks, st.maxLen), &sc)) return r;
+        launch_pack_forward(s, st, sc);
+        break;
+    }
     case KNZ_T_BWTS: {
         if (const int parts = bwt_parts_wanted(c, st.nBlocks); parts > 1)
             return bwt_in_parts(c, s, st, parts, [&](int nb) { return bwts_forward_scratch_bytes(nb, st.maxLen, (size_t)nb * st.maxLen); },
@@ -613,6 +621,13 @@ static int run_inverse_stage(Ctx* c, hipStream_t s, int t, const XfStage& st, in
     case KNZ_T_RLT: launch_rlt_inverse(s, st); break;
     case KNZ_T_RANK: launch_sbrt_inverse(s, st, 2); break;
     case KNZ_T_TIMESTAMP: launch_sbrt_inverse(s, st, 3); break;
+    case KNZ_T_PACK: {
+        static const char* const wsName[4] = { "packScratch", "packScratch2", "packScratch3", "packScratch4" };
+        void* sc;
+        if (int r = ws_get(c, wsName[lane < 0 ? 0 : (lane & 3)], pack_scratch_bytes(st.nBlocks, st.maxLen), &sc)) return r;
+        launch_pack_inverse(s, st, sc);
+        break;
+    }
     case KNZ_T_LZ: case KNZ_T_LZX: {
         void* sc = nullptr;
         size_t bytes = 0;
@@ -690,6 +705,12 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
     for (int i = 0; i < nTok; i++) {
         if (i < nHosted) { if (!host_stage_id(tok[i])) return fail(c, KNZ_ERR_INVALID_CODEC, "transform id %d is no host stage", tok[i]); }
         else if (!transform_supported(tok[i])) return fail(c, KNZ_ERR_INVALID_CODEC, "transform id %d not implemented on device", tok[i]);
+    }
+    // LZ / LZX behind PACK would have to take PACK's data type (min match 6 for DNA, refusal of SMALL_ALPHABET, LZCodec.cpp:179-191);
+    // the device LZ stages do not read it yet, so such chains are refused rather than encoded differently from the reference
+    for (int i = 0, pack = 0; i < nTok; i++) {
+        if (pack && (tok[i] == KNZ_T_LZ || tok[i] == KNZ_T_LZX)) return fail(c, KNZ_ERR_INVALID_CODEC, "LZ / LZX behind PACK is not implemented on device");
+        pack |= tok[i] == KNZ_T_PACK;
     }
     if (!entropy_supported(p->entropy_type)) return fail(c, KNZ_ERR_INVALID_CODEC, "entropy id %d not implemented on device", p->entropy_type);
     if (p->checksum_bits != 0 && p->checksum_bits != 32 && p->checksum_bits != 64) return fail(c, KNZ_ERR_INVALID_PARAM, "checksum must be 0, 32 or 64");
@@ -782,6 +803,14 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
         HIPCHK(c, hipStreamSynchronize(s));     // pinned scratch is reused below
     }
 
+    // ---- per-block data type (only PACK reads it): preset from the block's magic, or what the host stages left
+    bool wantType = false;
+    for (int i = nHosted; i < nTok; i++) wantType |= tok[i] == KNZ_T_PACK;
+    if (wantType) {
+        if (hs) HIPCHK(c, hipMemsetAsync(w.a.dtype, hs->reserved <= 9 ? (int)hs->reserved : 0, (size_t)nBlocks, s));
+        else launch_seq_fwd_dtype(s, w.a, nBlocks, d_in, bs);
+    }
+
     // ---- transform stages
     if (direct) launch_seq_fwd_direct(s, w.a, d_origLen, n, bs, nBlocks, nTok, d_in, w.d_viewPtr);
     for (int i = 0; i < nTok && !direct; i++) {
@@ -797,6 +826,7 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
         XfStage st;
         st.src = w.a.src; st.dst = w.a.dst; st.len = w.a.alen; st.cap = w.a.cap; st.ok = w.a.ok; st.newLen = w.a.newLen;
         st.nBlocks = nBlocks; st.maxLen = (u32)S; st.scratchU32 = w.scratch; st.entropyType = p->entropy_type;
+        st.dtype = wantType ? w.a.dtype : nullptr;
         if (int r = run_forward_stage(c, s, tok[i], st)) return r;
         launch_seq_fwd_commit(s, w.a, nBlocks, i);
     }
@@ -1173,7 +1203,7 @@ int knz_hip_entropy_decode_v(knz_ctx* ctx, int entropy_type, int bs_version, con
 }
 
 static int transform_host(Ctx* c, int t, int forward, const uint8_t* in, int32_t n, uint8_t* out, int32_t dstCap, int etype,
-                          int32_t* outLen, int32_t* ok, int bsVersion = 6)
+                          int32_t* outLen, int32_t* ok, int bsVersion = 6, int32_t* dataType = nullptr)
 {
     CTX_LOCK(c);
     ProfInstall pi_(c);
@@ -1202,12 +1232,21 @@ static int transform_host(Ctx* c, int t, int forward, const uint8_t* in, int32_t
     st.src = w.a.src; st.dst = w.a.dst; st.len = w.a.alen; st.cap = w.a.cap; st.ok = w.a.ok; st.newLen = w.a.newLen;
     st.nBlocks = 1; st.maxLen = (u32)n; st.scratchU32 = w.scratch; st.entropyType = etype; st.maxCap = (u32)dstCap;
     st.bsVersion = bsVersion;
+    u8 hdt = 0;
+    if (dataType) {
+        if (*dataType < 0 || *dataType > 9) return fail(c, KNZ_ERR_INVALID_PARAM, "data type %d out of range", *dataType);
+        hdt = (u8)*dataType;
+        HIPCHK(c, hipMemcpyAsync(w.a.dtype, &hdt, 1, hipMemcpyHostToDevice, s));
+        st.dtype = w.a.dtype;
+    }
     if (int r = forward ? run_forward_stage(c, s, t, st) : run_inverse_stage(c, s, t, st)) return r;
     HIPCHK(c, hipGetLastError());
     u8 hok = 0; u32 hlen = 0;
     HIPCHK(c, hipMemcpyAsync(&hok, w.a.ok, 1, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(&hlen, w.a.newLen, 4, hipMemcpyDeviceToHost, s));
+    if (dataType) HIPCHK(c, hipMemcpyAsync(&hdt, w.a.dtype, 1, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
+    if (dataType) *dataType = hdt;
     *ok = hok;
     if (hok) {
         *outLen = (int32_t)hlen;
@@ -1221,6 +1260,14 @@ int knz_hip_transform_forward(knz_ctx* ctx, int transform_type, const uint8_t* i
                               int entropy_type, int32_t* out_len, int32_t* ok)
 {
     return transform_host(reinterpret_cast<Ctx*>(ctx), transform_type, 1, in, n, out, dst_cap, entropy_type, out_len, ok);
+}
+
+int knz_hip_transform_forward_dt(knz_ctx* ctx, int transform_type, const uint8_t* in, int32_t n, uint8_t* out, int32_t dst_cap,
+                                 int entropy_type, int32_t* data_type, int32_t* out_len, int32_t* ok)
+{
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!data_type) return fail(c, KNZ_ERR_INVALID_PARAM, "no data type");
+    return transform_host(c, transform_type, 1, in, n, out, dst_cap, entropy_type, out_len, ok, 6, data_type);
 }
 
 int knz_hip_transform_inverse(knz_ctx* ctx, int transform_type, const uint8_t* in, int32_t n, uint8_t* out, int32_t dst_cap,

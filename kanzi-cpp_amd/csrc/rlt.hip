@@ -95,6 +95,8 @@ __global__ __launch_bounds__(64) void k_rlt_forward(XfStage st)
     if (lane == 0) { st.ok[b] = 0; st.newLen[b] = 0; }
     if (count == 0) { if (lane == 0) st.ok[b] = 1; return; }
     if (count < 16) return;
+    // RLT.cpp:60-65: DNA (6), BASE64 (5) and UTF8 (8) blocks are refused (st.dtype is set only in chains behind PACK)
+    if (st.dtype) { const int dt = st.dtype[b]; if (dt == 6 || dt == 5 || dt == 8) return; }
     const int maxEnc = (count <= 512) ? count + 32 : count;
     if ((int)st.cap[b] < maxEnc) return;
     const u8* src = st.src[b];

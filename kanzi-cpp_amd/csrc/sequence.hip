@@ -5,6 +5,7 @@
 // results for ZRLT/RLT).
 #include "common.hpp"
 #include "stages.hpp"
+#include "magic.hpp"
 
 namespace knz {
 
@@ -159,6 +160,13 @@ __global__ void k_seq_inv_commit(SeqArrays a, DecBlock* blocks, int nBlocks, int
     a.where[b] = a.swaps[b] ? ((a.where[b] == 1) ? 2 : 1) : 0;
 }
 
+__global__ void k_seq_fwd_dtype(SeqArrays a, int nBlocks, const u8* in, u64 inStride)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= nBlocks) return;
+    a.dtype[b] = (u8)knz_magic::data_type_preset(in + (size_t)b * inStride, a.origLen[b]);   // io/CompressedOutputStream.cpp:722-731
+}
+
 #define L1D(k, ...) hipLaunchKernelGGL(k, dim3((nBlocks + 255) / 256), dim3(256), 0, s, __VA_ARGS__)
 
 void launch_seq_fwd_direct(hipStream_t s, const SeqArrays& a, u32* origLen, u64 n, u32 blockSize, int nBlocks, int nStages, const u8* in, const u8** viewPtr)
@@ -171,6 +179,8 @@ void launch_seq_fwd_null(hipStream_t s, const SeqArrays& a, int nBlocks, int sta
 { KScope ks_("k_seq_fwd_null"); L1D(k_seq_fwd_null, a, nBlocks, stage); }
 void launch_seq_fwd_hosted(hipStream_t s, const SeqArrays& a, int nBlocks, int stage, int applied)
 { KScope ks_("k_seq_fwd_hosted"); L1D(k_seq_fwd_hosted, a, nBlocks, stage, applied); }
+void launch_seq_fwd_dtype(hipStream_t s, const SeqArrays& a, int nBlocks, const u8* in, u64 inStride)
+{ KScope ks_("k_seq_fwd_dtype"); L1D(k_seq_fwd_dtype, a, nBlocks, in, inStride); }
 void launch_seq_fwd_finish(hipStream_t s, const SeqArrays& a, int nBlocks, const u8* in, u64 inStride, u8* A, u8* B, u64 S, const u8** viewPtr)
 { KScope ks_("k_seq_fwd_finish"); L1D(k_seq_fwd_finish, a, nBlocks, in, inStride, A, B, S, viewPtr); }
 void launch_seq_inv_entropy_dst(hipStream_t s, const SeqArrays& a, DecBlock* blocks, int nBlocks, u8* out, u64 outStride, u8* A, u64 S, u8** entDst, u32 realMask,

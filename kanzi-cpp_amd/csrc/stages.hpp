@@ -61,6 +61,7 @@ struct XfStage {
     int entropyType;         // stream entropy id (RLT escape choice)
     int bsVersion = 6;       // bitstream version the blocks come from (inverse only: BWT block header of versions below 6)
     u32 maxCap = 0;          // upper bound of cap[] when the host knows one (inverse stages that size scratch by their output)
+    u8* dtype = nullptr;     // per-block Global::DataType (0 = UNDEFINED) read and written by PACK; nullptr: a fresh context per block
 };
 
 // zrlt_mtft.hip
@@ -85,6 +86,11 @@ int launch_bwts_forward(hipStream_t s, const XfStage& st, void* scratch, size_t 
 int launch_bwts_inverse(hipStream_t s, const XfStage& st, void* scratch, size_t scratchBytes, u32* h_pinned);
 size_t bwts_forward_scratch_bytes(int nBlocks, u32 VS, size_t total);
 size_t bwts_inverse_scratch_bytes(int nBlocks, u32 VS, size_t total);
+
+// pack.hip (AliasCodec; scratch: pack_scratch_bytes(nBlocks, maxLen) bytes)
+void launch_pack_forward(hipStream_t s, const XfStage& st, void* scratch);
+void launch_pack_inverse(hipStream_t s, const XfStage& st, void* scratch);
+size_t pack_scratch_bytes(int nBlocks, u32 maxLen);
 
 // fpaq.hip (probs: fpaq_probs_bytes(nBlocks, S) bytes of scratch, S = upper bound of the block lengths)
 void launch_fpaq_encode(hipStream_t s, BlockView view, const u32* origLen, u32 copyThreshold, int nBlocks, int maxChunks, ChunkDesc* desc, u8* tmp, u64 tmpStride,
@@ -131,12 +137,14 @@ struct SeqArrays {
     const u32* origLen;
     const u32* dataCap;      // reference buffer capacities (forward only)
     const u32* bufCap;
+    u8* dtype;               // per-block data type (forward: preset from the block's magic, io/CompressedOutputStream.cpp:722-731)
 };
 void launch_seq_fwd_direct(hipStream_t s, const SeqArrays& a, u32* origLen, u64 n, u32 blockSize, int nBlocks, int nStages, const u8* in, const u8** viewPtr);
 void launch_seq_fwd_prepare(hipStream_t s, const SeqArrays& a, int nBlocks, int stage, const u8* in, u64 inStride, u8* A, u8* B, u64 S);
 void launch_seq_fwd_null(hipStream_t s, const SeqArrays& a, int nBlocks, int stage);
 void launch_seq_fwd_hosted(hipStream_t s, const SeqArrays& a, int nBlocks, int stage, int applied);
 void launch_seq_fwd_commit(hipStream_t s, const SeqArrays& a, int nBlocks, int stage);
+void launch_seq_fwd_dtype(hipStream_t s, const SeqArrays& a, int nBlocks, const u8* in, u64 inStride);
 void launch_seq_fwd_finish(hipStream_t s, const SeqArrays& a, int nBlocks, const u8* in, u64 inStride, u8* A, u8* B, u64 S, const u8** viewPtr);
 void launch_seq_inv_entropy_dst(hipStream_t s, const SeqArrays& a, DecBlock* blocks, int nBlocks, u8* out, u64 outStride, u8* A, u64 S, u8** entDst, u32 realMask, u32 unit, u64 outCap);
 void launch_seq_inv_prepare(hipStream_t s, const SeqArrays& a, DecBlock* blocks, int nBlocks, int stage, u8* out, u64 outStride, u8* A, u8* B, u64 S, u32 capMid, u32 capFinal, u32 realMask, u64 outCap);

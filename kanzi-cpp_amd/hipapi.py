@@ -12,12 +12,12 @@ LIB_PATH = os.path.join(_HERE, "libknz_hip.so")
 
 E_NONE, E_HUFFMAN, E_FPAQ, E_ANS0, E_ANS1 = 0, 1, 2, 5, 8
 ENTROPY_IDS = {"NONE": 0, "HUFFMAN": 1, "FPAQ": 2, "ANS0": 5, "ANS1": 8}
-TRANSFORM_IDS = {"NONE": 0, "BWT": 1, "BWTS": 2, "LZ": 3, "RLT": 5, "ZRLT": 6, "MTFT": 7, "RANK": 8, "SRT": 13, "LZX": 16, "TIMESTAMP": 64}
+TRANSFORM_IDS = {"NONE": 0, "BWT": 1, "BWTS": 2, "LZ": 3, "RLT": 5, "ZRLT": 6, "MTFT": 7, "RANK": 8, "SRT": 13, "LZX": 16, "PACK": 18, "TIMESTAMP": 64}
 
 SYMBOLS = [
     "knz_hip_device_count", "knz_hip_create", "knz_hip_destroy", "knz_hip_last_error", "knz_hip_encode_bound",
     "knz_hip_encode_blocks", "knz_hip_decode_blocks", "knz_hip_entropy_encode", "knz_hip_entropy_decode",
-    "knz_hip_transform_forward", "knz_hip_transform_inverse", "knz_hip_malloc", "knz_hip_free",
+    "knz_hip_transform_forward", "knz_hip_transform_forward_dt", "knz_hip_transform_inverse", "knz_hip_malloc", "knz_hip_free",
     "knz_hip_memcpy_h2d", "knz_hip_memcpy_d2h", "knz_hip_sync", "knz_hip_memcpy_h2d_async", "knz_hip_memcpy_d2h_async", "knz_hip_copy_wait", "knz_hip_host_alloc", "knz_hip_host_free", "knz_hip_set_profiling", "knz_hip_get_kernel_times",
     "knz_hip_tune", "knz_hip_shift_bits", "knz_hip_encode_block_hosted", "knz_hip_decode_block_hosted",
     "knz_hip_entropy_decode_v", "knz_hip_transform_inverse_v",
@@ -85,6 +85,8 @@ def lib():
                                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.knz_hip_transform_inverse.argtypes = [vp, C.c_int, C.c_char_p, C.c_int32, u8p, C.c_int32,
                                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.knz_hip_transform_forward_dt.argtypes = [vp, C.c_int, C.c_char_p, C.c_int32, u8p, C.c_int32, C.c_int,
+                                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.knz_hip_malloc.argtypes = [vp, sz, C.POINTER(vp)]
         L.knz_hip_free.argtypes = [vp, vp]
         L.knz_hip_memcpy_h2d.argtypes = [vp, vp, C.c_char_p, sz]
@@ -196,6 +198,15 @@ class Context:
         e = ENTROPY_IDS[entropy.upper()] if entropy else -1
         self._chk(self.L.knz_hip_transform_forward(self.h, t, data, len(data), out, dst_cap, e, C.byref(ol), C.byref(ok)))
         return ok.value, C.string_at(out, ol.value)
+
+    def transform_forward_dt(self, transform, data, dst_cap, data_type, entropy=None):
+        """The forward stage with a Context data type: returns (ok, bytes, the data type the stage left)."""
+        t = TRANSFORM_IDS[transform.upper()]
+        out = (C.c_uint8 * (max(dst_cap, len(data)) + 2048))()
+        ol, ok, dt = C.c_int32(0), C.c_int32(0), C.c_int32(data_type)
+        e = ENTROPY_IDS[entropy.upper()] if entropy else -1
+        self._chk(self.L.knz_hip_transform_forward_dt(self.h, t, data, len(data), out, dst_cap, e, C.byref(dt), C.byref(ol), C.byref(ok)))
+        return ok.value, C.string_at(out, ol.value), dt.value
 
     def transform_inverse(self, transform, data, dst_cap, bs_version=0):
         t = TRANSFORM_IDS[transform.upper()]

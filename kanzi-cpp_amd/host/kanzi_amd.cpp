@@ -418,6 +418,7 @@ int DeviceTransform::getMaxEncodedLength(int n) const
     switch (_type) {
     case KNZ_T_BWT: return n + 33;                      // BWTBlockCodec.hpp:47-50
     case KNZ_T_SRT: return n + 1024;                    // SRT.hpp:38
+    case KNZ_T_PACK: return n + 1024;                   // AliasCodec.hpp:52-55
     case KNZ_T_RLT: return (n <= 512) ? n + 32 : n;     // RLT.hpp:43
     case KNZ_T_LZ: case KNZ_T_LZX: return ((n <= 1024) ? n + 16 : n + (n / 64)) + 2;    // LZCodec.hpp:91-95
     default: return n;
@@ -454,6 +455,31 @@ bool DeviceTransform::inverse(SliceArray<byte>& src, SliceArray<byte>& dst, int 
     int32_t outLen = 0, ok = 0;
     devCheck(c, knz_hip_transform_inverse_v(c, _type, _bsVersion == 0 ? 1 : _bsVersion, src._array + src._index, length, dst._array + dst._index,
                                             dst._length - dst._index, &outLen, &ok), "transform inverse");
+    if (!ok) return false;
+    src._index += length;
+    dst._index += outLen;
+    return true;
+}
+
+// (weak: device libraries built without PACK, such as the CPU stand-in the host layer is tested against, lack the symbol)
+#pragma weak knz_hip_transform_forward_dt
+
+bool AliasCodec::forward(SliceArray<byte>& src, SliceArray<byte>& dst, int length)
+{
+    if (_ctx == nullptr) return DeviceTransform::forward(src, dst, length);
+    if (length == 0) return true;
+    if (!SliceArray<byte>::isValid(src)) throw std::invalid_argument("Alias codec: Invalid input block");
+    if (!SliceArray<byte>::isValid(dst)) throw std::invalid_argument("Alias codec: Invalid output block");
+    if ((length < 0) || (length > src._length - src._index)) return false;
+    if (src._array == dst._array) return false;
+    if (&knz_hip_transform_forward_dt == nullptr) throw std::runtime_error("the device library has no PACK stage");
+    int32_t dt = _ctx->getInt("dataType", hoststage::DT_UNDEFINED);
+    if (dt < 0 || dt > 9) dt = hoststage::DT_UNDEFINED;
+    knz_ctx* c = deviceContext();
+    int32_t outLen = 0, ok = 0;
+    devCheck(c, knz_hip_transform_forward_dt(c, _type, src._array + src._index, length, dst._array + dst._index,
+                                             dst._length - dst._index, _entropy, &dt, &outLen, &ok), "transform forward");
+    if (dt != hoststage::DT_UNDEFINED) _ctx->putInt("dataType", dt);
     if (!ok) return false;
     src._index += length;
     dst._index += outLen;
@@ -796,10 +822,10 @@ static uint64 hostChecksum(const uint8_t* d, int length, int bits)
 static int textVariantOfEntropy(int etype) { return (etype == 0 || etype == 1 || etype == 4 || etype == 5) ? 2 : 1; }      // NONE, HUFFMAN, RANGE, ANS0
 
 // the host stages of one block, in chain order: data ends up in `a` or `b`; returns the buffer that holds it
-struct HostedResult { const uint8_t* data; int len; uint32_t applied; };
+struct HostedResult { const uint8_t* data; int len; uint32_t applied; int dataType; };
 static HostedResult runHostStages(const int* ids, int count, const uint8_t* block, int n, int blockSize, int etype, std::vector<uint8_t>& a, std::vector<uint8_t>& b)
 {
-    HostedResult r{ block, n, 0u };
+    HostedResult r{ block, n, 0u, hoststage::DT_UNDEFINED };
     if (n <= 15) return r;                                  // copy block: no stage runs (io/CompressedOutputStream.cpp:691-695)
     int dt = hoststage::presetDataType(block, n);
     std::vector<uint8_t>* bufs[2] = { &a, &b };
@@ -816,6 +842,7 @@ static HostedResult runHostStages(const int* ids, int count, const uint8_t* bloc
         r.data = out.data(); r.len = outLen; r.applied |= 1u << i;
         cur ^= 1;
     }
+    r.dataType = dt;        // (the stages set it whether they succeed or refuse: the device stages start from it)
     return r;
 }
 
@@ -885,6 +912,7 @@ TransformSequence<T>* TransformFactory<T>::newTransform(Context& ctx, uint64 fun
             case NONE_TYPE: transforms[nbtr++] = new NullTransform(ctx); break;
             case BWT_TYPE: transforms[nbtr++] = new BWTBlockCodec(ctx); break;
             case BWTS_TYPE: transforms[nbtr++] = new BWTS(ctx); break;
+            case PACK_TYPE: transforms[nbtr++] = new AliasCodec(ctx); break;
             case MTFT_TYPE: transforms[nbtr++] = new SBRT(SBRT::MODE_MTF, ctx); break;
             case RANK_TYPE: transforms[nbtr++] = new SBRT(SBRT::MODE_RANK, ctx); break;
             case SRT_TYPE: transforms[nbtr++] = new SRT(ctx); break;
@@ -1540,6 +1568,7 @@ void CompressedOutputStream::submit(Lane& ln)
         if (_checksum) hs.checksum = hostChecksum(orig, int(n), _checksum);
         const HostedResult r = runHostStages(_hostIds, _hosted, orig, int(n), _blockSize, _entropyType, ln.hostA, ln.hostB);
         hs.applied_mask = r.applied;
+        hs.reserved = uint32_t(r.dataType);
         if (r.applied) devCheck(c, knz_hip_memcpy_h2d(c, ln.dIn, r.data, size_t(r.len)), "h2d");
         devCheck(c, knz_hip_encode_block_hosted(c, &p, &hs, static_cast<const uint8_t*>(ln.dIn), size_t(r.len), pro.bytes.empty() ? nullptr : pro.bytes.data(), uint32_t(pro.nbits),
                                                 ln.firstBlock, ln.last ? 1 : 0, static_cast<uint8_t*>(ln.dOut), ln.dOutCap, &bits), "encode block");

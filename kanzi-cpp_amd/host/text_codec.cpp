@@ -19,71 +19,17 @@
 #include <string>
 #include <vector>
 
+#include "../csrc/magic.hpp"
+
 namespace kanzi_amd {
 namespace hoststage {
 
 // ------------------------------------------------------------------------------------------------
 // magic numbers and the data type a block starts with
 // ------------------------------------------------------------------------------------------------
-static uint32_t be32(const uint8_t* p) { return (uint32_t(p[0]) << 24) | (uint32_t(p[1]) << 16) | (uint32_t(p[2]) << 8) | uint32_t(p[3]); }
+uint32_t magicOf(const uint8_t* p) { return knz_magic::magic_of(p); }
 
-uint32_t magicOf(const uint8_t* p)
-{
-    static const uint32_t four[] = { 0x47494638u /* GIF */, 0x25504446u /* PDF */, 0x504B0304u /* ZIP */, 0x377ABCAFu /* 7z */, 0x89504E47u /* PNG */,
-                                     0x7F454C46u /* ELF */, 0xFEEDFACEu, 0xCEFAEDFEu, 0xFEEDFACFu, 0xCFFAEDFEu /* Mach-O */, 0x28B52FFDu /* zstd */,
-                                     0x81CFB2CEu /* brotli */, 0x4D534346u /* CAB */, 0x52494646u /* RIFF */, 0x664C6143u /* FLAC */, 0xFD377A58u /* xz */,
-                                     0x4B414E5Au /* KANZ */, 0x52617221u /* RAR */ };
-    const uint32_t k = be32(p);
-    if ((k & ~0x0Fu) == 0xFFD8FFE0u) return k;                                  // JPEG (the low nibble stays in the value)
-    if ((k >> 8) == 0x425A68u || (k >> 8) == 0x494433u) return k >> 8;          // bzip2, ID3
-    for (uint32_t m : four) if (k == m) return k;
-    const uint32_t k16 = k >> 16;
-    if (k16 == 0x1F8Bu || k16 == 0x424Du || k16 == 0x4D5Au) return k16;         // gzip, BMP, MZ
-    if (k16 == 0x5034u || k16 == 0x5035u || k16 == 0x5036u) {                   // binary PBM / PGM / PPM: "P4".."P6" + white space
-        const uint32_t c = (k >> 8) & 0xFF;
-        if (c == 0x07 || c == 0x0A || c == 0x0D || c == 0x20) return k16;
-    }
-    return 0;
-}
-
-static bool magicCompressed(uint32_t m)
-{
-    switch (m) {
-    case 0xFFD8FFE0u: case 0x47494638u: case 0x89504E47u: case 0x377ABCAFu: case 0x28B52FFDu: case 0x81CFB2CEu: case 0x4D534346u: case 0x504B0304u:
-    case 0x1F8Bu: case 0x425A68u: case 0x664C6143u: case 0x494433u: case 0xFD377A58u: case 0x4B414E5Au: case 0x52617221u:
-        return true;
-    default:
-        return false;
-    }
-}
-static bool magicMultimedia(uint32_t m)
-{
-    switch (m) {
-    case 0xFFD8FFE0u: case 0x47494638u: case 0x89504E47u: case 0x52494646u: case 0x664C6143u: case 0x494433u: case 0x424Du: case 0x5034u: case 0x5035u: case 0x5036u:
-        return true;
-    default:
-        return false;
-    }
-}
-static bool magicExecutable(uint32_t m)
-{
-    switch (m) {
-    case 0x7F454C46u: case 0x4D5Au: case 0xFEEDFACEu: case 0xCEFAEDFEu: case 0xFEEDFACFu: case 0xCFFAEDFEu:
-        return true;
-    default:
-        return false;
-    }
-}
-
-int presetDataType(const uint8_t* block, int n)
-{
-    if (n < 4) return DT_UNDEFINED;
-    const uint32_t m = magicOf(block);
-    if (magicCompressed(m)) return DT_BIN;
-    if (magicMultimedia(m)) return DT_MULTIMEDIA;
-    if (magicExecutable(m)) return DT_EXE;
-    return DT_UNDEFINED;
-}
+int presetDataType(const uint8_t* block, int n) { return n < 4 ? DT_UNDEFINED : knz_magic::data_type_preset(block, uint32_t(n)); }
 
 // ------------------------------------------------------------------------------------------------
 // character classes: 0 letter, 1 delimiter, -1 anything else
