@@ -2,6 +2,7 @@
 // transform / entropy / bit-assembly kernels on one HIP stream.
 #include "common.hpp"
 #include "stages.hpp"
+#include "max_encoded.hpp"
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -76,7 +77,7 @@ struct Ctx {
     std::mutex errMu;            // the last-error string is also written by the copy entry points, which do not take `mu`
     // Copy engine beside the kernels: one stream per direction, outside the lock above, so that a host thread can move the next
     // batch in (or the last one out) while another thread sits in knz_hip_encode_blocks / knz_hip_decode_blocks.
-    hipStream_t stream2[3] = { nullptr, nullptr, nullptr };       // further streams for the split of the BWT stages
+    hipStream_t stream2[3] = { nullptr, nullptr, nullptr };       // side streams of fork_join (split BWT stages, decode lanes)
     hipEvent_t evFork = nullptr, evJoin[3] = { nullptr, nullptr, nullptr };
     std::mutex copyMu;
     hipStream_t copyIn = nullptr, copyOut = nullptr;
@@ -98,7 +99,8 @@ static int fail(Ctx* c, int code, const char* fmt, ...)
 
 #define HIPCHK(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(c, -1, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
-static int ws_get(Ctx* c, const char* name, size_t bytes, void** out)
+// (s: the stream that uses the buffer first -- the KNZ_POISON_WS fill is queued there)
+static int ws_get(Ctx* c, const std::string& name, size_t bytes, void** out, hipStream_t s)
 {
     WsBuf& w = c->ws[name];
     if (w.cap < bytes) {
@@ -112,9 +114,16 @@ static int ws_get(Ctx* c, const char* name, size_t bytes, void** out)
     // KNZ_POISON_WS=1 (debugging aid): fill every workspace with a pattern on every request, so that a kernel that
     // relies on what an earlier call left behind fails deterministically instead of once in a few thousand runs
     static const int poison = getenv("KNZ_POISON_WS") ? atoi(getenv("KNZ_POISON_WS")) : 0;
-    if (poison && bytes) HIPCHK(c, hipMemsetAsync(w.p, poison == 2 ? 0xFF : 0xA5, bytes, c->stream));
+    if (poison && bytes) HIPCHK(c, hipMemsetAsync(w.p, poison == 2 ? 0xFF : 0xA5, bytes, s));
     return 0;
 }
+
+// Lanes: lane -1 (a whole batch) and lane 0 use a workspace's plain name and the start of the pinned area. Lane k >= 1 -- part k of a split
+// BWT / BWTS stage, or range k of a decode (the two never run at once and share) -- has workspaces of its own, named base + (k + 1), and
+// slice k of the pinned area for its read-backs (the context's is 1 MiB).
+static std::string lane_ws(const char* base, int lane) { return lane <= 0 ? std::string(base) : base + std::to_string(lane + 1); }
+constexpr size_t PINNED_LANE_U32 = 32768;
+static u32* lane_pinned(Ctx* c, int lane) { return reinterpret_cast<u32*>(c->pinned) + PINNED_LANE_U32 * (lane < 0 ? 0 : lane); }
 
 thread_local ProfHook* g_prof = nullptr;
 
@@ -156,21 +165,7 @@ static int count_transforms(uint64_t t, int* tok)
 }
 
 static bool host_stage_id(int t) { return t == KNZ_T_TEXT || t == KNZ_T_UTF; }
-static bool transform_supported(int t) { return t == KNZ_T_NONE || t == KNZ_T_ZRLT || t == KNZ_T_MTFT || t == KNZ_T_BWT || t == KNZ_T_BWTS || t == KNZ_T_SRT || t == KNZ_T_RLT || t == KNZ_T_LZ || t == KNZ_T_LZX || t == KNZ_T_RANK || t == KNZ_T_TIMESTAMP || t == KNZ_T_PACK; }
 static bool entropy_supported(int e) { return e == KNZ_E_NONE || e == KNZ_E_ANS0 || e == KNZ_E_ANS1 || e == KNZ_E_HUFFMAN || e == KNZ_E_FPAQ; }
-
-static int max_encoded_len(int t, int n)
-{
-    switch (t) {
-    case KNZ_T_BWT: return n + 33;
-    case KNZ_T_SRT: return n + 1024;
-    case KNZ_T_PACK: return n + 1024;                                                  // AliasCodec.hpp:52-55
-    case KNZ_T_RLT: return (n <= 512) ? n + 32 : n;
-    case KNZ_T_LZ: case KNZ_T_LZX: return ((n <= 1024) ? n + 16 : n + n / 64) + 2;     // LZCodec.hpp:91-95
-    case KNZ_T_UTF: return n + 8192;                                                   // UTFCodec.hpp:54 (a host stage: only its share of the chain's buffer size matters here)
-    default: return n;
-    }
-}
 
 }  // namespace knz
 
@@ -431,13 +426,6 @@ int knz_hip_shift_bits(knz_ctx* ctx, const uint8_t* d_in, uint64_t nbits, uint32
 // ------------------------------------------------------------------------------------------------
 // shared plumbing
 // ------------------------------------------------------------------------------------------------
-static int seq_required(const int* tok, int nTok, int n)
-{
-    int req = n;
-    for (int i = 0; i < nTok; i++) { const int nx = max_encoded_len(tok[i], req); if (nx > req) req = nx; }
-    return req;
-}
-
 struct SeqWs {
     SeqArrays a;
     u32* d_capEven; u32* d_capOdd;
@@ -447,15 +435,14 @@ struct SeqWs {
     u32* scratch;
 };
 
-// (sfx: "" or the suffix of a decode lane -- the parts of a pipelined decode have workspaces of their own)
-static int seq_alloc(Ctx* c, int nBlocks, u64 S, bool needAB, size_t scratchU32, SeqWs* w, const char* sfx = "")
+// (the workspaces of `lane`, first used on stream s)
+static int seq_alloc(Ctx* c, int nBlocks, u64 S, bool needAB, size_t scratchU32, SeqWs* w, int lane, hipStream_t s)
 {
     u8* base;
     const size_t nb = (size_t)nBlocks;
-    const std::string nSmall = std::string("seqSmall") + sfx, nA = std::string("xfA") + sfx, nB = std::string("xfB") + sfx, nScr = std::string("xfScratch") + sfx;
     // one slab for all small per-block arrays
     const size_t bytes = nb * (6 * 1 + 4 * 6 + 8 * 4) + 1024;
-    if (int r = ws_get(c, nSmall.c_str(), bytes + 256, (void**)&base)) return r;
+    if (int r = ws_get(c, lane_ws("seqSmall", lane), bytes + 256, (void**)&base, s)) return r;
     size_t off = 0;
     auto take = [&](size_t sz, size_t align) { off = (off + align - 1) & ~(align - 1); u8* p = base + off; off += sz; return p; };
     w->a.src = (const u8**)take(nb * 8, 16);
@@ -479,22 +466,224 @@ static int seq_alloc(Ctx* c, int nBlocks, u64 S, bool needAB, size_t scratchU32,
     w->S = S;
     w->A = w->B = nullptr;
     if (needAB) {
-        if (int r = ws_get(c, nA.c_str(), (size_t)S * nb + 256, (void**)&w->A)) return r;
-        if (int r = ws_get(c, nB.c_str(), (size_t)S * nb + 256, (void**)&w->B)) return r;
+        if (int r = ws_get(c, lane_ws("xfA", lane), (size_t)S * nb + 256, (void**)&w->A, s)) return r;
+        if (int r = ws_get(c, lane_ws("xfB", lane), (size_t)S * nb + 256, (void**)&w->B, s)) return r;
     }
     w->scratch = nullptr;
-    if (scratchU32) { if (int r = ws_get(c, nScr.c_str(), scratchU32 * 4 + 64, (void**)&w->scratch)) return r; }
+    if (scratchU32) { if (int r = ws_get(c, lane_ws("xfScratch", lane), scratchU32 * 4 + 64, (void**)&w->scratch, s)) return r; }
     return 0;
 }
 
-static size_t stage_scratch_u32(int t, int nBlocks, u32 maxLen, bool forward = true)
+// The stage record of a batch over the workspaces `w` (bsVersion, maxCap and dtype are left to the caller)
+static XfStage xf_stage(const SeqWs& w, int nBlocks, u32 maxLen, int entropyType)
 {
-    switch (t) {
-    case KNZ_T_ZRLT: return zrlt_scratch_u32(nBlocks, maxLen);
-    case KNZ_T_MTFT: return mtft_scratch_u32(nBlocks, maxLen);
-    case KNZ_T_SRT: return forward ? srt_scratch_u32(nBlocks, maxLen) : srt_inverse_scratch_u32(nBlocks, maxLen);
-    default: return 0;
+    XfStage st;
+    st.src = w.a.src; st.dst = w.a.dst; st.len = w.a.alen; st.cap = w.a.cap; st.ok = w.a.ok; st.newLen = w.a.newLen;
+    st.nBlocks = nBlocks; st.maxLen = maxLen; st.scratchU32 = w.scratch; st.entropyType = entropyType;
+    return st;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the device transforms
+// ------------------------------------------------------------------------------------------------
+// One launch of a stage: on stream s over st, with the stage's own scratch (ws, wsBytes) and a pinned read-back area. Returns 0, or a
+// failure code with the context's error set.
+struct StageCall { Ctx* c; hipStream_t s; const XfStage& st; void* ws; size_t wsBytes; u32* pinned; };
+
+static int failed(const StageCall& k, const char* what) { return fail(k.c, -1, "%s failed: %s", what, hipGetErrorString(hipGetLastError())); }
+
+// Whether a stage over a whole batch may run as several parts side by side (bwt_parts_wanted), and whether each part needs a host thread
+// of its own (a stage that reads the device back between its launches)
+enum Split { NO_SPLIT, SPLIT_QUEUED, SPLIT_THREADS };
+
+struct XfDir {
+    size_t (*scratchU32)(int nBlocks, u32 maxLen);   // words of the chain's shared stage scratch (XfStage::scratchU32), or nullptr
+    size_t (*wsBytes)(int nBlocks, u32 maxLen);      // bytes of the stage's own scratch XfInfo::ws, or nullptr
+    int (*launch)(const StageCall&);
+    Split split;
+};
+
+// What the drivers know of one device transform. Everything else about it lives in its launchers, and its size bound in max_encoded.hpp.
+struct XfInfo {
+    int id;
+    const char* ws;              // name of the stage's own scratch (one name for both directions; stages that never run at once share one)
+    XfDir fwd, inv;
+    bool setsType = false;       // reads and sets the per-block data type (XfStage::dtype)
+    bool ignoresType = false;    // would have to read the data type and does not: refused behind a stage that sets it
+    bool lanes = true;           // the inverse may run in decode lanes (decode_impl)
+};
+
+static int lz_inverse(const StageCall& k)
+{
+    Ctx* c = k.c; const XfStage& st = k.st;
+    void* sc = nullptr;
+    size_t bytes = 0;
+    if (st.maxCap != 0 && st.maxCap <= (1u << 30) && !lz_serial_decode(-1)) {
+        // about 20 bytes per output byte; when the device cannot spare that (1 GiB blocks, a 2 GiB batch), or the workspace would
+        // exceed the budget below, the blocks are decoded by the one-wave-per-block decoder, which needs no scratch
+        bytes = lz_inverse_scratch_bytes(st.nBlocks, st.maxCap);
+        static const size_t budget = getenv("KNZ_LZ_INV_SCRATCH_MAX") ? (size_t)atoll(getenv("KNZ_LZ_INV_SCRATCH_MAX")) : ((size_t)48 << 30);
+        WsBuf& wb = c->ws["lzInvScratch"];
+        if (bytes > budget) { bytes = 0; }
+        else if (wb.cap >= bytes) sc = wb.p;
+        else {
+            if (wb.p) { HIPCHK(c, hipFree(wb.p)); wb.p = nullptr; wb.cap = 0; }
+            const size_t want = bytes + (bytes >> 3) + 4096;
+            void* p = nullptr;
+            if (hipMalloc(&p, want) == hipSuccess) { wb.p = p; wb.cap = want; sc = p; }
+            else { (void)hipGetLastError(); bytes = 0; }           // out of memory: the serial decoder
+        }
     }
+    launch_lz_inverse(k.s, st, sc, bytes, st.maxCap);
+    return 0;
+}
+
+static const XfInfo XF[] = {
+    { .id = KNZ_T_ZRLT, .fwd = { .scratchU32 = zrlt_scratch_u32, .launch = [](const StageCall& k) { launch_zrlt_forward(k.s, k.st); return 0; } },
+                        .inv = { .scratchU32 = zrlt_scratch_u32, .launch = [](const StageCall& k) { launch_zrlt_inverse(k.s, k.st); return 0; } } },
+    { .id = KNZ_T_MTFT, .fwd = { .scratchU32 = mtft_scratch_u32, .launch = [](const StageCall& k) { launch_mtft_forward(k.s, k.st); return 0; } },
+                        .inv = { .scratchU32 = mtft_scratch_u32, .launch = [](const StageCall& k) { launch_mtft_inverse(k.s, k.st); return 0; } } },
+    // (the BWT and BWTS stages synchronise their stream: the suffix sort reads counters back between rounds, the BWTS inverse reads
+    // convergence flags every round; the BWT inverse only queues launches)
+    { .id = KNZ_T_BWT, .ws = "bwtScratch",
+      .fwd = { .wsBytes = [](int nb, u32 m) { return bwt_forward_scratch_bytes(nb, m, (size_t)nb * m); },
+               .launch = [](const StageCall& k) { return launch_bwt_forward(k.s, k.st, k.ws, k.wsBytes, k.pinned) ? failed(k, "BWT forward") : 0; },
+               .split = SPLIT_THREADS },
+      .inv = { .wsBytes = [](int nb, u32 m) { return bwt_inverse_scratch_bytes(nb, m, (size_t)nb * m); },
+               .launch = [](const StageCall& k) { return launch_bwt_inverse(k.s, k.st, k.ws, k.wsBytes, k.pinned) ? failed(k, "BWT inverse") : 0; },
+               .split = SPLIT_QUEUED } },
+    { .id = KNZ_T_BWTS, .ws = "bwtScratch",
+      .fwd = { .wsBytes = [](int nb, u32 m) { return bwts_forward_scratch_bytes(nb, m, (size_t)nb * m); },
+               .launch = [](const StageCall& k) { return launch_bwts_forward(k.s, k.st, k.ws, k.wsBytes, k.pinned) ? failed(k, "BWTS forward") : 0; },
+               .split = SPLIT_THREADS },
+      .inv = { .wsBytes = [](int nb, u32 m) { return bwts_inverse_scratch_bytes(nb, m, (size_t)nb * m); },
+               .launch = [](const StageCall& k) { return launch_bwts_inverse(k.s, k.st, k.ws, k.wsBytes, k.pinned) ? failed(k, "BWTS inverse") : 0; },
+               .split = SPLIT_THREADS } },
+    { .id = KNZ_T_SRT, .fwd = { .scratchU32 = srt_scratch_u32, .launch = [](const StageCall& k) { launch_srt_forward(k.s, k.st); return 0; } },
+                       .inv = { .scratchU32 = srt_inverse_scratch_u32, .launch = [](const StageCall& k) { launch_srt_inverse(k.s, k.st); return 0; } } },
+    { .id = KNZ_T_RLT, .fwd = { .launch = [](const StageCall& k) { launch_rlt_forward(k.s, k.st); return 0; } },
+                       .inv = { .launch = [](const StageCall& k) { launch_rlt_inverse(k.s, k.st); return 0; } } },
+    // LZ / LZX behind PACK would have to take PACK's data type (min match 6 for DNA, refusal of SMALL_ALPHABET, LZCodec.cpp:179-191);
+    // the device LZ stages do not read it yet, so such chains are refused rather than encoded differently from the reference. The
+    // inverse has one scratch (lzInvScratch, lz_inverse), so it runs on no decode lane.
+    { .id = KNZ_T_LZ, .ws = "lzScratch",
+      .fwd = { .wsBytes = [](int nb, u32 m) { return lz_forward_scratch_bytes(KNZ_T_LZ, nb, m); },
+               .launch = [](const StageCall& k) { return launch_lz_forward(k.s, k.st, KNZ_T_LZ, k.ws, k.wsBytes) ? failed(k, "LZ forward") : 0; } },
+      .inv = { .launch = lz_inverse },
+      .ignoresType = true, .lanes = false },
+    { .id = KNZ_T_LZX, .ws = "lzScratch",
+      .fwd = { .wsBytes = [](int nb, u32 m) { return lz_forward_scratch_bytes(KNZ_T_LZX, nb, m); },
+               .launch = [](const StageCall& k) { return launch_lz_forward(k.s, k.st, KNZ_T_LZX, k.ws, k.wsBytes) ? failed(k, "LZ forward") : 0; } },
+      .inv = { .launch = lz_inverse },
+      .ignoresType = true, .lanes = false },
+    { .id = KNZ_T_RANK, .fwd = { .launch = [](const StageCall& k) { launch_sbrt_forward(k.s, k.st, 2); return 0; } },
+                        .inv = { .launch = [](const StageCall& k) { launch_sbrt_inverse(k.s, k.st, 2); return 0; } } },
+    { .id = KNZ_T_TIMESTAMP, .fwd = { .launch = [](const StageCall& k) { launch_sbrt_forward(k.s, k.st, 3); return 0; } },
+                             .inv = { .launch = [](const StageCall& k) { launch_sbrt_inverse(k.s, k.st, 3); return 0; } } },
+    // (AliasCodec; the data type it starts from is preset from the block's magic or taken from the host stages, encode_impl)
+    { .id = KNZ_T_PACK, .ws = "packScratch",
+      .fwd = { .wsBytes = pack_scratch_bytes, .launch = [](const StageCall& k) { launch_pack_forward(k.s, k.st, k.ws); return 0; } },
+      .inv = { .wsBytes = pack_scratch_bytes, .launch = [](const StageCall& k) { launch_pack_inverse(k.s, k.st, k.ws); return 0; } },
+      .setsType = true },
+};
+
+static const XfInfo* xf_info(int t) { for (const XfInfo& x : XF) if (x.id == t) return &x; return nullptr; }
+
+static int unsupported(Ctx* c, int t) { return fail(c, KNZ_ERR_INVALID_CODEC, "transform id %d not implemented on device", t); }
+
+static size_t scratch_u32(const XfDir& d, int nBlocks, u32 maxLen) { return d.scratchU32 ? d.scratchU32(nBlocks, maxLen) : 0; }
+
+// A chain as a batch entry point takes it: the ids in stream order, and the table row of every stage the device runs (nullptr: NONE, or
+// one of the leading stages the host runs)
+struct Chain { int n = 0; int tok[8]; const XfInfo* xf[8]; };
+
+// The checks every batch entry point makes: the chain's ids (host stages first, device stages behind them), LZ / LZX behind PACK (encoding
+// only), the entropy id, the checksum width
+static int parse_chain(Ctx* c, const knz_params* p, int nHosted, bool encoding, Chain* ch)
+{
+    ch->n = count_transforms(p->transform_type, ch->tok);
+    if (nHosted < 0 || nHosted > ch->n) return fail(c, KNZ_ERR_INVALID_PARAM, "host stage count %d does not fit the chain", nHosted);
+    for (int i = 0; i < ch->n; i++) {
+        const int t = ch->tok[i];
+        ch->xf[i] = nullptr;
+        if (i < nHosted) { if (!host_stage_id(t)) return fail(c, KNZ_ERR_INVALID_CODEC, "transform id %d is no host stage", t); }
+        else if (t != KNZ_T_NONE && (ch->xf[i] = xf_info(t)) == nullptr) return unsupported(c, t);
+    }
+    for (int i = 0, typed = 0; encoding && i < ch->n; i++) {
+        if (ch->xf[i] == nullptr) continue;
+        if (typed && ch->xf[i]->ignoresType) return fail(c, KNZ_ERR_INVALID_CODEC, "LZ / LZX behind PACK is not implemented on device");
+        typed |= ch->xf[i]->setsType;
+    }
+    if (!entropy_supported(p->entropy_type)) return fail(c, KNZ_ERR_INVALID_CODEC, "entropy id %d not implemented on device", p->entropy_type);
+    if (p->checksum_bits != 0 && p->checksum_bits != 32 && p->checksum_bits != 64) return fail(c, KNZ_ERR_INVALID_PARAM, "checksum must be 0, 32 or 64");
+    return 0;
+}
+
+// buffer size of a block of n bytes: the largest any prefix of the chain may write (TransformSequence::getMaxEncodedLength)
+static int seq_required(const Chain& ch, int n)
+{
+    int req = n;
+    for (int i = 0; i < ch.n; i++) req = std::max(req, knz_max_encoded_len(ch.tok[i], req));
+    return req;
+}
+
+static size_t chain_scratch_u32(const Chain& ch, bool forward, int nBlocks, u32 maxLen)
+{
+    size_t most = 0;
+    for (int i = 0; i < ch.n; i++) if (ch.xf[i]) most = std::max(most, scratch_u32(forward ? ch.xf[i]->fwd : ch.xf[i]->inv, nBlocks, maxLen));
+    return most;
+}
+
+// part k of n parts of nBlocks blocks: runs of consecutive blocks, the first nBlocks % n one block longer
+static void cut(int nBlocks, int n, int k, int* first, int* count)
+{
+    *first = k * (nBlocks / n) + std::min(k, nBlocks % n);
+    *count = nBlocks / n + (k < nBlocks % n ? 1 : 0);
+}
+
+using PartFn = std::function<int(int, hipStream_t)>;
+
+// Parts 0..n-1 of one piece of work side by side: part 0 on `s`, part k on side stream k-1, which starts behind what is queued on `s`.
+// prepare(k, q) (optional: workspaces) runs for every part on the caller's thread, then run(k, q): there as well, or with `threads` on helper
+// thread k-1 for k >= 1. Every side stream is joined into `s` before the return, whatever failed; after a failure the streams are also
+// synchronised, so that no kernel is left running on a lane's workspaces when the caller releases the context. Returns the first failure.
+static int fork_join(Ctx* c, hipStream_t s, int n, bool threads, const PartFn& run, const PartFn& prepare = nullptr)
+{
+    if (n == 1) { const int r = prepare ? prepare(0, s) : 0; return r ? r : run(0, s); }
+    HIPCHK(c, hipSetDevice(c->device));                          // the side streams belong to the context's device
+    for (int k = 1; k < n; k++)
+        if (c->stream2[k - 1] == nullptr) HIPCHK(c, hipStreamCreateWithFlags(&c->stream2[k - 1], hipStreamNonBlocking));
+    for (hipEvent_t* e : { &c->evFork, &c->evJoin[0], &c->evJoin[1], &c->evJoin[2] })
+        if (*e == nullptr) HIPCHK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    const hipStream_t q[4] = { s, c->stream2[0], c->stream2[1], c->stream2[2] };
+    HIPCHK(c, hipEventRecord(c->evFork, s));
+    int rc = 0;
+    auto check = [&](hipError_t e, const char* what) { if (e != hipSuccess && rc == 0) rc = fail(c, -1, "%s failed: %s", what, hipGetErrorString(e)); };
+    for (int k = 1; k < n && rc == 0; k++) check(hipStreamWaitEvent(q[k], c->evFork, 0), "waiting for the fork");
+    for (int k = 0; k < n && rc == 0 && prepare; k++) rc = prepare(k, q[k]);
+    if (rc == 0 && !threads) {
+        for (int k = 0; k < n && rc == 0; k++) rc = run(k, q[k]);
+    } else if (rc == 0) {
+        int part[4] = { 0, 0, 0, 0 }, begun = 1;
+        try {
+            for (; begun < n; begun++)
+                c->helpers[begun - 1].run([&, k = begun] {
+                    part[k] = hipSetDevice(c->device) == hipSuccess ? run(k, q[k]) : fail(c, -1, "a helper thread cannot select the device");
+                });
+        } catch (...) {
+            rc = fail(c, -1, "cannot start a helper thread");
+        }
+        if (rc == 0) part[0] = run(0, s);
+        for (int k = 1; k < begun; k++) c->helpers[k - 1].wait();
+        for (int k = 0; k < n && rc == 0; k++) rc = part[k];
+    }
+    for (int k = 1; k < n; k++) {                                // `s` continues behind every side stream
+        hipError_t e = hipEventRecord(c->evJoin[k - 1], q[k]);
+        if (e == hipSuccess) e = hipStreamWaitEvent(s, c->evJoin[k - 1], 0);
+        check(e, "joining a side stream");
+    }
+    if (rc) for (int k = 0; k < n; k++) hipStreamSynchronize(q[k]);
+    return rc;
 }
 
 // The BWT stages of a batch in several parts at once. A suffix sort (and the inverse's list ranking) is a long sequence of launches
@@ -511,177 +700,30 @@ static int bwt_parts_wanted(const Ctx* c, int nBlocks)
     return parts;
 }
 
-static int bwt_in_parts(Ctx* c, hipStream_t s, const XfStage& st, int parts, const std::function<size_t(int)>& scratchBytes,
-                        const std::function<int(hipStream_t, const XfStage&, void*, size_t, u32*)>& launch, const char* what, bool needThreads)
+// One stage over the batch `st` on stream s. lane -1: a whole batch, which a stage that allows it runs as parts side by side (part k with
+// lane k's scratch and read-back area); lane k >= 0: decode lane k, not split further.
+static int run_stage(Ctx* c, hipStream_t s, const XfInfo& x, bool forward, const XfStage& st, int lane = -1)
 {
-    static const char* const wsName[4] = { "bwtScratch", "bwtScratch2", "bwtScratch3", "bwtScratch4" };
+    const XfDir& d = forward ? x.fwd : x.inv;
+    const int parts = (lane < 0 && d.split != NO_SPLIT) ? bwt_parts_wanted(c, st.nBlocks) : 1;
     XfStage part[4];
-    void* sc[4];
-    size_t bytes[4];
-    int first = 0;
+    void* ws[4] = { nullptr, nullptr, nullptr, nullptr };
+    size_t bytes[4] = { 0, 0, 0, 0 };
     for (int k = 0; k < parts; k++) {
-        const int nb = st.nBlocks / parts + (k < st.nBlocks % parts ? 1 : 0);
+        int first, nb;
+        cut(st.nBlocks, parts, k, &first, &nb);
         part[k] = st;
         part[k].nBlocks = nb;
         part[k].src += first; part[k].dst += first; part[k].len += first; part[k].cap += first; part[k].ok += first; part[k].newLen += first;
-        first += nb;
-        bytes[k] = scratchBytes(nb);
-        if (int r = ws_get(c, wsName[k], bytes[k], &sc[k])) return r;
     }
-    HIPCHK(c, hipSetDevice(c->device));                          // the extra streams belong to the context's device
-    for (int k = 1; k < parts; k++)
-        if (c->stream2[k - 1] == nullptr) HIPCHK(c, hipStreamCreateWithFlags(&c->stream2[k - 1], hipStreamNonBlocking));
-    if (c->evFork == nullptr) {
-        HIPCHK(c, hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming));
-        for (int k = 0; k < 3; k++) HIPCHK(c, hipEventCreateWithFlags(&c->evJoin[k], hipEventDisableTiming));
-    }
-    HIPCHK(c, hipEventRecord(c->evFork, s));                     // the other streams start behind what is queued on the first
-    for (int k = 1; k < parts; k++) HIPCHK(c, hipStreamWaitEvent(c->stream2[k - 1], c->evFork, 0));
-    int rc[4] = { 0, 0, 0, 0 };
-    if (!needThreads) {
-        // a stage that never waits for the device (the inverse): the caller's thread queues every part on its stream
-        for (int k = 0; k < parts; k++) rc[k] = launch(k ? c->stream2[k - 1] : s, part[k], sc[k], bytes[k], reinterpret_cast<u32*>(c->pinned) + 32768 * k);
-    } else {
-        try {
-            for (int k = 1; k < parts; k++)
-                c->helpers[k - 1].run([&, k] {
-                    if (hipSetDevice(c->device) != hipSuccess) { rc[k] = -1; return; }
-                    rc[k] = launch(c->stream2[k - 1], part[k], sc[k], bytes[k], reinterpret_cast<u32*>(c->pinned) + 32768 * k);   // own read-back area (the context's is 1 MiB)
-                });
-        } catch (...) {
-            for (int k = 1; k < parts; k++) c->helpers[k - 1].wait();
-            return fail(c, -1, "%s: cannot start a helper thread", what);
-        }
-        rc[0] = launch(s, part[0], sc[0], bytes[0], reinterpret_cast<u32*>(c->pinned));
-        for (int k = 1; k < parts; k++) c->helpers[k - 1].wait();
-    }
-    for (int k = 0; k < parts; k++) if (rc[k] != 0) return fail(c, -1, "%s failed: %s", what, hipGetErrorString(hipGetLastError()));
-    for (int k = 1; k < parts; k++) {                            // and the first stream continues behind the others
-        HIPCHK(c, hipEventRecord(c->evJoin[k - 1], c->stream2[k - 1]));
-        HIPCHK(c, hipStreamWaitEvent(s, c->evJoin[k - 1], 0));
-    }
-    return 0;
-}
-
-static int run_forward_stage(Ctx* c, hipStream_t s, int t, const XfStage& st)
-{
-    switch (t) {
-    case KNZ_T_ZRLT: launch_zrlt_forward(s, st); break;
-    case KNZ_T_MTFT: launch_mtft_forward(s, st); break;
-    case KNZ_T_SRT: launch_srt_forward(s, st); break;
-    case KNZ_T_RLT: launch_rlt_forward(s, st); break;
-    case KNZ_T_RANK: launch_sbrt_forward(s, st, 2); break;
-    case KNZ_T_TIMESTAMP: launch_sbrt_forward(s, st, 3); break;
-    case KNZ_T_LZ: case KNZ_T_LZX: {
-        const size_t bytes = lz_forward_scratch_bytes(t, st.nBlocks, st.maxLen);
-        void* sc;
-        if (int r = ws_get(c, "lzScratch", bytes, &sc)) return r;
-        if (launch_lz_forward(s, st, t, sc, bytes) != 0) return fail(c, -1, "LZ forward failed: %s", hipGetErrorString(hipGetLastError()));
-        break;
-    }
-    case KNZ_T_BWT: {
-        if (const int parts = bwt_parts_wanted(c, st.nBlocks); parts > 1)
-            return bwt_in_parts(c, s, st, parts, [&](int nb) { return bwt_forward_scratch_bytes(nb, st.maxLen, (size_t)nb * st.maxLen); },
-                                 [](hipStream_t q, const XfStage& h, void* sc, size_t bytes, u32* pin) { return launch_bwt_forward(q, h, sc, bytes, pin); }, "BWT forward", true);
-        const size_t bytes = bwt_forward_scratch_bytes(st.nBlocks, st.maxLen, (size_t)st.nBlocks * st.maxLen);
-        void* sc;
-        if (int r = ws_get(c, "bwtScratch", bytes, &sc)) return r;
-        if (launch_bwt_forward(s, st, sc, bytes, reinterpret_cast<u32*>(c->pinned)) != 0) return fail(c, -1, "BWT forward failed: %s", hipGetErrorString(hipGetLastError()));
-        break;
-    }
-    case KNZ_T_PACK: {
-        void* sc;
-        if (int r = ws_get(c, "packScratch", pack_scratch_bytes(st.nBlocks, st.maxLen), &sc)) return r;
-        launch_pack_forward(s, st, sc);
-        break;
-    }
-    case KNZ_T_BWTS: {
-        if (const int parts = bwt_parts_wanted(c, st.nBlocks); parts > 1)
-            return bwt_in_parts(c, s, st, parts, [&](int nb) { return bwts_forward_scratch_bytes(nb, st.maxLen, (size_t)nb * st.maxLen); },
-                                 [](hipStream_t q, const XfStage& h, void* sc, size_t bytes, u32* pin) { return launch_bwts_forward(q, h, sc, bytes, pin); }, "BWTS forward", true);
-        const size_t bytes = bwts_forward_scratch_bytes(st.nBlocks, st.maxLen, (size_t)st.nBlocks * st.maxLen);
-        void* sc;
-        if (int r = ws_get(c, "bwtScratch", bytes, &sc)) return r;
-        if (launch_bwts_forward(s, st, sc, bytes, reinterpret_cast<u32*>(c->pinned)) != 0) return fail(c, -1, "BWTS forward failed: %s", hipGetErrorString(hipGetLastError()));
-        break;
-    }
-    default: break;
-    }
-    return 0;
-}
-
-// lane >= 0: one part of a pipelined decode (decode_impl): the BWT inverse of the part is not split further and uses the scratch and the
-// read-back area of split part `lane`
-static int run_inverse_stage(Ctx* c, hipStream_t s, int t, const XfStage& st, int lane = -1)
-{
-    switch (t) {
-    case KNZ_T_ZRLT: launch_zrlt_inverse(s, st); break;
-    case KNZ_T_MTFT: launch_mtft_inverse(s, st); break;
-    case KNZ_T_SRT: launch_srt_inverse(s, st); break;
-    case KNZ_T_RLT: launch_rlt_inverse(s, st); break;
-    case KNZ_T_RANK: launch_sbrt_inverse(s, st, 2); break;
-    case KNZ_T_TIMESTAMP: launch_sbrt_inverse(s, st, 3); break;
-    case KNZ_T_PACK: {
-        static const char* const wsName[4] = { "packScratch", "packScratch2", "packScratch3", "packScratch4" };
-        void* sc;
-        if (int r = ws_get(c, wsName[lane < 0 ? 0 : (lane & 3)], pack_scratch_bytes(st.nBlocks, st.maxLen), &sc)) return r;
-        launch_pack_inverse(s, st, sc);
-        break;
-    }
-    case KNZ_T_LZ: case KNZ_T_LZX: {
-        void* sc = nullptr;
-        size_t bytes = 0;
-        if (st.maxCap != 0 && st.maxCap <= (1u << 30) && !lz_serial_decode(-1)) {
-            // about 20 bytes per output byte; when the device cannot spare that (1 GiB blocks, a 2 GiB batch), or the workspace would
-            // exceed the budget below, the blocks are decoded by the one-wave-per-block decoder, which needs no scratch
-            bytes = lz_inverse_scratch_bytes(st.nBlocks, st.maxCap);
-            static const size_t budget = getenv("KNZ_LZ_INV_SCRATCH_MAX") ? (size_t)atoll(getenv("KNZ_LZ_INV_SCRATCH_MAX")) : ((size_t)48 << 30);
-            WsBuf& wb = c->ws["lzInvScratch"];
-            if (bytes > budget) { bytes = 0; }
-            else if (wb.cap >= bytes) sc = wb.p;
-            else {
-                if (wb.p) { HIPCHK(c, hipFree(wb.p)); wb.p = nullptr; wb.cap = 0; }
-                const size_t want = bytes + (bytes >> 3) + 4096;
-                void* p = nullptr;
-                if (hipMalloc(&p, want) == hipSuccess) { wb.p = p; wb.cap = want; sc = p; }
-                else { (void)hipGetLastError(); bytes = 0; }           // out of memory: the serial decoder
-            }
-        }
-        launch_lz_inverse(s, st, sc, bytes, st.maxCap);
-        break;
-    }
-    case KNZ_T_BWT: {
-        if (lane < 0) {
-            if (const int parts = bwt_parts_wanted(c, st.nBlocks); parts > 1)
-                return bwt_in_parts(c, s, st, parts, [&](int nb) { return bwt_inverse_scratch_bytes(nb, st.maxLen, (size_t)nb * st.maxLen); },
-                                     [](hipStream_t q, const XfStage& h, void* sc, size_t bytes, u32* pin) { return launch_bwt_inverse(q, h, sc, bytes, pin); }, "BWT inverse", false);
-        }
-        static const char* const wsName[4] = { "bwtScratch", "bwtScratch2", "bwtScratch3", "bwtScratch4" };
-        const int k = lane < 0 ? 0 : (lane & 3);
-        const size_t bytes = bwt_inverse_scratch_bytes(st.nBlocks, st.maxLen, (size_t)st.nBlocks * st.maxLen);
-        void* sc;
-        if (int r = ws_get(c, wsName[k], bytes, &sc)) return r;
-        if (launch_bwt_inverse(s, st, sc, bytes, reinterpret_cast<u32*>(c->pinned) + 32768 * k) != 0) return fail(c, -1, "BWT inverse failed: %s", hipGetErrorString(hipGetLastError()));
-        break;
-    }
-    case KNZ_T_BWTS: {
-        // (the inverse reads convergence flags back every round: the parts of a split batch run on helper threads)
-        if (lane < 0) {
-            if (const int parts = bwt_parts_wanted(c, st.nBlocks); parts > 1)
-                return bwt_in_parts(c, s, st, parts, [&](int nb) { return bwts_inverse_scratch_bytes(nb, st.maxLen, (size_t)nb * st.maxLen); },
-                                     [](hipStream_t q, const XfStage& h, void* sc, size_t bytes, u32* pin) { return launch_bwts_inverse(q, h, sc, bytes, pin); }, "BWTS inverse", true);
-        }
-        static const char* const wsName[4] = { "bwtScratch", "bwtScratch2", "bwtScratch3", "bwtScratch4" };
-        const int k = lane < 0 ? 0 : (lane & 3);
-        const size_t bytes = bwts_inverse_scratch_bytes(st.nBlocks, st.maxLen, (size_t)st.nBlocks * st.maxLen);
-        void* sc;
-        if (int r = ws_get(c, wsName[k], bytes, &sc)) return r;
-        if (launch_bwts_inverse(s, st, sc, bytes, reinterpret_cast<u32*>(c->pinned) + 32768 * k) != 0) return fail(c, -1, "BWTS inverse failed: %s", hipGetErrorString(hipGetLastError()));
-        break;
-    }
-    default: break;
-    }
-    return 0;
+    auto at = [&](int k) { return lane < 0 ? k : lane; };      // the lane whose scratch and read-back area part k uses
+    return fork_join(c, s, parts, d.split == SPLIT_THREADS,
+                     [&](int k, hipStream_t q) { return d.launch({ c, q, part[k], ws[k], bytes[k], lane_pinned(c, at(k)) }); },
+                     [&](int k, hipStream_t q) {
+                         if (d.wsBytes == nullptr) return 0;
+                         bytes[k] = d.wsBytes(part[k].nBlocks, st.maxLen);
+                         return ws_get(c, lane_ws(x.ws, at(k)), bytes[k], &ws[k], q);
+                     });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -698,22 +740,10 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
         return fail(c, KNZ_ERR_INVALID_PARAM, "device buffers must be 16-byte aligned");
     const u32 bs = (u32)p->block_size;
     if (framing && (bs < 1024 || bs > (1u << 30) || (bs & 15))) return fail(c, KNZ_ERR_INVALID_PARAM, "invalid block size %u", bs);
-    int tok[8];
-    const int nTok = count_transforms(p->transform_type, tok);
+    Chain ch;
     const int nHosted = hs ? hs->stages : 0;
-    if (nHosted < 0 || nHosted > nTok) return fail(c, KNZ_ERR_INVALID_PARAM, "host stage count %d does not fit the chain", nHosted);
-    for (int i = 0; i < nTok; i++) {
-        if (i < nHosted) { if (!host_stage_id(tok[i])) return fail(c, KNZ_ERR_INVALID_CODEC, "transform id %d is no host stage", tok[i]); }
-        else if (!transform_supported(tok[i])) return fail(c, KNZ_ERR_INVALID_CODEC, "transform id %d not implemented on device", tok[i]);
-    }
-    // LZ / LZX behind PACK would have to take PACK's data type (min match 6 for DNA, refusal of SMALL_ALPHABET, LZCodec.cpp:179-191);
-    // the device LZ stages do not read it yet, so such chains are refused rather than encoded differently from the reference
-    for (int i = 0, pack = 0; i < nTok; i++) {
-        if (pack && (tok[i] == KNZ_T_LZ || tok[i] == KNZ_T_LZX)) return fail(c, KNZ_ERR_INVALID_CODEC, "LZ / LZX behind PACK is not implemented on device");
-        pack |= tok[i] == KNZ_T_PACK;
-    }
-    if (!entropy_supported(p->entropy_type)) return fail(c, KNZ_ERR_INVALID_CODEC, "entropy id %d not implemented on device", p->entropy_type);
-    if (p->checksum_bits != 0 && p->checksum_bits != 32 && p->checksum_bits != 64) return fail(c, KNZ_ERR_INVALID_PARAM, "checksum must be 0, 32 or 64");
+    if (int r = parse_chain(c, p, nHosted, true, &ch)) return r;
+    const int nTok = ch.n;
     hipStream_t s = c->stream;
 
     const int nBlocks = (n == 0) ? 0 : (int)((n + bs - 1) / bs);
@@ -729,13 +759,13 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
     const size_t needOut = ((size_t)prologueBits + 7) / 8 + 16;
     if (outCap < needOut) return fail(c, KNZ_ERR_WRITE_FILE, "output buffer too small");
     u64* d_total;
-    if (int r = ws_get(c, "total", 64, (void**)&d_total)) return r;
+    if (int r = ws_get(c, "total", 64, (void**)&d_total, s)) return r;
 
     if (nBlocks == 0) {
         HIPCHK(c, hipMemsetAsync(d_out, 0, needOut, s));
         if (prologueBits) {
             u8* d_pro;
-            if (int r = ws_get(c, "prologue", 256, (void**)&d_pro)) return r;
+            if (int r = ws_get(c, "prologue", 256, (void**)&d_pro, s)) return r;
             HIPCHK(c, hipMemcpyAsync(d_pro, prologue, (prologueBits + 7) / 8, hipMemcpyHostToDevice, s));
             launch_put_prologue(s, reinterpret_cast<u32*>(d_out), d_pro, prologueBits);
         }
@@ -746,23 +776,22 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
 
     // ---- block bookkeeping
     u32 *d_origLen; BlockInfo* d_info;
-    if (int r = ws_get(c, "origLen", sizeof(u32) * nBlocks, (void**)&d_origLen)) return r;
-    if (int r = ws_get(c, "info", sizeof(BlockInfo) * nBlocks, (void**)&d_info)) return r;
+    if (int r = ws_get(c, "origLen", sizeof(u32) * nBlocks, (void**)&d_origLen, s)) return r;
+    if (int r = ws_get(c, "info", sizeof(BlockInfo) * nBlocks, (void**)&d_info, s)) return r;
     const int maxIn = (int)((n < bs) ? n : bs);
-    const int required = seq_required(tok, nTok, maxIn);
+    const int required = seq_required(ch, maxIn);
     const u64 S = ((u64)required + 255) & ~255ull;
-    bool realStages = false;
-    size_t scratch = 0;
-    for (int i = 0; i < nTok; i++) if (tok[i] != KNZ_T_NONE) { realStages = true; const size_t q = (i < nHosted) ? 0 : stage_scratch_u32(tok[i], nBlocks, (u32)S); if (q > scratch) scratch = q; }
+    bool realStages = false, wantType = false;              // (wantType: a device stage reads the per-block data type)
+    for (int i = 0; i < nTok; i++) { realStages |= ch.tok[i] != KNZ_T_NONE; wantType |= ch.xf[i] && ch.xf[i]->setsType; }
     SeqWs w;
-    if (int r = seq_alloc(c, nBlocks, S, realStages, scratch, &w)) return r;
+    if (int r = seq_alloc(c, nBlocks, S, realStages, chain_scratch_u32(ch, true, nBlocks, (u32)S), &w, -1, s)) return r;
     w.a.origLen = d_origLen;
     const bool direct = !realStages && !p->checksum_bits;      // NullTransforms only: one bookkeeping launch
     if (!direct) launch_init_blocks(s, n, bs, nBlocks, d_origLen, w.a.len);
     // block checksums of the ORIGINAL bytes (io/CompressedOutputStream.cpp:675-682)
     u64* d_sums = nullptr;
     if (p->checksum_bits) {
-        if (int r = ws_get(c, "sums", sizeof(u64) * nBlocks, (void**)&d_sums)) return r;
+        if (int r = ws_get(c, "sums", sizeof(u64) * nBlocks, (void**)&d_sums, s)) return r;
         if (hs) {
             // (the checksum is the ORIGINAL block's: the host computed it before its stages ran)
             u64* hsum = reinterpret_cast<u64*>(c->pinned) + 512;
@@ -787,10 +816,10 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
             const int64_t gid = firstBlock + b;
             const int slot = (int)(gid % jobs);
             const u32 len = hs ? hs->orig_len : (u32)(((size_t)(b + 1) * bs <= n) ? bs : n - (size_t)b * bs);      // (the reference sizes its buffers by the block as read)
-            const u32 req = (u32)seq_required(tok, nTok, (int)len);
+            const u32 req = (u32)seq_required(ch, (int)len);
             // a slot's buffer is at least what a full block needed earlier on that slot
             u32 bufc = slotBuf[slot];
-            if (gid >= jobs) { const u32 full = (u32)seq_required(tok, nTok, (int)bs); if (bufc < full) bufc = full; }
+            if (gid >= jobs) { const u32 full = (u32)seq_required(ch, (int)bs); if (bufc < full) bufc = full; }
             if (bufc < req) bufc = req;
             slotBuf[slot] = bufc;
             u32 datac = (slot == 0) ? std::max(bs + (bs >> 3), 256u * 1024u) : std::max(bs + (bs >> 6), 65536u);
@@ -803,9 +832,7 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
         HIPCHK(c, hipStreamSynchronize(s));     // pinned scratch is reused below
     }
 
-    // ---- per-block data type (only PACK reads it): preset from the block's magic, or what the host stages left
-    bool wantType = false;
-    for (int i = nHosted; i < nTok; i++) wantType |= tok[i] == KNZ_T_PACK;
+    // ---- per-block data type: preset from the block's magic, or what the host stages left
     if (wantType) {
         if (hs) HIPCHK(c, hipMemsetAsync(w.a.dtype, hs->reserved <= 9 ? (int)hs->reserved : 0, (size_t)nBlocks, s));
         else launch_seq_fwd_dtype(s, w.a, nBlocks, d_in, bs);
@@ -819,15 +846,13 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
             launch_seq_fwd_hosted(s, w.a, nBlocks, i, (hs->applied_mask >> i) & 1u);
             continue;
         }
-        if (tok[i] == KNZ_T_NONE) {
+        if (ch.xf[i] == nullptr) {
             launch_seq_fwd_null(s, w.a, nBlocks, i);
             continue;
         }
-        XfStage st;
-        st.src = w.a.src; st.dst = w.a.dst; st.len = w.a.alen; st.cap = w.a.cap; st.ok = w.a.ok; st.newLen = w.a.newLen;
-        st.nBlocks = nBlocks; st.maxLen = (u32)S; st.scratchU32 = w.scratch; st.entropyType = p->entropy_type;
+        XfStage st = xf_stage(w, nBlocks, (u32)S, p->entropy_type);
         st.dtype = wantType ? w.a.dtype : nullptr;
-        if (int r = run_forward_stage(c, s, tok[i], st)) return r;
+        if (int r = run_stage(c, s, *ch.xf[i], true, st)) return r;
         launch_seq_fwd_commit(s, w.a, nBlocks, i);
     }
     if (!direct) launch_seq_fwd_finish(s, w.a, nBlocks, d_in, bs, w.A, w.B, S, w.d_viewPtr);
@@ -845,33 +870,33 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
     const int maxChunks = chunksPerBlock * (int)slotMul;
     const size_t nSlots = (size_t)nBlocks * maxChunks;
     ChunkDesc* d_desc; u8* d_tmp; uint2* d_encTab;
-    if (int r = ws_get(c, "desc", sizeof(ChunkDesc) * nSlots, (void**)&d_desc)) return r;
+    if (int r = ws_get(c, "desc", sizeof(ChunkDesc) * nSlots, (void**)&d_desc, s)) return r;
     if (p->entropy_type == KNZ_E_ANS0) {
-        if (int r = ws_get(c, "chunkTmp", (size_t)TMP_STRIDE * nSlots, (void**)&d_tmp)) return r;
-        if (int r = ws_get(c, "encTab", sizeof(uint2) * 256 * nSlots, (void**)&d_encTab)) return r;
+        if (int r = ws_get(c, "chunkTmp", (size_t)TMP_STRIDE * nSlots, (void**)&d_tmp, s)) return r;
+        if (int r = ws_get(c, "encTab", sizeof(uint2) * 256 * nSlots, (void**)&d_encTab, s)) return r;
         launch_ans0_encode(s, view, nBlocks, maxChunks, d_desc, d_encTab, d_tmp);
     } else if (ans1) {
         const size_t nCh = (size_t)nBlocks * chunksPerBlock;
         Ans1EncWs aw;
         aw.payStride = (2ull * std::min<u64>(S, ANS1_CHUNK) + 511) & ~255ull;
-        if (int r = ws_get(c, "ans1Hist", ans1_hist_bytes(nCh), (void**)&aw.hist)) return r;
-        if (int r = ws_get(c, "ans1EncTab", ans1_enctab_bytes(nCh), (void**)&aw.encTab)) return r;
-        if (int r = ws_get(c, "chunkTmp", (size_t)HDR_BYTES * nSlots, (void**)&d_tmp)) return r;
-        if (int r = ws_get(c, "ans1Pay", (size_t)aw.payStride * nCh, (void**)&aw.pay)) return r;
+        if (int r = ws_get(c, "ans1Hist", ans1_hist_bytes(nCh), (void**)&aw.hist, s)) return r;
+        if (int r = ws_get(c, "ans1EncTab", ans1_enctab_bytes(nCh), (void**)&aw.encTab, s)) return r;
+        if (int r = ws_get(c, "chunkTmp", (size_t)HDR_BYTES * nSlots, (void**)&d_tmp, s)) return r;
+        if (int r = ws_get(c, "ans1Pay", (size_t)aw.payStride * nCh, (void**)&aw.pay, s)) return r;
         aw.hdr = d_tmp;
         hdrStride = HDR_BYTES;
         launch_ans1_encode(s, view, nBlocks, chunksPerBlock, d_desc, aw);
     } else if (p->entropy_type == KNZ_E_HUFFMAN) {
-        if (int r = ws_get(c, "chunkTmp", (size_t)TMP_STRIDE * nSlots, (void**)&d_tmp)) return r;
+        if (int r = ws_get(c, "chunkTmp", (size_t)TMP_STRIDE * nSlots, (void**)&d_tmp, s)) return r;
         launch_huffman_encode(s, view, nBlocks, maxChunks, d_desc, d_tmp);
     } else if (p->entropy_type == KNZ_E_FPAQ) {
         const u64 fStride = (4u << 20) + (4u << 17) + 256;      // FPAQEncoder.cpp:65-68 buffer size (+ slack)
-        if (int r = ws_get(c, "chunkTmp", (size_t)fStride * nSlots, (void**)&d_tmp)) return r;
+        if (int r = ws_get(c, "chunkTmp", (size_t)fStride * nSlots, (void**)&d_tmp, s)) return r;
         u16* d_fprobs;
-        if (int r = ws_get(c, "fpaqProbs", fpaq_probs_bytes(nBlocks, S), (void**)&d_fprobs)) return r;
+        if (int r = ws_get(c, "fpaqProbs", fpaq_probs_bytes(nBlocks, S), (void**)&d_fprobs, s)) return r;
         launch_fpaq_encode(s, view, d_origLen, framing ? 15u : 0u, nBlocks, maxChunks, d_desc, d_tmp, fStride, d_fprobs, S);
     } else {
-        if (int r = ws_get(c, "chunkTmp", 64, (void**)&d_tmp)) return r;
+        if (int r = ws_get(c, "chunkTmp", 64, (void**)&d_tmp, s)) return r;
         launch_none_encode(s, view, nBlocks, maxChunks, d_desc);
     }
 
@@ -894,7 +919,7 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
     }
     if (prologueBits) {
         u8* d_pro;
-        if (int r = ws_get(c, "prologue", 256, (void**)&d_pro)) return r;
+        if (int r = ws_get(c, "prologue", 256, (void**)&d_pro, s)) return r;
         HIPCHK(c, hipMemcpyAsync(d_pro, prologue, (prologueBits + 7) / 8, hipMemcpyHostToDevice, s));
         launch_put_prologue(s, reinterpret_cast<u32*>(d_out), d_pro, prologueBits);
     }
@@ -941,20 +966,10 @@ static int decode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, uint64_
         return fail(c, KNZ_ERR_INVALID_PARAM, "device buffers must be 16-byte aligned");
     const u32 bs = (u32)p->block_size;
     if (framing && (bs < 1024 || bs > (1u << 30) || (bs & 15))) return fail(c, KNZ_ERR_INVALID_PARAM, "invalid block size %u", bs);
-    int tok[8];
-    const int nTok = count_transforms(p->transform_type, tok);
-    if (nHosted < 0 || nHosted > nTok) return fail(c, KNZ_ERR_INVALID_PARAM, "host stage count %d does not fit the chain", nHosted);
-    int tokAll[8];                                           // (the whole chain sizes the buffers, as in the encoder: a UTF stage adds 8 KiB of room)
-    for (int i = 0; i < nTok; i++) tokAll[i] = tok[i];
-    for (int i = 0; i < nTok; i++) {
-        if (i < nHosted) {
-            // the caller undoes these after the call: for the device they are stages that leave the data alone
-            if (!host_stage_id(tok[i])) return fail(c, KNZ_ERR_INVALID_CODEC, "transform id %d is no host stage", tok[i]);
-            tok[i] = KNZ_T_NONE;
-        } else if (!transform_supported(tok[i])) return fail(c, KNZ_ERR_INVALID_CODEC, "transform id %d not implemented on device", tok[i]);
-    }
-    if (!entropy_supported(p->entropy_type)) return fail(c, KNZ_ERR_INVALID_CODEC, "entropy id %d not implemented on device", p->entropy_type);
-    if (p->checksum_bits != 0 && p->checksum_bits != 32 && p->checksum_bits != 64) return fail(c, KNZ_ERR_INVALID_PARAM, "checksum must be 0, 32 or 64");
+    // (the host stages in front are undone by the caller after the call: for the device they are stages that leave the data alone)
+    Chain ch;
+    if (int r = parse_chain(c, p, nHosted, false, &ch)) return r;
+    const int nTok = ch.n;
     // bitstream version of the blocks (0 = current). Below 6 the Huffman chunks, the BWT block header and the LZ blocks have their
     // old layouts (HuffmanDecoder.cpp:349-459, BWTBlockCodec.cpp:140-164, LZCodec.cpp:614-760)
     const int bsVersion = (p->bs_version == 0) ? 6 : p->bs_version;
@@ -970,8 +985,8 @@ static int decode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, uint64_
     int64_t bound = framing ? (int64_t)(outCap / bs) + 2 : 1;
     if (maxBlocks > 0 && maxBlocks < bound) bound = maxBlocks;
     DecBlock* d_blocks; void* d_walk;
-    if (int r = ws_get(c, "decBlocks", sizeof(DecBlock) * (size_t)bound, (void**)&d_blocks)) return r;
-    if (int r = ws_get(c, "walk", 64, &d_walk)) return r;
+    if (int r = ws_get(c, "decBlocks", sizeof(DecBlock) * (size_t)bound, (void**)&d_blocks, s)) return r;
+    if (int r = ws_get(c, "walk", 64, &d_walk, s)) return r;
     launch_walk_blocks(s, src, startBit, bound, framing, rawLen, p->checksum_bits, bs, d_blocks, d_walk);
     WalkResultHost* h_walk = reinterpret_cast<WalkResultHost*>(c->pinned);
     HIPCHK(c, hipMemcpyAsync(h_walk, d_walk, sizeof(WalkResultHost), hipMemcpyDeviceToHost, s));
@@ -987,31 +1002,44 @@ static int decode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, uint64_
 
     // workspace stride: large enough for every valid preTransformLength of this chain
     const u32 unit = framing ? bs : rawLen;
-    const int required = seq_required(tokAll, nTok, (int)unit);
+    const int required = seq_required(ch, (int)unit);     // (the whole chain sizes the buffers, as in the encoder: a UTF stage adds 8 KiB of room)
     const u64 S = ((u64)required + 255) & ~255ull;
     const u32 maxPre = (u32)S;
-    bool realStages = false;
-    for (int i = 0; i < nTok; i++) if (tok[i] != KNZ_T_NONE) realStages = true;
     const int maxChunks = (int)((S + ENT_CHUNK - 1) / ENT_CHUNK);
     const u64 outStride = framing ? bs : 0;
-    u32 realMask = 0;
-    for (int i = 0; i < nTok; i++) if (tok[i] != KNZ_T_NONE) realMask |= 1u << (7 - i);
+    u32 realMask = 0;                                        // the device's stages
+    bool lanesOk = true;
+    for (int i = 0; i < nTok; i++) if (ch.xf[i]) { realMask |= 1u << (7 - i); lanesOk &= ch.xf[i]->lanes; }
+    const bool realStages = realMask != 0;
 
-    // One range of the batch's blocks through entropy decoder and inverse chain, on stream `sp` with the workspaces of lane `lane` (-1: the
-    // whole batch on the context's stream, the BWT inverse split into parts as before). The blocks are independent and the walk above has
-    // left every block's place in the stream in d_blocks, so a range is a smaller decode of its own: its entries of d_blocks, its part of
-    // the caller's output.
-    auto issue = [&](int lane, int b0, int nb, hipStream_t sp) -> int {
-        const std::string sfxS = lane <= 0 ? std::string() : std::string("#") + std::to_string(lane);
-        const char* sfx = sfxS.c_str();
-        auto wsName = [&](const char* base) { return std::string(base) + sfx; };
+    // Up to three ranges side by side (knob dec_parts / KNZ_DEC_PARTS, default 3, at least KNZ_DEC_PART_MIN = 2 blocks per range -- 7 blocks: decode
+    // 4.42 -> 4.04 ms; 4 blocks: no difference --; chains with inverse stages only; not
+    // while per-kernel timing is on, not for chains with a stage that has no lanes): the entropy decoders are chains with a few
+    // waves per CU and the row ranking of the BWT inverse is latency as well -- they run under the other ranges' bandwidth-bound kernels instead
+    // of in front of them. Measured (26 blocks of 8 MiB, 1 / 2 / 3 ranges): decode 9.96 / 9.76 / 9.63 ms on the stand-in, 10.49 / 10.17 / 9.86 on the
+    // real files; entropy-only chains (configs 1, 2) lose 2-5 % to the extra launches and stay one range.
+    int lanes = 1;
+    {
+        const int want = dec_parts_knob().load();
+        static const int least = [] { const char* e = getenv("KNZ_DEC_PART_MIN"); const int x = e ? atoi(e) : 2; return x < 1 ? 1 : x; }();      // fewest blocks per range
+        if (framing && realStages && !c->profiling && lanesOk && nHosted == 0 && want > 1) {
+            lanes = want > 3 ? 3 : want;
+            while (lanes > 1 && nBlocks < least * lanes) lanes--;
+        }
+    }
+
+    // Range k of the batch's blocks through entropy decoder and inverse chain, on stream `sp` with the workspaces of lane k (one range: lane
+    // -1, the whole batch, whose BWT inverse may be split into parts). The blocks are independent and the walk above has left every block's
+    // place in the stream in d_blocks, so a range is a smaller decode of its own: its entries of d_blocks, its part of the caller's output.
+    auto range = [&](int k, hipStream_t sp) -> int {
+        const int lane = lanes > 1 ? k : -1;
+        int b0, nb;
+        cut(nBlocks, lanes, k, &b0, &nb);
         DecBlock* blk = d_blocks + b0;
         uint8_t* out = d_out + (size_t)b0 * outStride;
         const u64 room = (u64)outCap - (u64)b0 * outStride;
-        size_t scratch = 0;
-        for (int i = 0; i < nTok; i++) if (tok[i] != KNZ_T_NONE) { const size_t q = stage_scratch_u32(tok[i], nb, (u32)S, false); if (q > scratch) scratch = q; }
         SeqWs w;
-        if (int r = seq_alloc(c, nb, S, realStages, scratch, &w, sfx)) return r;
+        if (int r = seq_alloc(c, nb, S, realStages, chain_scratch_u32(ch, false, nb, (u32)S), &w, lane, sp)) return r;
         const size_t nSlots = (size_t)nb * maxChunks;
         // entropy stage decodes into workspace A (or straight into the output when no transform applies)
         // with inverse stages the entropy decoder writes into the workspace (any valid preTransformLength fits);
@@ -1020,18 +1048,18 @@ static int decode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, uint64_
         launch_seq_inv_entropy_dst(sp, w.a, blk, nb, out, outStride, w.A, S, w.d_entDst, realMask, unit, room);
         if (p->entropy_type == KNZ_E_ANS0) {
             void* d_meta;
-            if (int r = ws_get(c, wsName("ansDecChunks").c_str(), ans0_dec_chunk_bytes() * nSlots, &d_meta)) return r;
+            if (int r = ws_get(c, lane_ws("ansDecChunks", lane), ans0_dec_chunk_bytes() * nSlots, &d_meta, sp)) return r;
             launch_ans0_decode(sp, src, blk, nb, maxChunks, d_meta, w.d_entDst);
         } else if (p->entropy_type == KNZ_E_ANS1) {
             const int chunksPerBlock = (int)((S + ANS1_CHUNK - 1) / ANS1_CHUNK);
             const size_t nCh = (size_t)nb * chunksPerBlock;
             Ans1DecWs aw;
-            if (int r = ws_get(c, wsName("ans1Meta").c_str(), ans1_meta_bytes(nCh), &aw.meta)) return r;
-            if (int r = ws_get(c, wsName("ans1SlotTab").c_str(), ans1_slottab_bytes(nCh), (void**)&aw.slotTab)) return r;
+            if (int r = ws_get(c, lane_ws("ans1Meta", lane), ans1_meta_bytes(nCh), &aw.meta, sp)) return r;
+            if (int r = ws_get(c, lane_ws("ans1SlotTab", lane), ans1_slottab_bytes(nCh), (void**)&aw.slotTab, sp)) return r;
             launch_ans1_decode(sp, src, blk, nb, chunksPerBlock, aw, w.d_entDst);
         } else if (p->entropy_type == KNZ_E_HUFFMAN) {
             void* d_meta;
-            if (int r = ws_get(c, wsName("hufDecChunks").c_str(), huffman_dec_chunk_bytes() * nSlots, &d_meta)) return r;
+            if (int r = ws_get(c, lane_ws("hufDecChunks", lane), huffman_dec_chunk_bytes() * nSlots, &d_meta, sp)) return r;
             launch_huffman_decode(sp, src, blk, nb, maxChunks, d_meta, w.d_entDst, bsVersion);
         } else if (p->entropy_type == KNZ_E_FPAQ) {
             launch_fpaq_decode(sp, src, blk, nb, w.d_entDst);
@@ -1044,62 +1072,24 @@ static int decode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, uint64_
             const u32 blkLenModel = std::max(bs + 512u, bs + (bs >> 4));
             const u32 capMid = framing ? (u32)std::min<u64>(S, blkLenModel) : (u32)p->jobs;
             for (int i = nTok - 1; i >= 0; i--) {
-                if (tok[i] == KNZ_T_NONE) continue;
+                if (ch.xf[i] == nullptr) continue;
                 launch_seq_inv_prepare(sp, w.a, blk, nb, i, out, outStride, w.A, w.B, S, capMid, capFinal, realMask, framing ? room : ~0ull);
-                XfStage st;
-                st.src = w.a.src; st.dst = w.a.dst; st.len = w.a.alen; st.cap = w.a.cap; st.ok = w.a.ok; st.newLen = w.a.newLen;
-                st.nBlocks = nb; st.maxLen = (u32)S; st.scratchU32 = w.scratch; st.entropyType = p->entropy_type; st.bsVersion = bsVersion;
+                XfStage st = xf_stage(w, nb, (u32)S, p->entropy_type);
+                st.bsVersion = bsVersion;
                 st.maxCap = std::max(capMid, capFinal);
-                if (int r = run_inverse_stage(c, sp, tok[i], st, lane)) return r;
-                launch_seq_inv_commit(sp, w.a, blk, nb, i, tok[i]);
+                if (int r = run_stage(c, sp, *ch.xf[i], false, st, lane)) return r;
+                launch_seq_inv_commit(sp, w.a, blk, nb, i, ch.tok[i]);
             }
         }
         if (p->checksum_bits && framing && nHosted == 0) {
             u64* d_sums;
-            if (int r = ws_get(c, wsName("sums").c_str(), sizeof(u64) * nb, (void**)&d_sums)) return r;
+            if (int r = ws_get(c, lane_ws("sums", lane), sizeof(u64) * nb, (void**)&d_sums, sp)) return r;
             launch_verify_checksums(sp, blk, nb, p->checksum_bits, out, outStride, w.d_viewPtr, w.a.alen, d_sums);
         }
         return 0;
     };
 
-    // Up to three ranges side by side (knob dec_parts / KNZ_DEC_PARTS, default 3, at least KNZ_DEC_PART_MIN = 2 blocks per range -- 7 blocks: decode
-    // 4.42 -> 4.04 ms; 4 blocks: no difference --; chains with inverse stages only; not
-    // while per-kernel timing is on, not for chains with an LZ stage, whose scratch has one name): the entropy decoders are chains with a few
-    // waves per CU and the row ranking of the BWT inverse is latency as well -- they run under the other ranges' bandwidth-bound kernels instead
-    // of in front of them. Measured (26 blocks of 8 MiB, 1 / 2 / 3 ranges): decode 9.96 / 9.76 / 9.63 ms on the stand-in, 10.49 / 10.17 / 9.86 on the
-    // real files; entropy-only chains (configs 1, 2) lose 2-5 % to the extra launches and stay one range.
-    int lanes = 1;
-    {
-        bool lz = false;
-        for (int i = 0; i < nTok; i++) if (tok[i] == KNZ_T_LZ || tok[i] == KNZ_T_LZX) lz = true;
-        const int want = dec_parts_knob().load();
-        static const int least = [] { const char* e = getenv("KNZ_DEC_PART_MIN"); const int x = e ? atoi(e) : 2; return x < 1 ? 1 : x; }();      // fewest blocks per range
-        if (framing && realStages && !c->profiling && !lz && nHosted == 0 && want > 1) {
-            lanes = want > 3 ? 3 : want;
-            while (lanes > 1 && nBlocks < least * lanes) lanes--;
-        }
-    }
-    if (lanes == 1) {
-        if (int r = issue(-1, 0, nBlocks, s)) return r;
-    } else {
-        for (int k = 1; k < lanes; k++)
-            if (c->stream2[k - 1] == nullptr) HIPCHK(c, hipStreamCreateWithFlags(&c->stream2[k - 1], hipStreamNonBlocking));
-        if (c->evFork == nullptr) {
-            HIPCHK(c, hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming));
-            for (int k = 0; k < 3; k++) HIPCHK(c, hipEventCreateWithFlags(&c->evJoin[k], hipEventDisableTiming));
-        }
-        HIPCHK(c, hipEventRecord(c->evFork, s));
-        int first = 0, rc = 0;
-        for (int k = 0; k < lanes; k++) {
-            const int nb = nBlocks / lanes + (k < nBlocks % lanes ? 1 : 0);
-            hipStream_t sp = k ? c->stream2[k - 1] : s;
-            if (k) HIPCHK(c, hipStreamWaitEvent(sp, c->evFork, 0));
-            if (rc == 0) rc = issue(k, first, nb, sp);
-            first += nb;
-            if (k) { HIPCHK(c, hipEventRecord(c->evJoin[k - 1], sp)); HIPCHK(c, hipStreamWaitEvent(s, c->evJoin[k - 1], 0)); }
-        }
-        if (rc) { hipStreamSynchronize(s); return rc; }
-    }
+    if (int r = fork_join(c, s, lanes, false, range)) return r;
     HIPCHK(c, hipGetLastError());
     // results
     std::vector<DecBlock> hb((size_t)nBlocks);
@@ -1160,8 +1150,8 @@ int knz_hip_entropy_encode(knz_ctx* ctx, int entropy_type, const uint8_t* in, ui
     p.entropy_type = entropy_type; p.block_size = (int32_t)((n + 15) & ~15u); p.transform_type = 0;
     u8 *d_in, *d_out;
     const size_t cap = knz_hip_encode_bound(&p, n);
-    if (int r = ws_get(c, "stageIn", (size_t)n + 64, (void**)&d_in)) return r;
-    if (int r = ws_get(c, "stageOut", cap, (void**)&d_out)) return r;
+    if (int r = ws_get(c, "stageIn", (size_t)n + 64, (void**)&d_in, c->stream)) return r;
+    if (int r = ws_get(c, "stageOut", cap, (void**)&d_out, c->stream)) return r;
     HIPCHK(c, hipMemcpyAsync(d_in, in, n, hipMemcpyHostToDevice, c->stream));
     u64 bits = 0;
     if (int r = encode_impl(c, &p, d_in, n, nullptr, 0, 0, 0, 0, d_out, cap, &bits)) return r;
@@ -1190,8 +1180,8 @@ int knz_hip_entropy_decode_v(knz_ctx* ctx, int entropy_type, int bs_version, con
     p.entropy_type = entropy_type; p.block_size = (int32_t)((n + 15) & ~15u); p.bs_version = bs_version;
     const size_t inBytes = (size_t)((in_bits + 7) >> 3);
     u8 *d_in, *d_out;
-    if (int r = ws_get(c, "stageIn", inBytes + 64, (void**)&d_in)) return r;
-    if (int r = ws_get(c, "stageOut", (size_t)n + 64, (void**)&d_out)) return r;
+    if (int r = ws_get(c, "stageIn", inBytes + 64, (void**)&d_in, c->stream)) return r;
+    if (int r = ws_get(c, "stageOut", (size_t)n + 64, (void**)&d_out, c->stream)) return r;
     HIPCHK(c, hipMemcpyAsync(d_in, in, inBytes, hipMemcpyHostToDevice, c->stream));
     u64 ob = 0;
     if (int r = decode_impl(c, &p, d_in, in_bits, start_bit, 1, 0, n, d_out, n, &ob, nullptr, nullptr, decoded, used_bits)) return r;
@@ -1208,17 +1198,18 @@ static int transform_host(Ctx* c, int t, int forward, const uint8_t* in, int32_t
     CTX_LOCK(c);
     ProfInstall pi_(c);
     *outLen = 0; *ok = 0;
-    if (!transform_supported(t) || t == KNZ_T_NONE) return fail(c, KNZ_ERR_INVALID_CODEC, "transform id %d not implemented on device", t);
+    const XfInfo* x = xf_info(t);
+    if (x == nullptr) return unsupported(c, t);
     if (n < 0 || dstCap < 0) return fail(c, KNZ_ERR_INVALID_PARAM, "negative size");
     if (n == 0) { *ok = 1; return 0; }
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const u32 maxLen = (u32)std::max(n, dstCap) + 2048;
     SeqWs w;
-    if (int r = seq_alloc(c, 1, maxLen, false, stage_scratch_u32(t, 1, maxLen, forward != 0), &w)) return r;
+    if (int r = seq_alloc(c, 1, maxLen, false, scratch_u32(forward ? x->fwd : x->inv, 1, maxLen), &w, -1, s)) return r;
     u8 *d_in, *d_out;
-    if (int r = ws_get(c, "stageIn", (size_t)n + 64, (void**)&d_in)) return r;
-    if (int r = ws_get(c, "stageOut", (size_t)maxLen + 64, (void**)&d_out)) return r;
+    if (int r = ws_get(c, "stageIn", (size_t)n + 64, (void**)&d_in, s)) return r;
+    if (int r = ws_get(c, "stageOut", (size_t)maxLen + 64, (void**)&d_out, s)) return r;
     HIPCHK(c, hipMemcpyAsync(d_in, in, (size_t)n, hipMemcpyHostToDevice, s));
     struct { const u8* src; u8* dst; u32 len; u32 cap; } h;
     h.src = d_in; h.dst = d_out; h.len = (u32)n; h.cap = (u32)dstCap;
@@ -1228,9 +1219,8 @@ static int transform_host(Ctx* c, int t, int forward, const uint8_t* in, int32_t
     HIPCHK(c, hipMemcpyAsync(w.a.cap, &h.cap, 4, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemsetAsync(w.a.ok, 0, 1, s));
     HIPCHK(c, hipMemsetAsync(w.a.newLen, 0, 4, s));
-    XfStage st;
-    st.src = w.a.src; st.dst = w.a.dst; st.len = w.a.alen; st.cap = w.a.cap; st.ok = w.a.ok; st.newLen = w.a.newLen;
-    st.nBlocks = 1; st.maxLen = (u32)n; st.scratchU32 = w.scratch; st.entropyType = etype; st.maxCap = (u32)dstCap;
+    XfStage st = xf_stage(w, 1, (u32)n, etype);
+    st.maxCap = (u32)dstCap;
     st.bsVersion = bsVersion;
     u8 hdt = 0;
     if (dataType) {
@@ -1239,7 +1229,7 @@ static int transform_host(Ctx* c, int t, int forward, const uint8_t* in, int32_t
         HIPCHK(c, hipMemcpyAsync(w.a.dtype, &hdt, 1, hipMemcpyHostToDevice, s));
         st.dtype = w.a.dtype;
     }
-    if (int r = forward ? run_forward_stage(c, s, t, st) : run_inverse_stage(c, s, t, st)) return r;
+    if (int r = run_stage(c, s, *x, forward != 0, st)) return r;
     HIPCHK(c, hipGetLastError());
     u8 hok = 0; u32 hlen = 0;
     HIPCHK(c, hipMemcpyAsync(&hok, w.a.ok, 1, hipMemcpyDeviceToHost, s));

@@ -5,6 +5,7 @@
 #include "kanzi_amd.hpp"
 #include "kanzi_api.h"
 #include "host_stages.hpp"
+#include "../csrc/max_encoded.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -413,17 +414,7 @@ DeviceTransform::DeviceTransform(int type, Context* ctx) : _type(type), _entropy
     deviceContext();        // fail early (and loudly) when there is no GPU
 }
 
-int DeviceTransform::getMaxEncodedLength(int n) const
-{
-    switch (_type) {
-    case KNZ_T_BWT: return n + 33;                      // BWTBlockCodec.hpp:47-50
-    case KNZ_T_SRT: return n + 1024;                    // SRT.hpp:38
-    case KNZ_T_PACK: return n + 1024;                   // AliasCodec.hpp:52-55
-    case KNZ_T_RLT: return (n <= 512) ? n + 32 : n;     // RLT.hpp:43
-    case KNZ_T_LZ: case KNZ_T_LZX: return ((n <= 1024) ? n + 16 : n + (n / 64)) + 2;    // LZCodec.hpp:91-95
-    default: return n;
-    }
-}
+int DeviceTransform::getMaxEncodedLength(int n) const { return knz_max_encoded_len(_type, n); }
 
 bool DeviceTransform::forward(SliceArray<byte>& src, SliceArray<byte>& dst, int length)
 {

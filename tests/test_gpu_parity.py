@@ -472,6 +472,38 @@ def test_decode_in_ranges_side_by_side(hip, oracle):
         L.knz_hip_tune(b"dec_parts", 3)
 
 
+def test_bwt_split_into_parts_gives_one_stream(hip, oracle):
+    """The BWT and BWTS stages of a batch run as 1 to 4 parts side by side (knob bwt_split, csrc/api.hip run_stage / fork_join: part k with a
+    stream, scratch and read-back area of its own). Whatever the number of parts, the stream is the expected one -- the oracle's for BWT,
+    the reference's for BWTS (tests/golden/bwts.json, "ranged") -- and decodes back to the input, as one range (whose inverse is split the
+    same way) and as three."""
+    import json
+    import bwts_cases
+    hipapi = importlib.import_module("kanzi_amd.hipapi")
+    L = hipapi.lib()
+    d = vectors.make(("mixed", 17 * 65536 + 12345, 41))
+    rc, want = oracle.compress(d, "BWT+MTFT+ZRLT", "ANS0", 65536, headerless=1)
+    assert rc == 0
+    rec = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bwts.json")))["ranged"]
+    ds = bwts_cases.make(rec["recipe"])
+    assert hashlib.md5(ds).hexdigest() == rec["input_md5"] and len(ds) == rec["n"]
+    try:
+        for parts in (1, 2, 3, 4):
+            assert L.knz_hip_tune(b"bwt_split", parts) == 0
+            out, bits, hb = gpu_compress(hip, d, "BWT+MTFT+ZRLT", "ANS0", 65536, headerless=1)
+            assert out == want, ("BWT", parts)
+            outs, bits, hbs = gpu_compress(hip, ds, rec["chain"], rec["entropy"], rec["block_size"], rec["checksum"], orig_size=rec["n"])
+            assert len(outs) == rec["knz_len"] and hashlib.md5(outs).hexdigest() == rec["knz_md5"], ("BWTS", parts)
+            for ranges in (1, 3):
+                assert L.knz_hip_tune(b"dec_parts", ranges) == 0
+                assert gpu_decompress(hip, out, "BWT+MTFT+ZRLT", "ANS0", 65536, len(d), 0) == d, ("BWT", parts, ranges)
+                back = gpu_decompress(hip, outs, rec["chain"], rec["entropy"], rec["block_size"], rec["n"], hbs, checksum=rec["checksum"])
+                assert back == ds, ("BWTS", parts, ranges)
+    finally:
+        L.knz_hip_tune(b"bwt_split", 3)
+        L.knz_hip_tune(b"dec_parts", 3)
+
+
 def test_suffix_sort_label_and_key_forms_give_one_stream(hip):
     """Round 6: the suffix sort keeps its labels as versioned 64-bit entries and refines small groups in one kernel (k_bwt_f_small_fused); blocks
     above 256 MiB use 32-bit labels with separate key kernels (KNZ_BWT_PLAIN_LABELS); the fused kernel ranks the members of a group on
