@@ -63,7 +63,7 @@ struct FwdView {
     u32* gbits;          // group-start bit per slot (bit k of word w = slot 32 w + k); set for every slot >= total
     u32* gnew;           // group starts found in the current round; merged into gbits when the round is over (a window must
                          // not see the subgroups a neighbouring window has just made: their keys belong to the old order)
-    u32* counters;       // [0] != 0: small groups are left, [1] medium descriptors, [2] large descriptors, [3] members of large groups
+    u32* counters;       // [64] words, the slots of FwdCounter
     const u32* ovr;      // [total] by slot: run length R of the members of a group the run round left unresolved (valid where rtbits is set)
     const u32* rtbits;   // bit per slot: the slot belongs to such a group. Its members are c^R followed by different things, so the key that
                          // tells them apart is the label R positions on -- the doubling rounds look there (at max(R, h)) instead of h positions
@@ -71,6 +71,31 @@ struct FwdView {
     uint2* medStage;     // medium groups found in the current round, one slot per 256 slots of SA (a medium group has more than 256
                          // members, so two of them never start in the same 256): written without atomics, compacted -- in slot order --
                          // into the next round's descriptor list by k_bwt_f_med_compact
+};
+
+// Slots of FwdView::counters. Slots 0-15 are zeroed in front of every doubling round and read back after it; the host reads its copy
+// slot for slot (FwdSort::fetch).
+enum FwdCounter : u32 {
+    CNT_SMALL_LEFT = 0,          // != 0: small groups are left
+    CNT_MED = 1,                 // medium descriptors (k_bwt_f_med_compact)
+    CNT_LARGE = 2,               // large descriptors
+    CNT_LARGE_MEMBERS = 3,       // members of large groups
+    CNT_RUN = 4,                 // run groups (round 0)
+    CNT_RUN_MEMBERS = 5,         // their members
+    CNT_RUN_LONGEST = 6,         // longest run (run round)
+    CNT_SUPER = 7,               // groups listed for the chain round (k_bwt_f_super)
+    CNT_RUNS = 8,                // runs of run-group bytes (run round)
+    CNT_STAT_SMALL = 10,         // small members worked on (knob bwt_stats)
+    CNT_STAT_SMALL_GROUPS = 11,  // small groups worked on (knob bwt_stats)
+    CNT_STAT_MED = 12,           // medium members worked on (knob bwt_stats)
+    CNT_TIED = 13,               // small members still tied after the round (the windows' counts summed)
+    CNT_PROBE_CAND = 14,         // after round 0, owned by the probe: candidates of k_bwt_f_probe (k_bwt_f_probe_scan)
+    CNT_LINKED = 14,             // in a doubling round, owned by the link step: members linked (k_bwt_f_link_payoff)
+    CNT_LINK_TIED = 15,          // link step: members of the linked windows still tied after the round
+    CNT_ROUND_SLOTS = 16,
+    CNT_PROBE_SLOTS = 2,         // slots 0-1 (CNT_SMALL_LEFT, CNT_MED): what the probe zeroes, recounts and reads back
+    CNT_LONGEST_BLOCK = 32,      // longest block the transform applies to (k_bwt_bases)
+    CNT_NSYM = 33,               // round-0 key length the entropy asks for (k_bwt_f_choose_nsym)
 };
 
 // ---- labels --------------------------------------------------------------------------------------------------------------------------
@@ -104,6 +129,13 @@ __device__ __forceinline__ u32 lab_cur(const FwdView& v, u32 q, u32 bb)
 __device__ __forceinline__ void lab_set(const FwdView& v, u32 p, u32 bb, u32 lab, u32 was)
 {
     if (v.ISA2 == nullptr) { v.ISA[p] = lab; return; }
+#ifdef KNZ_EMU
+    // `was` must be the label the position had when the round began (the placing kernels pass the group's first slot)
+    if (v.round != 0 && lab_old(v, p, bb) != was) {
+        fprintf(stderr, "lab_set: round %u position %u: was %u, label %u\n", v.round, p, was, lab_old(v, p, bb));
+        abort();
+    }
+#endif
     const u64 nw = (u64)(lab - bb), ow = (v.round == 0) ? nw : (u64)(was - bb);
     v.ISA2[p] = nw | (ow << LAB_BITS) | ((u64)v.round << 56);
 }
@@ -117,9 +149,9 @@ __device__ __forceinline__ u32 gather_key(const FwdView& v, u32 gp, u32 h, u32 b
 __device__ __forceinline__ void classify_child(const FwdView& v, uint2* __restrict__ medNext, uint2* __restrict__ largeNext, u32 start, u32 size, u32& surv)
 {
     if (size > MED_CAP) {
-        const u32 at = atomicAdd(&v.counters[2], 1u);
+        const u32 at = atomicAdd(&v.counters[CNT_LARGE], 1u);
         largeNext[at] = make_uint2(start, size);
-        atomicAdd(&v.counters[3], size);
+        atomicAdd(&v.counters[CNT_LARGE_MEMBERS], size);
     } else if (size > SM_G) {
         v.medStage[start >> 8] = make_uint2(start, size);
     } else if (size > 1) {
@@ -150,8 +182,8 @@ __device__ __forceinline__ int agg_note(ClassAgg& A, u32 size, bool run, u32& su
 // one thread, between two barriers
 __device__ __forceinline__ void agg_reserve(ClassAgg& A, const FwdView& v)
 {
-    if (A.cnt[1]) { A.base[1] = atomicAdd(&v.counters[2], A.cnt[1]); atomicAdd(&v.counters[3], A.elems[1]); }
-    if (A.cnt[2]) { A.base[2] = atomicAdd(&v.counters[4], A.cnt[2]); atomicAdd(&v.counters[5], A.elems[2]); }
+    if (A.cnt[1]) { A.base[1] = atomicAdd(&v.counters[CNT_LARGE], A.cnt[1]); atomicAdd(&v.counters[CNT_LARGE_MEMBERS], A.elems[1]); }
+    if (A.cnt[2]) { A.base[2] = atomicAdd(&v.counters[CNT_RUN], A.cnt[2]); atomicAdd(&v.counters[CNT_RUN_MEMBERS], A.elems[2]); }
 }
 
 __device__ __forceinline__ void agg_write(const ClassAgg& A, const FwdView& v, int kind, u32 local, u32 start, u32 size, uint2* __restrict__ largeNext,
@@ -621,7 +653,7 @@ __global__ __launch_bounds__(256) void k_bwt_f_r0_place_text(BwtView bv, FwdView
             hKind[k] = agg_note(A, size, runGroup, surv, hLocal[k]);
         }
     }
-    if (__ballot(surv != 0) != 0 && (tid & 63) == 0) v.counters[0] = 1;
+    if (__ballot(surv != 0) != 0 && (tid & 63) == 0) v.counters[CNT_SMALL_LEFT] = 1;
     __syncthreads();
     if (tid == 0) agg_reserve(A, v);
     __syncthreads();
@@ -654,7 +686,7 @@ __global__ __launch_bounds__(256) void k_bwt_f_gather_small(FwdView v, u32 h, in
         u32 off = h;
         if ((sRt[i >> 5] >> (i & 31)) & 1u) { const u32 r = v.ovr[slot]; off = r > h ? r : h; }
         v.K[slot] = gather_key(v, v.SA[slot], off, v.base[b], v.base[b + 1]);
-        if (stats) { atomicAdd(&v.counters[10], 1u); if (i == s) atomicAdd(&v.counters[11], 1u); }      // (developer statistics, knob bwt_stats)
+        if (stats) { atomicAdd(&v.counters[CNT_STAT_SMALL], 1u); if (i == s) atomicAdd(&v.counters[CNT_STAT_SMALL_GROUPS], 1u); }      // (developer statistics, knob bwt_stats)
     }
 }
 
@@ -706,7 +738,7 @@ __global__ __launch_bounds__(256) void k_bwt_f_sort_small(FwdView v, u32* __rest
         // members that are still tied, per window (summed by a scan: the host decides by their number whether the next round looks for
         // links first; one counter for all windows would be an atomic per wave on one address)
         const u32 ws = wave_sum(surv);
-        if ((threadIdx.x & 63) == 0) { sWs[threadIdx.x >> 6] = ws; if (ws) v.counters[0] = 1; }
+        if ((threadIdx.x & 63) == 0) { sWs[threadIdx.x >> 6] = ws; if (ws) v.counters[CNT_SMALL_LEFT] = 1; }
     }
     __syncthreads();
     if (threadIdx.x == 0 && survTile) survTile[blockIdx.x] = sWs[0] + sWs[1] + sWs[2] + sWs[3];
@@ -757,7 +789,7 @@ __global__ __launch_bounds__(256) void k_bwt_f_small_fused(FwdView v, u32 h, u32
         sSA[i] = gp;
         const u32 key = gather_key(v, gp, off, bb[k], v.base[b + 1]);
         sK[i] = PACKED ? ((key << 8) | (i - gs[k])) : key;
-        if (stats) { atomicAdd(&v.counters[10], 1u); if (i == gs[k]) atomicAdd(&v.counters[11], 1u); }      // (developer statistics, knob bwt_stats)
+        if (stats) { atomicAdd(&v.counters[CNT_STAT_SMALL], 1u); if (i == gs[k]) atomicAdd(&v.counters[CNT_STAT_SMALL_GROUPS], 1u); }      // (developer statistics, knob bwt_stats)
     }
     __syncthreads();
     u32 surv = 0;
@@ -801,7 +833,7 @@ __global__ __launch_bounds__(256) void k_bwt_f_small_fused(FwdView v, u32 h, u32
     }
     {
         const u32 ws = wave_sum(surv);
-        if ((threadIdx.x & 63) == 0) { sWs[threadIdx.x >> 6] = ws; if (ws) v.counters[0] = 1; }
+        if ((threadIdx.x & 63) == 0) { sWs[threadIdx.x >> 6] = ws; if (ws) v.counters[CNT_SMALL_LEFT] = 1; }
     }
     __syncthreads();
     if (threadIdx.x == 0 && survTile) survTile[blockIdx.x] = sWs[0] + sWs[1] + sWs[2] + sWs[3];
@@ -1009,7 +1041,7 @@ __global__ __launch_bounds__(GATHER_THREADS) void k_bwt_f_gather_desc(FwdView v,
         u32 off = h;                                        // (uniform for the group)
         if (v.rtbits && ((v.rtbits[d.x >> 5] >> (d.x & 31)) & 1u)) { const u32 r = v.ovr[d.x]; off = r > h ? r : h; }
         // (block base, label the members carry): what the sorting kernel needs per group without a chain of dependent loads of its own
-        if (threadIdx.x == 0) { descInfo[g] = make_uint2(bb, lab_old(v, v.SA[d.x], bb)); if (stats) atomicAdd(&v.counters[12], d.y); }
+        if (threadIdx.x == 0) { descInfo[g] = make_uint2(bb, lab_old(v, v.SA[d.x], bb)); if (stats) atomicAdd(&v.counters[CNT_STAT_MED], d.y); }
         // eight members per thread at a time: all position loads, then all key loads, then the stores -- two memory
         // latencies per batch instead of two per member
         for (u32 i0 = 0; i0 < d.y; i0 += 8 * GATHER_THREADS) {
@@ -1204,7 +1236,7 @@ __device__ __forceinline__ void med_write_back(MedLds<THREADS, ROWS>& L, const F
             for (int r = 0; r < ROWS; r++) if (r == row) { hSize[r] = size; hKind[r] = agg_note(A, size, false, surv, hLocal[r]); }
         }
     }
-    if (__ballot(surv != 0) != 0 && lane == 0) v.counters[0] = 1;
+    if (__ballot(surv != 0) != 0 && lane == 0) v.counters[CNT_SMALL_LEFT] = 1;
     __syncthreads();
     if (tid == 0) agg_reserve(A, v);
     __syncthreads();
@@ -1265,7 +1297,7 @@ __device__ __forceinline__ void med_majority_write_back(MedLds<THREADS, ROWS>& L
             else if (size > 1) surv = 1;
         }
     }
-    if (__ballot(surv != 0) != 0 && (tid & 63) == 0) v.counters[0] = 1;
+    if (__ballot(surv != 0) != 0 && (tid & 63) == 0) v.counters[CNT_SMALL_LEFT] = 1;
 }
 
 // One workgroup refines one group of 257..ROWS*THREADS members (descriptors of other sizes are left to the other
@@ -1310,7 +1342,7 @@ __global__ __launch_bounds__(THREADS, (THREADS >= 1024 ? 4 : THREADS / 128)) voi
         c = med_block_sum(L, c);
         if (c < n && 2 * c >= n && n <= SUPER_CAP && m == info.y - info.x + 1u) {
             // the majority looks at the group itself (a periodic stretch whose period divides h): k_bwt_f_super finishes it in one round
-            if (tid == 0) { const u32 at = atomicAdd(&v.counters[7], 1u); superList[at] = make_uint4(gs, n, info.x, info.y); }
+            if (tid == 0) { const u32 at = atomicAdd(&v.counters[CNT_SUPER], 1u); superList[at] = make_uint4(gs, n, info.x, info.y); }
             __syncthreads();
             continue;
         }
@@ -1426,7 +1458,7 @@ __global__ __launch_bounds__(1024) void k_bwt_f_super(FwdView v, const uint4* __
     __shared__ u32 sCmax;
     const int tid = (int)threadIdx.x, lane = tid & 63;
     const unsigned long long ltMask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    const u32 nList = v.counters[7];
+    const u32 nList = v.counters[CNT_SUPER];
     for (u32 g = blockIdx.x; g < nList; g += gridDim.x) {
         const uint4 d = superList[g];
         const u32 gs = d.x, n = d.y;                       // 256 < n <= CAP
@@ -1571,7 +1603,7 @@ constexpr u32 PROBE_PMAX = 2048;
 // period-256 stretches the text comparison costs 3.4 ms and saves 1.7. Any other period never meets h.)
 __global__ __launch_bounds__(256) void k_bwt_f_probe_scan(FwdView v, const uint2* __restrict__ desc, u32 depth, const u32* __restrict__ rtbits, u32* __restrict__ cand)
 {
-    const u32 nDesc = v.counters[1];
+    const u32 nDesc = v.counters[CNT_MED];
     for (u32 g = blockIdx.x * 256 + threadIdx.x; g < nDesc; g += gridDim.x * 256) {
         const uint2 d = desc[g];
         const u32 gs = d.x, n = d.y;
@@ -1579,7 +1611,7 @@ __global__ __launch_bounds__(256) void k_bwt_f_probe_scan(FwdView v, const uint2
         if (rtbits != nullptr && ((rtbits[gs >> 5] >> (gs & 31)) & 1u)) continue;         // (groups of the run round know their offset already)
         const u32 a0 = v.SA[gs + (n >> 1) - 2], a1 = v.SA[gs + (n >> 1) - 1], a2 = v.SA[gs + (n >> 1)], a3 = v.SA[gs + (n >> 1) + 1];
         const u32 pd = a2 - a1;
-        if ((a1 - a0 == pd) && (a3 - a2 == pd) && (pd > depth) && (pd <= 2048u) && ((pd & (pd - 1)) != 0)) cand[atomicAdd(&v.counters[14], 1u)] = g;
+        if ((a1 - a0 == pd) && (a3 - a2 == pd) && (pd > depth) && (pd <= 2048u) && ((pd & (pd - 1)) != 0)) cand[atomicAdd(&v.counters[CNT_PROBE_CAND], 1u)] = g;
     }
 }
 
@@ -1758,7 +1790,7 @@ __global__ __launch_bounds__(256) void k_bwt_f_large_place(FwdView v, const uint
             hKind = agg_note(A, hSize, false, surv, hLocal);
         }
     }
-    if (__ballot(surv != 0) != 0 && (threadIdx.x & 63) == 0) v.counters[0] = 1;
+    if (__ballot(surv != 0) != 0 && (threadIdx.x & 63) == 0) v.counters[CNT_SMALL_LEFT] = 1;
     __syncthreads();
     if (threadIdx.x == 0) agg_reserve(A, v);
     __syncthreads();
@@ -1883,7 +1915,7 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_len(BwtView bv, FwdView v, co
     }
     rmax = wave_max(rmax);
     // longest run: sizes the key of the run-length sort (read first: one atomic per wave on one address would serialise the launch)
-    if ((tid & 63) == 0 && rmax > __atomic_load_n(&v.counters[6], __ATOMIC_RELAXED)) atomicMax(&v.counters[6], rmax);
+    if ((tid & 63) == 0 && rmax > __atomic_load_n(&v.counters[CNT_RUN_LONGEST], __ATOMIC_RELAXED)) atomicMax(&v.counters[CNT_RUN_LONGEST], rmax);
 }
 
 // the run groups as ordinary groups (when the run-length round cannot take them)
@@ -2089,7 +2121,7 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_place(FwdView v, const uint2*
             hKind = agg_note(A, hSize, false, surv, hLocal);
         }
     }
-    if (__ballot(surv != 0) != 0 && (tid & 63) == 0) v.counters[0] = 1;
+    if (__ballot(surv != 0) != 0 && (tid & 63) == 0) v.counters[CNT_SMALL_LEFT] = 1;
     __syncthreads();
     if (tid == 0) agg_reserve(A, v);
     __syncthreads();
@@ -2308,124 +2340,178 @@ size_t bwt_forward_scratch_bytes(int nBlocks, u32 VS, size_t total)
 
 #define GRID1(n) dim3((unsigned)(((n) + 255) / 256)), dim3(256), 0, s
 
-// Returns 0 or a negative HIP error. Synchronises the stream (the sizes of the work lists are read back per round).
-// sa == nullptr: the BWT block codec (emits header + BWT bytes). Otherwise the suffix arrays only, left in the scratch (bwt_suffix_arrays).
-static int bwt_forward_run(hipStream_t s, const XfStage& st, void* scratch, size_t scratchBytes, u32* h_pinned, BwtSuffixArrays* sa)
-{
-    BwtView bv; bv.src = st.src; bv.dst = st.dst; bv.len = st.len; bv.cap = st.cap; bv.VS = st.maxLen; bv.nBlocks = st.nBlocks;
-    const size_t maxTotal = (size_t)st.nBlocks * bv.VS;
-    FwdScratch w;
-    if (fwd_carve(reinterpret_cast<u8*>(scratch), st.nBlocks, maxTotal, &w, bv.VS) > scratchBytes) return -2;
+static int bits_for(u64 n, int lo) { while ((1ull << lo) < n) lo++; return lo; }     // the least b >= lo with 2^b >= n
+
+// When the link step (k_bwt_f_link_small) runs, once the rounds are past the depth where most ties are chance. Whether it pays is a
+// property of the data (it does where groups are whole repeats: copied spans, files that hold a part twice; it does not where every group
+// has members that leave it one by one, as in the file mix of config 9): the first application, at h = 32, is a trial; what it linked
+// against what was still tied after the round decides whether the rounds that follow apply it too, and every application is judged again.
+// The trial is made on the windows of up to THREE WHOLE BLOCKS of the batch, the first, the middle and the last one (a run never leaves its
+// block, so a block's runs are complete; a sample of windows all over the batch would cut every run), and must pay in each of them: 0.15 ms
+// per 8 MiB where the step applied to a 212 MB batch costs 2-4 ms. (Round 5 looked at the first block only: in the real-file corpus that
+// is one shared object, the trial said yes, and the application to the whole batch cost 3.5 ms for 1.7 ms of later rounds.)
+struct LinkPlan {
+    enum Mode { UNTRIED, TRIAL, ON, APPLIED, OFF } mode = UNTRIED;     // TRIAL, APPLIED: the step ran in the round before, to be judged
+    int trials = 0; u32 retryH = 0xFFFFFFFFu;
+    // judges the previous application by its payoff (members linked, their windows' members still tied) and decides this round's (true: run)
+    bool next(u32 h, u32 survMembers, u32 total, u32 linked, u32 tied, bool stats)
+    {
+        if (mode == TRIAL || mode == APPLIED) {
+            const bool paid = linked >= 4096 && tied < linked / 2;
+            mode = paid ? ON : OFF;
+            if (!paid) retryH = (trials < 2) ? h * 8 : 0xFFFFFFFFu;    // (chance ties of the early rounds may have hidden the repeats: once more, three rounds on)
+            if (stats) fprintf(stderr, "link step: %u members linked, %u of the windows' members still tied after the round -> %s\n", linked, tied, paid ? "on" : "off");
+        }
+        if (mode == OFF && h >= retryH) mode = UNTRIED;
+        if (mode == UNTRIED && survMembers >= total / 8) { mode = TRIAL; trials++; return true; }
+        if (mode == ON && survMembers >= total / 64) { mode = APPLIED; return true; }
+        return false;
+    }
+};
+
+// One forward suffix sort, phase by phase (bwt_forward_run). A phase that reads the counters back (fetch) synchronises the stream: the
+// phases after it size their launches by what came back.
+struct FwdSort {
+    hipStream_t s; const XfStage& st; u32* hp;            // hp: host copy of the counters, slot for slot (word 0: `total`, after the set-up)
     const FwdTuning tune = fwd_tuning();
-    { KScope ks_("k_bwt_f_bases"); hipLaunchKernelGGL(k_bwt_bases, dim3(1), dim3(64), 0, s, bv, w.base, st.ok, w.counters + 32, sa ? 1 : 0); }
-    hipMemsetAsync(st.newLen, 0, sizeof(u32) * st.nBlocks, s);
-    { KScope ks_("k_bwt_f_r0_hist");                                // byte histograms: the key length of round 0, later its digit counts
-      hipMemsetAsync(w.byteHist, 0, 1024ull * st.nBlocks, s);
-      hipLaunchKernelGGL(k_bwt_f_bytehist, dim3(64, (unsigned)st.nBlocks), dim3(256), 0, s, bv, w.base, w.byteHist);
-      hipLaunchKernelGGL(k_bwt_f_choose_nsym, dim3(1), dim3(256), 0, s, w.byteHist, st.nBlocks, w.counters + 32, w.counters + 33); }
-    if (hipMemcpyAsync(h_pinned, w.base + st.nBlocks, 4, hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
-    if (hipMemcpyAsync(h_pinned + 1, w.counters + 32, 8, hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
-    if (hipStreamSynchronize(s) != hipSuccess) return -1;
-    const u32 total = h_pinned[0];
-    if (sa) { sa->SA = w.SA; sa->base = w.base; sa->total = total; }
-    if (total == 0) return 0;
-    FwdView v; v.base = w.base; v.nBlocks = st.nBlocks; v.total = total; v.SA = w.SA; v.ISA = w.ISA; v.K = w.K; v.ISA2 = (w.ISA2 != nullptr && !tune.plainLabels) ? w.ISA2 : (u64*)nullptr; v.round = 0; v.gbits = w.gbits; v.gnew = w.gnew; v.counters = w.counters; v.medStage = w.medStage; v.ovr = nullptr; v.rtbits = nullptr;
-    const u32 medSlots = (u32)((size_t)total / 256 + 1);
-    hipMemsetAsync(w.medStage, 0, 8ull * w.medSlots, s);
-    // the medium groups staged by the kernels of a round -> descriptor list `dst` (in slot order) and counters[1]
-    auto compactMedium = [&](uint2* dst) {
+    BwtView bv; FwdView v; FwdScratch w; size_t maxTotal;
+    prims::RsWs rs1;                                       // the single-segment sorts of the rounds: [0, seg2[1])
+    u32 total, medSlots, nTiles; int nsym, pbits, kbits;   // (tiles: windows of SM_TS slots)
+    u32 h = 1; int cur = 0;                                // offset of the doubling round; its lists w.med[cur], w.large[cur] (the next round's: cur ^ 1)
+    u64 *keysFree, *keysFree2;                             // key buffers of the rounds (keysFree2: round 0's sorted keys until they are placed)
+    u32 nRun, runElems, surv, nMed, nLarge, largeElems, survMembers;   // run groups of round 0 and their members; left: small groups (!= 0),
+                                                                       // medium and large groups, large members, small members still tied
+    LinkPlan link; LinkTrial linkTr; std::chrono::steady_clock::time_point statT;
+    // counters [first, first + n) -> hp[first, first + n), then the stream synchronised
+    int fetch(u32 first, u32 n) { return hipMemcpyAsync(hp + first, w.counters + first, 4 * (size_t)n, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess ? 0 : -1; }
+    void merge_bits() { hipLaunchKernelGGL(k_bwt_f_merge_bits, GRID1(total / 32 + 2), w.gbits, w.gnew, total / 32 + 2); }
+    // the doubling rounds look max(R, h) positions on for the members of a group the run round left (FwdView::ovr, rtbits)
+    void enable_run_tiebits() { if (!v.rtbits) { hipMemsetAsync(w.rtbits, 0, 4 * w.gbitsWords, s); v.ovr = w.ovr; v.rtbits = w.rtbits; } }
+    // the medium groups staged by the kernels of a round -> descriptor list `dst` (in slot order) and CNT_MED
+    void compact_medium(uint2* dst)
+    {
         KScope ks_("k_bwt_f_med_compact");
         hipLaunchKernelGGL(k_bwt_f_med_flags, GRID1(medSlots), w.medStage, medSlots, w.medFlags);
-        prims::launch_scan<prims::SCAN_SUM_EXCL>(s, w.medFlags, w.medPrefix, medSlots, nullptr, w.scanTmp, w.counters + 1);
+        prims::launch_scan<prims::SCAN_SUM_EXCL>(s, w.medFlags, w.medPrefix, medSlots, nullptr, w.scanTmp, w.counters + CNT_MED);
         hipLaunchKernelGGL(k_bwt_f_med_compact, GRID1(medSlots), w.medStage, medSlots, w.medPrefix, dst);
-    };
-
-    // ---- round 0: the suffixes of every block sorted by their first nsym symbols. Keys = [nsym bytes | position in the block];
-    // one stable LSD pass per symbol, the first one reads the text, the blocks are the segments of the sort.
-    int pbits = 1;
-    while ((1ull << pbits) < (u64)h_pinned[1]) pbits++;           // positions inside the longest block the transform applies to
-    // Four or five symbols (as many as fit the key beside the position when the block is larger than 8 / 16 MiB), by the batch's order-0
-    // entropy (k_bwt_f_choose_nsym). Measured on 212 MB with 8 MiB blocks, MB/s of the whole round trip, round 3: 4 symbols 4437 (mixed
-    // stand-in) / 3859 (text); 5 symbols with h = 5, 10, ...: 4243 / 4155; 5 symbols with h = 4, 8, ...: 4319 / 3970. Round 4 (the
-    // doubling offsets stay 4, 8, ...): 4 symbols 5034 / 4314, 5 symbols 4961 / 4564 -- text likes the deeper first round, the stand-in
-    // (periodic and sparse stretches, noise) gains nothing from it and pays the fifth pass.
-    const int fit = (64 - pbits) / 8;
-    const int want = (h_pinned[2] == 5u) ? 5 : 4;                   // (k_bwt_f_choose_nsym: the batch's order-0 entropy)
-    int nsym = fit < want ? fit : want;
-    if (tune.nsym >= 1) nsym = tune.nsym < fit ? tune.nsym : fit;   // tuning knob: other round-0 key lengths
-    if (nsym < 1) return -4;
-    prims::RsWs rs = prims::rs_carve(w.rsMem, maxTotal, st.nBlocks + 1, w.base, st.nBlocks);
-    { KScope ks_("k_bwt_f_r0_layout"); prims::rs_launch_layout(s, rs); }
-    u64* kin = w.keysA; u64* kout = w.keysB;
-    const bool oneRead = prims::rs_onesweep_knob().load() != 0 && nsym <= prims::RS_MAXPASS
-                         && (size_t)bv.VS < (size_t)prims::RS_VAL_MASK;   // 30-bit counts in the look-back words (a 1 GiB block: count + scatter)
-    if (oneRead) {                                                // the digits of all passes counted from the text, once
-        KScope ks_("k_bwt_f_r0_sort");
-        hipLaunchKernelGGL(k_bwt_f_r0_counts, dim3((unsigned)rs.L.nSeg), dim3(256), 0, s, bv, w.base, w.byteHist, nsym, rs.L);
-        hipLaunchKernelGGL(prims::k_rs_digit_bases, dim3((unsigned)rs.L.nSeg, (unsigned)nsym), dim3(256), 0, s, rs.L);
     }
-    for (int pass = 0; pass < nsym; pass++) {
-        KScope ks_("k_bwt_f_r0_sort");
-        if (pass == 0) {
-            TextSrc src; src.src = bv.src; src.P = nsym; src.pbits = pbits; src.shift = pbits;
-            if (oneRead) prims::rs_launch_pass_os<u64, false>(s, rs, src, (const u32*)nullptr, kout, (u32*)nullptr, (size_t)bv.VS, pass);
-            else prims::rs_launch_pass<u64, false>(s, rs, src, (const u32*)nullptr, kout, (u32*)nullptr, (size_t)bv.VS);
-        } else {
-            prims::DigitOfKey<u64> src; src.keys = kin; src.shift = pbits + 8 * pass; src.mask = 255u;
-            if (oneRead) prims::rs_launch_pass_os<u64, false>(s, rs, src, (const u32*)nullptr, kout, (u32*)nullptr, (size_t)bv.VS, pass);
-            else prims::rs_launch_pass<u64, false>(s, rs, src, (const u32*)nullptr, kout, (u32*)nullptr, (size_t)bv.VS);
+    // running maximum of t0 into t1 (the last group start at or before an element; `last`) and running minimum of t2 into t3 (the first
+    // one at or after it, mirrored) over n values; with a bit map over `len` elements, t0 / t2 are first taken per window of `wordsPerWin` words
+    void bounds(u32 n, bool last, const u32* bits = nullptr, u32 len = 0, u32 wordsPerWin = 0)
+    {
+        if (bits) { KScope ks_("k_bwt_f_r0_winsum"); hipLaunchKernelGGL(k_bwt_f_r0_winsum, GRID1(n), bits, len, n, w.t0, w.t2, wordsPerWin); }
+        if (last) { KScope ks_("k_bwt_f_scan_max"); prims::launch_scan<prims::SCAN_MAX_INCL>(s, w.t0, w.t1, n, nullptr, w.scanTmp); }
+        KScope ks_("k_bwt_f_scan_min"); prims::launch_scan<prims::SCAN_MIN_INCL>(s, w.t2, w.t3, n, nullptr, w.scanTmp);
+    }
+    // a sort of n keys as one segment; 0: the result is in (ka, va), 1: in (kb, vb)
+    template <class KEY, bool HAS_VAL> int sort_one_segment(u32 n, KEY* ka, KEY* kb, u32* va, u32* vb, int loBit, int hiBit, bool oneRead = true)
+    {
+        hipLaunchKernelGGL(prims::k_rs_one_segment, dim3(1), dim3(64), 0, s, w.seg2, n);
+        prims::rs_launch_layout(s, rs1);
+        return prims::rs_sort<KEY, HAS_VAL>(s, rs1, ka, kb, va, vb, (size_t)n, loBit, hiBit, oneRead);
+    }
+    // bases of the blocks, byte histograms and the round-0 key length; `total` read back (0: nothing to sort)
+    int setup(void* scratch, size_t scratchBytes, BwtSuffixArrays* sa)
+    {
+        bv.src = st.src; bv.dst = st.dst; bv.len = st.len; bv.cap = st.cap; bv.VS = st.maxLen; bv.nBlocks = st.nBlocks;
+        maxTotal = (size_t)st.nBlocks * bv.VS;
+        if (fwd_carve(reinterpret_cast<u8*>(scratch), st.nBlocks, maxTotal, &w, bv.VS) > scratchBytes) return -2;
+        { KScope ks_("k_bwt_f_bases"); hipLaunchKernelGGL(k_bwt_bases, dim3(1), dim3(64), 0, s, bv, w.base, st.ok, w.counters + CNT_LONGEST_BLOCK, sa ? 1 : 0); }
+        hipMemsetAsync(st.newLen, 0, sizeof(u32) * st.nBlocks, s);
+        { KScope ks_("k_bwt_f_r0_hist");                                // byte histograms: the key length of round 0, later its digit counts
+          hipMemsetAsync(w.byteHist, 0, 1024ull * st.nBlocks, s);
+          hipLaunchKernelGGL(k_bwt_f_bytehist, dim3(64, (unsigned)st.nBlocks), dim3(256), 0, s, bv, w.base, w.byteHist);
+          hipLaunchKernelGGL(k_bwt_f_choose_nsym, dim3(1), dim3(256), 0, s, w.byteHist, st.nBlocks, w.counters + CNT_LONGEST_BLOCK, w.counters + CNT_NSYM); }
+        if (hipMemcpyAsync(hp, w.base + st.nBlocks, 4, hipMemcpyDeviceToHost, s) != hipSuccess || fetch(CNT_LONGEST_BLOCK, 2)) return -1;
+        total = hp[0];
+        if (sa) { sa->SA = w.SA; sa->base = w.base; sa->total = total; }
+        if (total == 0) return 0;
+        v.base = w.base; v.nBlocks = st.nBlocks; v.total = total; v.SA = w.SA; v.ISA = w.ISA; v.K = w.K; v.ISA2 = (w.ISA2 != nullptr && !tune.plainLabels) ? w.ISA2 : (u64*)nullptr;
+        v.round = 0; v.gbits = w.gbits; v.gnew = w.gnew; v.counters = w.counters; v.medStage = w.medStage; v.ovr = nullptr; v.rtbits = nullptr;
+        medSlots = (u32)((size_t)total / 256 + 1); nTiles = (total + SM_TS - 1) / SM_TS;
+        survMembers = total;                                          // (not counted before the first round: assume many)
+        hipMemsetAsync(w.medStage, 0, 8ull * w.medSlots, s);
+        pbits = bits_for(hp[CNT_LONGEST_BLOCK], 1);                   // positions inside the longest block the transform applies to
+        // Four or five symbols (as many as fit the key beside the position when the block is larger than 8 / 16 MiB), by the batch's order-0
+        // entropy (k_bwt_f_choose_nsym). Measured on 212 MB with 8 MiB blocks, MB/s of the whole round trip, round 3: 4 symbols 4437 (mixed
+        // stand-in) / 3859 (text); 5 symbols with h = 5, 10, ...: 4243 / 4155; 5 symbols with h = 4, 8, ...: 4319 / 3970. Round 4 (the
+        // doubling offsets stay 4, 8, ...): 4 symbols 5034 / 4314, 5 symbols 4961 / 4564 -- text likes the deeper first round, the stand-in
+        // (periodic and sparse stretches, noise) gains nothing from it and pays the fifth pass.
+        const int fit = (64 - pbits) / 8, want = (hp[CNT_NSYM] == 5u) ? 5 : 4;
+        nsym = fit < want ? fit : want;
+        if (tune.nsym >= 1) nsym = tune.nsym < fit ? tune.nsym : fit;   // tuning knob: other round-0 key lengths
+        if (nsym < 1) return -4;
+        // The doubling starts at the largest power of two the round-0 depth covers (groups and labels of depth nsym >= h are what a round
+        // with offset h needs): h = 4, 8, 16, ... meets the periods real data has (record and row sizes are powers of two more often than
+        // not), which is what lets the chain round (k_bwt_f_super) see a group look at itself.
+        while (2 * h <= (u32)nsym) h <<= 1;
+        return 0;
+    }
+    // Round 0: the suffixes of every block sorted by their first nsym symbols. Keys = [nsym bytes | position in the block]; one stable LSD
+    // pass per symbol, the first one reads the text, the blocks are the segments of the sort.
+    void round0_sort()
+    {
+        const prims::RsWs rs = prims::rs_carve(w.rsMem, maxTotal, st.nBlocks + 1, w.base, st.nBlocks);
+        rs1 = prims::rs_carve(w.rsMem, maxTotal, st.nBlocks + 1, w.seg2, 1);
+        { KScope ks_("k_bwt_f_r0_layout"); prims::rs_launch_layout(s, rs); }
+        u64* kin = w.keysA; u64* kout = w.keysB;
+        const bool oneRead = prims::rs_onesweep_knob().load() != 0 && nsym <= prims::RS_MAXPASS
+                             && (size_t)bv.VS < (size_t)prims::RS_VAL_MASK;   // 30-bit counts in the look-back words (a 1 GiB block: count + scatter)
+        if (oneRead) {                                                // the digits of all passes counted from the text, once
+            KScope ks_("k_bwt_f_r0_sort");
+            hipLaunchKernelGGL(k_bwt_f_r0_counts, dim3((unsigned)rs.L.nSeg), dim3(256), 0, s, bv, w.base, w.byteHist, nsym, rs.L);
+            hipLaunchKernelGGL(prims::k_rs_digit_bases, dim3((unsigned)rs.L.nSeg, (unsigned)nsym), dim3(256), 0, s, rs.L);
         }
-        std::swap(kin, kout);
+        auto sortPass = [&](const auto& src, int pass) {
+            if (oneRead) prims::rs_launch_pass_os<u64, false>(s, rs, src, nullptr, kout, nullptr, (size_t)bv.VS, pass);
+            else prims::rs_launch_pass<u64, false>(s, rs, src, nullptr, kout, nullptr, (size_t)bv.VS);
+        };
+        for (int pass = 0; pass < nsym; pass++) {
+            KScope ks_("k_bwt_f_r0_sort");
+            if (pass == 0) { TextSrc src; src.src = bv.src; src.P = nsym; src.pbits = pbits; src.shift = pbits; sortPass(src, pass); }
+            else { prims::DigitOfKey<u64> src; src.keys = kin; src.shift = pbits + 8 * pass; src.mask = 255u; sortPass(src, pass); }
+            std::swap(kin, kout);
+        }
+        keysFree = kout; keysFree2 = kin;                             // (the last pass wrote into what is now `kin`)
     }
-    const u64* sortedKeys = kin;                                  // (the last pass wrote into what is now `kin`)
-    u64* keysFree = kout;                                         // scratch for the rounds that follow
-    u64* keysFree2 = const_cast<u64*>(sortedKeys);                // free again once r0_place has read it
-    // every bit from `total` on is set (end sentinel, and windows may look past the end)
-    hipMemsetAsync(w.gbits, 0xFF, 4 * w.gbitsWords, s);
-    hipMemsetAsync(w.gnew, 0, 4 * w.gbitsWords, s);
-    hipMemsetAsync(w.counters, 0, 64, s);
-    { KScope ks_("k_bwt_f_r0_flags"); hipLaunchKernelGGL(k_bwt_f_r0_flags, dim3((total + 256 * R0F_ROWS - 1) / (256 * R0F_ROWS)), dim3(256), 0, s, sortedKeys, w.base, st.nBlocks, total, nsym, pbits,
-                                                         reinterpret_cast<unsigned long long*>(w.gbits)); }
-    // group starts before / after every window of SM_TS slots (the windows of the placement): two scans over ~total/1792 values
-    const u32 nWinP = (total + SM_TS - 1) / SM_TS;
-    { KScope ks_("k_bwt_f_r0_winsum"); hipLaunchKernelGGL(k_bwt_f_r0_winsum, GRID1(nWinP), w.gbits, total, nWinP, w.t0, w.t2, SM_TS / 32); }
-    { KScope ks_("k_bwt_f_scan_max"); prims::launch_scan<prims::SCAN_MAX_INCL>(s, w.t0, w.t1, nWinP, nullptr, w.scanTmp); }
-    { KScope ks_("k_bwt_f_scan_min"); prims::launch_scan<prims::SCAN_MIN_INCL>(s, w.t2, w.t3, nWinP, nullptr, w.scanTmp); }
-    int cur = 0;
-    int kbits = 1;
-    while ((1ull << kbits) < (u64)bv.VS + 2) kbits++;
-    // the run-length round needs descriptor index + (kbits + 1) + kbits bits in one 64-bit key
-    // (2 * kbits + 1 >= 64 needs VS >= 2^31 - 1: no block of an encode, only a per-stage call, knz_hip_transform_forward, with n or dst_cap
-    // that close to 2 GiB)
-    const bool runRound = (2 * kbits + 1) < 64 && !tune.noRunRound;
-    { KScope ks_("k_bwt_f_r0_place");
-      hipLaunchKernelGGL(k_bwt_f_r0_place_text, dim3(nWinP), dim3(256), 0, s, bv, v, w.t1, w.t3, nWinP, w.large[cur], sortedKeys, nsym, pbits, runRound ? w.runList : (uint2*)nullptr);
-      hipLaunchKernelGGL(k_bwt_f_merge_bits, GRID1(total / 32 + 2), w.gbits, w.gnew, total / 32 + 2); }
-    if (hipMemcpyAsync(h_pinned, w.counters, 64, hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
-    if (hipStreamSynchronize(s) != hipSuccess) return -1;
-    u32 nRun = h_pinned[4], runElems = h_pinned[5];
-    bool medCompacted = false;
-    const int maxKeyBits = 2 * kbits + 1;
-    if (nRun && ((u64)nRun > (1ull << (64 - maxKeyBits)) || tune.runFallback)) {     // (the knob: tests force this path)
-        // more run groups than the key has index bits left for (thousands of blocks in one batch): they go the ordinary way
+    // Round 0's groups from its sorted keys: the small ones refined on the text behind the key, the others listed, the run groups apart
+    int round0_place()
+    {
+        // every bit from `total` on is set (end sentinel, and windows may look past the end)
+        hipMemsetAsync(w.gbits, 0xFF, 4 * w.gbitsWords, s); hipMemsetAsync(w.gnew, 0, 4 * w.gbitsWords, s);
+        hipMemsetAsync(w.counters, 0, 4 * CNT_ROUND_SLOTS, s);
+        { KScope ks_("k_bwt_f_r0_flags"); hipLaunchKernelGGL(k_bwt_f_r0_flags, dim3((total + 256 * R0F_ROWS - 1) / (256 * R0F_ROWS)), dim3(256), 0, s, keysFree2, w.base, st.nBlocks, total, nsym, pbits,
+                                                             reinterpret_cast<unsigned long long*>(w.gbits)); }
+        // group starts before / after every window of SM_TS slots (the windows of the placement): two scans over ~total/1792 values
+        bounds(nTiles, true, w.gbits, total, SM_TS / 32);
+        kbits = bits_for((u64)bv.VS + 2, 1);
+        // the run-length round needs descriptor index + (kbits + 1) + kbits bits in one 64-bit key
+        // (2 * kbits + 1 >= 64 needs VS >= 2^31 - 1: no block of an encode, only a per-stage call, knz_hip_transform_forward, with n or dst_cap
+        // that close to 2 GiB)
+        const bool runRound = (2 * kbits + 1) < 64 && !tune.noRunRound;
+        { KScope ks_("k_bwt_f_r0_place");
+          hipLaunchKernelGGL(k_bwt_f_r0_place_text, dim3(nTiles), dim3(256), 0, s, bv, v, w.t1, w.t3, nTiles, w.large[cur], keysFree2, nsym, pbits, runRound ? w.runList : (uint2*)nullptr);
+          merge_bits(); }
+        if (fetch(0, CNT_ROUND_SLOTS)) return -1;
+        nRun = hp[CNT_RUN]; runElems = hp[CNT_RUN_MEMBERS];
+        return 0;
+    }
+    // the run groups go the ordinary way (the medium and large lists)
+    int run_fallback()
+    {
         { KScope ks_("k_bwt_f_run_fallback"); hipLaunchKernelGGL(k_bwt_f_run_fallback, GRID1(nRun), v, w.runList, nRun, w.med[cur], w.large[cur]); }
-        if (hipMemcpyAsync(h_pinned, w.counters, 64, hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
-        if (hipStreamSynchronize(s) != hipSuccess) return -1;
-        nRun = 0;
+        nRun = 0; return fetch(0, CNT_ROUND_SLOTS);
     }
-    // candidates for k_bwt_f_probe among the medium groups of the list just compacted (their number comes back with the counters)
-    u32* probeCand = w.medFlags;                                  // (free between two compactions)
-    auto probeScan = [&]() {
-        KScope ks_("k_bwt_f_probe");
-        hipLaunchKernelGGL(k_bwt_f_probe_scan, dim3(256), dim3(256), 0, s, v, w.med[cur], (u32)nsym, v.rtbits, probeCand);
-    };
-    prims::RsWs rs1 = prims::rs_carve(w.rsMem, maxTotal, st.nBlocks + 1, w.seg2, 1);     // single-segment sorts of the rounds: [0, seg2[1])
-    if (nRun) {
-        // run lengths of every position (text order), then one sort of the run groups' members on (run length, what follows)
+    // Run round: the run groups of round 0 (4 equal symbols) in one round by run length: the run lengths of every position (text order),
+    // the runs sorted, then one sort of the members on (run length, what follows)
+    int run_round()
+    {
+        // more run groups than the key has index bits left for (thousands of blocks in one batch; the knob: tests force this path)
+        if (nRun && ((u64)nRun > (1ull << (64 - (2 * kbits + 1))) || tune.runFallback) && run_fallback()) return -1;
+        if (!nRun) return 0;
         const u32 nWin = (total + SM_WIN - 1) / SM_WIN;          // (windows of 2048 positions)
-        { KScope ks_("k_bwt_f_run_ends"); hipLaunchKernelGGL(k_bwt_f_run_ends, dim3((total + SM_WIN - 1) / SM_WIN), dim3(256), 0, s, bv, v, reinterpret_cast<u8*>(w.ebits)); }
-        { KScope ks_("k_bwt_f_r0_winsum"); hipLaunchKernelGGL(k_bwt_f_r0_winsum, GRID1(nWin), w.ebits, total, nWin, w.t0, w.t2, SM_WIN / 32); }
-        { KScope ks_("k_bwt_f_scan_min"); prims::launch_scan<prims::SCAN_MIN_INCL>(s, w.t2, w.t3, nWin, nullptr, w.scanTmp); }
+        { KScope ks_("k_bwt_f_run_ends"); hipLaunchKernelGGL(k_bwt_f_run_ends, dim3(nWin), dim3(256), 0, s, bv, v, reinterpret_cast<u8*>(w.ebits)); }
+        bounds(nWin, false, w.ebits, total, SM_WIN / 32);
         // run lengths of every position, and the starts of the runs of run-group bytes as a bit map
         hipMemsetAsync(w.classTab, 0xFF, 1024ull * (size_t)st.nBlocks, s);
         { KScope ks_("k_bwt_f_run_classes"); hipLaunchKernelGGL(k_bwt_f_run_classes, GRID1(nRun), bv, v, w.runList, nRun, w.classTab); }
@@ -2433,255 +2519,198 @@ static int bwt_forward_run(hipStream_t s, const XfStage& st, void* scratch, size
                                                             reinterpret_cast<unsigned long long*>(w.rbits), w.rcount); }
         // the runs themselves, compacted in position order (the windows of k_bwt_f_run_len cover whole words up to nWin * 2048)
         const u32 nRW = nWin * (SM_WIN / 32);
-        { KScope ks_("k_bwt_f_scan_sum"); prims::launch_scan<prims::SCAN_SUM_EXCL>(s, w.rcount, w.rprefix, nRW, nullptr, w.scanTmp, w.counters + 8); }
+        { KScope ks_("k_bwt_f_scan_sum"); prims::launch_scan<prims::SCAN_SUM_EXCL>(s, w.rcount, w.rprefix, nRW, nullptr, w.scanTmp, w.counters + CNT_RUNS); }
         { KScope ks_("k_bwt_f_run_compact"); hipLaunchKernelGGL(k_bwt_f_run_compact, GRID1(nRW), w.rbits, w.rprefix, nRW, w.runPos); }
-        if (hipMemcpyAsync(h_pinned + 8, w.counters + 6, 12, hipMemcpyDeviceToHost, s) != hipSuccess) return -1;     // longest run, -, number of runs
-        if (hipStreamSynchronize(s) != hipSuccess) return -1;
-        const u32 nRuns = h_pinned[10];
-        int hbits = 1;
-        while ((1ull << hbits) < (u64)h_pinned[8] + 1) hbits++;
-        hbits++;                                                  // both halves of the order: R and 2^hbits - 1 - R
-        const int keyBits = hbits + kbits;
-        int rbits = 0;
-        while ((1u << rbits) < nRun) rbits++;
-        int idxBits = 1;
-        while ((1ull << idxBits) < (u64)nRuns) idxBits++;
-        if (nRuns == 0 || nRuns > w.maxRuns || rbits + hbits > 32 || idxBits + kbits + 1 + rbits > 64) {
-            // more runs than the tables hold (a round-0 key shorter than 4 symbols) or fields that do not fit their words: the run groups
-            // go the ordinary way
-            { KScope ks_("k_bwt_f_run_fallback"); hipLaunchKernelGGL(k_bwt_f_run_fallback, GRID1(nRun), v, w.runList, nRun, w.med[cur], w.large[cur]); }
-            if (hipMemcpyAsync(h_pinned, w.counters, 64, hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
-            if (hipStreamSynchronize(s) != hipSuccess) return -1;
-            nRun = 0;
-        }
-      if (nRun) {
+        if (fetch(CNT_RUN_LONGEST, 3)) return -1;
+        const u32 nRuns = hp[CNT_RUNS];
+        const int hbits = bits_for((u64)hp[CNT_RUN_LONGEST] + 1, 1) + 1;     // (+ 1: both halves of the order: R and 2^hbits - 1 - R)
+        const int rbits = bits_for(nRun, 0), idxBits = bits_for(nRuns, 1);
+        // more runs than the tables hold (a round-0 key shorter than 4 symbols) or fields that do not fit their words: the ordinary way
+        if (nRuns == 0 || nRuns > w.maxRuns || rbits + hbits > 32 || idxBits + kbits + 1 + rbits > 64) return run_fallback();
         { KScope ks_("k_bwt_f_large_prefix"); hipLaunchKernelGGL(k_bwt_f_large_prefix, dim3(1), dim3(1024), 0, s, w.runList, nRun, w.loff, w.base, st.nBlocks, w.lbase); }
         { KScope ks_("k_bwt_f_run_table"); hipLaunchKernelGGL(k_bwt_f_run_table, GRID1(nRuns), bv, v, w.runPos, nRuns, w.K, w.classTab, kbits, idxBits, w.runKeysA, w.runE, w.runL); }
         const u64* rkSorted;
         { KScope ks_("k_bwt_f_sort_runs");
-          hipLaunchKernelGGL(prims::k_rs_one_segment, dim3(1), dim3(64), 0, s, w.seg2, nRuns);
-          prims::rs_launch_layout(s, rs1);
-          const int r = prims::rs_sort<u64, false>(s, rs1, w.runKeysA, w.runKeysB, (u32*)nullptr, (u32*)nullptr, (size_t)nRuns, idxBits, idxBits + kbits + 1 + rbits);
-          rkSorted = r ? w.runKeysB : w.runKeysA; }
+          rkSorted = sort_one_segment<u64, false>(nRuns, w.runKeysA, w.runKeysB, nullptr, nullptr, idxBits, idxBits + kbits + 1 + rbits) ? w.runKeysB : w.runKeysA; }
         { KScope ks_("k_bwt_f_run_sorted"); hipLaunchKernelGGL(k_bwt_f_run_sorted, GRID1(nRuns), rkSorted, nRuns, idxBits, w.runE, w.runL, (u32)nsym, w.sE, w.sKey, w.rcnt); }
         { KScope ks_("k_bwt_f_scan_sum"); prims::launch_scan<prims::SCAN_SUM_EXCL>(s, w.rcnt, w.moff, nRuns, nullptr, w.scanTmp); }
         { KScope ks_("k_bwt_f_run_members"); hipLaunchKernelGGL(k_bwt_f_run_members, dim3((runElems + 2047) / 2048), dim3(256), 0, s, w.moff, nRuns, runElems, w.sKey, kbits, hbits,
                                                                 (u32)nsym, keysFree); }
         u64* rk; u32* rv = w.valsA;
         { KScope ks_("k_bwt_f_sort_members");
-          hipLaunchKernelGGL(prims::k_rs_one_segment, dim3(1), dim3(64), 0, s, w.seg2, runElems);
-          prims::rs_launch_layout(s, rs1);
-          const int r = prims::rs_sort<u64, false>(s, rs1, keysFree, keysFree2, (u32*)nullptr, (u32*)nullptr, (size_t)runElems, 32, 32 + hbits + rbits);
-          const u64* sortedM = r ? keysFree2 : keysFree;
+          const int r = sort_one_segment<u64, false>(runElems, keysFree, keysFree2, nullptr, nullptr, 32, 32 + hbits + rbits);
           rk = r ? keysFree : keysFree2;
-          hipLaunchKernelGGL(k_bwt_f_run_expand, GRID1(runElems), sortedM, runElems, w.sKey, w.sE, kbits, hbits, rk, rv, w.valsB); }
-        {
-            // ties among the sorted members as a bit map, heads and sizes per window of 2048 members (the bit map reuses the run-end map,
-            // which nobody reads any more)
-            u32* mbits = w.ebits;
-            const u32 nWinM = (runElems + SM_WIN - 1) / SM_WIN;
-            { KScope ks_("k_bwt_f_large_flags"); hipLaunchKernelGGL(k_bwt_f_run_flags, dim3(nWinM * (SM_WIN / 256)), dim3(256), 0, s, rk, runElems, reinterpret_cast<unsigned long long*>(mbits)); }
-            { KScope ks_("k_bwt_f_r0_winsum"); hipLaunchKernelGGL(k_bwt_f_r0_winsum, GRID1(nWinM), mbits, runElems, nWinM, w.t0, w.t2, SM_WIN / 32); }
-            { KScope ks_("k_bwt_f_scan_max"); prims::launch_scan<prims::SCAN_MAX_INCL>(s, w.t0, w.t1, nWinM, nullptr, w.scanTmp); }
-            { KScope ks_("k_bwt_f_scan_min"); prims::launch_scan<prims::SCAN_MIN_INCL>(s, w.t2, w.t3, nWinM, nullptr, w.scanTmp); }
-            { KScope ks_("k_bwt_f_large_place");
-              hipMemsetAsync(w.rtbits, 0, 4 * w.gbitsWords, s);
-              hipLaunchKernelGGL(k_bwt_f_run_place, dim3((runElems + 255) / 256), dim3(256), 0, s, v, w.runList, w.loff, runElems, keyBits, rk, rv, mbits, w.t1, w.t3, nWinM, w.large[cur],
-                                 w.valsB, w.ovr, w.rtbits, w.lbase);
-              v.ovr = w.ovr; v.rtbits = w.rtbits; }
-        }
-        { KScope ks_("k_bwt_f_merge_bits"); hipLaunchKernelGGL(k_bwt_f_merge_bits, GRID1(total / 32 + 2), w.gbits, w.gnew, total / 32 + 2); }
-        compactMedium(w.med[cur]);
-        probeScan();
-        medCompacted = true;
-        if (hipMemcpyAsync(h_pinned, w.counters, 64, hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
-        if (hipStreamSynchronize(s) != hipSuccess) return -1;
-      }
+          hipLaunchKernelGGL(k_bwt_f_run_expand, GRID1(runElems), r ? keysFree2 : keysFree, runElems, w.sKey, w.sE, kbits, hbits, rk, rv, w.valsB); }
+        // ties among the sorted members as a bit map, heads and sizes per window of 2048 members (the bit map reuses the run-end map, which
+        // nobody reads any more)
+        u32* mbits = w.ebits; const u32 nWinM = (runElems + SM_WIN - 1) / SM_WIN;
+        { KScope ks_("k_bwt_f_large_flags"); hipLaunchKernelGGL(k_bwt_f_run_flags, dim3(nWinM * (SM_WIN / 256)), dim3(256), 0, s, rk, runElems, reinterpret_cast<unsigned long long*>(mbits)); }
+        bounds(nWinM, true, mbits, runElems, SM_WIN / 32);
+        { KScope ks_("k_bwt_f_large_place");
+          hipMemsetAsync(w.rtbits, 0, 4 * w.gbitsWords, s);
+          hipLaunchKernelGGL(k_bwt_f_run_place, dim3((runElems + 255) / 256), dim3(256), 0, s, v, w.runList, w.loff, runElems, hbits + kbits, rk, rv, mbits, w.t1, w.t3, nWinM, w.large[cur],
+                             w.valsB, w.ovr, w.rtbits, w.lbase);
+          v.ovr = w.ovr; v.rtbits = w.rtbits; }
+        { KScope ks_("k_bwt_f_merge_bits"); merge_bits(); }
+        return 0;
     }
-    if (!medCompacted) {
-        compactMedium(w.med[cur]);
-        probeScan();
-        if (hipMemcpyAsync(h_pinned, w.counters, 64, hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
-        if (hipStreamSynchronize(s) != hipSuccess) return -1;
+    // Round 0's medium groups compacted, and periodic stretches of a period the doubling offsets never meet taken apart by looking at the
+    // text (k_bwt_f_probe) before the first round: the groups it takes apart are void in the list (length 0), their parts that are medium
+    // groups are appended to it. Candidates among the medium groups of the list just compacted; their number comes back with the counters.
+    int probe()
+    {
+        u32* probeCand = w.medFlags;                                  // (free between two compactions)
+        compact_medium(w.med[cur]);
+        { KScope ks_("k_bwt_f_probe"); hipLaunchKernelGGL(k_bwt_f_probe_scan, dim3(256), dim3(256), 0, s, v, w.med[cur], (u32)nsym, v.rtbits, probeCand); }
+        if (fetch(0, CNT_ROUND_SLOTS)) return -1;
+        surv = hp[CNT_SMALL_LEFT]; nMed = hp[CNT_MED]; nLarge = hp[CNT_LARGE]; largeElems = hp[CNT_LARGE_MEMBERS];
+        if (const u32 nCand = hp[CNT_PROBE_CAND]) {
+            enable_run_tiebits();
+            hipMemsetAsync(w.counters, 0, 4 * CNT_PROBE_SLOTS, s);
+            { KScope ks_("k_bwt_f_probe");
+              hipLaunchKernelGGL(k_bwt_f_probe, dim3(std::min<u32>(nCand, 4096)), dim3(512), 0, s, bv, v, w.med[cur], probeCand, nCand, (u32)nsym, w.med[cur ^ 1], w.large[cur], w.ovr, w.rtbits);
+              merge_bits(); }
+            compact_medium(w.med[cur] + nMed);
+            if (fetch(0, CNT_PROBE_SLOTS)) return -1;
+            surv |= hp[CNT_SMALL_LEFT]; nMed += hp[CNT_MED];
+        }
+        if (tune.stats) fprintf(stderr, "after round 0 (nsym %d, total %u): run groups %u (%u members); small left %u, medium %u, large %u (%u members)\n",
+                                nsym, total, nRun, runElems, surv, nMed, nLarge, largeElems);
+        statT = std::chrono::steady_clock::now();
+        return 0;
     }
-    u32 surv = h_pinned[0], nMed = h_pinned[1], nLarge = h_pinned[2], largeElems = h_pinned[3];
-    if (const u32 nCand = h_pinned[14]) {
-        // Periodic stretches of a period the doubling offsets never meet, by looking at the text (k_bwt_f_probe), before the first round: the
-        // groups it takes apart are void in the list (length 0), their parts that are medium groups are appended to it
-        if (!v.rtbits) { hipMemsetAsync(w.rtbits, 0, 4 * w.gbitsWords, s); v.ovr = w.ovr; v.rtbits = w.rtbits; }
-        hipMemsetAsync(w.counters, 0, 8, s);
-        { KScope ks_("k_bwt_f_probe");
-          hipLaunchKernelGGL(k_bwt_f_probe, dim3(std::min<u32>(nCand, 4096)), dim3(512), 0, s, bv, v, w.med[cur], probeCand, nCand, (u32)nsym, w.med[cur ^ 1], w.large[cur], w.ovr, w.rtbits);
-          hipLaunchKernelGGL(k_bwt_f_merge_bits, GRID1(total / 32 + 2), w.gbits, w.gnew, total / 32 + 2); }
-        compactMedium(w.med[cur] + nMed);
-        if (hipMemcpyAsync(h_pinned, w.counters, 8, hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
-        if (hipStreamSynchronize(s) != hipSuccess) return -1;
-        surv |= h_pinned[0];
-        nMed += h_pinned[1];
+    // Link step: small groups inside long repeats linked to the group one position on (k_bwt_f_link_small); a trial looks at whole
+    // blocks, the first, the middle and the last one of the batch (blocks next to each other would share a window)
+    void link_step()
+    {
+        KScope ks_("k_bwt_f_link");
+        u32* posflag = w.ebits; u32* linked = w.rbits; u32* rev = w.rcount; u32* sufRev = w.rprefix;
+        const bool trial = link.mode == LinkPlan::TRIAL; linkTr.n = 0;
+        if (trial) { linkTr.blk[linkTr.n++] = 0; if (st.nBlocks >= 5) linkTr.blk[linkTr.n++] = st.nBlocks / 2; if (st.nBlocks >= 3) linkTr.blk[linkTr.n++] = st.nBlocks - 1; }
+        const u32 nW = total / 32 + 1;
+        hipMemsetAsync(posflag, 0, 4 * (size_t)nW, s);
+        hipMemsetAsync(linked, 0, 4 * ((size_t)nTiles * (SM_TS / 32) + 64), s);
+        enable_run_tiebits();
+        // (a block covers at most VS / SM_TS + 2 windows; the kernels' window stride is 1: every window)
+        const u32 nTrial = (u32)std::min<u64>((u64)nTiles, ((u64)bv.VS + SM_TS - 1) / SM_TS + 2);
+        const dim3 gridL(trial ? nTrial : nTiles, (unsigned)(linkTr.n ? linkTr.n : 1));
+        hipLaunchKernelGGL(k_bwt_f_link_small, gridL, dim3(256), 0, s, v, posflag, linked, tune.stats, 1u, w.linkedTile, linkTr);
+        hipLaunchKernelGGL(k_bwt_f_link_zeros, GRID1(nW), posflag, nW, rev);
+        prims::launch_scan<prims::SCAN_MIN_INCL>(s, rev, sufRev, nW, nullptr, w.scanTmp);
+        hipLaunchKernelGGL(k_bwt_f_link_apply, gridL, dim3(256), 0, s, v, posflag, sufRev, nW, linked, h, w.ovr, w.rtbits, 1u, linkTr);
     }
-    if (tune.stats) fprintf(stderr, "after round 0 (nsym %d, total %u): run groups %u (%u members); small left %u, medium %u, large %u (%u members)\n",
-                            nsym, total, nRun, runElems, surv, nMed, nLarge, largeElems);
-    std::chrono::steady_clock::time_point statT = std::chrono::steady_clock::now();
-
-    const int npass = (kbits + 7) / 8;
-    const u32 nTiles = (total + SM_TS - 1) / SM_TS;
-    // The doubling starts at the largest power of two the round-0 depth covers (groups and labels of depth nsym >= h are what a round
-    // with offset h needs): h = 4, 8, 16, ... meets the periods real data has (record and row sizes are powers of two more often than
-    // not), which is what lets the chain round (k_bwt_f_super) see a group look at itself.
-    u32 h = 1;
-    while (2 * h <= (u32)nsym) h <<= 1;
-    u32 survMembers = total;                                        // (not counted before the first round: assume many)
-    int linkMode = 0;                                               // 0 not tried, 1 sampled, 2 on, 3 applied (to be judged), 4 off
-    u32 linkStepUsed = 1, linkRetryH = 0xFFFFFFFFu;
-    LinkTrial linkTr; linkTr.n = 0;
-    int linkTrials = 0;
-    while (surv || nMed || nLarge) {
-        if (h > bv.VS) return -5;                                    // cannot happen: suffixes of one block differ in length
-        { KScope ks_("k_bwt_f_round"); hipMemsetAsync(w.counters, 0, 64, s); }      // (the scope counts the doubling rounds for the profile)
-        v.round++;                                                   // (the number the round's label writes carry; at most log2(block) + a few)
-        if (v.round > 255) return -5;
-        const int nxt = cur ^ 1;
-        // -- small groups inside long repeats: links first (k_bwt_f_link_small), once the rounds are past the depth where most ties are chance
-        // Whether it pays is a property of the data (it does where groups are whole repeats: copied spans, files that hold a part twice;
-        // it does not where every group has members that leave it one by one, as in the file mix of config 9): the first application, at
-        // h = 32, is a trial; what it linked against what was still tied after the round decides whether the rounds that follow apply it
-        // too, and every application is judged again. The trial is made on the windows of up to THREE WHOLE BLOCKS of the batch, the first,
-        // the middle and the last one (a run never leaves its block, so a block's runs are complete; a sample of windows all over the
-        // batch would cut every run), and must pay in each of them: 0.15 ms per 8 MiB where the step applied to a 212 MB batch costs
-        // 2-4 ms. (Round 5 looked at the first block only: in the real-file corpus that is one shared object, the trial said yes, and
-        // the application to the whole batch cost 3.5 ms for 1.7 ms of later rounds.)
-        bool linkNow = false;
-        u32 linkStep = 1;
-        if (surv && tune.link && h >= (u32)(tune.link > 1 ? tune.link : 32)) {
-            if (linkMode == 1 || linkMode == 3) {                    // judge the application of the round before
-                const u32 linkedN = h_pinned[14], tiedN = h_pinned[15];
-                const bool paid = linkedN >= 4096 && tiedN < linkedN / 2;
-                linkMode = paid ? 2 : 4;                              // 2: apply, 4: not now
-                if (!paid) linkRetryH = (linkTrials < 2) ? h * 8 : 0xFFFFFFFFu;    // (chance ties of the early rounds may have hidden the repeats: once more, three rounds on)
-                if (tune.stats) fprintf(stderr, "link step: %u members linked, %u of the windows' members still tied after the round -> %s\n", linkedN, tiedN, paid ? "on" : "off");
-            }
-            if (linkMode == 4 && h >= linkRetryH) linkMode = 0;
-            if (linkMode == 0 && survMembers >= total / 8) { linkNow = true; linkMode = 1; linkTrials++; }              // the trial
-            else if (linkMode == 2 && survMembers >= total / 64) { linkNow = true; linkMode = 3; }
-        }
-        if (linkNow) {
-            KScope ks_("k_bwt_f_link");
-            u32* posflag = w.ebits; u32* linked = w.rbits; u32* rev = w.rcount; u32* sufRev = w.rprefix;
-            // the trial looks at whole blocks: the first, the middle and the last one of the batch (blocks next to each other would share a window)
-            linkTr.n = 0;
-            if (linkMode == 1) {
-                linkTr.blk[linkTr.n++] = 0;
-                if (st.nBlocks >= 5) linkTr.blk[linkTr.n++] = st.nBlocks / 2;
-                if (st.nBlocks >= 3) linkTr.blk[linkTr.n++] = st.nBlocks - 1;
-            }
-            const u32 nW = total / 32 + 1;
-            hipMemsetAsync(posflag, 0, 4 * (size_t)nW, s);
-            hipMemsetAsync(linked, 0, 4 * ((size_t)nTiles * (SM_TS / 32) + 64), s);
-            if (!v.rtbits) { hipMemsetAsync(w.rtbits, 0, 4 * w.gbitsWords, s); v.ovr = w.ovr; v.rtbits = w.rtbits; }
-            // (a block covers at most VS / SM_TS + 2 windows)
-            const u32 nTrial = (u32)std::min<u64>((u64)nTiles, ((u64)bv.VS + SM_TS - 1) / SM_TS + 2);
-            const dim3 gridL(linkMode == 1 ? nTrial : (nTiles + linkStep - 1) / linkStep, (unsigned)(linkTr.n ? linkTr.n : 1));
-            hipLaunchKernelGGL(k_bwt_f_link_small, gridL, dim3(256), 0, s, v, posflag, linked, tune.stats, linkStep, w.linkedTile, linkTr);
-            hipLaunchKernelGGL(k_bwt_f_link_zeros, GRID1(nW), posflag, nW, rev);
-            prims::launch_scan<prims::SCAN_MIN_INCL>(s, rev, sufRev, nW, nullptr, w.scanTmp);
-            hipLaunchKernelGGL(k_bwt_f_link_apply, gridL, dim3(256), 0, s, v, posflag, sufRev, nW, linked, h, w.ovr, w.rtbits, linkStep, linkTr);
-            linkStepUsed = linkStep;
-        }
-        // -- all keys first (with versioned labels the small groups fetch theirs in the kernel that sorts them: k_bwt_f_small_fused)
-        const bool fused = v.ISA2 != nullptr;
-        if (surv && !fused) { KScope ks_("k_bwt_f_gather_small"); hipLaunchKernelGGL(k_bwt_f_gather_small, dim3(nTiles), dim3(256), 0, s, v, h, tune.stats); }
-        if (nMed) {
-            // (the list is in slot order: k_bwt_f_med_compact)
-            KScope ks_("k_bwt_f_gather_desc");
-            hipLaunchKernelGGL(k_bwt_f_gather_desc, dim3(1024), dim3(GATHER_THREADS), 0, s, v, w.med[cur], nMed, h, w.descInfo, tune.stats);
-        }
-        int lbits = 0;
-        bool small32 = false;
-        u64* lkA = keysFree; u64* lkB = keysFree2;
-        if (nLarge) {
-            while ((1u << lbits) < nLarge) lbits++;
-            small32 = (kbits + lbits) <= 32;
-            { KScope ks_("k_bwt_f_large_prefix"); hipLaunchKernelGGL(k_bwt_f_large_prefix, dim3(1), dim3(1024), 0, s, w.large[cur], nLarge, w.loff, w.base, st.nBlocks, w.lbase); }
-            KScope ks_("k_bwt_f_large_keys");
-            if (small32) hipLaunchKernelGGL(k_bwt_f_large_keys<u32>, GRID1(largeElems), v, w.large[cur], nLarge, w.loff, largeElems, h, kbits, reinterpret_cast<u32*>(lkA), w.valsA);
-            else hipLaunchKernelGGL(k_bwt_f_large_keys<u64>, GRID1(largeElems), v, w.large[cur], nLarge, w.loff, largeElems, h, kbits, lkA, w.valsA);
-        }
-        // -- then the refinements
-        if (surv) { KScope ks_("k_bwt_f_sort_small");
-                    if (fused && pbits <= 23 && !tune.noPack) hipLaunchKernelGGL(k_bwt_f_small_fused<true>, dim3(nTiles), dim3(256), 0, s, v, h, tune.link ? w.survTile : (u32*)nullptr, tune.stats);
-                    else if (fused) hipLaunchKernelGGL(k_bwt_f_small_fused<false>, dim3(nTiles), dim3(256), 0, s, v, h, tune.link ? w.survTile : (u32*)nullptr, tune.stats);
-                    else hipLaunchKernelGGL(k_bwt_f_sort_small, dim3(nTiles), dim3(256), 0, s, v, tune.link ? w.survTile : (u32*)nullptr);
-                    if (linkNow) hipLaunchKernelGGL(k_bwt_f_link_payoff, dim3(1), dim3(256), 0, s, v, w.linkedTile, w.survTile, nTiles, linkStepUsed, w.counters + 14, linkTr);
-                    if (tune.link) prims::launch_scan<prims::SCAN_SUM_EXCL>(s, w.survTile, w.survTile, nTiles, nullptr, w.scanTmp, w.counters + 13); }
-        if (nMed) {
-            // two workgroup shapes over the same list, each takes the groups of its size class: 256 threads x 8 elements (21 KB of LDS,
-            // groups up to 2048) and 512 threads x 16 elements (76 KB: two groups per CU in flight)
-            { KScope ks_("k_bwt_f_sort_medium");
-              const dim3 gridM(std::min<u32>(nMed, 8192));
-              hipLaunchKernelGGL((k_bwt_f_sort_medium<256, 8>), gridM, dim3(256), 0, s, v, w.med[cur], nMed, npass, SM_G, w.med[nxt], w.large[nxt], w.descInfo, w.superList);
-              hipLaunchKernelGGL((k_bwt_f_sort_medium<512, 16>), gridM, dim3(512), 0, s, v, w.med[cur], nMed, npass, 2048u, w.med[nxt], w.large[nxt], w.descInfo, w.superList); }
-            // groups whose majority looks at the group itself (sort_medium has listed them; the kernel reads the count itself)
-            { KScope ks_("k_bwt_f_super"); hipLaunchKernelGGL(k_bwt_f_super, dim3(std::min<u32>(nMed, 512)), dim3(1024), 0, s, v, w.superList, h, npass, w.med[nxt], w.large[nxt]); }
-        }
-        if (nLarge) {
-            u32* k32a = reinterpret_cast<u32*>(lkA); u32* k32b = reinterpret_cast<u32*>(lkB);
-            int r;
-            { KScope ks_("k_bwt_f_sort_large");
-              hipLaunchKernelGGL(prims::k_rs_one_segment, dim3(1), dim3(64), 0, s, w.seg2, largeElems);
-              prims::rs_launch_layout(s, rs1);
-              // (count + scatter passes here: with the many passes of these keys, most of them on constant digits, counting all of
-              // them ahead costs more than it saves -- period 3 / 5 / 7 / 768 at 8 MiB: 11.1-17.6 ms against 11.8-18.2)
-              // (from LARGE_OS_MIN members on the passes are the one-sweep ones; real files' 27 M members in the first round: 4.11 -> 3.94 ms,
-              // and counted for every sort they cost the many small ones of periodic data more than they save: 4.11 -> 4.56)
-              const bool os = largeElems >= LARGE_OS_MIN;
-              r = small32 ? prims::rs_sort<u32, true>(s, rs1, k32a, k32b, w.valsA, w.valsB, (size_t)largeElems, 0, kbits + lbits, os)
-                          : prims::rs_sort<u64, true>(s, rs1, lkA, lkB, w.valsA, w.valsB, (size_t)largeElems, 0, kbits + lbits, os); }
-            const u32* sk32 = r ? k32b : k32a; const u64* sk64 = r ? lkB : lkA; const u32* sv = r ? w.valsB : w.valsA;
-            { KScope ks_("k_bwt_f_large_flags");
-              if (small32) hipLaunchKernelGGL(k_bwt_f_large_flags<u32>, GRID1(largeElems), sk32, largeElems, w.t0, w.t2);
-              else hipLaunchKernelGGL(k_bwt_f_large_flags<u64>, GRID1(largeElems), sk64, largeElems, w.t0, w.t2); }
-            { KScope ks_("k_bwt_f_scan_max"); prims::launch_scan<prims::SCAN_MAX_INCL>(s, w.t0, w.t1, largeElems, nullptr, w.scanTmp); }
-            { KScope ks_("k_bwt_f_scan_min"); prims::launch_scan<prims::SCAN_MIN_INCL>(s, w.t2, w.t3, largeElems, nullptr, w.scanTmp); }
-            { KScope ks_("k_bwt_f_large_place");
-              if (small32) hipLaunchKernelGGL(k_bwt_f_large_place<u32>, GRID1(largeElems), v, w.large[cur], w.loff, largeElems, kbits, sk32, sv, w.t1, w.t3, w.med[nxt], w.large[nxt], w.lbase);
-              else hipLaunchKernelGGL(k_bwt_f_large_place<u64>, GRID1(largeElems), v, w.large[cur], w.loff, largeElems, kbits, sk64, sv, w.t1, w.t3, w.med[nxt], w.large[nxt], w.lbase); }
-        }
-        { KScope ks_("k_bwt_f_merge_bits"); hipLaunchKernelGGL(k_bwt_f_merge_bits, GRID1(total / 32 + 2), w.gbits, w.gnew, total / 32 + 2); }
-        compactMedium(w.med[nxt]);
-        if (hipMemcpyAsync(h_pinned, w.counters, 64, hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
-        if (hipStreamSynchronize(s) != hipSuccess) return -1;
-        surv = h_pinned[0]; nMed = h_pinned[1]; nLarge = h_pinned[2]; largeElems = h_pinned[3];
-        survMembers = h_pinned[13];
+    // small groups, ranked in windows of the bit map (with versioned labels the kernel fetches their keys itself); the link step's payoff
+    void sort_small(bool linked)
+    {
+        KScope ks_("k_bwt_f_sort_small");
+        u32* survTile = tune.link ? w.survTile : nullptr;
+        if (v.ISA2 && pbits <= 23 && !tune.noPack) hipLaunchKernelGGL(k_bwt_f_small_fused<true>, dim3(nTiles), dim3(256), 0, s, v, h, survTile, tune.stats);
+        else if (v.ISA2) hipLaunchKernelGGL(k_bwt_f_small_fused<false>, dim3(nTiles), dim3(256), 0, s, v, h, survTile, tune.stats);
+        else hipLaunchKernelGGL(k_bwt_f_sort_small, dim3(nTiles), dim3(256), 0, s, v, survTile);
+        if (linked) hipLaunchKernelGGL(k_bwt_f_link_payoff, dim3(1), dim3(256), 0, s, v, w.linkedTile, w.survTile, nTiles, 1u, w.counters + CNT_LINKED, linkTr);
+        if (tune.link) prims::launch_scan<prims::SCAN_SUM_EXCL>(s, w.survTile, w.survTile, nTiles, nullptr, w.scanTmp, w.counters + CNT_TIED);
+    }
+    // medium groups: two workgroup shapes over the same list, each takes the groups of its size class: 256 threads x 8 elements (21 KB of
+    // LDS, groups up to 2048) and 512 threads x 16 elements (76 KB: two groups per CU in flight); then the chain round
+    void sort_medium()
+    {
+        const int npass = (kbits + 7) / 8, nxt = cur ^ 1;
+        { KScope ks_("k_bwt_f_sort_medium"); const dim3 gridM(std::min<u32>(nMed, 8192));
+          hipLaunchKernelGGL((k_bwt_f_sort_medium<256, 8>), gridM, dim3(256), 0, s, v, w.med[cur], nMed, npass, SM_G, w.med[nxt], w.large[nxt], w.descInfo, w.superList);
+          hipLaunchKernelGGL((k_bwt_f_sort_medium<512, 16>), gridM, dim3(512), 0, s, v, w.med[cur], nMed, npass, 2048u, w.med[nxt], w.large[nxt], w.descInfo, w.superList); }
+        // groups whose majority looks at the group itself (sort_medium has listed them; the kernel reads the count itself)
+        { KScope ks_("k_bwt_f_super"); hipLaunchKernelGGL(k_bwt_f_super, dim3(std::min<u32>(nMed, 512)), dim3(1024), 0, s, v, w.superList, h, npass, w.med[nxt], w.large[nxt]); }
+    }
+    // large groups: (descriptor index, key) pairs, KEY = u32 where kbits + lbits bits fit. The keys are gathered before any kernel of the
+    // round changes a label; the sort and the placement come after the small and medium groups.
+    template <class KEY> void large_keys()
+    {
+        { KScope ks_("k_bwt_f_large_prefix"); hipLaunchKernelGGL(k_bwt_f_large_prefix, dim3(1), dim3(1024), 0, s, w.large[cur], nLarge, w.loff, w.base, st.nBlocks, w.lbase); }
+        KScope ks_("k_bwt_f_large_keys");
+        hipLaunchKernelGGL(k_bwt_f_large_keys<KEY>, GRID1(largeElems), v, w.large[cur], nLarge, w.loff, largeElems, h, kbits, reinterpret_cast<KEY*>(keysFree), w.valsA);
+    }
+    template <class KEY> void sort_large(int lbits)
+    {
+        KEY* ka = reinterpret_cast<KEY*>(keysFree); KEY* kb = reinterpret_cast<KEY*>(keysFree2); int r;
+        { KScope ks_("k_bwt_f_sort_large");
+          // (count + scatter passes here: with the many passes of these keys, most of them on constant digits, counting all of
+          // them ahead costs more than it saves -- period 3 / 5 / 7 / 768 at 8 MiB: 11.1-17.6 ms against 11.8-18.2)
+          // (from LARGE_OS_MIN members on the passes are the one-sweep ones; real files' 27 M members in the first round: 4.11 -> 3.94 ms,
+          // and counted for every sort they cost the many small ones of periodic data more than they save: 4.11 -> 4.56)
+          r = sort_one_segment<KEY, true>(largeElems, ka, kb, w.valsA, w.valsB, 0, kbits + lbits, largeElems >= LARGE_OS_MIN); }
+        const KEY* sk = r ? kb : ka; const u32* sv = r ? w.valsB : w.valsA;
+        { KScope ks_("k_bwt_f_large_flags"); hipLaunchKernelGGL(k_bwt_f_large_flags<KEY>, GRID1(largeElems), sk, largeElems, w.t0, w.t2); }
+        bounds(largeElems, true);
+        { KScope ks_("k_bwt_f_large_place");
+          hipLaunchKernelGGL(k_bwt_f_large_place<KEY>, GRID1(largeElems), v, w.large[cur], w.loff, largeElems, kbits, sk, sv, w.t1, w.t3, w.med[cur ^ 1], w.large[cur ^ 1], w.lbase); }
+    }
+    // the round's group starts merged, its medium groups compacted into the next round's list, the counters read back
+    int end_round()
+    {
+        { KScope ks_("k_bwt_f_merge_bits"); merge_bits(); }
+        compact_medium(w.med[cur ^ 1]);
+        if (fetch(0, CNT_ROUND_SLOTS)) return -1;
+        surv = hp[CNT_SMALL_LEFT]; nMed = hp[CNT_MED]; nLarge = hp[CNT_LARGE]; largeElems = hp[CNT_LARGE_MEMBERS]; survMembers = hp[CNT_TIED];
         if (tune.stats) {
             // windows that still hold tied small groups (from the scanned per-window counts; developer statistics only)
-            std::vector<u32> hs(nTiles);
-            u32 activeTiles = 0;
+            std::vector<u32> hs(nTiles); u32 activeTiles = 0;
             if (tune.link && hipMemcpyAsync(hs.data(), w.survTile, 4 * (size_t)nTiles, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess) {
                 for (u32 t = 0; t + 1 < nTiles; t++) activeTiles += hs[t + 1] != hs[t] ? 1u : 0u;
                 fprintf(stderr, "  windows with tied small groups after the round: %u of %u\n", activeTiles, nTiles);
             }
             const std::chrono::steady_clock::time_point now = std::chrono::steady_clock::now();
             fprintf(stderr, "round h=%u (%.3f ms): small members worked on %u in %u groups, medium members %u; after it: small left %u, medium groups %u, large %u (%u members); %u groups took the chain round; %u small members still tied\n",
-                    h, std::chrono::duration<double, std::milli>(now - statT).count(), h_pinned[10], h_pinned[11], h_pinned[12], surv, nMed, nLarge, largeElems, h_pinned[7], h_pinned[13]);
+                    h, std::chrono::duration<double, std::milli>(now - statT).count(), hp[CNT_STAT_SMALL], hp[CNT_STAT_SMALL_GROUPS], hp[CNT_STAT_MED], surv, nMed, nLarge, largeElems,
+                    hp[CNT_SUPER], hp[CNT_TIED]);
             statT = now;
         }
-        cur = nxt;
-        h <<= 1;
+        cur ^= 1; h <<= 1;
+        return 0;
     }
-    if (sa) return hipGetLastError() == hipSuccess ? 0 : -1;
-    const dim3 gridB((unsigned)std::min<size_t>(((size_t)bv.VS + 255) / 256, 4096), st.nBlocks);
-    { KScope ks_("k_bwt_f_emit"); hipLaunchKernelGGL(k_bwt_f_emit, gridB, dim3(256), 0, s, bv, w.base, st.ok, w.SA, v, st.newLen); }
+    // One doubling round on offset h: all keys first (a round sorts on the labels as they stood when it began), then the refinements
+    int round()
+    {
+        if (h > bv.VS) return -5;                                    // cannot happen: suffixes of one block differ in length
+        { KScope ks_("k_bwt_f_round"); hipMemsetAsync(w.counters, 0, 4 * CNT_ROUND_SLOTS, s); }     // (the scope counts the doubling rounds for the profile)
+        if (++v.round > 255) return -5;                              // (the number the round's label writes carry; at most log2(block) + a few)
+        const bool linked = surv && tune.link && h >= (u32)(tune.link > 1 ? tune.link : 32)
+                            && link.next(h, survMembers, total, hp[CNT_LINKED], hp[CNT_LINK_TIED], tune.stats);
+        if (linked) link_step();
+        // (with versioned labels the small groups fetch their keys in k_bwt_f_small_fused; the medium list is in slot order: k_bwt_f_med_compact)
+        if (surv && !v.ISA2) { KScope ks_("k_bwt_f_gather_small"); hipLaunchKernelGGL(k_bwt_f_gather_small, dim3(nTiles), dim3(256), 0, s, v, h, tune.stats); }
+        if (nMed) { KScope ks_("k_bwt_f_gather_desc"); hipLaunchKernelGGL(k_bwt_f_gather_desc, dim3(1024), dim3(GATHER_THREADS), 0, s, v, w.med[cur], nMed, h, w.descInfo, tune.stats); }
+        const int lbits = bits_for(nLarge, 0); const bool key32 = kbits + lbits <= 32;
+        if (nLarge) { if (key32) large_keys<u32>(); else large_keys<u64>(); }
+        if (surv) sort_small(linked);
+        if (nMed) sort_medium();
+        if (nLarge) { if (key32) sort_large<u32>(lbits); else sort_large<u64>(lbits); }
+        return end_round();
+    }
+    // the codec's output: header and BWT bytes
+    void emit()
+    {
+        KScope ks_("k_bwt_f_emit");
+        hipLaunchKernelGGL(k_bwt_f_emit, dim3((unsigned)std::min<size_t>(((size_t)bv.VS + 255) / 256, 4096), st.nBlocks), dim3(256), 0, s, bv, w.base, st.ok, w.SA, v, st.newLen);
+    }
+};
+
+// Returns 0 or a negative HIP error. Synchronises the stream (the sizes of the work lists are read back per round).
+// sa == nullptr: the BWT block codec (emits header + BWT bytes). Otherwise the suffix arrays only, left in the scratch (bwt_suffix_arrays).
+static int bwt_forward_run(hipStream_t s, const XfStage& st, void* scratch, size_t scratchBytes, u32* h_pinned, BwtSuffixArrays* sa)
+{
+    FwdSort f{ s, st, h_pinned };
+    if (int r = f.setup(scratch, scratchBytes, sa)) return r;
+    if (f.total == 0) return 0;
+    f.round0_sort();
+    if (f.round0_place() || f.run_round() || f.probe()) return -1;
+    while (f.surv || f.nMed || f.nLarge) if (int r = f.round()) return r;
+    if (!sa) f.emit();
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int launch_bwt_forward(hipStream_t s, const XfStage& st, void* scratch, size_t scratchBytes, u32* h_pinned)
-{
-    return bwt_forward_run(s, st, scratch, scratchBytes, h_pinned, nullptr);
-}
-
+{ return bwt_forward_run(s, st, scratch, scratchBytes, h_pinned, nullptr); }
 int bwt_suffix_arrays(hipStream_t s, const XfStage& st, void* scratch, size_t scratchBytes, u32* h_pinned, BwtSuffixArrays* out)
-{
-    return bwt_forward_run(s, st, scratch, scratchBytes, h_pinned, out);
-}
+{ return bwt_forward_run(s, st, scratch, scratchBytes, h_pinned, out); }
 
 }  // namespace knz
