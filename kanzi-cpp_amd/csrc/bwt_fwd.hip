@@ -48,6 +48,8 @@ constexpr u32 SM_G = 256;          // largest "small" group
 constexpr u32 MED_CAP = 8192;
 constexpr u32 SUPER_CAP = 8192;    // largest group the chain round and the periodic-stretch probe take
 constexpr int GATHER_THREADS = 512;        // workgroup of k_bwt_f_gather_desc
+constexpr u32 GATHER_ROWS = 16;            // members it holds per thread: a medium group whole
+static_assert(MED_CAP <= GATHER_ROWS * GATHER_THREADS, "k_bwt_f_gather_desc judges a medium group from one batch of loads");
 constexpr u32 LARGE_OS_MIN = 1000000;      // members from which the sort of the large groups uses the one-sweep radix passes
 constexpr u32 NO_BIT = 0x7FFFFFFFu;
 
@@ -73,7 +75,7 @@ struct FwdView {
                          // into the next round's descriptor list by k_bwt_f_med_compact
 };
 
-// Slots of FwdView::counters. Slots 0-15 are zeroed in front of every doubling round and read back after it; the host reads its copy
+// Slots of FwdView::counters. Slots 0-23 are zeroed in front of every doubling round and read back after it; the host reads its copy
 // slot for slot (FwdSort::fetch).
 enum FwdCounter : u32 {
     CNT_SMALL_LEFT = 0,          // != 0: small groups are left
@@ -92,7 +94,12 @@ enum FwdCounter : u32 {
     CNT_PROBE_CAND = 14,         // after round 0, owned by the probe: candidates of k_bwt_f_probe (k_bwt_f_probe_scan)
     CNT_LINKED = 14,             // in a doubling round, owned by the link step: members linked (k_bwt_f_link_payoff)
     CNT_LINK_TIED = 15,          // link step: members of the linked windows still tied after the round
-    CNT_ROUND_SLOTS = 16,
+    CNT_STAT_MED_GROUPS = 16,    // medium groups worked on (knob bwt_stats, like the four below)
+    CNT_STAT_UNSPLIT = 17,       // medium groups whose members all carry one key: the round cannot split them
+    CNT_STAT_UNSPLIT_MEMBERS = 18,
+    CNT_STAT_MAJ = 19,           // medium groups that take med_majority_write_back (a majority key and at most THREADS others)
+    CNT_STAT_MAJ_MEMBERS = 20,
+    CNT_ROUND_SLOTS = 24,
     CNT_PROBE_SLOTS = 2,         // slots 0-1 (CNT_SMALL_LEFT, CNT_MED): what the probe zeroes, recounts and reads back
     CNT_LONGEST_BLOCK = 32,      // longest block the transform applies to (k_bwt_bases)
     CNT_NSYM = 33,               // round-0 key length the entropy asks for (k_bwt_f_choose_nsym)
@@ -1027,31 +1034,72 @@ __global__ __launch_bounds__(256) void k_bwt_f_link_apply(FwdView v, const u32* 
 // The 32 workgroups that run on one XCD (workgroup index mod 8 -- an observed placement, used for speed only) walk through one
 // contiguous eighth of the list side by side, so that a line of ISA fetched for one group is found in that XCD's L2 by the
 // 31 groups next to it, instead of being fetched from memory once per group.
-__global__ __launch_bounds__(GATHER_THREADS) void k_bwt_f_gather_desc(FwdView v, const uint2* __restrict__ desc, u32 nDesc, u32 h, uint2* __restrict__ descInfo, int stats)
+// A group whose members all carry ONE key cannot be split by the round (every member looks at the same group `off` positions on: the inside
+// of a periodic stretch, of a table, of records with a shared prefix, until the offset reaches past an end). The whole group is held in
+// registers (up to GATHER_ROWS members per thread: MED_CAP of them per workgroup), so the kernel sees that before it has stored a key: it
+// then stores none, stages the group for the next round's list as med_write_back would have, and makes this round's descriptor void
+// (length 0, like a group k_bwt_f_probe took apart): no sorting workgroup looks at the group -- SA, labels (an entry the round did not
+// write reads as "unchanged") and the bit map already say what it would write. `skip` == 0 (knob bwt_no_unsplit_skip): every group is
+// stored and sorted.
+// The keys of the group's first ROWS * GATHER_THREADS members (all of them when `judge`): all position loads, then all key loads, then the
+// stores -- two memory latencies per batch instead of two per member. judge: true comes back, and nothing is stored, when no key differs
+// from key0, the first member's. ROWS fits the group (the real files' medium groups have some 800 members, a stretch's thousands).
+template <int ROWS>
+__device__ __forceinline__ bool gather_rows(const FwdView& v, u32 gs, u32 n, u32 off, u32 bb, u32 be, bool judge, u32 key0, u32* sDiff)
+{
+    u32 gp[ROWS], key[ROWS];
+#pragma unroll
+    for (int k = 0; k < ROWS; k++) { const u32 i = (u32)k * GATHER_THREADS + threadIdx.x; gp[k] = (i < n) ? v.SA[gs + i] : bb; }
+#pragma unroll
+    for (int k = 0; k < ROWS; k++) { const u32 i = (u32)k * GATHER_THREADS + threadIdx.x; key[k] = (i < n) ? gather_key(v, gp[k], off, bb, be) : key0; }
+    if (judge) {                                            // (uniform)
+        bool diff = false;
+#pragma unroll
+        for (int k = 0; k < ROWS; k++) diff = diff || key[k] != key0;       // (a slot behind the group's end holds key0)
+        if (__ballot(diff) != 0 && (threadIdx.x & 63) == 0) *sDiff = 1;
+        __syncthreads();
+        if (*sDiff == 0) return true;
+    }
+#pragma unroll
+    for (int k = 0; k < ROWS; k++) { const u32 i = (u32)k * GATHER_THREADS + threadIdx.x; if (i < n) v.K[gs + i] = key[k]; }
+    return false;
+}
+
+__global__ __launch_bounds__(GATHER_THREADS) void k_bwt_f_gather_desc(FwdView v, uint2* __restrict__ desc, u32 nDesc, u32 h, uint2* __restrict__ descInfo, int stats, int skip)
 {
     __shared__ int sBlk;
+    __shared__ u32 sDiff;
     const u32 xcd = blockIdx.x & 7, lanesPerXcd = gridDim.x >> 3, slot = blockIdx.x >> 3;      // the grid is a multiple of 8 workgroups
     const u32 per = (nDesc + 7) / 8;
     const u32 lo = xcd * per, hi = (lo + per < nDesc) ? lo + per : nDesc;
     for (u32 g = lo + slot; g < hi; g += lanesPerXcd) {
         const uint2 d = desc[g];
-        if (threadIdx.x == 0) sBlk = find_block(v.base, v.nBlocks, d.x);
+        if (threadIdx.x == 0) { sBlk = find_block(v.base, v.nBlocks, d.x); sDiff = 0; }
         __syncthreads();
         const u32 bb = v.base[sBlk], be = v.base[sBlk + 1];
         u32 off = h;                                        // (uniform for the group)
         if (v.rtbits && ((v.rtbits[d.x >> 5] >> (d.x & 31)) & 1u)) { const u32 r = v.ovr[d.x]; off = r > h ? r : h; }
+        // the first member's label and key, by every thread for itself (one address for the workgroup, in flight beside the loads below)
+        const u32 gp0 = v.SA[d.x];
+        const u32 lab = lab_old(v, gp0, bb), key0 = gather_key(v, gp0, off, bb, be);
+        // a verdict needs the group whole; the label inside the group's range and more than SM_G members: what med_write_back's
+        // "label unchanged, staged again" rests on (true of every group the rounds make; anything else is stored and sorted)
+        const bool judge = skip && d.y > SM_G && d.y <= GATHER_ROWS * (u32)GATHER_THREADS && lab - d.x < d.y;
+        bool unsplit = false;
+        if (d.y <= 1 * GATHER_THREADS) unsplit = gather_rows<1>(v, d.x, d.y, off, bb, be, judge, key0, &sDiff);
+        else if (d.y <= 2 * GATHER_THREADS) unsplit = gather_rows<2>(v, d.x, d.y, off, bb, be, judge, key0, &sDiff);
+        else if (d.y <= 4 * GATHER_THREADS) unsplit = gather_rows<4>(v, d.x, d.y, off, bb, be, judge, key0, &sDiff);
+        else if (d.y <= 8 * GATHER_THREADS) unsplit = gather_rows<8>(v, d.x, d.y, off, bb, be, judge, key0, &sDiff);
+        else for (u32 i0 = 0; i0 < d.y; i0 += GATHER_ROWS * GATHER_THREADS)                       // (once for a medium group)
+            unsplit = gather_rows<(int)GATHER_ROWS>(v, d.x + i0, d.y - i0, off, bb, be, judge, key0, &sDiff);
         // (block base, label the members carry): what the sorting kernel needs per group without a chain of dependent loads of its own
-        if (threadIdx.x == 0) { descInfo[g] = make_uint2(bb, lab_old(v, v.SA[d.x], bb)); if (stats) atomicAdd(&v.counters[CNT_STAT_MED], d.y); }
-        // eight members per thread at a time: all position loads, then all key loads, then the stores -- two memory
-        // latencies per batch instead of two per member
-        for (u32 i0 = 0; i0 < d.y; i0 += 8 * GATHER_THREADS) {
-            u32 gp[8], key[8];
-#pragma unroll
-            for (int k = 0; k < 8; k++) { const u32 i = i0 + (u32)k * GATHER_THREADS + threadIdx.x; gp[k] = (i < d.y) ? v.SA[d.x + i] : bb; }
-#pragma unroll
-            for (int k = 0; k < 8; k++) { const u32 i = i0 + (u32)k * GATHER_THREADS + threadIdx.x; key[k] = (i < d.y) ? gather_key(v, gp[k], off, bb, be) : 0u; }
-#pragma unroll
-            for (int k = 0; k < 8; k++) { const u32 i = i0 + (u32)k * GATHER_THREADS + threadIdx.x; if (i < d.y) v.K[d.x + i] = key[k]; }
+        if (threadIdx.x == 0) {
+            descInfo[g] = make_uint2(bb, lab);
+            if (unsplit) { v.medStage[d.x >> 8] = d; desc[g] = make_uint2(d.x, 0u); }      // (every thread has read desc[g] in front of the verdict's barrier)
+            if (stats && d.y) {
+                atomicAdd(&v.counters[CNT_STAT_MED], d.y); atomicAdd(&v.counters[CNT_STAT_MED_GROUPS], 1u);
+                if (unsplit) { atomicAdd(&v.counters[CNT_STAT_UNSPLIT], 1u); atomicAdd(&v.counters[CNT_STAT_UNSPLIT_MEMBERS], d.y); }
+            }
         }
         __syncthreads();
     }
@@ -1308,7 +1356,8 @@ __device__ __forceinline__ void med_majority_write_back(MedLds<THREADS, ROWS>& L
 // (Round 6 measured the keys fetched inside this kernel, versioned labels as in k_bwt_f_small_fused: gather + sort of the medium groups
 // 9.1 -> 11.0 ms on the real files, 5.5 -> 6.9 on the stand-in -- a sorting workgroup waits for its own three dependent loads, the gather kernel
 // keeps eight groups per CU in flight and walks the list XCD by XCD. The keys stay a kernel of their own.)
-template <int THREADS, int ROWS>
+// (STATS: the instantiation the knob bwt_stats launches; it counts the groups that come out unsplit and the ones of the majority path.)
+template <int THREADS, int ROWS, bool STATS>
 __global__ __launch_bounds__(THREADS, (THREADS >= 1024 ? 4 : THREADS / 128)) void k_bwt_f_sort_medium(FwdView v, const uint2* __restrict__ desc, u32 nDesc, int npass, u32 minLen,
                                                                uint2* __restrict__ medNext, uint2* __restrict__ largeNext, const uint2* __restrict__ descInfo,
                                                                uint4* __restrict__ superList)
@@ -1346,6 +1395,7 @@ __global__ __launch_bounds__(THREADS, (THREADS >= 1024 ? 4 : THREADS / 128)) voi
             __syncthreads();
             continue;
         }
+        if (STATS && tid == 0 && c == n) { atomicAdd(&v.counters[CNT_STAT_UNSPLIT], 1u); atomicAdd(&v.counters[CNT_STAT_UNSPLIT_MEMBERS], n); }
         if (c < n) {
             if (2 * c >= n) {
                 // ---- stable split: [others (nOth)][members with key m (c)]
@@ -1398,7 +1448,7 @@ __global__ __launch_bounds__(THREADS, (THREADS >= 1024 ? 4 : THREADS / 128)) voi
                     u32 lessQ = 0;
                     if ((u32)tid < nOth) lessQ = (L.oK[tid] < m) ? 1u : 0u;
                     lessQ = med_block_sum(L, lessQ);
-                    if (tid == 0) { L.oldLab = info.y; L.blkBase = info.x; }
+                    if (tid == 0) { L.oldLab = info.y; L.blkBase = info.x; if (STATS) { atomicAdd(&v.counters[CNT_STAT_MAJ], 1u); atomicAdd(&v.counters[CNT_STAT_MAJ_MEMBERS], n); } }
                     __syncthreads();
                     med_majority_write_back<THREADS, ROWS>(L, v, gs, n, nOth, c, lessQ, m);
                     __syncthreads();
@@ -2232,13 +2282,14 @@ __global__ __launch_bounds__(256) void k_bwt_f_med_compact(uint2* __restrict__ s
 // knobs (tests, diagnostics): read from the environment once per process, or set through knz_hip_tune(). Each one forces, at test
 // sizes, a path that some inputs take by themselves (round-0 key length, no run round, the run groups' fall-back, the plain labels of
 // blocks above 256 MiB, the plain keys of blocks above 8 MiB, where the link step starts), or reports (stats).
-struct FwdTuning { int nsym; int noRunRound; int runFallback; int stats; int link; int plainLabels; int noPack; };
+struct FwdTuning { int nsym; int noRunRound; int runFallback; int stats; int link; int plainLabels; int noPack; int noUnsplitSkip; };
 static FwdTuning& fwd_tuning()
 {
     static FwdTuning t = [] {
-        FwdTuning x; x.nsym = 0; x.noRunRound = 0; x.runFallback = 0; x.stats = 0; x.link = 1; x.plainLabels = 0; x.noPack = 0;     // link: 0 off, 1 on (from h = 32), n > 1: from h = n
+        FwdTuning x; x.nsym = 0; x.noRunRound = 0; x.runFallback = 0; x.stats = 0; x.link = 1; x.plainLabels = 0; x.noPack = 0; x.noUnsplitSkip = 0;     // link: 0 off, 1 on (from h = 32), n > 1: from h = n
         if (getenv("KNZ_BWT_PLAIN_LABELS")) x.plainLabels = 1;
         if (getenv("KNZ_BWT_NO_PACK")) x.noPack = 1;
+        if (getenv("KNZ_BWT_NO_UNSPLIT_SKIP")) x.noUnsplitSkip = 1;
         if (const char* e = getenv("KNZ_BWT_LINK")) x.link = atoi(e);
         if (getenv("KNZ_BWT_STATS")) x.stats = 1;
         if (const char* e = getenv("KNZ_BWT_NSYM")) x.nsym = atoi(e);
@@ -2259,6 +2310,7 @@ int bwt_forward_tune(const char* key, int value)
     else if (!strcmp(key, "bwt_link")) t.link = value;
     else if (!strcmp(key, "bwt_plain_labels")) t.plainLabels = value;
     else if (!strcmp(key, "bwt_no_pack")) t.noPack = value;      // small groups ranked on plain keys (three counts per pair) also where the packed keys fit
+    else if (!strcmp(key, "bwt_no_unsplit_skip")) t.noUnsplitSkip = value;      // medium groups whose keys are all equal stored and sorted like any other
     else return -1;
     return 0;
 }
@@ -2616,8 +2668,10 @@ struct FwdSort {
     {
         const int npass = (kbits + 7) / 8, nxt = cur ^ 1;
         { KScope ks_("k_bwt_f_sort_medium"); const dim3 gridM(std::min<u32>(nMed, 8192));
-          hipLaunchKernelGGL((k_bwt_f_sort_medium<256, 8>), gridM, dim3(256), 0, s, v, w.med[cur], nMed, npass, SM_G, w.med[nxt], w.large[nxt], w.descInfo, w.superList);
-          hipLaunchKernelGGL((k_bwt_f_sort_medium<512, 16>), gridM, dim3(512), 0, s, v, w.med[cur], nMed, npass, 2048u, w.med[nxt], w.large[nxt], w.descInfo, w.superList); }
+          const auto sort256 = tune.stats ? k_bwt_f_sort_medium<256, 8, true> : k_bwt_f_sort_medium<256, 8, false>;
+          const auto sort512 = tune.stats ? k_bwt_f_sort_medium<512, 16, true> : k_bwt_f_sort_medium<512, 16, false>;
+          hipLaunchKernelGGL(sort256, gridM, dim3(256), 0, s, v, w.med[cur], nMed, npass, SM_G, w.med[nxt], w.large[nxt], w.descInfo, w.superList);
+          hipLaunchKernelGGL(sort512, gridM, dim3(512), 0, s, v, w.med[cur], nMed, npass, 2048u, w.med[nxt], w.large[nxt], w.descInfo, w.superList); }
         // groups whose majority looks at the group itself (sort_medium has listed them; the kernel reads the count itself)
         { KScope ks_("k_bwt_f_super"); hipLaunchKernelGGL(k_bwt_f_super, dim3(std::min<u32>(nMed, 512)), dim3(1024), 0, s, v, w.superList, h, npass, w.med[nxt], w.large[nxt]); }
     }
@@ -2662,6 +2716,8 @@ struct FwdSort {
             fprintf(stderr, "round h=%u (%.3f ms): small members worked on %u in %u groups, medium members %u; after it: small left %u, medium groups %u, large %u (%u members); %u groups took the chain round; %u small members still tied\n",
                     h, std::chrono::duration<double, std::milli>(now - statT).count(), hp[CNT_STAT_SMALL], hp[CNT_STAT_SMALL_GROUPS], hp[CNT_STAT_MED], surv, nMed, nLarge, largeElems,
                     hp[CNT_SUPER], hp[CNT_TIED]);
+            fprintf(stderr, "  medium groups worked on %u (%u members): all keys equal in %u (%u members)%s, majority path %u (%u members)\n", hp[CNT_STAT_MED_GROUPS], hp[CNT_STAT_MED],
+                    hp[CNT_STAT_UNSPLIT], hp[CNT_STAT_UNSPLIT_MEMBERS], tune.noUnsplitSkip ? "" : " -- left alone", hp[CNT_STAT_MAJ], hp[CNT_STAT_MAJ_MEMBERS]);
             statT = now;
         }
         cur ^= 1; h <<= 1;
@@ -2678,7 +2734,7 @@ struct FwdSort {
         if (linked) link_step();
         // (with versioned labels the small groups fetch their keys in k_bwt_f_small_fused; the medium list is in slot order: k_bwt_f_med_compact)
         if (surv && !v.ISA2) { KScope ks_("k_bwt_f_gather_small"); hipLaunchKernelGGL(k_bwt_f_gather_small, dim3(nTiles), dim3(256), 0, s, v, h, tune.stats); }
-        if (nMed) { KScope ks_("k_bwt_f_gather_desc"); hipLaunchKernelGGL(k_bwt_f_gather_desc, dim3(1024), dim3(GATHER_THREADS), 0, s, v, w.med[cur], nMed, h, w.descInfo, tune.stats); }
+        if (nMed) { KScope ks_("k_bwt_f_gather_desc"); hipLaunchKernelGGL(k_bwt_f_gather_desc, dim3(1024), dim3(GATHER_THREADS), 0, s, v, w.med[cur], nMed, h, w.descInfo, tune.stats, tune.noUnsplitSkip ? 0 : 1); }
         const int lbits = bits_for(nLarge, 0); const bool key32 = kbits + lbits <= 32;
         if (nLarge) { if (key32) large_keys<u32>(); else large_keys<u64>(); }
         if (surv) sort_small(linked);
