@@ -73,7 +73,17 @@ struct FwdView {
     uint2* medStage;     // medium groups found in the current round, one slot per 256 slots of SA (a medium group has more than 256
                          // members, so two of them never start in the same 256): written without atomics, compacted -- in slot order --
                          // into the next round's descriptor list by k_bwt_f_med_compact
+    uint2* verdictNow;   // per staging slot: (key, verdict_word) of a medium group this round leaves whole (k_bwt_f_gather_desc's verdict,
+                         // k_bwt_f_med_sleep); null: not recorded (knob bwt_no_group_sleep)
+    const uint2* verdictWas;     // what the round before recorded (the two buffers take turns; an entry names its round)
 };
+
+// What a round knows of a medium group it left whole, by the group's staging slot: .x = the one key all members carried (the label of the
+// group they all found, as gather_key gives it), .y = [round, 8 bits | status | members, 16 bits]. PLAIN: the key was looked up at the
+// round's plain offset h and is no past-the-end sentinel -- what k_bwt_f_med_sleep may build on; WHOLE: left whole, nothing more said.
+constexpr u32 VERDICT_WHOLE = 1, VERDICT_PLAIN = 2;
+__host__ __device__ __forceinline__ u32 verdict_word(u32 round, u32 status, u32 members) { return (round << 24) | (status << 16) | members; }
+static_assert(MED_CAP < (1u << 16), "verdict_word keeps a medium group's size in 16 bits");
 
 // Slots of FwdView::counters. Slots 0-23 are zeroed in front of every doubling round and read back after it; the host reads its copy
 // slot for slot (FwdSort::fetch).
@@ -99,6 +109,8 @@ enum FwdCounter : u32 {
     CNT_STAT_UNSPLIT_MEMBERS = 18,
     CNT_STAT_MAJ = 19,           // medium groups that take med_majority_write_back (a majority key and at most THREADS others)
     CNT_STAT_MAJ_MEMBERS = 20,
+    CNT_STAT_ASLEEP = 21,        // medium groups k_bwt_f_med_sleep kept out of the gather (counted among the ones above as well)
+    CNT_STAT_ASLEEP_MEMBERS = 22,
     CNT_ROUND_SLOTS = 24,
     CNT_PROBE_SLOTS = 2,         // slots 0-1 (CNT_SMALL_LEFT, CNT_MED): what the probe zeroes, recounts and reads back
     CNT_LONGEST_BLOCK = 32,      // longest block the transform applies to (k_bwt_bases)
@@ -1074,6 +1086,7 @@ __global__ __launch_bounds__(GATHER_THREADS) void k_bwt_f_gather_desc(FwdView v,
     const u32 lo = xcd * per, hi = (lo + per < nDesc) ? lo + per : nDesc;
     for (u32 g = lo + slot; g < hi; g += lanesPerXcd) {
         const uint2 d = desc[g];
+        if (d.y == 0) continue;                             // (uniform) void: taken apart by the probe, or asleep (k_bwt_f_med_sleep)
         if (threadIdx.x == 0) { sBlk = find_block(v.base, v.nBlocks, d.x); sDiff = 0; }
         __syncthreads();
         const u32 bb = v.base[sBlk], be = v.base[sBlk + 1];
@@ -1095,13 +1108,65 @@ __global__ __launch_bounds__(GATHER_THREADS) void k_bwt_f_gather_desc(FwdView v,
         // (block base, label the members carry): what the sorting kernel needs per group without a chain of dependent loads of its own
         if (threadIdx.x == 0) {
             descInfo[g] = make_uint2(bb, lab);
-            if (unsplit) { v.medStage[d.x >> 8] = d; desc[g] = make_uint2(d.x, 0u); }      // (every thread has read desc[g] in front of the verdict's barrier)
-            if (stats && d.y) {
+            if (unsplit) {                                  // (every thread has read desc[g] in front of the verdict's barrier)
+                v.medStage[d.x >> 8] = d; desc[g] = make_uint2(d.x, 0u);
+                if (v.verdictNow) v.verdictNow[d.x >> 8] = make_uint2(key0, verdict_word(v.round, (off == h && key0 != 0u) ? VERDICT_PLAIN : VERDICT_WHOLE, d.y));
+            }
+            if (stats) {
                 atomicAdd(&v.counters[CNT_STAT_MED], d.y); atomicAdd(&v.counters[CNT_STAT_MED_GROUPS], 1u);
                 if (unsplit) { atomicAdd(&v.counters[CNT_STAT_UNSPLIT], 1u); atomicAdd(&v.counters[CNT_STAT_UNSPLIT_MEMBERS], d.y); }
             }
         }
         __syncthreads();
+    }
+}
+
+// Medium groups that sleep through a round: the verdict is known from the round before without a member being read. Write T(G) for the
+// group all members of G found h positions on in the round of offset h ("all keys equal"). When, in that round, G' = T(G) was itself left
+// whole on one key, G'' = T(G'), and G'' came out of the round whole, then in this round (offset 2h) every member m of G has m + h in G',
+// so m + 2h in G'', and G'' still carries its label: all keys of G are equal again and T(G) is now G''. One thread per descriptor looks
+// that up -- the list is in slot order and a label is a slot inside its group's range, so a binary search finds the group of a label --
+// and then does for G what k_bwt_f_gather_desc does on such a verdict: stages it for the next round, voids this round's descriptor (the
+// gather passes a void one by without a load), records the new target. The rule composes, so a group can sleep round after round; it
+// holds for any period, for tables and for records with a shared prefix. Anything else is gathered as before: an offset that is not the
+// plain h (run tie, link step), for G now or for G or G' then; a past-the-end key; a target that is small, large, split or relabelled (it
+// has no record of the round before); a target that is G itself (no finite group is all-equal on itself: a guard only, the chain round's
+// groups have a majority, not all, that looks at the group and are never recorded).
+// The records read are the round before's, the ones written this round's (FwdView::verdictWas / verdictNow): no thread sees its target's
+// new state. Another thread may void the descriptor a search reads: the start stays, and sizes come from the records.
+__device__ __forceinline__ bool sleep_target(const FwdView& v, const uint2* __restrict__ desc, u32 nDesc, u32 lab, u32 bb, bool plain, u32& start, u32& key)
+{
+    u32 lo = 0, hi = nDesc;                                 // first descriptor that starts behind the label
+    while (lo < hi) { const u32 mid = (lo + hi) >> 1; if (desc[mid].x <= lab) lo = mid + 1; else hi = mid; }
+    if (lo == 0) return false;
+    start = desc[lo - 1].x;
+    const uint2 t = v.verdictWas[start >> 8];
+    const u32 status = (t.y >> 16) & 3u;
+    if ((t.y >> 24) != v.round - 1u || (plain ? status != VERDICT_PLAIN : status == 0u) || lab - start >= (t.y & 0xFFFFu)) return false;
+    key = t.x;
+    return lab_old(v, v.SA[start], bb) == lab;              // the group of that range does carry the label
+}
+
+__global__ __launch_bounds__(256) void k_bwt_f_med_sleep(FwdView v, uint2* __restrict__ desc, u32 nDesc, int stats)
+{
+    const u32 g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= nDesc) return;
+    const uint2 d = desc[g];
+    if (d.y <= SM_G || d.y > MED_CAP) return;
+    const uint2 was = v.verdictWas[d.x >> 8];
+    if (was.y != verdict_word(v.round - 1u, VERDICT_PLAIN, d.y)) return;
+    if (v.rtbits && ((v.rtbits[d.x >> 5] >> (d.x & 31)) & 1u)) return;
+    const u32 bb = v.base[find_block(v.base, v.nBlocks, d.x)];
+    u32 s1, k1, s2, k2;
+    if (!sleep_target(v, desc, nDesc, bb + was.x - 1u, bb, true, s1, k1) || s1 == d.x) return;
+    if (!sleep_target(v, desc, nDesc, bb + k1 - 1u, bb, false, s2, k2) || s2 == d.x) return;
+    v.verdictNow[d.x >> 8] = make_uint2(k1, verdict_word(v.round, VERDICT_PLAIN, d.y));
+    v.medStage[d.x >> 8] = d;
+    desc[g] = make_uint2(d.x, 0u);
+    if (stats) {
+        atomicAdd(&v.counters[CNT_STAT_MED], d.y); atomicAdd(&v.counters[CNT_STAT_MED_GROUPS], 1u);
+        atomicAdd(&v.counters[CNT_STAT_UNSPLIT], 1u); atomicAdd(&v.counters[CNT_STAT_UNSPLIT_MEMBERS], d.y);
+        atomicAdd(&v.counters[CNT_STAT_ASLEEP], 1u); atomicAdd(&v.counters[CNT_STAT_ASLEEP_MEMBERS], d.y);
     }
 }
 
@@ -2282,14 +2347,15 @@ __global__ __launch_bounds__(256) void k_bwt_f_med_compact(uint2* __restrict__ s
 // knobs (tests, diagnostics): read from the environment once per process, or set through knz_hip_tune(). Each one forces, at test
 // sizes, a path that some inputs take by themselves (round-0 key length, no run round, the run groups' fall-back, the plain labels of
 // blocks above 256 MiB, the plain keys of blocks above 8 MiB, where the link step starts), or reports (stats).
-struct FwdTuning { int nsym; int noRunRound; int runFallback; int stats; int link; int plainLabels; int noPack; int noUnsplitSkip; };
+struct FwdTuning { int nsym; int noRunRound; int runFallback; int stats; int link; int plainLabels; int noPack; int noUnsplitSkip; int noGroupSleep; };
 static FwdTuning& fwd_tuning()
 {
     static FwdTuning t = [] {
-        FwdTuning x; x.nsym = 0; x.noRunRound = 0; x.runFallback = 0; x.stats = 0; x.link = 1; x.plainLabels = 0; x.noPack = 0; x.noUnsplitSkip = 0;     // link: 0 off, 1 on (from h = 32), n > 1: from h = n
+        FwdTuning x; x.nsym = 0; x.noRunRound = 0; x.runFallback = 0; x.stats = 0; x.link = 1; x.plainLabels = 0; x.noPack = 0; x.noUnsplitSkip = 0; x.noGroupSleep = 0;     // link: 0 off, 1 on (from h = 32), n > 1: from h = n
         if (getenv("KNZ_BWT_PLAIN_LABELS")) x.plainLabels = 1;
         if (getenv("KNZ_BWT_NO_PACK")) x.noPack = 1;
         if (getenv("KNZ_BWT_NO_UNSPLIT_SKIP")) x.noUnsplitSkip = 1;
+        if (getenv("KNZ_BWT_NO_GROUP_SLEEP")) x.noGroupSleep = 1;
         if (const char* e = getenv("KNZ_BWT_LINK")) x.link = atoi(e);
         if (getenv("KNZ_BWT_STATS")) x.stats = 1;
         if (const char* e = getenv("KNZ_BWT_NSYM")) x.nsym = atoi(e);
@@ -2311,6 +2377,7 @@ int bwt_forward_tune(const char* key, int value)
     else if (!strcmp(key, "bwt_plain_labels")) t.plainLabels = value;
     else if (!strcmp(key, "bwt_no_pack")) t.noPack = value;      // small groups ranked on plain keys (three counts per pair) also where the packed keys fit
     else if (!strcmp(key, "bwt_no_unsplit_skip")) t.noUnsplitSkip = value;      // medium groups whose keys are all equal stored and sorted like any other
+    else if (!strcmp(key, "bwt_no_group_sleep")) t.noGroupSleep = value;        // every such group gathered in every round (no k_bwt_f_med_sleep, no records)
     else return -1;
     return 0;
 }
@@ -2321,7 +2388,7 @@ struct FwdScratch {
     u32* SA; u32* ISA; u32* K; u64* ISA2;
     u32* t0; u32* t1; u32* t2; u32* t3;
     u32* gbits; u32* gnew; u32* rtbits; u32* ovr; size_t gbitsWords;
-    uint2* med[2]; uint2* medStage; u32* medFlags; u32* medPrefix; size_t medSlots; uint2* descInfo; uint2* large[2]; uint2* runList; uint4* superList; u32* ebits;
+    uint2* med[2]; uint2* medStage; uint2* medVerdict[2]; u32* medFlags; u32* medPrefix; size_t medSlots; uint2* descInfo; uint2* large[2]; uint2* runList; uint4* superList; u32* ebits;
     u32* loff; u32* lbase;
     u32* survTile;       // members still tied after a round's small-group sort, per window
     u32* linkedTile;     // members the link step linked, per window
@@ -2359,6 +2426,7 @@ static size_t fwd_carve(u8* p, int nBlocks, size_t total, FwdScratch* w, u32 VS)
     w->med[0] = (uint2*)take(8 * maxMed); w->med[1] = (uint2*)take(8 * maxMed);
     w->medSlots = total / 256 + 2;
     w->medStage = (uint2*)take(8 * w->medSlots); w->medFlags = (u32*)take(4 * w->medSlots + 64); w->medPrefix = (u32*)take(4 * w->medSlots + 64);
+    w->medVerdict[0] = (uint2*)take(16 * w->medSlots); w->medVerdict[1] = w->medVerdict[0] + w->medSlots;
     w->large[0] = (uint2*)take(8 * maxLarge); w->large[1] = (uint2*)take(8 * maxLarge);
     w->runList = (uint2*)take(8 * maxMed);
     w->superList = (uint4*)take(16 * maxMed);
@@ -2429,6 +2497,7 @@ struct FwdSort {
     BwtView bv; FwdView v; FwdScratch w; size_t maxTotal;
     prims::RsWs rs1;                                       // the single-segment sorts of the rounds: [0, seg2[1])
     u32 total, medSlots, nTiles; int nsym, pbits, kbits;   // (tiles: windows of SM_TS slots)
+    bool groupSleep = false;                               // medium groups sleep through rounds whose verdict is known (k_bwt_f_med_sleep)
     u32 h = 1; int cur = 0;                                // offset of the doubling round; its lists w.med[cur], w.large[cur] (the next round's: cur ^ 1)
     u64 *keysFree, *keysFree2;                             // key buffers of the rounds (keysFree2: round 0's sorted keys until they are placed)
     u32 nRun, runElems, surv, nMed, nLarge, largeElems, survMembers;   // run groups of round 0 and their members; left: small groups (!= 0),
@@ -2480,9 +2549,12 @@ struct FwdSort {
         if (total == 0) return 0;
         v.base = w.base; v.nBlocks = st.nBlocks; v.total = total; v.SA = w.SA; v.ISA = w.ISA; v.K = w.K; v.ISA2 = (w.ISA2 != nullptr && !tune.plainLabels) ? w.ISA2 : (u64*)nullptr;
         v.round = 0; v.gbits = w.gbits; v.gnew = w.gnew; v.counters = w.counters; v.medStage = w.medStage; v.ovr = nullptr; v.rtbits = nullptr;
+        v.verdictNow = nullptr; v.verdictWas = nullptr;
         medSlots = (u32)((size_t)total / 256 + 1); nTiles = (total + SM_TS - 1) / SM_TS;
         survMembers = total;                                          // (not counted before the first round: assume many)
         hipMemsetAsync(w.medStage, 0, 8ull * w.medSlots, s);
+        groupSleep = !tune.noUnsplitSkip && !tune.noGroupSleep;      // (the records are the verdicts of the unsplit skip)
+        if (groupSleep) hipMemsetAsync(w.medVerdict[0], 0, 16ull * w.medSlots, s);      // (round 0 in every record: no round reads that)
         pbits = bits_for(hp[CNT_LONGEST_BLOCK], 1);                   // positions inside the longest block the transform applies to
         // Four or five symbols (as many as fit the key beside the position when the block is larger than 8 / 16 MiB), by the batch's order-0
         // entropy (k_bwt_f_choose_nsym). Measured on 212 MB with 8 MiB blocks, MB/s of the whole round trip, round 3: 4 symbols 4437 (mixed
@@ -2716,8 +2788,8 @@ struct FwdSort {
             fprintf(stderr, "round h=%u (%.3f ms): small members worked on %u in %u groups, medium members %u; after it: small left %u, medium groups %u, large %u (%u members); %u groups took the chain round; %u small members still tied\n",
                     h, std::chrono::duration<double, std::milli>(now - statT).count(), hp[CNT_STAT_SMALL], hp[CNT_STAT_SMALL_GROUPS], hp[CNT_STAT_MED], surv, nMed, nLarge, largeElems,
                     hp[CNT_SUPER], hp[CNT_TIED]);
-            fprintf(stderr, "  medium groups worked on %u (%u members): all keys equal in %u (%u members)%s, majority path %u (%u members)\n", hp[CNT_STAT_MED_GROUPS], hp[CNT_STAT_MED],
-                    hp[CNT_STAT_UNSPLIT], hp[CNT_STAT_UNSPLIT_MEMBERS], tune.noUnsplitSkip ? "" : " -- left alone", hp[CNT_STAT_MAJ], hp[CNT_STAT_MAJ_MEMBERS]);
+            fprintf(stderr, "  medium groups worked on %u (%u members): all keys equal in %u (%u members)%s, majority path %u (%u members), asleep %u (%u members)\n", hp[CNT_STAT_MED_GROUPS], hp[CNT_STAT_MED],
+                    hp[CNT_STAT_UNSPLIT], hp[CNT_STAT_UNSPLIT_MEMBERS], tune.noUnsplitSkip ? "" : " -- left alone", hp[CNT_STAT_MAJ], hp[CNT_STAT_MAJ_MEMBERS], hp[CNT_STAT_ASLEEP], hp[CNT_STAT_ASLEEP_MEMBERS]);
             statT = now;
         }
         cur ^= 1; h <<= 1;
@@ -2734,6 +2806,9 @@ struct FwdSort {
         if (linked) link_step();
         // (with versioned labels the small groups fetch their keys in k_bwt_f_small_fused; the medium list is in slot order: k_bwt_f_med_compact)
         if (surv && !v.ISA2) { KScope ks_("k_bwt_f_gather_small"); hipLaunchKernelGGL(k_bwt_f_gather_small, dim3(nTiles), dim3(256), 0, s, v, h, tune.stats); }
+        // the first round's list is not in slot order (the probe appends) and has no round before it
+        if (groupSleep) { v.verdictNow = w.medVerdict[v.round & 1]; v.verdictWas = w.medVerdict[(v.round & 1) ^ 1]; }
+        if (groupSleep && nMed && v.round >= 2) { KScope ks_("k_bwt_f_med_sleep"); hipLaunchKernelGGL(k_bwt_f_med_sleep, GRID1(nMed), v, w.med[cur], nMed, tune.stats); }
         if (nMed) { KScope ks_("k_bwt_f_gather_desc"); hipLaunchKernelGGL(k_bwt_f_gather_desc, dim3(1024), dim3(GATHER_THREADS), 0, s, v, w.med[cur], nMed, h, w.descInfo, tune.stats, tune.noUnsplitSkip ? 0 : 1); }
         const int lbits = bits_for(nLarge, 0); const bool key32 = kbits + lbits <= 32;
         if (nLarge) { if (key32) large_keys<u32>(); else large_keys<u64>(); }
