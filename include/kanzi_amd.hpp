@@ -277,6 +277,16 @@ public:
 private:
     Context* _ctx;
 };
+// transform/FSDCodec.hpp: MM, getMaxEncodedLength = n + (n < 1024 ? 64 : n >> 4). forward() reads the Context's "dataType" and writes
+// back what the stage left there (MULTIMEDIA, or detectSimpleType's verdict of its samples: FSDCodec.cpp:124-129, :198-207).
+class FSDCodec : public DeviceTransform {
+public:
+    FSDCodec() : DeviceTransform(KNZ_T_MM, nullptr), _ctx(nullptr) {}
+    explicit FSDCodec(Context& ctx) : DeviceTransform(KNZ_T_MM, &ctx), _ctx(&ctx) {}
+    bool forward(SliceArray<byte>& src, SliceArray<byte>& dst, int length);
+private:
+    Context* _ctx;
+};
 class SBRT : public DeviceTransform {
 public:
     static const int MODE_MTF = 1, MODE_RANK = 2, MODE_TIMESTAMP = 3;

@@ -28,7 +28,7 @@ extern "C" {
 
 /* kanzi ids: entropy (entropy/EntropyEncoderFactory.hpp:37-52) and transforms (transform/TransformFactory.hpp:49-73) */
 enum { KNZ_E_NONE = 0, KNZ_E_HUFFMAN = 1, KNZ_E_FPAQ = 2, KNZ_E_ANS0 = 5, KNZ_E_ANS1 = 8 };
-enum { KNZ_T_NONE = 0, KNZ_T_BWT = 1, KNZ_T_BWTS = 2, KNZ_T_LZ = 3, KNZ_T_RLT = 5, KNZ_T_ZRLT = 6, KNZ_T_MTFT = 7, KNZ_T_RANK = 8, KNZ_T_SRT = 13, KNZ_T_LZX = 16, KNZ_T_PACK = 18,
+enum { KNZ_T_NONE = 0, KNZ_T_BWT = 1, KNZ_T_BWTS = 2, KNZ_T_LZ = 3, KNZ_T_RLT = 5, KNZ_T_ZRLT = 6, KNZ_T_MTFT = 7, KNZ_T_RANK = 8, KNZ_T_SRT = 13, KNZ_T_MM = 15, KNZ_T_LZX = 16, KNZ_T_PACK = 18,
        KNZ_T_TIMESTAMP = 64 /* SBRT's third mode: no kanzi id, never part of a chain; per-stage entry points only */,
        KNZ_T_TEXT = 10, KNZ_T_UTF = 17 /* stages that run on the HOST in front of the device chain: knz_hip_encode_block_hosted / _decode_ */ };
 
@@ -111,7 +111,7 @@ KNZ_API int knz_hip_decode_blocks(knz_ctx* ctx, const knz_params* p, const uint8
  *                 device stages see); clear = the stage refused the block and the block went on unchanged
  *   orig_len      length of the block before any stage (decides copy blocks and the buffer sizes of the reference)
  *   reserved      the data type the host stages left in the block's Context (Global::DataType: 0 UNDEFINED, 1 TEXT, 2 MULTIMEDIA,
- *                 3 EXE, 4 NUMERIC, 5 BASE64, 6 DNA, 7 BIN, 8 UTF8, 9 SMALL_ALPHABET); the device stages that read it (PACK) start
+ *                 3 EXE, 4 NUMERIC, 5 BASE64, 6 DNA, 7 BIN, 8 UTF8, 9 SMALL_ALPHABET); the device stages that read it (PACK, MM) start
  *                 from it. 0 when the caller does not track it; values above 9 count as 0
  *   checksum      XXHash32 / 64 of the ORIGINAL block when p->checksum_bits != 0 (the device only ever sees the transformed bytes)
  * d_in holds the n bytes the host stages left. Everything else as knz_hip_encode_blocks with exactly one block; the block header
@@ -156,6 +156,7 @@ KNZ_API int knz_hip_entropy_decode_v(knz_ctx* ctx, int entropy_type, int bs_vers
  *   KNZ_T_RLT   RLT                  transform/RLT.cpp:39-221,247-369
  *   KNZ_T_LZ / KNZ_T_LZX   LZCodec -> LZXCodec<false> / LZXCodec<true>   transform/LZCodec.cpp:119-456,470-640
  *   KNZ_T_PACK  AliasCodec           transform/AliasCodec.cpp:38-209,211-371
+ *   KNZ_T_MM    FSDCodec             transform/FSDCodec.cpp:103-291,293-386
  * (the inverse of LZ/LZX expects what the reference expects: two readable bytes behind `in + n`,
  * LZCodec.cpp:486-490; the library stages the input itself, so callers need not pad). */
 KNZ_API int knz_hip_transform_forward(knz_ctx* ctx, int transform_type, const uint8_t* in, int32_t n,
@@ -164,7 +165,8 @@ KNZ_API int knz_hip_transform_inverse(knz_ctx* ctx, int transform_type, const ui
                                       uint8_t* out, int32_t dst_cap, int32_t* out_len, int32_t* ok);
 /* The forward stage with the "dataType" entry of the block's Context (Global::DataType, 0 UNDEFINED .. 9 SMALL_ALPHABET, as in
  * knz_host_stages.reserved): *data_type goes in, and comes back as the stage left it. PACK refuses MULTIMEDIA, UTF8, EXE and
- * BIN and sets detectSimpleType's result on an UNDEFINED block; RLT refuses DNA, BASE64 and UTF8; the other stages ignore it.
+ * BIN and sets detectSimpleType's result on an UNDEFINED block; MM takes UNDEFINED, MULTIMEDIA and BIN blocks only and leaves
+ * MULTIMEDIA once it has found a distance, or detectSimpleType's result of its samples when it has not; RLT refuses DNA, BASE64 and UTF8; the other stages ignore it.
  * knz_hip_transform_forward is this call with a fresh Context (UNDEFINED). */
 KNZ_API int knz_hip_transform_forward_dt(knz_ctx* ctx, int transform_type, const uint8_t* in, int32_t n, uint8_t* out,
                                          int32_t dst_cap, int entropy_type, int32_t* data_type, int32_t* out_len, int32_t* ok);

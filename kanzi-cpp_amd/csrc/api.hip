@@ -585,6 +585,11 @@ static const XfInfo XF[] = {
       .fwd = { .wsBytes = pack_scratch_bytes, .launch = [](const StageCall& k) { launch_pack_forward(k.s, k.st, k.ws); return 0; } },
       .inv = { .wsBytes = pack_scratch_bytes, .launch = [](const StageCall& k) { launch_pack_inverse(k.s, k.st, k.ws); return 0; } },
       .setsType = true },
+    // (FSDCodec; it leaves MULTIMEDIA or detectSimpleType's verdict on the blocks it looks at, which RLT behind it reads)
+    { .id = KNZ_T_MM, .ws = "mmScratch",
+      .fwd = { .wsBytes = mm_scratch_bytes, .launch = [](const StageCall& k) { launch_mm_forward(k.s, k.st, k.ws); return 0; } },
+      .inv = { .wsBytes = mm_scratch_bytes, .launch = [](const StageCall& k) { launch_mm_inverse(k.s, k.st, k.ws); return 0; } },
+      .setsType = true },
 };
 
 static const XfInfo* xf_info(int t) { for (const XfInfo& x : XF) if (x.id == t) return &x; return nullptr; }

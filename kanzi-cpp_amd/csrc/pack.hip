@@ -17,6 +17,7 @@
 // byte is written, and nothing is written for a block they reject.
 #include "common.hpp"
 #include "stages.hpp"
+#include "datatype.hpp"
 
 namespace knz {
 
@@ -29,7 +30,6 @@ constexpr u32 PK_MIN = 1024;                    // AliasCodec::MIN_BLOCK_SIZE
 constexpr int PK_SEL_T = 1024;                  // threads of the pair selection (64 bins each)
 
 enum { PK_NONE = 0, PK_ONE = 1, PK_BITS2 = 2, PK_BITS4 = 3, PK_DIGRAM = 4 };
-enum { DT_UNDEFINED = 0, DT_TEXT, DT_MULTIMEDIA, DT_EXE, DT_NUMERIC, DT_BASE64, DT_DNA, DT_BIN, DT_UTF8, DT_SMALL_ALPHABET };
 
 // per-block scratch (u32 words)
 constexpr u32 PK_H0 = 0;                        // [256] order-0 histogram
@@ -116,26 +116,6 @@ __device__ __forceinline__ PkFn pk_walk(const u8* __restrict__ src, const u32* _
     }
     f.x0 = xs[0]; f.x1 = xs[1]; f.c0 = cs[0]; f.c1 = cs[1];
     return f;
-}
-
-__device__ int pk_simple_type(u32 count, const u32* f0)            // Global::detectSimpleType
-{
-    const char dna[] = "acgntuACGNTU";
-    const char num[] = "0123456789+-*/=,.:; ";
-    const char b64[] = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/";
-    int sum = 0;
-    for (int i = 0; i < 12; i++) sum += (int)f0[(u8)dna[i]];
-    if (sum > (int)count - (int)count / 12) return DT_DNA;
-    sum = 0;
-    for (int i = 0; i < 20; i++) sum += (int)f0[(u8)num[i]];
-    if (sum == (int)count) return DT_NUMERIC;
-    sum = (f0[0x3D] == 1) ? 1 : 0;
-    for (int i = 0; i < 64; i++) sum += (int)f0[(u8)b64[i]];
-    if (sum == (int)count) return DT_BASE64;
-    int distinct = 0;
-    for (int i = 0; i < 256; i++) distinct += f0[i] ? 1 : 0;
-    if (distinct == 256) return DT_BIN;
-    return distinct <= 4 ? DT_SMALL_ALPHABET : DT_UNDEFINED;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

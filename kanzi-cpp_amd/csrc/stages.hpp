@@ -61,7 +61,7 @@ struct XfStage {
     int entropyType;         // stream entropy id (RLT escape choice)
     int bsVersion = 6;       // bitstream version the blocks come from (inverse only: BWT block header of versions below 6)
     u32 maxCap = 0;          // upper bound of cap[] when the host knows one (inverse stages that size scratch by their output)
-    u8* dtype = nullptr;     // per-block Global::DataType (0 = UNDEFINED) read and written by PACK; nullptr: a fresh context per block
+    u8* dtype = nullptr;     // per-block Global::DataType (0 = UNDEFINED) read and written by PACK and MM; nullptr: a fresh context per block
 };
 
 // zrlt_mtft.hip
@@ -91,6 +91,11 @@ size_t bwts_inverse_scratch_bytes(int nBlocks, u32 VS, size_t total);
 void launch_pack_forward(hipStream_t s, const XfStage& st, void* scratch);
 void launch_pack_inverse(hipStream_t s, const XfStage& st, void* scratch);
 size_t pack_scratch_bytes(int nBlocks, u32 maxLen);
+
+// mm.hip (FSDCodec; scratch: mm_scratch_bytes(nBlocks, maxLen) bytes; reads and writes XfStage::dtype like PACK)
+void launch_mm_forward(hipStream_t s, const XfStage& st, void* scratch);
+void launch_mm_inverse(hipStream_t s, const XfStage& st, void* scratch);
+size_t mm_scratch_bytes(int nBlocks, u32 maxLen);
 
 // fpaq.hip (probs: fpaq_probs_bytes(nBlocks, S) bytes of scratch, S = upper bound of the block lengths)
 void launch_fpaq_encode(hipStream_t s, BlockView view, const u32* origLen, u32 copyThreshold, int nBlocks, int maxChunks, ChunkDesc* desc, u8* tmp, u64 tmpStride,

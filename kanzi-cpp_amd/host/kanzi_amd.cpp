@@ -477,6 +477,28 @@ bool AliasCodec::forward(SliceArray<byte>& src, SliceArray<byte>& dst, int lengt
     return true;
 }
 
+bool FSDCodec::forward(SliceArray<byte>& src, SliceArray<byte>& dst, int length)
+{
+    if (_ctx == nullptr) return DeviceTransform::forward(src, dst, length);
+    if (length == 0) return true;
+    if (!SliceArray<byte>::isValid(src)) throw std::invalid_argument("FSD codec: Invalid input block");
+    if (!SliceArray<byte>::isValid(dst)) throw std::invalid_argument("FSD codec: Invalid output block");
+    if ((length < 0) || (length > src._length - src._index)) return false;
+    if (src._array == dst._array) return false;
+    if (&knz_hip_transform_forward_dt == nullptr) throw std::runtime_error("the device library has no MM stage");
+    int32_t dt = _ctx->getInt("dataType", hoststage::DT_UNDEFINED);
+    if (dt < 0 || dt > 9) dt = hoststage::DT_UNDEFINED;
+    knz_ctx* c = deviceContext();
+    int32_t outLen = 0, ok = 0;
+    devCheck(c, knz_hip_transform_forward_dt(c, _type, src._array + src._index, length, dst._array + dst._index,
+                                             dst._length - dst._index, _entropy, &dt, &outLen, &ok), "transform forward");
+    _ctx->putInt("dataType", dt);           // (the quick exit writes detectSimpleType's verdict whatever it is)
+    if (!ok) return false;
+    src._index += length;
+    dst._index += outLen;
+    return true;
+}
+
 // BWTS.cpp:44-52 / :196-202: a block above MAX_BLOCK_SIZE is not a recoverable error
 static void bwtsCheckSize(int length)
 {
@@ -904,6 +926,7 @@ TransformSequence<T>* TransformFactory<T>::newTransform(Context& ctx, uint64 fun
             case BWT_TYPE: transforms[nbtr++] = new BWTBlockCodec(ctx); break;
             case BWTS_TYPE: transforms[nbtr++] = new BWTS(ctx); break;
             case PACK_TYPE: transforms[nbtr++] = new AliasCodec(ctx); break;
+            case MM_TYPE: transforms[nbtr++] = new FSDCodec(ctx); break;
             case MTFT_TYPE: transforms[nbtr++] = new SBRT(SBRT::MODE_MTF, ctx); break;
             case RANK_TYPE: transforms[nbtr++] = new SBRT(SBRT::MODE_RANK, ctx); break;
             case SRT_TYPE: transforms[nbtr++] = new SRT(ctx); break;
