@@ -416,6 +416,18 @@ class HuffmanEncoder : public DeviceEntropyEncoder { public: HuffmanEncoder(Outp
 class HuffmanDecoder : public DeviceEntropyDecoder { public: HuffmanDecoder(InputBitStream& ibs, Context* pCtx = nullptr, int chunkSize = HuffmanCommon::MAX_CHUNK_SIZE); };
 class FPAQEncoder : public DeviceEntropyEncoder { public: explicit FPAQEncoder(OutputBitStream& obs) : DeviceEntropyEncoder(obs, KNZ_E_FPAQ) {} };
 class FPAQDecoder : public DeviceEntropyDecoder { public: explicit FPAQDecoder(InputBitStream& ibs) : DeviceEntropyDecoder(ibs, KNZ_E_FPAQ) {} };
+// entropy/RangeEncoder.hpp:39, RangeDecoder.hpp:43: chunks of 32 KiB, log range 12 (lowered for short chunks by the coder itself); the same
+// checks and messages, and the same refusal of a valid value other than the default.
+class RangeEncoder : public DeviceEntropyEncoder {
+public:
+    static const int DEFAULT_CHUNK_SIZE = 1 << 15, DEFAULT_LOG_RANGE = 12, MAX_CHUNK_SIZE = 1 << 30;
+    RangeEncoder(OutputBitStream& obs, int chunkSize = DEFAULT_CHUNK_SIZE, int logRange = DEFAULT_LOG_RANGE);
+};
+class RangeDecoder : public DeviceEntropyDecoder {
+public:
+    static const int DEFAULT_CHUNK_SIZE = 1 << 15, MAX_CHUNK_SIZE = 1 << 30;
+    RangeDecoder(InputBitStream& ibs, int chunkSize = DEFAULT_CHUNK_SIZE);
+};
 class NullEntropyEncoder : public DeviceEntropyEncoder { public: explicit NullEntropyEncoder(OutputBitStream& obs) : DeviceEntropyEncoder(obs, KNZ_E_NONE) {} };
 class NullEntropyDecoder : public DeviceEntropyDecoder { public: explicit NullEntropyDecoder(InputBitStream& ibs) : DeviceEntropyDecoder(ibs, KNZ_E_NONE) {} };
 

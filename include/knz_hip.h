@@ -27,7 +27,7 @@ extern "C" {
 #define KNZ_API __attribute__((visibility("default")))
 
 /* kanzi ids: entropy (entropy/EntropyEncoderFactory.hpp:37-52) and transforms (transform/TransformFactory.hpp:49-73) */
-enum { KNZ_E_NONE = 0, KNZ_E_HUFFMAN = 1, KNZ_E_FPAQ = 2, KNZ_E_ANS0 = 5, KNZ_E_ANS1 = 8 };
+enum { KNZ_E_NONE = 0, KNZ_E_HUFFMAN = 1, KNZ_E_FPAQ = 2, KNZ_E_RANGE = 4, KNZ_E_ANS0 = 5, KNZ_E_ANS1 = 8 };
 enum { KNZ_T_NONE = 0, KNZ_T_BWT = 1, KNZ_T_BWTS = 2, KNZ_T_LZ = 3, KNZ_T_RLT = 5, KNZ_T_ZRLT = 6, KNZ_T_MTFT = 7, KNZ_T_RANK = 8, KNZ_T_SRT = 13, KNZ_T_MM = 15, KNZ_T_LZX = 16, KNZ_T_PACK = 18,
        KNZ_T_TIMESTAMP = 64 /* SBRT's third mode: no kanzi id, never part of a chain; per-stage entry points only */,
        KNZ_T_TEXT = 10, KNZ_T_UTF = 17 /* stages that run on the HOST in front of the device chain: knz_hip_encode_block_hosted / _decode_ */ };
@@ -214,6 +214,10 @@ KNZ_API int knz_hip_get_kernel_times(knz_ctx* ctx, knz_kernel_time* out, int cap
  * batch size, 1024 / 4096 force it), "mtf_chain" (1: MTFT forward ranks by the byte-serial kernel of rounds 2-4).
  * Returns 0, or -1 for an unknown name. No knob changes a result. */
 KNZ_API int knz_hip_tune(const char* name, int value);
+
+/* Test hook: q[i] = floor(d[i] / r[i]) by the RANGE decoder's reciprocal-based divide (host arrays; every pair must satisfy what the
+ * decoder has checked before it divides: r >= 1 and d < r * 2^15). */
+KNZ_API int knz_hip_range_divide(knz_ctx* ctx, const uint64_t* d, const uint64_t* r, uint32_t n, uint32_t* q);
 
 #ifdef __cplusplus
 }

@@ -52,9 +52,7 @@ __global__ __launch_bounds__(64) void k_ans0_stats(BlockView view, int maxChunks
     }
     const u32 n = (len - start < ENT_CHUNK) ? (len - start) : ENT_CHUNK;
 
-    // 8 private histograms, chosen by lane: one ds_add instruction never sends more than 8 lanes to the same
-    // copy, which is what bounds the same-address serialisation on skewed data (text: 15 % spaces)
-    __shared__ u32 hist[8][264];                 // row stride 264: copy c of a symbol sits 8c banks away, not in the same bank
+    __shared__ u32 hist[8][264];                 // 8 private histograms (ans_chunk_counts)
     __shared__ u32 hdrw[HDR_WORDS];
     __shared__ u32 grpMax[64];
     for (int i = lane; i < 8 * 264; i += 64) (&hist[0][0])[i] = 0;
@@ -62,39 +60,9 @@ __global__ __launch_bounds__(64) void k_ans0_stats(BlockView view, int maxChunks
     grpMax[lane] = 0;
     __syncthreads();
 
-    // ---- histogram (Global.cpp:170-221): 16 bytes per lane per iteration
-    u32* myHist = hist[lane & 7];
-    const u32 n16 = n & ~15u;
-    const bool aligned = ((reinterpret_cast<uintptr_t>(blk) & 15) == 0);
-    if (aligned) {
-        const uint4* p4 = reinterpret_cast<const uint4*>(blk);
-        for (u32 i = lane; i < (n16 >> 4); i += 64) {
-            const uint4 v = p4[i];
-            const u32 w[4] = { v.x, v.y, v.z, v.w };
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                atomicAdd(&myHist[w[k] & 0xFF], 1u);
-                atomicAdd(&myHist[(w[k] >> 8) & 0xFF], 1u);
-                atomicAdd(&myHist[(w[k] >> 16) & 0xFF], 1u);
-                atomicAdd(&myHist[w[k] >> 24], 1u);
-            }
-        }
-    } else {
-        for (u32 i = lane; i < n16; i += 64) atomicAdd(&myHist[blk[i]], 1u);
-    }
-    for (u32 i = n16 + lane; i < n; i += 64) atomicAdd(&myHist[blk[i]], 1u);
-    __syncthreads();
-
     // lane owns symbols 4*lane .. 4*lane+3
     u32 f[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int s = 4 * lane + k;
-        u32 acc = 0;
-#pragma unroll
-        for (int c = 0; c < 8; c++) acc += hist[c][s];
-        f[k] = acc;
-    }
+    ans_chunk_counts(lane, blk, n, hist, f);
     u32 present = 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) present |= (f[k] != 0 ? 1u : 0u) << k;

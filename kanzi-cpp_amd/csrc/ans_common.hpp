@@ -5,13 +5,53 @@
 namespace knz {
 
 // ------------------------------------------------------------------------------------------------
+// Byte counts of one chunk by one wave (Global.cpp:170-221), shared by the order-0 rANS and the RANGE statistics kernels: 16 bytes per
+// lane per iteration into 8 private histograms chosen by lane -- one ds_add instruction never sends more than 8 lanes to the same copy,
+// which is what bounds the same-address serialisation on skewed data (text: 15 % spaces). Row stride 264: copy c of a symbol sits 8c
+// banks away, not in the same bank. `hist` must be zero; f[k] = count of symbol 4 * lane + k.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void ans_chunk_counts(int lane, const u8* blk, u32 n, u32 (*hist)[264], u32 f[4])
+{
+    u32* myHist = hist[lane & 7];
+    const u32 n16 = n & ~15u;
+    const bool aligned = ((reinterpret_cast<uintptr_t>(blk) & 15) == 0);
+    if (aligned) {
+        const uint4* p4 = reinterpret_cast<const uint4*>(blk);
+        for (u32 i = lane; i < (n16 >> 4); i += 64) {
+            const uint4 v = p4[i];
+            const u32 w[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                atomicAdd(&myHist[w[k] & 0xFF], 1u);
+                atomicAdd(&myHist[(w[k] >> 8) & 0xFF], 1u);
+                atomicAdd(&myHist[(w[k] >> 16) & 0xFF], 1u);
+                atomicAdd(&myHist[w[k] >> 24], 1u);
+            }
+        }
+    } else {
+        for (u32 i = lane; i < n16; i += 64) atomicAdd(&myHist[blk[i]], 1u);
+    }
+    for (u32 i = n16 + lane; i < n; i += 64) atomicAdd(&myHist[blk[i]], 1u);
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int s = 4 * lane + k;
+        u32 acc = 0;
+#pragma unroll
+        for (int c = 0; c < 8; c++) acc += hist[c][s];
+        f[k] = acc;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // pieces shared by order 0 (one table per 16 KiB chunk) and order 1 (one table per context of a 4 MiB chunk);
 // one wave, lane owns symbols 4*lane .. 4*lane+3
 // ------------------------------------------------------------------------------------------------
-template <u32 LR>
-__device__ void ans_normalize(int lane, u32 f[4], u32 n, u32 asz)
+// (LR a run-time value: the RANGE coder lowers it for short chunks; the rANS coders pass a constant through the wrappers below, which the
+// compiler folds)
+__device__ __forceinline__ void ans_normalize_lr(int lane, u32 f[4], u32 n, u32 asz, const u32 LR)
 {
-    constexpr u32 SCALE = 1u << LR;
+    const u32 SCALE = 1u << LR;
     // normalizeFrequencies (EntropyUtils.cpp:131-245), totalFreq = n, scale = 2^LR
     if (n != SCALE) {
         if (asz == 1) {
@@ -105,13 +145,16 @@ __device__ void ans_normalize(int lane, u32 f[4], u32 n, u32 asz)
 
 }
 
-// Appends the alphabet + frequency groups of one table to the LDS bit buffer `hdrw` at bit `pos`
-// (ANSRangeEncoder.cpp:119-155, EntropyUtils.cpp:57-89); returns the new position.
 template <u32 LR>
-__device__ u32 ans_header_bits(int lane, const u32 f[4], u32 present, u32 asz, u32 rankBase, bool lrPrefix,
-                               u32* hdrw, u32* grpMax, u32* grpOff, u32 pos)
+__device__ void ans_normalize(int lane, u32 f[4], u32 n, u32 asz) { ans_normalize_lr(lane, f, n, asz, LR); }
+
+// Appends the alphabet + frequency groups of one table to the LDS bit buffer `hdrw` at bit `pos`
+// (ANSRangeEncoder.cpp:119-155, EntropyUtils.cpp:57-89); returns the new position. The 3 bits of LR - 8 go in front of the alphabet
+// (lrWhere 1: rANS order 0), behind a non-empty one (2: RANGE, RangeEncoder.cpp:83-93) or nowhere (0).
+__device__ __forceinline__ u32 ans_header_bits_lr(int lane, const u32 f[4], u32 present, u32 asz, u32 rankBase, int lrWhere, const u32 LR,
+                                                  u32* hdrw, u32* grpMax, u32* grpOff, u32 pos)
 {
-    if (lrPrefix) { if (lane == 0) or_bits_words(hdrw, pos, LR - 8, 3); pos += 3; }
+    if (lrWhere == 1) { if (lane == 0) or_bits_words(hdrw, pos, LR - 8, 3); pos += 3; }
     if (asz == 0) {
         if (lane == 0) or_bits_words(hdrw, pos, 1, 2);   // FULL_ALPHABET(0), ALPHABET_0(1)
         pos += 2;
@@ -135,10 +178,11 @@ __device__ u32 ans_header_bits(int lane, const u32 f[4], u32 present, u32 asz, u
         }
         pos += 8 * (lastMask + 1);
     }
+    if (lrWhere == 2 && asz != 0) { if (lane == 0) or_bits_words(hdrw, pos, LR - 8, 3); pos += 3; }
 
     if (asz > 1) {
         const u32 chk = (asz >= 64) ? 8u : 6u;
-        const u32 llr = 4;                           // log2(12) + 1
+        const u32 llr = 4;                           // log2(LR) + 1 for every LR from 8 to 15
         // per group maximum of bitlen(f-1) over alphabet indices 1..asz-1
         u32 r = rankBase;
 #pragma unroll
@@ -180,6 +224,13 @@ __device__ u32 ans_header_bits(int lane, const u32 f[4], u32 present, u32 asz, u
     __syncthreads();
 
     return pos;
+}
+
+template <u32 LR>
+__device__ u32 ans_header_bits(int lane, const u32 f[4], u32 present, u32 asz, u32 rankBase, bool lrPrefix,
+                               u32* hdrw, u32* grpMax, u32* grpOff, u32 pos)
+{
+    return ans_header_bits_lr(lane, f, present, asz, rankBase, lrPrefix ? 1 : 0, LR, hdrw, grpMax, grpOff, pos);
 }
 
 // ANSEncSymbol::reset for the 4 symbols of every lane (ANSRangeEncoder.hpp:92-117)

@@ -165,7 +165,7 @@ static int count_transforms(uint64_t t, int* tok)
 }
 
 static bool host_stage_id(int t) { return t == KNZ_T_TEXT || t == KNZ_T_UTF; }
-static bool entropy_supported(int e) { return e == KNZ_E_NONE || e == KNZ_E_ANS0 || e == KNZ_E_ANS1 || e == KNZ_E_HUFFMAN || e == KNZ_E_FPAQ; }
+static bool entropy_supported(int e) { return e == KNZ_E_NONE || e == KNZ_E_ANS0 || e == KNZ_E_ANS1 || e == KNZ_E_HUFFMAN || e == KNZ_E_FPAQ || e == KNZ_E_RANGE; }
 
 }  // namespace knz
 
@@ -269,6 +269,8 @@ size_t knz_hip_encode_bound(const knz_params* p, size_t n)
     size_t bound = 2 * n + nb * 64 + ((n / ENT_CHUNK) + nb) * (HDR_BYTES + 32) + 4096;
     // order-1 rANS writes 256 frequency tables per 4 MiB chunk (<= 3498 bits each), however small the block
     if (p->entropy_type == KNZ_E_ANS1) bound += (n / ANS1_CHUNK + nb) * 256 * (size_t)HDR_BYTES;
+    // RANGE: a chunk of c bytes leaves at most c + c / 64 + 2 units of 28 bits and 60 bits of low (range.hip), behind its header
+    if (p->entropy_type == KNZ_E_RANGE) bound = 4 * (n + n / 64) + nb * 64 + (n / RANGE_CHUNK + nb) * (HDR_BYTES + 64) + 4096;
     return bound;
 }
 
@@ -868,9 +870,10 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
 
     // ---- entropy stage
     const bool ans1 = (p->entropy_type == KNZ_E_ANS1);
-    const u32 entChunk = (p->entropy_type == KNZ_E_FPAQ || ans1) ? (4u << 20) : ENT_CHUNK;
+    const bool rangeCoder = (p->entropy_type == KNZ_E_RANGE);
+    const u32 entChunk = (p->entropy_type == KNZ_E_FPAQ || ans1) ? (4u << 20) : rangeCoder ? RANGE_CHUNK : ENT_CHUNK;
     const u32 slotMul = ans1 ? ANS1_SLOTS : 1u;
-    u32 hdrStride = TMP_STRIDE;
+    u32 hdrStride = rangeCoder ? RANGE_STRIDE : TMP_STRIDE;
     const int chunksPerBlock = (int)((S + entChunk - 1) / entChunk);
     const int maxChunks = chunksPerBlock * (int)slotMul;
     const size_t nSlots = (size_t)nBlocks * maxChunks;
@@ -900,6 +903,11 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
         u16* d_fprobs;
         if (int r = ws_get(c, "fpaqProbs", fpaq_probs_bytes(nBlocks, S), (void**)&d_fprobs, s)) return r;
         launch_fpaq_encode(s, view, d_origLen, framing ? 15u : 0u, nBlocks, maxChunks, d_desc, d_tmp, fStride, d_fprobs, S);
+    } else if (rangeCoder) {
+        u32* d_cumFreq;
+        if (int r = ws_get(c, "chunkTmp", (size_t)RANGE_STRIDE * nSlots, (void**)&d_tmp, s)) return r;
+        if (int r = ws_get(c, "rangeCumFreq", sizeof(u32) * 256 * nSlots, (void**)&d_cumFreq, s)) return r;
+        launch_range_encode(s, view, d_origLen, framing ? 15u : 0u, nBlocks, maxChunks, d_desc, d_cumFreq, d_tmp);
     } else {
         if (int r = ws_get(c, "chunkTmp", 64, (void**)&d_tmp, s)) return r;
         launch_none_encode(s, view, nBlocks, maxChunks, d_desc);
@@ -1068,6 +1076,8 @@ static int decode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, uint64_
             launch_huffman_decode(sp, src, blk, nb, maxChunks, d_meta, w.d_entDst, bsVersion);
         } else if (p->entropy_type == KNZ_E_FPAQ) {
             launch_fpaq_decode(sp, src, blk, nb, w.d_entDst);
+        } else if (p->entropy_type == KNZ_E_RANGE) {
+            launch_range_decode(sp, src, blk, nb, w.d_entDst, framing);
         } else {
             launch_none_decode(sp, src, blk, nb, w.d_entDst);
         }
@@ -1194,6 +1204,25 @@ int knz_hip_entropy_decode_v(knz_ctx* ctx, int entropy_type, int bs_version, con
         HIPCHK(c, hipMemcpyAsync(out, d_out, n, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
+    return 0;
+}
+
+int knz_hip_range_divide(knz_ctx* ctx, const uint64_t* d, const uint64_t* r, uint32_t n, uint32_t* q)
+{
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    CTX_LOCK(c);
+    if (n == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    u64 *d_d, *d_r; u32* d_q;
+    if (int rc = ws_get(c, "stageIn", 16 * (size_t)n + 64, (void**)&d_d, c->stream)) return rc;
+    if (int rc = ws_get(c, "stageOut", 4 * (size_t)n + 64, (void**)&d_q, c->stream)) return rc;
+    d_r = d_d + n;
+    HIPCHK(c, hipMemcpyAsync(d_d, d, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_r, r, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    launch_range_div_probe(c->stream, d_d, d_r, n, d_q);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(q, d_q, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 

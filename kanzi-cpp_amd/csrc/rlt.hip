@@ -102,7 +102,7 @@ __global__ __launch_bounds__(64) void k_rlt_forward(XfStage st)
     const u8* src = st.src[b];
     u8* dst = st.dst[b];
     const int etype = st.entropyType;
-    const bool findBestEscape = !(etype == KNZ_E_NONE || etype == KNZ_E_ANS0 || etype == KNZ_E_HUFFMAN || etype == 4);
+    const bool findBestEscape = !(etype == KNZ_E_NONE || etype == KNZ_E_ANS0 || etype == KNZ_E_HUFFMAN || etype == KNZ_E_RANGE);
     __shared__ u32 freqs[256];
     __shared__ int shEscape;
     __shared__ __attribute__((aligned(16))) u8 winBuf[RLT_WIN + 32];

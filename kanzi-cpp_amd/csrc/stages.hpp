@@ -47,6 +47,17 @@ void launch_ans1_decode(hipStream_t s, BitSrc src, DecBlock* blocks, int nBlocks
 size_t ans1_meta_bytes(size_t nChunks);
 size_t ans1_slottab_bytes(size_t nChunks);
 
+// range.hip (RANGE, entropy id 4: chunks of 32,768 bytes). A chunk of n bytes leaves at most RANGE_MAX_UNITS(n) = n + n / 64 + 2 units of
+// 28 bits (derived at k_range_encode) and 60 bits of low: the staging region of a chunk slot holds that behind the header buffer.
+constexpr u32 RANGE_CHUNK = 1u << 15;
+constexpr u32 RANGE_MAX_UNITS = RANGE_CHUNK + RANGE_CHUNK / 64 + 2;
+constexpr u32 RANGE_PAY_BYTES = ((28u * RANGE_MAX_UNITS + 60u + 31u) / 32u * 4u + 255u) & ~255u;      // 116,736
+constexpr u32 RANGE_STRIDE = HDR_BYTES + RANGE_PAY_BYTES;                                            // a multiple of 64
+void launch_range_encode(hipStream_t s, BlockView view, const u32* origLen, u32 copyThreshold, int nBlocks, int maxChunks, ChunkDesc* desc,
+                         u32* cumFreq, u8* tmp);
+void launch_range_decode(hipStream_t s, BitSrc src, DecBlock* blocks, int nBlocks, u8* const* outPtr, int framing);
+void launch_range_div_probe(hipStream_t s, const u64* d, const u64* r, u32 n, u32* q);      // range_div on n pairs (tests)
+
 // One transform stage over a batch (all arrays are device arrays indexed by block).
 struct XfStage {
     const u8* const* src;

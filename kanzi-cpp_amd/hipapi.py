@@ -10,8 +10,8 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libknz_hip.so")
 
-E_NONE, E_HUFFMAN, E_FPAQ, E_ANS0, E_ANS1 = 0, 1, 2, 5, 8
-ENTROPY_IDS = {"NONE": 0, "HUFFMAN": 1, "FPAQ": 2, "ANS0": 5, "ANS1": 8}
+E_NONE, E_HUFFMAN, E_FPAQ, E_RANGE, E_ANS0, E_ANS1 = 0, 1, 2, 4, 5, 8
+ENTROPY_IDS = {"NONE": 0, "HUFFMAN": 1, "FPAQ": 2, "RANGE": 4, "ANS0": 5, "ANS1": 8}
 TRANSFORM_IDS = {"NONE": 0, "BWT": 1, "BWTS": 2, "LZ": 3, "RLT": 5, "ZRLT": 6, "MTFT": 7, "RANK": 8, "SRT": 13, "MM": 15, "LZX": 16, "PACK": 18, "TIMESTAMP": 64}
 
 SYMBOLS = [
@@ -20,7 +20,7 @@ SYMBOLS = [
     "knz_hip_transform_forward", "knz_hip_transform_forward_dt", "knz_hip_transform_inverse", "knz_hip_malloc", "knz_hip_free",
     "knz_hip_memcpy_h2d", "knz_hip_memcpy_d2h", "knz_hip_sync", "knz_hip_memcpy_h2d_async", "knz_hip_memcpy_d2h_async", "knz_hip_copy_wait", "knz_hip_host_alloc", "knz_hip_host_free", "knz_hip_set_profiling", "knz_hip_get_kernel_times",
     "knz_hip_tune", "knz_hip_shift_bits", "knz_hip_encode_block_hosted", "knz_hip_decode_block_hosted",
-    "knz_hip_entropy_decode_v", "knz_hip_transform_inverse_v",
+    "knz_hip_entropy_decode_v", "knz_hip_transform_inverse_v", "knz_hip_range_divide",
 ]
 
 
@@ -96,6 +96,7 @@ def lib():
         L.knz_hip_get_kernel_times.argtypes = [vp, C.POINTER(KernelTime), C.c_int]
         L.knz_hip_tune.argtypes = [C.c_char_p, C.c_int]
         L.knz_hip_shift_bits.argtypes = [vp, u8p, C.c_uint64, C.c_uint32, u8p]
+        L.knz_hip_range_divide.argtypes = [vp, vp, vp, C.c_uint32, vp]
         _lib = L
     return _lib
 
@@ -176,7 +177,7 @@ class Context:
     # ---- per-stage API on host buffers
     def entropy_encode(self, entropy, data):
         e = ENTROPY_IDS[entropy.upper()]
-        cap = 2 * len(data) + 65536
+        cap = (4 if e == E_RANGE else 2) * len(data) + 65536     # (RANGE: up to 28 bits per byte and a bit, knz_hip_encode_bound)
         out = (C.c_uint8 * cap)()
         bits = C.c_uint64(0)
         self._chk(self.L.knz_hip_entropy_encode(self.h, e, data, len(data), out, cap, C.byref(bits)))
@@ -214,6 +215,14 @@ class Context:
         ol, ok = C.c_int32(0), C.c_int32(0)
         self._chk(self.L.knz_hip_transform_inverse_v(self.h, t, bs_version, data, len(data), out, dst_cap, C.byref(ol), C.byref(ok)))
         return ok.value, C.string_at(out, ol.value)
+
+    def range_divide(self, d, r):
+        """The RANGE decoder's divide on numpy uint64 arrays of (code - low, range) pairs: floor(d / r) as uint32."""
+        import numpy as np
+        d, r = np.ascontiguousarray(d, dtype=np.uint64), np.ascontiguousarray(r, dtype=np.uint64)
+        q = np.zeros(len(d), dtype=np.uint32)
+        self._chk(self.L.knz_hip_range_divide(self.h, d.ctypes.data, r.ctypes.data, len(d), q.ctypes.data))
+        return q
 
     # ---- profiling
     def set_profiling(self, on):

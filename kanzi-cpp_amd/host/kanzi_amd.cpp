@@ -1048,6 +1048,20 @@ HuffmanDecoder::HuffmanDecoder(InputBitStream& ibs, Context* pCtx, int chunkSize
     checkHuffmanArgs(chunkSize);
 }
 
+// entropy/RangeEncoder.cpp:37-54, RangeDecoder.cpp:40-51
+static void checkRangeArgs(int chunkSize, int logRange)
+{
+    if (chunkSize < 1024) throw std::invalid_argument("The chunk size must be at least 1024");
+    if (chunkSize > RangeEncoder::MAX_CHUNK_SIZE) throw std::invalid_argument("The chunk size must be at most 2^30");
+    if ((logRange < 8) || (logRange > 15)) throw std::invalid_argument("Invalid range parameter: " + std::to_string(logRange) + " (must be in [8..15])");
+    if (chunkSize != RangeEncoder::DEFAULT_CHUNK_SIZE || logRange != RangeEncoder::DEFAULT_LOG_RANGE)
+        throw std::invalid_argument("Range codec: the device kernels are built for the default chunk size (32768) and range (12)");
+}
+
+RangeEncoder::RangeEncoder(OutputBitStream& obs, int chunkSize, int logRange) : DeviceEntropyEncoder(obs, KNZ_E_RANGE) { checkRangeArgs(chunkSize, logRange); }
+
+RangeDecoder::RangeDecoder(InputBitStream& ibs, int chunkSize) : DeviceEntropyDecoder(ibs, KNZ_E_RANGE) { checkRangeArgs(chunkSize, RangeEncoder::DEFAULT_LOG_RANGE); }
+
 static const struct { const char* name; short type; } ENAMES[] = {
     {"NONE", 0}, {"HUFFMAN", 1}, {"FPAQ", 2}, {"RANGE", 4}, {"ANS0", 5}, {"CM", 6}, {"TPAQ", 7}, {"ANS1", 8}, {"TPAQX", 9} };
 
@@ -1072,6 +1086,7 @@ EntropyEncoder* EntropyEncoderFactory::newEncoder(OutputBitStream& obs, Context&
     case ANS0_TYPE: return new ANSRangeEncoder(obs, 0);
     case ANS1_TYPE: return new ANSRangeEncoder(obs, 1);
     case FPAQ_TYPE: return new FPAQEncoder(obs);
+    case RANGE_TYPE: return new RangeEncoder(obs);
     case NONE_TYPE: return new NullEntropyEncoder(obs);
     default: throw std::invalid_argument(std::string("Entropy codec '") + getName(entropyType) + "' has no device kernel");
     }
@@ -1084,6 +1099,7 @@ EntropyDecoder* EntropyDecoderFactory::newDecoder(InputBitStream& ibs, Context& 
     case EntropyEncoderFactory::ANS0_TYPE: return new ANSRangeDecoder(ibs, 0);
     case EntropyEncoderFactory::ANS1_TYPE: return new ANSRangeDecoder(ibs, 1);
     case EntropyEncoderFactory::FPAQ_TYPE: return new FPAQDecoder(ibs);
+    case EntropyEncoderFactory::RANGE_TYPE: return new RangeDecoder(ibs);
     case EntropyEncoderFactory::NONE_TYPE: return new NullEntropyDecoder(ibs);
     default: throw std::invalid_argument(std::string("Entropy codec '") + getName(entropyType) + "' has no device kernel");
     }

@@ -4,7 +4,7 @@
 //   kanzi_amd_cli -c -i FILE [-o FILE.knz] [-t TRANSFORMS] [-e ENTROPY] [-l LEVEL] [-b SIZE] [-j JOBS] [-x | -x32 | -x64] [-f]
 //   kanzi_amd_cli -d -i FILE.knz [-o FILE] [-j JOBS] [--from=N] [--to=N] [-f]
 //
-// Levels 0, 1, 5 and 6 are in (5 and 6: TEXT and UTF on the host in front of the device chain, host/text_codec.cpp).
+// -e takes NONE, HUFFMAN, ANS0, ANS1, FPAQ and RANGE. Levels 0, 1, 5 and 6 are in (5 and 6: TEXT and UTF on the host in front of the device chain, host/text_codec.cpp).
 // What it does not do (and says so instead of guessing): directories, stdin/stdout, `-y` info, levels whose chains need the
 // reference's CPU-only transforms (EXE, DNA, ROLZ, LZP) or entropy coders (CM, TPAQ), or LZ / LZX behind PACK or MM (the device LZ
 // stages do not read the data type those leave, which level 3 needs): levels 2-4 and 7-9. PACK and MM themselves run on the device (-t).
