@@ -296,8 +296,9 @@ public:
 class SRT : public DeviceTransform { public: explicit SRT(Context& ctx) : DeviceTransform(KNZ_T_SRT, &ctx) {} SRT() : DeviceTransform(KNZ_T_SRT, nullptr) {} };
 class ZRLT : public DeviceTransform { public: explicit ZRLT(Context& ctx) : DeviceTransform(KNZ_T_ZRLT, &ctx) {} ZRLT() : DeviceTransform(KNZ_T_ZRLT, nullptr) {} };
 class RLT : public DeviceTransform { public: explicit RLT(Context& ctx) : DeviceTransform(KNZ_T_RLT, &ctx) {} RLT() : DeviceTransform(KNZ_T_RLT, nullptr) {} };
-// transform/LZCodec.hpp:27-52: "LZ" (16-bit hash) or "LZX" (19-bit hash, deeper look-ahead) chosen by the context's
-// "lz" entry, which TransformFactory sets (TransformFactory.hpp:257-267). LZP has no device kernel.
+// transform/LZCodec.hpp:27-52: "LZ" (16-bit hash), "LZX" (19-bit hash, deeper look-ahead) or "LZP" (LZPCodec: matches of 64 bytes
+// and more at the position a 4-byte context predicts) chosen by the context's "lz" entry, which TransformFactory sets
+// (TransformFactory.hpp:257-267).
 class LZCodec : public DeviceTransform {
 public:
     LZCodec() : DeviceTransform(KNZ_T_LZ, nullptr) {}

@@ -28,7 +28,7 @@ extern "C" {
 
 /* kanzi ids: entropy (entropy/EntropyEncoderFactory.hpp:37-52) and transforms (transform/TransformFactory.hpp:49-73) */
 enum { KNZ_E_NONE = 0, KNZ_E_HUFFMAN = 1, KNZ_E_FPAQ = 2, KNZ_E_RANGE = 4, KNZ_E_ANS0 = 5, KNZ_E_ANS1 = 8 };
-enum { KNZ_T_NONE = 0, KNZ_T_BWT = 1, KNZ_T_BWTS = 2, KNZ_T_LZ = 3, KNZ_T_RLT = 5, KNZ_T_ZRLT = 6, KNZ_T_MTFT = 7, KNZ_T_RANK = 8, KNZ_T_SRT = 13, KNZ_T_MM = 15, KNZ_T_LZX = 16, KNZ_T_PACK = 18,
+enum { KNZ_T_NONE = 0, KNZ_T_BWT = 1, KNZ_T_BWTS = 2, KNZ_T_LZ = 3, KNZ_T_RLT = 5, KNZ_T_ZRLT = 6, KNZ_T_MTFT = 7, KNZ_T_RANK = 8, KNZ_T_SRT = 13, KNZ_T_LZP = 14, KNZ_T_MM = 15, KNZ_T_LZX = 16, KNZ_T_PACK = 18,
        KNZ_T_TIMESTAMP = 64 /* SBRT's third mode: no kanzi id, never part of a chain; per-stage entry points only */,
        KNZ_T_TEXT = 10, KNZ_T_UTF = 17 /* stages that run on the HOST in front of the device chain: knz_hip_encode_block_hosted / _decode_ */ };
 
@@ -155,6 +155,7 @@ KNZ_API int knz_hip_entropy_decode_v(knz_ctx* ctx, int entropy_type, int bs_vers
  *   KNZ_T_ZRLT  ZRLT                 transform/ZRLT.cpp:27-117,119-215
  *   KNZ_T_RLT   RLT                  transform/RLT.cpp:39-221,247-369
  *   KNZ_T_LZ / KNZ_T_LZX   LZCodec -> LZXCodec<false> / LZXCodec<true>   transform/LZCodec.cpp:119-456,470-640
+ *   KNZ_T_LZP   LZPCodec             transform/LZCodec.cpp:771-879,881-992
  *   KNZ_T_PACK  AliasCodec           transform/AliasCodec.cpp:38-209,211-371
  *   KNZ_T_MM    FSDCodec             transform/FSDCodec.cpp:103-291,293-386
  * (the inverse of LZ/LZX expects what the reference expects: two readable bytes behind `in + n`,

@@ -592,6 +592,11 @@ static const XfInfo XF[] = {
       .fwd = { .wsBytes = mm_scratch_bytes, .launch = [](const StageCall& k) { launch_mm_forward(k.s, k.st, k.ws); return 0; } },
       .inv = { .wsBytes = mm_scratch_bytes, .launch = [](const StageCall& k) { launch_mm_inverse(k.s, k.st, k.ws); return 0; } },
       .setsType = true },
+    // (LZPCodec; it neither reads nor writes the data type. Both directions keep a table per block in the stage's scratch, which
+    // run_stage takes per lane through lane_ws, so the inverse runs in decode lanes, each lane with tables of its own)
+    { .id = KNZ_T_LZP, .ws = "lzpScratch",
+      .fwd = { .wsBytes = lzp_scratch_bytes, .launch = [](const StageCall& k) { launch_lzp_forward(k.s, k.st, k.ws); return 0; } },
+      .inv = { .wsBytes = lzp_scratch_bytes, .launch = [](const StageCall& k) { launch_lzp_inverse(k.s, k.st, k.ws); return 0; } } },
 };
 
 static const XfInfo* xf_info(int t) { for (const XfInfo& x : XF) if (x.id == t) return &x; return nullptr; }

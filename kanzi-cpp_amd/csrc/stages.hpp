@@ -108,6 +108,11 @@ void launch_mm_forward(hipStream_t s, const XfStage& st, void* scratch);
 void launch_mm_inverse(hipStream_t s, const XfStage& st, void* scratch);
 size_t mm_scratch_bytes(int nBlocks, u32 maxLen);
 
+// lzp.hip (LZPCodec; scratch: lzp_scratch_bytes(nBlocks, maxLen) bytes, one table of 65,536 positions per block, cleared by the launcher)
+void launch_lzp_forward(hipStream_t s, const XfStage& st, void* scratch);
+void launch_lzp_inverse(hipStream_t s, const XfStage& st, void* scratch);
+size_t lzp_scratch_bytes(int nBlocks, u32 maxLen);
+
 // fpaq.hip (probs: fpaq_probs_bytes(nBlocks, S) bytes of scratch, S = upper bound of the block lengths)
 void launch_fpaq_encode(hipStream_t s, BlockView view, const u32* origLen, u32 copyThreshold, int nBlocks, int maxChunks, ChunkDesc* desc, u8* tmp, u64 tmpStride,
                         u16* probs, u64 S);

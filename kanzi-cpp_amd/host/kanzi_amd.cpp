@@ -523,8 +523,8 @@ bool BWTS::inverse(SliceArray<byte>& src, SliceArray<byte>& dst, int length)
 
 static int lzTypeFromContext(Context& ctx)
 {
-    const int t = ctx.getInt("lz", 3);
-    if (t == 14) throw std::invalid_argument("LZP has no device kernel (out of scope of the accelerated block pipeline)");
+    const int t = ctx.getInt("lz", 3);                    // TransformFactory.hpp:257-267
+    if (t == 14) return KNZ_T_LZP;
     return (t == 16) ? KNZ_T_LZX : KNZ_T_LZ;
 }
 
@@ -756,13 +756,13 @@ bool UTFCodec::inverse(SliceArray<byte>& src, SliceArray<byte>& dst, int length)
 // Leading stages of a chain that run on the host. TEXT / UTF anywhere else in a chain has no place to run: refused.
 // Chains the device runs far faster than one host thread copies memory (entropy coders alone, the byte transforms: tens of GB/s):
 // the staging copies of such a stream are spread over the helper threads. With a sorting or matching stage in the chain (BWT, LZ,
-// LZX; SRT / RANK are chains per block) the device is what a batch waits for and the extra threads only got in the way (measured,
+// LZX, LZP; SRT / RANK are chains per block) the device is what a batch waits for and the extra threads only got in the way (measured,
 // config 3 end to end: 2.94-3.14 GB/s with the copies on the caller's thread, 2.72-2.94 with four threads; config 2: 3.1 -> 3.9).
 static bool chainIsHostBound(uint64 ttype)
 {
     for (int i = 0; i < 8; i++) {
         const int t = int((ttype >> (42 - 6 * i)) & 63);
-        if (t == KNZ_T_BWT || t == KNZ_T_BWTS || t == KNZ_T_LZ || t == KNZ_T_LZX || t == KNZ_T_SRT || t == KNZ_T_RANK || t == KNZ_T_TEXT || t == KNZ_T_UTF) return false;
+        if (t == KNZ_T_BWT || t == KNZ_T_BWTS || t == KNZ_T_LZ || t == KNZ_T_LZX || t == KNZ_T_LZP || t == KNZ_T_SRT || t == KNZ_T_RANK || t == KNZ_T_TEXT || t == KNZ_T_UTF) return false;
     }
     return true;
 }
@@ -934,6 +934,7 @@ TransformSequence<T>* TransformFactory<T>::newTransform(Context& ctx, uint64 fun
             case RLT_TYPE: transforms[nbtr++] = new RLT(ctx); break;
             case LZ_TYPE: ctx.putInt("lz", LZ_TYPE); transforms[nbtr++] = new LZCodec(ctx); break;
             case LZX_TYPE: ctx.putInt("lz", LZX_TYPE); transforms[nbtr++] = new LZCodec(ctx); break;
+            case LZP_TYPE: ctx.putInt("lz", LZP_TYPE); transforms[nbtr++] = new LZCodec(ctx); break;
             case DICT_TYPE:
                 ctx.putInt("textcodec", hoststage::textVariantFor(ctx.has("entropy") ? ctx.getString("entropy").c_str() : ""));
                 transforms[nbtr++] = new TextCodec(ctx);

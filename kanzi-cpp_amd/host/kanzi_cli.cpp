@@ -6,8 +6,10 @@
 //
 // -e takes NONE, HUFFMAN, ANS0, ANS1, FPAQ and RANGE. Levels 0, 1, 5 and 6 are in (5 and 6: TEXT and UTF on the host in front of the device chain, host/text_codec.cpp).
 // What it does not do (and says so instead of guessing): directories, stdin/stdout, `-y` info, levels whose chains need the
-// reference's CPU-only transforms (EXE, DNA, ROLZ, LZP) or entropy coders (CM, TPAQ), or LZ / LZX behind PACK or MM (the device LZ
-// stages do not read the data type those leave, which level 3 needs): levels 2-4 and 7-9. PACK and MM themselves run on the device (-t).
+// reference's CPU-only transforms (EXE, DNA, ROLZ) or entropy coders (CM, TPAQ), or LZ / LZX behind PACK or MM (the device LZ
+// stages do not read the data type those leave, which level 3 needs): levels 2-4 and 7-9. PACK, MM and LZP themselves run on the
+// device (-t, LZP in any position behind the host stages); level 7 (LZP+TEXT+UTF+BWT+LZP / CM) still needs the CM coder and a host
+// stage behind a device stage.
 // Files written here are byte-identical to `kanzi -c` with the same -t/-e/-b/-x/-j, and either tool reads the other's files
 // (tests/test_host_stub.py, tests/test_gpu_host_api.py).
 #include <cstdio>
@@ -83,7 +85,7 @@ int main(int argc, char** argv)
         else if (level == 1) { transform = "LZX"; entropy = "NONE"; }
         else if (level == 5) { transform = "TEXT+UTF+BWT+RANK+ZRLT"; entropy = "ANS0"; }      // TEXT and UTF run on the host, the rest on the device
         else if (level == 6) { transform = "TEXT+UTF+BWT+SRT+ZRLT"; entropy = "FPAQ"; if (!blockGiven) block = 8 << 20; }      // (BlockCompressor.cpp:121-124: 8 MiB blocks by default)
-        else { fprintf(stderr, "level %d needs transforms or entropy coders that only exist in the CPU reference (EXE/DNA/ROLZ/LZP, CM/TPAQ) or LZX behind PACK / MM (level 3); use -t/-e\n", level); return Error::ERR_INVALID_CODEC; }
+        else { fprintf(stderr, "level %d needs transforms or entropy coders that only exist in the CPU reference (EXE/DNA/ROLZ, CM/TPAQ), LZX behind PACK / MM (level 3) or TEXT behind LZP (level 7); use -t/-e\n", level); return Error::ERR_INVALID_CODEC; }
     }
     if (transform.empty()) transform = "NONE";
     if (entropy.empty()) entropy = "NONE";
