@@ -46,6 +46,7 @@ constexpr u32 SM_G = 256;          // largest "small" group
 // LDS, one workgroup per CU): period-768 blocks 19.0 -> 9.8 ms, but real files 51.7 -> 52.6, the stand-in 26.6 -> 26.9 -- for groups of that
 // size the global sort of (descriptor, key) pairs is no slower than one workgroup per CU. Stays 8,192.
 constexpr u32 MED_CAP = 8192;
+constexpr u32 MED_LO_CAP = 2048;   // medium groups up to here are sorted by workgroups of 256 threads x 8 members, larger ones by 512 x 16
 constexpr u32 SUPER_CAP = 8192;    // largest group the chain round and the periodic-stretch probe take
 constexpr int GATHER_THREADS = 512;        // workgroup of k_bwt_f_gather_desc
 constexpr u32 GATHER_ROWS = 16;            // members it holds per thread: a medium group whole
@@ -97,6 +98,7 @@ enum FwdCounter : u32 {
     CNT_RUN_LONGEST = 6,         // longest run (run round)
     CNT_SUPER = 7,               // groups listed for the chain round (k_bwt_f_super)
     CNT_RUNS = 8,                // runs of run-group bytes (run round)
+    CNT_MED_LO = 9,              // medium descriptors of the lower size class, up to MED_LO_CAP members (k_bwt_f_med_compact)
     CNT_STAT_SMALL = 10,         // small members worked on (knob bwt_stats)
     CNT_STAT_SMALL_GROUPS = 11,  // small groups worked on (knob bwt_stats)
     CNT_STAT_MED = 12,           // medium members worked on (knob bwt_stats)
@@ -1413,6 +1415,120 @@ __device__ __forceinline__ void med_majority_write_back(MedLds<THREADS, ROWS>& L
     if (__ballot(surv != 0) != 0 && (tid & 63) == 0) v.counters[CNT_SMALL_LEFT] = 1;
 }
 
+// The refinement of one group whose keys and positions are in LDS (oK / oV [0, n), position order; the workgroup in step behind the
+// stores): chain-round listing, majority split or radix sort, write-back. info = (block base, the members' label). storeKeys: the keys
+// are nowhere but in LDS (k_bwt_f_medium_fused), so a group listed for the chain round, which reads them from K, stores them there first.
+// Left with the workgroup in step.
+template <int THREADS, int ROWS, bool STATS>
+__device__ __forceinline__ void med_sort_group(MedLds<THREADS, ROWS>& L, const FwdView& v, u32 gs, u32 n, uint2 info, int npass, bool storeKeys,
+                                               uint2* __restrict__ medNext, uint2* __restrict__ largeNext, uint4* __restrict__ superList)
+{
+    constexpr int WAVES = THREADS / 64;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long ltMask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    if (tid == 0) { L.oldLab = info.y; L.blkBase = info.x; }
+    // majority candidate: the key two of three probes agree on, else the middle one
+    const u32 ka = L.oK[n >> 2], kb = L.oK[n >> 1], kc = L.oK[(n >> 2) * 3];
+    const u32 m = (ka == kc) ? ka : kb;
+    u32 c = 0;
+    for (u32 i = (u32)tid; i < n; i += THREADS) c += (L.oK[i] == m) ? 1u : 0u;
+    c = med_block_sum(L, c);
+    if (c < n && 2 * c >= n && n <= SUPER_CAP && m == info.y - info.x + 1u) {
+        // the majority looks at the group itself (a periodic stretch whose period divides h): k_bwt_f_super finishes it in one round
+        if (tid == 0) { const u32 at = atomicAdd(&v.counters[CNT_SUPER], 1u); superList[at] = make_uint4(gs, n, info.x, info.y); }
+        if (storeKeys) for (u32 i = (u32)tid; i < n; i += THREADS) v.K[gs + i] = L.oK[i];
+        __syncthreads();
+        return;
+    }
+    if (STATS && tid == 0 && c == n) { atomicAdd(&v.counters[CNT_STAT_UNSPLIT], 1u); atomicAdd(&v.counters[CNT_STAT_UNSPLIT_MEMBERS], n); }
+    if (c < n) {
+        if (2 * c >= n) {
+            // ---- stable split: [others (nOth)][members with key m (c)]
+            const int R = (int)((n + THREADS - 1) / THREADS);
+            const u32 waveBase = (u32)wave * (u32)R * 64u;
+            u32 key[ROWS], val[ROWS], pos[ROWS];
+            u32 runO = 0, runE = 0;
+#pragma unroll
+            for (int r = 0; r < ROWS; r++) {
+                key[r] = m; val[r] = 0; pos[r] = 0xFFFFFFFFu;
+                if (r < R) {
+                    const u32 idx = waveBase + (u32)r * 64u + (u32)lane;
+                    const bool valid = idx < n;
+                    if (valid) { key[r] = L.oK[idx]; val[r] = L.oV[idx]; }
+                    const bool oth = valid && key[r] != m, same = valid && key[r] == m;
+                    const unsigned long long bo = __ballot(oth), be = __ballot(same);
+                    if (oth) pos[r] = runO + (u32)__popcll(bo & ltMask);
+                    if (same) pos[r] = 0x80000000u | (runE + (u32)__popcll(be & ltMask));
+                    runO += (u32)__popcll(bo);
+                    runE += (u32)__popcll(be);
+                }
+            }
+            if (lane == 0) { L.wtot[wave] = runO; L.wtot2[wave] = runE; }
+            __syncthreads();
+            u32 baseO = 0, baseE = 0, nOth = 0;
+            for (int w = 0; w < WAVES; w++) { if (w < wave) { baseO += L.wtot[w]; baseE += L.wtot2[w]; } nOth += L.wtot[w]; }
+#pragma unroll
+            for (int r = 0; r < ROWS; r++) {
+                if (r < R && pos[r] != 0xFFFFFFFFu) {
+                    const u32 at = (pos[r] & 0x80000000u) ? (nOth + baseE + (pos[r] & 0x7FFFFFFFu)) : (baseO + pos[r]);
+                    L.oK[at] = key[r];
+                    L.oV[at] = val[r];
+                }
+            }
+            __syncthreads();
+            if (nOth <= (u32)THREADS) {
+                // few others: rank by counting (stable: smaller keys, then equal keys that come earlier)
+                u32 kk = 0, vv = 0, at = 0;
+                if ((u32)tid < nOth) {
+                    kk = L.oK[tid]; vv = L.oV[tid];
+                    for (u32 j = 0; j < nOth; j++) { const u32 kj = L.oK[j]; at += (kj < kk || (kj == kk && j < (u32)tid)) ? 1u : 0u; }
+                }
+                __syncthreads();
+                if ((u32)tid < nOth) { L.oK[at] = kk; L.oV[at] = vv; }
+                __syncthreads();
+                // A group that keeps its majority and loses a handful of members (round after round, for a periodic stretch): the
+                // majority is written where it goes straight from the split order and keeps its label, each of the few others finds the
+                // members it stays with by looking left and right among the sorted others -- no rearranging of the whole group, no bit map
+                // over it, no scans (med_write_back does all that for the general case)
+                u32 lessQ = 0;
+                if ((u32)tid < nOth) lessQ = (L.oK[tid] < m) ? 1u : 0u;
+                lessQ = med_block_sum(L, lessQ);
+                if (tid == 0) { L.oldLab = info.y; L.blkBase = info.x; if (STATS) { atomicAdd(&v.counters[CNT_STAT_MAJ], 1u); atomicAdd(&v.counters[CNT_STAT_MAJ_MEMBERS], n); } }
+                __syncthreads();
+                med_majority_write_back<THREADS, ROWS>(L, v, gs, n, nOth, c, lessQ, m);
+                __syncthreads();
+                return;
+            } else {
+                med_radix_sort<THREADS, ROWS>(L, nOth, npass);
+            }
+            u32 less = 0;
+            for (u32 i = (u32)tid; i < nOth; i += THREADS) less += (L.oK[i] < m) ? 1u : 0u;
+            less = med_block_sum(L, less);
+            // ---- [others < m][key m][others > m]
+#pragma unroll
+            for (int k = 0; k < ROWS; k++) {
+                const u32 i = (u32)tid + (u32)k * THREADS;
+                if (i < n) { key[k] = L.oK[i]; val[k] = L.oV[i]; }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < ROWS; k++) {
+                const u32 i = (u32)tid + (u32)k * THREADS;
+                if (i < n) {
+                    const u32 at = (i < less) ? i : (i < nOth ? i + c : less + (i - nOth));
+                    L.oK[at] = key[k];
+                    L.oV[at] = val[k];
+                }
+            }
+            __syncthreads();
+        } else {
+            med_radix_sort<THREADS, ROWS>(L, n, npass);
+        }
+    }
+    med_write_back<THREADS, ROWS>(L, v, gs, n, medNext, largeNext);
+    __syncthreads();
+}
+
 // One workgroup refines one group of 257..ROWS*THREADS members (descriptors of other sizes are left to the other
 // instantiations of the kernel): keys and positions into LDS, sort, subgroup boundaries, SA / ISA / bit map / children.
 // A group in which one key holds the majority (periodic stretches and runs: every member but the ones near the end of the
@@ -1427,11 +1543,9 @@ __global__ __launch_bounds__(THREADS, (THREADS >= 1024 ? 4 : THREADS / 128)) voi
                                                                uint2* __restrict__ medNext, uint2* __restrict__ largeNext, const uint2* __restrict__ descInfo,
                                                                uint4* __restrict__ superList)
 {
-    constexpr int WAVES = THREADS / 64;
     constexpr u32 CAP = (u32)ROWS * THREADS;
     __shared__ MedLds<THREADS, ROWS> L;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned long long ltMask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    const int tid = (int)threadIdx.x;
 
     for (u32 g = blockIdx.x; g < nDesc; g += gridDim.x) {
         const uint2 d = desc[g];
@@ -1447,106 +1561,72 @@ __global__ __launch_bounds__(THREADS, (THREADS >= 1024 ? 4 : THREADS / 128)) voi
             for (int r = 0; r < ROWS; r++) { const u32 i = (u32)tid + (u32)r * THREADS; if (i < n) { L.oK[i] = k[r]; L.oV[i] = p[r]; } }
         }
         __syncthreads();
-        if (tid == 0) { L.oldLab = info.y; L.blkBase = info.x; }
-        // majority candidate: the key two of three probes agree on, else the middle one
-        const u32 ka = L.oK[n >> 2], kb = L.oK[n >> 1], kc = L.oK[(n >> 2) * 3];
-        const u32 m = (ka == kc) ? ka : kb;
-        u32 c = 0;
-        for (u32 i = (u32)tid; i < n; i += THREADS) c += (L.oK[i] == m) ? 1u : 0u;
-        c = med_block_sum(L, c);
-        if (c < n && 2 * c >= n && n <= SUPER_CAP && m == info.y - info.x + 1u) {
-            // the majority looks at the group itself (a periodic stretch whose period divides h): k_bwt_f_super finishes it in one round
-            if (tid == 0) { const u32 at = atomicAdd(&v.counters[CNT_SUPER], 1u); superList[at] = make_uint4(gs, n, info.x, info.y); }
+        med_sort_group<THREADS, ROWS, STATS>(L, v, gs, n, info, npass, false, medNext, largeNext, superList);
+    }
+}
+
+// Versioned labels: fetch, judge and sort a medium group in one workgroup. The launch gets the descriptors of ONE size class (classIdx:
+// their indexes in the round's list, in slot order -- k_bwt_f_med_compact), so no workgroup is dealt a group of the other shape; the eight
+// XCDs walk contiguous eighths of the class side by side, as k_bwt_f_gather_desc does with the list. The members' positions and keys
+// (gather_key: lab_old answers with the label a position had when the round began, whatever the round has written since) stay in
+// registers until the verdict: all keys equal -> the group is staged again and its verdict recorded, as k_bwt_f_gather_desc does, and
+// nothing else is written; else they go to LDS and through med_sort_group. No key passes through K (but the ones of a group listed for
+// the chain round) and nothing through descInfo. skip == 0 (knob bwt_no_unsplit_skip): every group is sorted.
+template <int THREADS, int ROWS, bool STATS>
+__global__ __launch_bounds__(THREADS, 4) void k_bwt_f_medium_fused(FwdView v, const uint2* __restrict__ desc, const u32* __restrict__ classIdx, u32 nClass, u32 h, int npass,
+                                                               int skip, uint2* __restrict__ medNext, uint2* __restrict__ largeNext, uint4* __restrict__ superList)
+{
+    constexpr u32 CAP = (u32)ROWS * THREADS;
+    __shared__ MedLds<THREADS, ROWS> L;
+    __shared__ u32 sDiff;
+    const int tid = (int)threadIdx.x;
+    const u32 xcd = blockIdx.x & 7, lanesPerXcd = gridDim.x >> 3, slot = blockIdx.x >> 3;      // the grid is a multiple of 8 workgroups
+    const u32 per = (nClass + 7) / 8;
+    const u32 lo = xcd * per, hi = (lo + per < nClass) ? lo + per : nClass;
+    if (tid == 0) sDiff = 0;
+    __syncthreads();
+    for (u32 g = lo + slot; g < hi; g += lanesPerXcd) {
+        const uint2 d = desc[classIdx[g]];
+        const u32 gs = d.x, n = d.y;
+        if (n <= SM_G || n > CAP) continue;                 // (uniform) void: taken apart by the probe, or asleep (k_bwt_f_med_sleep)
+        const int blk = find_block(v.base, v.nBlocks, gs);  // (uniform)
+        const u32 bb = v.base[blk], be = v.base[blk + 1];
+        u32 off = h;                                        // (uniform for the group)
+        if (v.rtbits && ((v.rtbits[gs >> 5] >> (gs & 31)) & 1u)) { const u32 r = v.ovr[gs]; off = r > h ? r : h; }
+        // the first member's label and key, by every thread for itself (one address for the workgroup, in flight beside the loads below)
+        const u32 gp0 = v.SA[gs];
+        const u32 lab = lab_old(v, gp0, bb), key0 = gather_key(v, gp0, off, bb, be);
+        const bool judge = skip && lab - gs < n;           // (the label inside the group's range: see k_bwt_f_gather_desc)
+        u32 gp[ROWS], key[ROWS];
+#pragma unroll
+        for (int r = 0; r < ROWS; r++) { const u32 i = (u32)tid + (u32)r * THREADS; gp[r] = (i < n) ? v.SA[gs + i] : bb; }
+#pragma unroll
+        for (int r = 0; r < ROWS; r++) { const u32 i = (u32)tid + (u32)r * THREADS; key[r] = (i < n) ? gather_key(v, gp[r], off, bb, be) : key0; }
+        bool unsplit = false;
+        if (judge) {                                        // (uniform; sDiff is 0 here)
+            bool diff = false;
+#pragma unroll
+            for (int r = 0; r < ROWS; r++) diff = diff || key[r] != key0;       // (a slot behind the group's end holds key0)
+            if (__ballot(diff) != 0 && (tid & 63) == 0) sDiff = 1;
             __syncthreads();
-            continue;
+            unsplit = sDiff == 0;
         }
-        if (STATS && tid == 0 && c == n) { atomicAdd(&v.counters[CNT_STAT_UNSPLIT], 1u); atomicAdd(&v.counters[CNT_STAT_UNSPLIT_MEMBERS], n); }
-        if (c < n) {
-            if (2 * c >= n) {
-                // ---- stable split: [others (nOth)][members with key m (c)]
-                const int R = (int)((n + THREADS - 1) / THREADS);
-                const u32 waveBase = (u32)wave * (u32)R * 64u;
-                u32 key[ROWS], val[ROWS], pos[ROWS];
-                u32 runO = 0, runE = 0;
-#pragma unroll
-                for (int r = 0; r < ROWS; r++) {
-                    key[r] = m; val[r] = 0; pos[r] = 0xFFFFFFFFu;
-                    if (r < R) {
-                        const u32 idx = waveBase + (u32)r * 64u + (u32)lane;
-                        const bool valid = idx < n;
-                        if (valid) { key[r] = L.oK[idx]; val[r] = L.oV[idx]; }
-                        const bool oth = valid && key[r] != m, same = valid && key[r] == m;
-                        const unsigned long long bo = __ballot(oth), be = __ballot(same);
-                        if (oth) pos[r] = runO + (u32)__popcll(bo & ltMask);
-                        if (same) pos[r] = 0x80000000u | (runE + (u32)__popcll(be & ltMask));
-                        runO += (u32)__popcll(bo);
-                        runE += (u32)__popcll(be);
-                    }
-                }
-                if (lane == 0) { L.wtot[wave] = runO; L.wtot2[wave] = runE; }
-                __syncthreads();
-                u32 baseO = 0, baseE = 0, nOth = 0;
-                for (int w = 0; w < WAVES; w++) { if (w < wave) { baseO += L.wtot[w]; baseE += L.wtot2[w]; } nOth += L.wtot[w]; }
-#pragma unroll
-                for (int r = 0; r < ROWS; r++) {
-                    if (r < R && pos[r] != 0xFFFFFFFFu) {
-                        const u32 at = (pos[r] & 0x80000000u) ? (nOth + baseE + (pos[r] & 0x7FFFFFFFu)) : (baseO + pos[r]);
-                        L.oK[at] = key[r];
-                        L.oV[at] = val[r];
-                    }
-                }
-                __syncthreads();
-                if (nOth <= (u32)THREADS) {
-                    // few others: rank by counting (stable: smaller keys, then equal keys that come earlier)
-                    u32 kk = 0, vv = 0, at = 0;
-                    if ((u32)tid < nOth) {
-                        kk = L.oK[tid]; vv = L.oV[tid];
-                        for (u32 j = 0; j < nOth; j++) { const u32 kj = L.oK[j]; at += (kj < kk || (kj == kk && j < (u32)tid)) ? 1u : 0u; }
-                    }
-                    __syncthreads();
-                    if ((u32)tid < nOth) { L.oK[at] = kk; L.oV[at] = vv; }
-                    __syncthreads();
-                    // A group that keeps its majority and loses a handful of members (round after round, for a periodic stretch): the
-                    // majority is written where it goes straight from the split order and keeps its label, each of the few others finds the
-                    // members it stays with by looking left and right among the sorted others -- no rearranging of the whole group, no bit map
-                    // over it, no scans (med_write_back does all that for the general case)
-                    u32 lessQ = 0;
-                    if ((u32)tid < nOth) lessQ = (L.oK[tid] < m) ? 1u : 0u;
-                    lessQ = med_block_sum(L, lessQ);
-                    if (tid == 0) { L.oldLab = info.y; L.blkBase = info.x; if (STATS) { atomicAdd(&v.counters[CNT_STAT_MAJ], 1u); atomicAdd(&v.counters[CNT_STAT_MAJ_MEMBERS], n); } }
-                    __syncthreads();
-                    med_majority_write_back<THREADS, ROWS>(L, v, gs, n, nOth, c, lessQ, m);
-                    __syncthreads();
-                    continue;
-                } else {
-                    med_radix_sort<THREADS, ROWS>(L, nOth, npass);
-                }
-                u32 less = 0;
-                for (u32 i = (u32)tid; i < nOth; i += THREADS) less += (L.oK[i] < m) ? 1u : 0u;
-                less = med_block_sum(L, less);
-                // ---- [others < m][key m][others > m]
-#pragma unroll
-                for (int k = 0; k < ROWS; k++) {
-                    const u32 i = (u32)tid + (u32)k * THREADS;
-                    if (i < n) { key[k] = L.oK[i]; val[k] = L.oV[i]; }
-                }
-                __syncthreads();
-#pragma unroll
-                for (int k = 0; k < ROWS; k++) {
-                    const u32 i = (u32)tid + (u32)k * THREADS;
-                    if (i < n) {
-                        const u32 at = (i < less) ? i : (i < nOth ? i + c : less + (i - nOth));
-                        L.oK[at] = key[k];
-                        L.oV[at] = val[k];
-                    }
-                }
-                __syncthreads();
-            } else {
-                med_radix_sort<THREADS, ROWS>(L, n, npass);
+        if (tid == 0) {
+            if (unsplit) {
+                v.medStage[gs >> 8] = d;
+                if (v.verdictNow) v.verdictNow[gs >> 8] = make_uint2(key0, verdict_word(v.round, (off == h && key0 != 0u) ? VERDICT_PLAIN : VERDICT_WHOLE, n));
+            }
+            if (STATS) {
+                atomicAdd(&v.counters[CNT_STAT_MED], n); atomicAdd(&v.counters[CNT_STAT_MED_GROUPS], 1u);
+                if (unsplit) { atomicAdd(&v.counters[CNT_STAT_UNSPLIT], 1u); atomicAdd(&v.counters[CNT_STAT_UNSPLIT_MEMBERS], n); }
             }
         }
-        med_write_back<THREADS, ROWS>(L, v, gs, n, medNext, largeNext);
+        if (unsplit) { __syncthreads(); continue; }         // (uniform; sDiff stays 0, and every thread has read it before the next group's verdict)
+#pragma unroll
+        for (int r = 0; r < ROWS; r++) { const u32 i = (u32)tid + (u32)r * THREADS; if (i < n) { L.oK[i] = key[r]; L.oV[i] = gp[r]; } }
         __syncthreads();
+        if (tid == 0) sDiff = 0;                            // (every thread has read it; the barriers of the sort lie in front of the next group's verdict)
+        med_sort_group<THREADS, ROWS, STATS>(L, v, gs, n, make_uint2(bb, lab), npass, true, medNext, largeNext, superList);
     }
 }
 
@@ -2329,33 +2409,47 @@ __global__ __launch_bounds__(256) void k_bwt_f_emit(BwtView v, const u32* __rest
 }
 
 // ------------------------------------------------------------------------------------------------
-// medium groups of the round that ends: the staging slots in order -> flags, (scan), descriptor list; the slots are cleared for the next round
+// medium groups of the round that ends: the staging slots in order -> flags, (scan), descriptor list; the slots are cleared for the next round.
+// The flags are two arrays behind each other, one per size class (up to MED_LO_CAP members, above), and ONE scan runs over both: a slot's
+// place among its class is its prefix (less the lower class's count, for the upper one), its place in the list the sum of the two. The
+// list is in slot order; idxLo / idxHi name, in slot order again, the list's descriptors of either class (k_bwt_f_medium_fused).
 __global__ __launch_bounds__(256) void k_bwt_f_med_flags(const uint2* __restrict__ stage, u32 nSlots, u32* __restrict__ flags)
 {
     const u32 i = blockIdx.x * 256 + threadIdx.x;
-    if (i < nSlots) flags[i] = stage[i].y ? 1u : 0u;
+    if (i >= nSlots) return;
+    const u32 n = stage[i].y;
+    flags[i] = (n != 0 && n <= MED_LO_CAP) ? 1u : 0u;
+    flags[nSlots + i] = (n > MED_LO_CAP) ? 1u : 0u;
 }
 
-__global__ __launch_bounds__(256) void k_bwt_f_med_compact(uint2* __restrict__ stage, u32 nSlots, const u32* __restrict__ prefix, uint2* __restrict__ medNext)
+// (at, atLo, atHi: what the list and the two indexes hold already -- the groups the probe appends to the first round's list)
+__global__ __launch_bounds__(256) void k_bwt_f_med_compact(uint2* __restrict__ stage, u32 nSlots, const u32* __restrict__ prefix, uint2* __restrict__ medNext,
+                                                           u32 at, u32* __restrict__ idxLo, u32 atLo, u32* __restrict__ idxHi, u32 atHi, u32* __restrict__ nLoOut)
 {
     const u32 i = blockIdx.x * 256 + threadIdx.x;
     if (i >= nSlots) return;
+    const u32 nLo = prefix[nSlots];                         // (the upper class's flags start there)
+    if (i == 0) *nLoOut = nLo;
     const uint2 d = stage[i];
-    if (d.y) { medNext[prefix[i]] = d; stage[i] = make_uint2(0u, 0u); }
+    if (d.y == 0) return;
+    const u32 pLo = prefix[i], pHi = prefix[nSlots + i] - nLo, g = at + pLo + pHi;
+    medNext[g] = d; stage[i] = make_uint2(0u, 0u);
+    if (d.y <= MED_LO_CAP) idxLo[atLo + pLo] = g; else idxHi[atHi + pHi] = g;
 }
 
 // knobs (tests, diagnostics): read from the environment once per process, or set through knz_hip_tune(). Each one forces, at test
 // sizes, a path that some inputs take by themselves (round-0 key length, no run round, the run groups' fall-back, the plain labels of
 // blocks above 256 MiB, the plain keys of blocks above 8 MiB, where the link step starts), or reports (stats).
-struct FwdTuning { int nsym; int noRunRound; int runFallback; int stats; int link; int plainLabels; int noPack; int noUnsplitSkip; int noGroupSleep; };
+struct FwdTuning { int nsym; int noRunRound; int runFallback; int stats; int link; int plainLabels; int noPack; int noUnsplitSkip; int noGroupSleep; int noMediumFuse; };
 static FwdTuning& fwd_tuning()
 {
     static FwdTuning t = [] {
-        FwdTuning x; x.nsym = 0; x.noRunRound = 0; x.runFallback = 0; x.stats = 0; x.link = 1; x.plainLabels = 0; x.noPack = 0; x.noUnsplitSkip = 0; x.noGroupSleep = 0;     // link: 0 off, 1 on (from h = 32), n > 1: from h = n
+        FwdTuning x; x.nsym = 0; x.noRunRound = 0; x.runFallback = 0; x.stats = 0; x.link = 1; x.plainLabels = 0; x.noPack = 0; x.noUnsplitSkip = 0; x.noGroupSleep = 0; x.noMediumFuse = 0;     // link: 0 off, 1 on (from h = 32), n > 1: from h = n
         if (getenv("KNZ_BWT_PLAIN_LABELS")) x.plainLabels = 1;
         if (getenv("KNZ_BWT_NO_PACK")) x.noPack = 1;
         if (getenv("KNZ_BWT_NO_UNSPLIT_SKIP")) x.noUnsplitSkip = 1;
         if (getenv("KNZ_BWT_NO_GROUP_SLEEP")) x.noGroupSleep = 1;
+        if (getenv("KNZ_BWT_NO_MEDIUM_FUSE")) x.noMediumFuse = 1;
         if (const char* e = getenv("KNZ_BWT_LINK")) x.link = atoi(e);
         if (getenv("KNZ_BWT_STATS")) x.stats = 1;
         if (const char* e = getenv("KNZ_BWT_NSYM")) x.nsym = atoi(e);
@@ -2378,6 +2472,7 @@ int bwt_forward_tune(const char* key, int value)
     else if (!strcmp(key, "bwt_no_pack")) t.noPack = value;      // small groups ranked on plain keys (three counts per pair) also where the packed keys fit
     else if (!strcmp(key, "bwt_no_unsplit_skip")) t.noUnsplitSkip = value;      // medium groups whose keys are all equal stored and sorted like any other
     else if (!strcmp(key, "bwt_no_group_sleep")) t.noGroupSleep = value;        // every such group gathered in every round (no k_bwt_f_med_sleep, no records)
+    else if (!strcmp(key, "bwt_no_medium_fuse")) t.noMediumFuse = value;        // medium groups through k_bwt_f_gather_desc and k_bwt_f_sort_medium on versioned labels too
     else return -1;
     return 0;
 }
@@ -2388,7 +2483,7 @@ struct FwdScratch {
     u32* SA; u32* ISA; u32* K; u64* ISA2;
     u32* t0; u32* t1; u32* t2; u32* t3;
     u32* gbits; u32* gnew; u32* rtbits; u32* ovr; size_t gbitsWords;
-    uint2* med[2]; uint2* medStage; uint2* medVerdict[2]; u32* medFlags; u32* medPrefix; size_t medSlots; uint2* descInfo; uint2* large[2]; uint2* runList; uint4* superList; u32* ebits;
+    uint2* med[2]; uint2* medStage; uint2* medVerdict[2]; u32* medFlags; u32* medPrefix; u32* medIdxLo; u32* medIdxHi; size_t medSlots; uint2* descInfo; uint2* large[2]; uint2* runList; uint4* superList; u32* ebits;
     u32* loff; u32* lbase;
     u32* survTile;       // members still tied after a round's small-group sort, per window
     u32* linkedTile;     // members the link step linked, per window
@@ -2425,7 +2520,8 @@ static size_t fwd_carve(u8* p, int nBlocks, size_t total, FwdScratch* w, u32 VS)
     w->ovr = (u32*)take(4 * total);
     w->med[0] = (uint2*)take(8 * maxMed); w->med[1] = (uint2*)take(8 * maxMed);
     w->medSlots = total / 256 + 2;
-    w->medStage = (uint2*)take(8 * w->medSlots); w->medFlags = (u32*)take(4 * w->medSlots + 64); w->medPrefix = (u32*)take(4 * w->medSlots + 64);
+    w->medStage = (uint2*)take(8 * w->medSlots); w->medFlags = (u32*)take(8 * w->medSlots + 64); w->medPrefix = (u32*)take(8 * w->medSlots + 64);     // (two flags per slot: k_bwt_f_med_flags)
+    w->medIdxLo = (u32*)take(4 * maxMed); w->medIdxHi = (u32*)take(4 * maxMed);
     w->medVerdict[0] = (uint2*)take(16 * w->medSlots); w->medVerdict[1] = w->medVerdict[0] + w->medSlots;
     w->large[0] = (uint2*)take(8 * maxLarge); w->large[1] = (uint2*)take(8 * maxLarge);
     w->runList = (uint2*)take(8 * maxMed);
@@ -2500,6 +2596,8 @@ struct FwdSort {
     bool groupSleep = false;                               // medium groups sleep through rounds whose verdict is known (k_bwt_f_med_sleep)
     u32 h = 1; int cur = 0;                                // offset of the doubling round; its lists w.med[cur], w.large[cur] (the next round's: cur ^ 1)
     u64 *keysFree, *keysFree2;                             // key buffers of the rounds (keysFree2: round 0's sorted keys until they are placed)
+    bool medFuse = false;                                  // medium groups through k_bwt_f_medium_fused (versioned labels; knob bwt_no_medium_fuse)
+    u32 nMedLo = 0;                                        // descriptors of the lower size class among the nMed of the list
     u32 nRun, runElems, surv, nMed, nLarge, largeElems, survMembers;   // run groups of round 0 and their members; left: small groups (!= 0),
                                                                        // medium and large groups, large members, small members still tied
     LinkPlan link; LinkTrial linkTr; std::chrono::steady_clock::time_point statT;
@@ -2508,13 +2606,14 @@ struct FwdSort {
     void merge_bits() { hipLaunchKernelGGL(k_bwt_f_merge_bits, GRID1(total / 32 + 2), w.gbits, w.gnew, total / 32 + 2); }
     // the doubling rounds look max(R, h) positions on for the members of a group the run round left (FwdView::ovr, rtbits)
     void enable_run_tiebits() { if (!v.rtbits) { hipMemsetAsync(w.rtbits, 0, 4 * w.gbitsWords, s); v.ovr = w.ovr; v.rtbits = w.rtbits; } }
-    // the medium groups staged by the kernels of a round -> descriptor list `dst` (in slot order) and CNT_MED
-    void compact_medium(uint2* dst)
+    // the medium groups staged by the kernels of a round -> descriptor list `dst` (in slot order) behind the `at` it holds, the indexes of
+    // its two size classes behind their atLo and at - atLo entries; CNT_MED and CNT_MED_LO count what was added
+    void compact_medium(uint2* dst, u32 at = 0, u32 atLo = 0)
     {
         KScope ks_("k_bwt_f_med_compact");
         hipLaunchKernelGGL(k_bwt_f_med_flags, GRID1(medSlots), w.medStage, medSlots, w.medFlags);
-        prims::launch_scan<prims::SCAN_SUM_EXCL>(s, w.medFlags, w.medPrefix, medSlots, nullptr, w.scanTmp, w.counters + CNT_MED);
-        hipLaunchKernelGGL(k_bwt_f_med_compact, GRID1(medSlots), w.medStage, medSlots, w.medPrefix, dst);
+        prims::launch_scan<prims::SCAN_SUM_EXCL>(s, w.medFlags, w.medPrefix, 2 * (size_t)medSlots, nullptr, w.scanTmp, w.counters + CNT_MED);
+        hipLaunchKernelGGL(k_bwt_f_med_compact, GRID1(medSlots), w.medStage, medSlots, w.medPrefix, dst, at, w.medIdxLo, atLo, w.medIdxHi, at - atLo, w.counters + CNT_MED_LO);
     }
     // running maximum of t0 into t1 (the last group start at or before an element; `last`) and running minimum of t2 into t3 (the first
     // one at or after it, mirrored) over n values; with a bit map over `len` elements, t0 / t2 are first taken per window of `wordsPerWin` words
@@ -2553,6 +2652,7 @@ struct FwdSort {
         medSlots = (u32)((size_t)total / 256 + 1); nTiles = (total + SM_TS - 1) / SM_TS;
         survMembers = total;                                          // (not counted before the first round: assume many)
         hipMemsetAsync(w.medStage, 0, 8ull * w.medSlots, s);
+        medFuse = v.ISA2 != nullptr && !tune.noMediumFuse;
         groupSleep = !tune.noUnsplitSkip && !tune.noGroupSleep;      // (the records are the verdicts of the unsplit skip)
         if (groupSleep) hipMemsetAsync(w.medVerdict[0], 0, 16ull * w.medSlots, s);      // (round 0 in every record: no round reads that)
         pbits = bits_for(hp[CNT_LONGEST_BLOCK], 1);                   // positions inside the longest block the transform applies to
@@ -2687,16 +2787,16 @@ struct FwdSort {
         compact_medium(w.med[cur]);
         { KScope ks_("k_bwt_f_probe"); hipLaunchKernelGGL(k_bwt_f_probe_scan, dim3(256), dim3(256), 0, s, v, w.med[cur], (u32)nsym, v.rtbits, probeCand); }
         if (fetch(0, CNT_ROUND_SLOTS)) return -1;
-        surv = hp[CNT_SMALL_LEFT]; nMed = hp[CNT_MED]; nLarge = hp[CNT_LARGE]; largeElems = hp[CNT_LARGE_MEMBERS];
+        surv = hp[CNT_SMALL_LEFT]; nMed = hp[CNT_MED]; nMedLo = hp[CNT_MED_LO]; nLarge = hp[CNT_LARGE]; largeElems = hp[CNT_LARGE_MEMBERS];
         if (const u32 nCand = hp[CNT_PROBE_CAND]) {
             enable_run_tiebits();
             hipMemsetAsync(w.counters, 0, 4 * CNT_PROBE_SLOTS, s);
             { KScope ks_("k_bwt_f_probe");
               hipLaunchKernelGGL(k_bwt_f_probe, dim3(std::min<u32>(nCand, 4096)), dim3(512), 0, s, bv, v, w.med[cur], probeCand, nCand, (u32)nsym, w.med[cur ^ 1], w.large[cur], w.ovr, w.rtbits);
               merge_bits(); }
-            compact_medium(w.med[cur] + nMed);
-            if (fetch(0, CNT_PROBE_SLOTS)) return -1;
-            surv |= hp[CNT_SMALL_LEFT]; nMed += hp[CNT_MED];
+            compact_medium(w.med[cur], nMed, nMedLo);
+            if (fetch(0, CNT_MED_LO + 1)) return -1;                    // (the probe's two slots, and the class count that goes with CNT_MED)
+            surv |= hp[CNT_SMALL_LEFT]; nMed += hp[CNT_MED]; nMedLo += hp[CNT_MED_LO];
         }
         if (tune.stats) fprintf(stderr, "after round 0 (nsym %d, total %u): run groups %u (%u members); small left %u, medium %u, large %u (%u members)\n",
                                 nsym, total, nRun, runElems, surv, nMed, nLarge, largeElems);
@@ -2734,16 +2834,24 @@ struct FwdSort {
         if (linked) hipLaunchKernelGGL(k_bwt_f_link_payoff, dim3(1), dim3(256), 0, s, v, w.linkedTile, w.survTile, nTiles, 1u, w.counters + CNT_LINKED, linkTr);
         if (tune.link) prims::launch_scan<prims::SCAN_SUM_EXCL>(s, w.survTile, w.survTile, nTiles, nullptr, w.scanTmp, w.counters + CNT_TIED);
     }
-    // medium groups: two workgroup shapes over the same list, each takes the groups of its size class: 256 threads x 8 elements (21 KB of
-    // LDS, groups up to 2048) and 512 threads x 16 elements (76 KB: two groups per CU in flight); then the chain round
+    // medium groups: two workgroup shapes, each takes the groups of its size class: 256 threads x 8 elements (21 KB of LDS, groups up to
+    // MED_LO_CAP) and 512 threads x 16 elements (76 KB: two groups per CU in flight); then the chain round. Fused (versioned labels): a
+    // launch per class over that class's index, none for a class without groups; else both shapes walk the whole list.
     void sort_medium()
     {
         const int npass = (kbits + 7) / 8, nxt = cur ^ 1;
-        { KScope ks_("k_bwt_f_sort_medium"); const dim3 gridM(std::min<u32>(nMed, 8192));
+        if (medFuse) {
+            KScope ks_("k_bwt_f_medium_fused"); const int skip = tune.noUnsplitSkip ? 0 : 1; const u32 nMedHi = nMed - nMedLo;
+            const auto fuse256 = tune.stats ? k_bwt_f_medium_fused<256, 8, true> : k_bwt_f_medium_fused<256, 8, false>;
+            const auto fuse512 = tune.stats ? k_bwt_f_medium_fused<512, 16, true> : k_bwt_f_medium_fused<512, 16, false>;
+            // (whole multiples of 8 workgroups, one eighth of a class per XCD; four and two workgroups per CU at once)
+            if (nMedLo) hipLaunchKernelGGL(fuse256, dim3(std::min<u32>((nMedLo + 7) / 8 * 8, 2048)), dim3(256), 0, s, v, w.med[cur], w.medIdxLo, nMedLo, h, npass, skip, w.med[nxt], w.large[nxt], w.superList);
+            if (nMedHi) hipLaunchKernelGGL(fuse512, dim3(std::min<u32>((nMedHi + 7) / 8 * 8, 1024)), dim3(512), 0, s, v, w.med[cur], w.medIdxHi, nMedHi, h, npass, skip, w.med[nxt], w.large[nxt], w.superList);
+        } else { KScope ks_("k_bwt_f_sort_medium"); const dim3 gridM(std::min<u32>(nMed, 8192));
           const auto sort256 = tune.stats ? k_bwt_f_sort_medium<256, 8, true> : k_bwt_f_sort_medium<256, 8, false>;
           const auto sort512 = tune.stats ? k_bwt_f_sort_medium<512, 16, true> : k_bwt_f_sort_medium<512, 16, false>;
           hipLaunchKernelGGL(sort256, gridM, dim3(256), 0, s, v, w.med[cur], nMed, npass, SM_G, w.med[nxt], w.large[nxt], w.descInfo, w.superList);
-          hipLaunchKernelGGL(sort512, gridM, dim3(512), 0, s, v, w.med[cur], nMed, npass, 2048u, w.med[nxt], w.large[nxt], w.descInfo, w.superList); }
+          hipLaunchKernelGGL(sort512, gridM, dim3(512), 0, s, v, w.med[cur], nMed, npass, MED_LO_CAP, w.med[nxt], w.large[nxt], w.descInfo, w.superList); }
         // groups whose majority looks at the group itself (sort_medium has listed them; the kernel reads the count itself)
         { KScope ks_("k_bwt_f_super"); hipLaunchKernelGGL(k_bwt_f_super, dim3(std::min<u32>(nMed, 512)), dim3(1024), 0, s, v, w.superList, h, npass, w.med[nxt], w.large[nxt]); }
     }
@@ -2776,7 +2884,7 @@ struct FwdSort {
         { KScope ks_("k_bwt_f_merge_bits"); merge_bits(); }
         compact_medium(w.med[cur ^ 1]);
         if (fetch(0, CNT_ROUND_SLOTS)) return -1;
-        surv = hp[CNT_SMALL_LEFT]; nMed = hp[CNT_MED]; nLarge = hp[CNT_LARGE]; largeElems = hp[CNT_LARGE_MEMBERS]; survMembers = hp[CNT_TIED];
+        surv = hp[CNT_SMALL_LEFT]; nMed = hp[CNT_MED]; nMedLo = hp[CNT_MED_LO]; nLarge = hp[CNT_LARGE]; largeElems = hp[CNT_LARGE_MEMBERS]; survMembers = hp[CNT_TIED];
         if (tune.stats) {
             // windows that still hold tied small groups (from the scanned per-window counts; developer statistics only)
             std::vector<u32> hs(nTiles); u32 activeTiles = 0;
@@ -2809,7 +2917,8 @@ struct FwdSort {
         // the first round's list is not in slot order (the probe appends) and has no round before it
         if (groupSleep) { v.verdictNow = w.medVerdict[v.round & 1]; v.verdictWas = w.medVerdict[(v.round & 1) ^ 1]; }
         if (groupSleep && nMed && v.round >= 2) { KScope ks_("k_bwt_f_med_sleep"); hipLaunchKernelGGL(k_bwt_f_med_sleep, GRID1(nMed), v, w.med[cur], nMed, tune.stats); }
-        if (nMed) { KScope ks_("k_bwt_f_gather_desc"); hipLaunchKernelGGL(k_bwt_f_gather_desc, dim3(1024), dim3(GATHER_THREADS), 0, s, v, w.med[cur], nMed, h, w.descInfo, tune.stats, tune.noUnsplitSkip ? 0 : 1); }
+        // (k_bwt_f_medium_fused fetches the medium groups' keys itself, behind the small groups' kernel)
+        if (nMed && !medFuse) { KScope ks_("k_bwt_f_gather_desc"); hipLaunchKernelGGL(k_bwt_f_gather_desc, dim3(1024), dim3(GATHER_THREADS), 0, s, v, w.med[cur], nMed, h, w.descInfo, tune.stats, tune.noUnsplitSkip ? 0 : 1); }
         const int lbits = bits_for(nLarge, 0); const bool key32 = kbits + lbits <= 32;
         if (nLarge) { if (key32) large_keys<u32>(); else large_keys<u64>(); }
         if (surv) sort_small(linked);
