@@ -429,6 +429,42 @@ public:
     static const int DEFAULT_CHUNK_SIZE = 1 << 15, MAX_CHUNK_SIZE = 1 << 30;
     RangeDecoder(InputBitStream& ibs, int chunkSize = DEFAULT_CHUNK_SIZE);
 };
+// entropy/Predictor.hpp, CMPredictor.hpp:27-52, BinaryEntropyEncoder.hpp:52, BinaryEntropyDecoder.hpp:52: the constructor shapes of the
+// reference. The coder runs on the device (csrc/cm.hip) and starts from the predictor's initial state, as every caller of the reference
+// does; the object is not read. The device kernels hold the tables of bitstream version 6, which every stream path of the reference
+// passes in its Context: a CMPredictor built without a Context, or with "bsVersion" 7 or more, would stand for the other table
+// (counter2[*][16] = 65535) and is refused with std::invalid_argument. Only a CMPredictor has a device kernel behind it.
+class Predictor {
+public:
+    virtual ~Predictor() {}
+    virtual void update(int bit) = 0;
+    virtual int get() = 0;        // the split, a 12-bit probability of a 1
+};
+class CMPredictor : public Predictor {
+public:
+    explicit CMPredictor(Context* pCtx = nullptr);
+    void update(int bit);
+    int get();
+private:
+    int _c1, _c2, _ctx, _runMask, _idx;
+    std::vector<int> _counter1, _counter2;        // [256][257], [512][17]
+};
+class BinaryEntropyEncoder : public DeviceEntropyEncoder {
+public:
+    BinaryEntropyEncoder(OutputBitStream& obs, Predictor* predictor, bool deallocate = true);
+    ~BinaryEntropyEncoder() { if (_deallocate) delete _predictor; }
+private:
+    Predictor* _predictor;
+    bool _deallocate;
+};
+class BinaryEntropyDecoder : public DeviceEntropyDecoder {
+public:
+    BinaryEntropyDecoder(InputBitStream& ibs, Predictor* predictor, bool deallocate = true);
+    ~BinaryEntropyDecoder() { if (_deallocate) delete _predictor; }
+private:
+    Predictor* _predictor;
+    bool _deallocate;
+};
 class NullEntropyEncoder : public DeviceEntropyEncoder { public: explicit NullEntropyEncoder(OutputBitStream& obs) : DeviceEntropyEncoder(obs, KNZ_E_NONE) {} };
 class NullEntropyDecoder : public DeviceEntropyDecoder { public: explicit NullEntropyDecoder(InputBitStream& ibs) : DeviceEntropyDecoder(ibs, KNZ_E_NONE) {} };
 

@@ -27,7 +27,7 @@ extern "C" {
 #define KNZ_API __attribute__((visibility("default")))
 
 /* kanzi ids: entropy (entropy/EntropyEncoderFactory.hpp:37-52) and transforms (transform/TransformFactory.hpp:49-73) */
-enum { KNZ_E_NONE = 0, KNZ_E_HUFFMAN = 1, KNZ_E_FPAQ = 2, KNZ_E_RANGE = 4, KNZ_E_ANS0 = 5, KNZ_E_ANS1 = 8 };
+enum { KNZ_E_NONE = 0, KNZ_E_HUFFMAN = 1, KNZ_E_FPAQ = 2, KNZ_E_RANGE = 4, KNZ_E_ANS0 = 5, KNZ_E_CM = 6, KNZ_E_ANS1 = 8 };
 enum { KNZ_T_NONE = 0, KNZ_T_BWT = 1, KNZ_T_BWTS = 2, KNZ_T_LZ = 3, KNZ_T_RLT = 5, KNZ_T_ZRLT = 6, KNZ_T_MTFT = 7, KNZ_T_RANK = 8, KNZ_T_SRT = 13, KNZ_T_LZP = 14, KNZ_T_MM = 15, KNZ_T_LZX = 16, KNZ_T_PACK = 18,
        KNZ_T_TIMESTAMP = 64 /* SBRT's third mode: no kanzi id, never part of a chain; per-stage entry points only */,
        KNZ_T_TEXT = 10, KNZ_T_UTF = 17 /* stages that run on the HOST in front of the device chain: knz_hip_encode_block_hosted / _decode_ */ };
@@ -67,7 +67,11 @@ typedef struct {
                                 The encoder writes version 6 only, like the reference. */
 } knz_params;
 
-/* Upper bound, in bytes, of the bit-packed output of knz_hip_encode_blocks for n input bytes. */
+/* Upper bound, in bytes, of the bit-packed output of knz_hip_encode_blocks for n input bytes.
+ * KNZ_E_CM: nothing tighter than the format's own ceiling of 32 bytes per input byte is known for CM, so the value is a FIRST tier --
+ * n + n / 8 plus framing, what the reference's own buffer starts at and what every input met so far stays below. An encode whose
+ * stream does not fit out_cap fails with KNZ_ERR_WRITE_FILE (the message names the size needed) and leaves the context usable;
+ * the second tier, knz_hip_encode_bound(p, n) + 32 * n, holds whatever the format can write. */
 KNZ_API size_t knz_hip_encode_bound(const knz_params* p, size_t n);
 
 /*

@@ -165,7 +165,7 @@ static int count_transforms(uint64_t t, int* tok)
 }
 
 static bool host_stage_id(int t) { return t == KNZ_T_TEXT || t == KNZ_T_UTF; }
-static bool entropy_supported(int e) { return e == KNZ_E_NONE || e == KNZ_E_ANS0 || e == KNZ_E_ANS1 || e == KNZ_E_HUFFMAN || e == KNZ_E_FPAQ || e == KNZ_E_RANGE; }
+static bool entropy_supported(int e) { return e == KNZ_E_NONE || e == KNZ_E_ANS0 || e == KNZ_E_ANS1 || e == KNZ_E_HUFFMAN || e == KNZ_E_FPAQ || e == KNZ_E_RANGE || e == KNZ_E_CM; }
 
 }  // namespace knz
 
@@ -271,6 +271,10 @@ size_t knz_hip_encode_bound(const knz_params* p, size_t n)
     if (p->entropy_type == KNZ_E_ANS1) bound += (n / ANS1_CHUNK + nb) * 256 * (size_t)HDR_BYTES;
     // RANGE: a chunk of c bytes leaves at most c + c / 64 + 2 units of 28 bits and 60 bits of low (range.hip), behind its header
     if (p->entropy_type == KNZ_E_RANGE) bound = 4 * (n + n / 64) + nb * 64 + (n / RANGE_CHUNK + nb) * (HDR_BYTES + 64) + 4096;
+    // CM: no bound is proved below the format's 32 bytes per byte, so this is the FIRST tier, what the encoder stages a block at
+    // (n + n / 8, cm.hip) plus var-ints and tails. An encode whose stream is longer fails with KNZ_ERR_WRITE_FILE and names the size;
+    // 32 * n on top of this value always holds it (include/knz_hip.h).
+    if (p->entropy_type == KNZ_E_CM) bound = (cm_tier1_div() ? n / cm_tier1_div() : n + n / 8) + nb * 64 + nb * (size_t)CM_MAX_CHUNKS * 16 + 4096;
     return bound;
 }
 
@@ -876,13 +880,17 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
     // ---- entropy stage
     const bool ans1 = (p->entropy_type == KNZ_E_ANS1);
     const bool rangeCoder = (p->entropy_type == KNZ_E_RANGE);
-    const u32 entChunk = (p->entropy_type == KNZ_E_FPAQ || ans1) ? (4u << 20) : rangeCoder ? RANGE_CHUNK : ENT_CHUNK;
-    const u32 slotMul = ans1 ? ANS1_SLOTS : 1u;
+    const bool cm = (p->entropy_type == KNZ_E_CM);
+    // (CM: the chunk length depends on the block's own length, so a block is ONE chunk of the framing's arithmetic that owns
+    // cm_max_chunks(S) slots; the slots a block does not use stay zero and add nothing)
+    const u32 entChunk = (p->entropy_type == KNZ_E_FPAQ || ans1) ? (4u << 20) : rangeCoder ? RANGE_CHUNK : cm ? 0x80000000u : ENT_CHUNK;
+    const u32 slotMul = ans1 ? ANS1_SLOTS : cm ? (u32)cm_max_chunks(S) : 1u;
     u32 hdrStride = rangeCoder ? RANGE_STRIDE : TMP_STRIDE;
     const int chunksPerBlock = (int)((S + entChunk - 1) / entChunk);
     const int maxChunks = chunksPerBlock * (int)slotMul;
     const size_t nSlots = (size_t)nBlocks * maxChunks;
     ChunkDesc* d_desc; u8* d_tmp; uint2* d_encTab;
+    u32* d_cmMarked = nullptr;
     if (int r = ws_get(c, "desc", sizeof(ChunkDesc) * nSlots, (void**)&d_desc, s)) return r;
     if (p->entropy_type == KNZ_E_ANS0) {
         if (int r = ws_get(c, "chunkTmp", (size_t)TMP_STRIDE * nSlots, (void**)&d_tmp, s)) return r;
@@ -913,6 +921,14 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
         if (int r = ws_get(c, "chunkTmp", (size_t)RANGE_STRIDE * nSlots, (void**)&d_tmp, s)) return r;
         if (int r = ws_get(c, "rangeCumFreq", sizeof(u32) * 256 * nSlots, (void**)&d_cumFreq, s)) return r;
         launch_range_encode(s, view, d_origLen, framing ? 15u : 0u, nBlocks, maxChunks, d_desc, d_cumFreq, d_tmp);
+    } else if (cm) {
+        const u64 cStride = cm_stage_stride(S);
+        void* d_cmCtrl;
+        if (int r = ws_get(c, "chunkTmp", (size_t)cStride * nBlocks, (void**)&d_tmp, s)) return r;
+        if (int r = ws_get(c, "cmCtrl", cm_ctrl_bytes(nBlocks), &d_cmCtrl, s)) return r;
+        // blocks that did not fit their staging are coded again into 32 n + 16 bytes each: workspace taken only then
+        launch_cm_encode(s, view, d_origLen, framing ? 15u : 0u, nBlocks, maxChunks, d_desc, d_tmp, cStride, d_cmCtrl);
+        d_cmMarked = static_cast<u32*>(d_cmCtrl);                 // how many blocks did not fit: read back with the total below
     } else {
         if (int r = ws_get(c, "chunkTmp", 64, (void**)&d_tmp, s)) return r;
         launch_none_encode(s, view, nBlocks, maxChunks, d_desc);
@@ -926,8 +942,29 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
     // The output must be zero before the OR-assembly; its size is only known on the device, so the
     // total is read back first (8 bytes) and only the used part is cleared.
     u64* h_total = reinterpret_cast<u64*>(c->pinned);
+    u32* h_marked = reinterpret_cast<u32*>(h_total + 1);
+    *h_marked = 0;
     HIPCHK(c, hipMemcpyAsync(h_total, d_total, sizeof(u64), hipMemcpyDeviceToHost, s));
+    if (d_cmMarked) HIPCHK(c, hipMemcpyAsync(h_marked, d_cmMarked, sizeof(u32), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
+    if (*h_marked) {
+        // CM, the rare path: blocks that did not fit their staging are coded again into 32 n + 16 bytes each (workspace taken only now),
+        // then the lengths are summed again
+        struct Big { Ctx* c; hipStream_t s; int rc; } big = { c, s, 0 };
+        auto bigAlloc = [](void* user, size_t bytes) -> void* {
+            Big* g = static_cast<Big*>(user);
+            void* m = nullptr;
+            g->rc = ws_get(g->c, "cmBig", bytes, &m, g->s);
+            return g->rc ? nullptr : m;
+        };
+        const int r = launch_cm_encode_again(s, view, d_origLen, framing ? 15u : 0u, nBlocks, maxChunks, d_desc, d_tmp, cm_stage_stride(S), d_cmMarked, bigAlloc, &big);
+        if (r == -2) return big.rc;                               // (ws_get has said why)
+        if (r < 0) return fail(c, -1, "CM encode failed: %s", hipGetErrorString(hipGetLastError()));
+        launch_block_sum(s, d_desc, d_info, d_blockLen, nBlocks, maxChunks, entChunk, slotMul);
+        launch_block_scan(s, d_info, d_blockLen, d_origLen, nBlocks, fp, d_total);
+        HIPCHK(c, hipMemcpyAsync(h_total, d_total, sizeof(u64), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+    }
     const u64 totalBits = *h_total;
     const size_t outBytes = (size_t)((totalBits + 7) >> 3);
     if (((outBytes + 8 + 3) & ~(size_t)3) > outCap) return fail(c, KNZ_ERR_WRITE_FILE, "output buffer too small: need %zu have %zu", (outBytes + 8 + 3) & ~(size_t)3, outCap);
@@ -1083,6 +1120,8 @@ static int decode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, uint64_
             launch_fpaq_decode(sp, src, blk, nb, w.d_entDst);
         } else if (p->entropy_type == KNZ_E_RANGE) {
             launch_range_decode(sp, src, blk, nb, w.d_entDst, framing);
+        } else if (p->entropy_type == KNZ_E_CM) {
+            launch_cm_decode(sp, src, blk, nb, w.d_entDst);
         } else {
             launch_none_decode(sp, src, blk, nb, w.d_entDst);
         }
@@ -1174,7 +1213,14 @@ int knz_hip_entropy_encode(knz_ctx* ctx, int entropy_type, const uint8_t* in, ui
     if (int r = ws_get(c, "stageOut", cap, (void**)&d_out, c->stream)) return r;
     HIPCHK(c, hipMemcpyAsync(d_in, in, n, hipMemcpyHostToDevice, c->stream));
     u64 bits = 0;
-    if (int r = encode_impl(c, &p, d_in, n, nullptr, 0, 0, 0, 0, d_out, cap, &bits)) return r;
+    int r = encode_impl(c, &p, d_in, n, nullptr, 0, 0, 0, 0, d_out, cap, &bits);
+    if (r == KNZ_ERR_WRITE_FILE && entropy_type == KNZ_E_CM) {
+        // the bound of CM is its first tier (knz_hip_encode_bound): the second holds whatever the format can write
+        const size_t cap2 = cap + 32 * (size_t)n;
+        if (int r2 = ws_get(c, "stageOut", cap2, (void**)&d_out, c->stream)) return r2;
+        r = encode_impl(c, &p, d_in, n, nullptr, 0, 0, 0, 0, d_out, cap2, &bits);
+    }
+    if (r) return r;
     const size_t bytes = (size_t)((bits + 7) >> 3);
     if (bytes > out_cap) return fail(c, KNZ_ERR_WRITE_FILE, "output buffer too small");
     HIPCHK(c, hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, c->stream));

@@ -25,6 +25,7 @@
 //     issued before the bit is known, the payload is pre-shifted to 32-bit units held one per lane (64 units per load).
 #include "common.hpp"
 #include "stages.hpp"
+#include "binary_tail.hpp"
 
 namespace knz {
 
@@ -152,30 +153,6 @@ __device__ __forceinline__ void fpaq_probs_family(BlockView view, int b, u32 fam
 // ------------------------------------------------------------------------------------------------
 // encoder, phase 2: the interval recurrence, one wave per block
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void fpaq_desc_finish(ChunkDesc& cd, u32 index, const u8* buf, u64 low)
-{
-    cd.hdrBits = 0; cd.aux = 0;
-    u8 mid[8];
-    u32 ml = 0;
-    u32 v = index;
-    while (v >= 128) { mid[ml++] = (u8)(0x80 | (v & 0x7F)); v >>= 7; }
-    mid[ml++] = (u8)v;
-    u32 mw[6] = { 0, 0, 0, 0, 0, 0 };
-    for (u32 i = 0; i < ml; i++) mw[i >> 2] |= (u32)mid[i] << (8 * (i & 3));
-    for (int i = 0; i < 6; i++) cd.mid[i] = mw[i];
-    cd.midLen = ml;
-    cd.nPieces = index ? 1 : 0;
-    cd.pieceBits[0] = 8 * index;
-    cd.piecePtr[0] = buf;
-    // 56 bits of low | 0xFFFFFF after every sub-chunk; the last one is written by dispose() (FPAQEncoder.cpp:92-110)
-    const u64 tail = (low | FPAQ_MASK24) & FPAQ_MASK56;
-    u32 tw[2] = { 0, 0 };
-    for (int k = 0; k < 7; k++) { const u32 byte = (u32)((tail >> (48 - 8 * k)) & 0xFF); tw[k >> 2] |= byte << (8 * (k & 3)); }
-    cd.trailer[0] = tw[0]; cd.trailer[1] = tw[1];
-    cd.trailerLen = 7;
-}
-
-
 __device__ __forceinline__ void fpaq_code_block(BlockView view, int b, const u32* __restrict__ origLen, u32 copyThreshold, int maxChunks,
                                                 ChunkDesc* __restrict__ desc, u8* __restrict__ tmp, u64 tmpStride, const u16* __restrict__ probs, u64 pStride,
                                                 const u32* __restrict__ progBlock, u32* ring)
@@ -239,7 +216,7 @@ __device__ __forceinline__ void fpaq_code_block(BlockView view, int b, const u32
             __syncthreads();
             index += 4 * cnt;
         }
-        if (lane == 0) fpaq_desc_finish(cds[ci], index, buf, low);
+        if (lane == 0) binary_desc_finish(cds[ci], index, buf, low);
         startChunk = endChunk;
         ci++;
     }

@@ -118,6 +118,26 @@ void launch_fpaq_encode(hipStream_t s, BlockView view, const u32* origLen, u32 c
                         u16* probs, u64 S);
 size_t fpaq_probs_bytes(int nBlocks, u64 S);
 void launch_fpaq_decode(hipStream_t s, BitSrc src, DecBlock* blocks, int nBlocks, u8* const* outPtr);
+
+// cm.hip (CM, entropy id 6). A block owns cm_max_chunks(S) ChunkDesc slots (1, or CM_MAX_CHUNKS when blocks can reach the size the
+// format splits at); its payload is staged at tmp + b * tmpStride, tmpStride = cm_stage_stride(S) (n + n / 8 + slack: no bound is proved
+// for CM). launch_cm_encode leaves the number of blocks that did not fit in the first 32-bit word of ctrlMem (cm_ctrl_bytes(nBlocks)
+// bytes of device memory); a caller that reads a non-zero count back calls launch_cm_encode_again before it uses the descriptors:
+// the marked blocks are coded again into 32 n + 16 bytes each, which it asks bigAlloc for (device memory that lives until the stream
+// is assembled; nullptr = failure). That call synchronises the stream; it returns the number of blocks coded again, -1 for a HIP
+// error, -2 when bigAlloc failed.
+constexpr u32 CM_MAX_CHUNKS = 17;            // ceil(count / (count >> 4)) for count >= 256
+typedef void* (*CmBigAlloc)(void* user, size_t bytes);
+int cm_max_chunks(u64 S);
+u32 cm_tier1_div();                          // 0, or the divisor KNZ_CM_TIER1_DIV sets for tests (cm.hip)
+u64 cm_stage_stride(u64 S);
+size_t cm_ctrl_bytes(int nBlocks);
+void launch_cm_encode(hipStream_t s, BlockView view, const u32* origLen, u32 copyThreshold, int nBlocks, int maxChunks, ChunkDesc* desc,
+                      u8* tmp, u64 tmpStride, void* ctrlMem);
+int launch_cm_encode_again(hipStream_t s, BlockView view, const u32* origLen, u32 copyThreshold, int nBlocks, int maxChunks, ChunkDesc* desc,
+                           u8* tmp, u64 tmpStride, void* ctrlMem, CmBigAlloc bigAlloc, void* user);
+void launch_cm_decode(hipStream_t s, BitSrc src, DecBlock* blocks, int nBlocks, u8* const* outPtr);
+
 void launch_srt_forward(hipStream_t s, const XfStage& st);          // scratch: srt_scratch_u32(nBlocks, maxLen) words
 size_t srt_scratch_u32(int nBlocks, u32 maxLen);
 void launch_srt_inverse(hipStream_t s, const XfStage& st);          // scratch: srt_inverse_scratch_u32(nBlocks, maxLen) words

@@ -10,8 +10,8 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libknz_hip.so")
 
-E_NONE, E_HUFFMAN, E_FPAQ, E_RANGE, E_ANS0, E_ANS1 = 0, 1, 2, 4, 5, 8
-ENTROPY_IDS = {"NONE": 0, "HUFFMAN": 1, "FPAQ": 2, "RANGE": 4, "ANS0": 5, "ANS1": 8}
+E_NONE, E_HUFFMAN, E_FPAQ, E_RANGE, E_ANS0, E_CM, E_ANS1 = 0, 1, 2, 4, 5, 6, 8
+ENTROPY_IDS = {"NONE": 0, "HUFFMAN": 1, "FPAQ": 2, "RANGE": 4, "ANS0": 5, "CM": 6, "ANS1": 8}
 TRANSFORM_IDS = {"NONE": 0, "BWT": 1, "BWTS": 2, "LZ": 3, "RLT": 5, "ZRLT": 6, "MTFT": 7, "RANK": 8, "SRT": 13, "LZP": 14, "MM": 15, "LZX": 16, "PACK": 18, "TIMESTAMP": 64}
 
 SYMBOLS = [
@@ -177,7 +177,8 @@ class Context:
     # ---- per-stage API on host buffers
     def entropy_encode(self, entropy, data):
         e = ENTROPY_IDS[entropy.upper()]
-        cap = (4 if e == E_RANGE else 2) * len(data) + 65536     # (RANGE: up to 28 bits per byte and a bit, knz_hip_encode_bound)
+        # (RANGE: up to 28 bits per byte and a bit; CM: the format's ceiling of 32 bytes per byte -- knz_hip_encode_bound)
+        cap = (34 if e == E_CM else 4 if e == E_RANGE else 2) * len(data) + 65536
         out = (C.c_uint8 * cap)()
         bits = C.c_uint64(0)
         self._chk(self.L.knz_hip_entropy_encode(self.h, e, data, len(data), out, cap, C.byref(bits)))

@@ -970,7 +970,13 @@ int DeviceEntropyEncoder::encode(const byte block[], uint blkptr, uint len)
     const size_t cap = knz_hip_encode_bound(&p, len) + 64;
     std::vector<byte> out(cap);
     uint64_t bits = 0;
-    devCheck(c, knz_hip_entropy_encode(c, _type, &block[blkptr], len, out.data(), cap, &bits), "entropy encode");
+    int rc = knz_hip_entropy_encode(c, _type, &block[blkptr], len, out.data(), cap, &bits);
+    if (rc == KNZ_ERR_WRITE_FILE && _type == KNZ_E_CM) {
+        // CM's bound is a first tier (include/knz_hip.h); the second holds whatever the format can write
+        out.resize(cap + 32 * size_t(len));
+        rc = knz_hip_entropy_encode(c, _type, &block[blkptr], len, out.data(), out.size(), &bits);
+    }
+    devCheck(c, rc, "entropy encode");
     uint64 done = 0;
     while (done < bits) {
         const uint64 chunk = std::min<uint64>(bits - done, uint64(1) << 30);   // multiple of 8 except for the last piece
@@ -1063,6 +1069,55 @@ RangeEncoder::RangeEncoder(OutputBitStream& obs, int chunkSize, int logRange) : 
 
 RangeDecoder::RangeDecoder(InputBitStream& ibs, int chunkSize) : DeviceEntropyDecoder(ibs, KNZ_E_RANGE) { checkRangeArgs(chunkSize, RangeEncoder::DEFAULT_LOG_RANGE); }
 
+// entropy/CMPredictor.cpp:27-53, CMPredictor.hpp:55-87
+CMPredictor::CMPredictor(Context* pCtx) : _c1(0), _c2(0), _ctx(1), _runMask(0), _idx(8), _counter1(256 * 257, 32768), _counter2(512 * 17)
+{
+    if (pCtx == nullptr) throw std::invalid_argument("CM predictor: without a Context the reference builds the table of bitstream version 7, which has no device kernel");
+    if (pCtx->getInt("bsVersion", 7) >= 7) throw std::invalid_argument("CM predictor: the table of bitstream version 7 and up has no device kernel");
+    for (int i = 0; i < 512; i++)
+        for (int j = 0; j <= 16; j++) _counter2[i * 17 + j] = j << 12;
+}
+
+int CMPredictor::get()
+{
+    const int* pc1 = &_counter1[_ctx * 257];
+    const int p = (13 * (pc1[256] + pc1[_c1]) + 6 * pc1[_c2]) >> 5;
+    _idx = p >> 12;
+    const int* pc2 = &_counter2[(_ctx | _runMask) * 17 + _idx];
+    return (p + p + 3 * (pc2[0] + pc2[1]) + 64) >> 7;
+}
+
+void CMPredictor::update(int bit)
+{
+    int* pc1 = &_counter1[_ctx * 257];
+    int* pc2 = &_counter2[(_ctx | _runMask) * 17 + _idx];
+    const int target = bit ? 65536 - 16 : 0;       // p -= (p - 65536 + 16) >> r after a 1, p -= p >> r after a 0
+    pc1[256] -= (pc1[256] - target) >> 2;
+    pc1[_c1] -= (pc1[_c1] - target) >> 4;
+    pc2[0] -= (pc2[0] - target) >> 6;
+    pc2[1] -= (pc2[1] - target) >> 6;
+    _ctx = 2 * _ctx + (bit ? 1 : 0);
+    if (_ctx > 255) {
+        _c2 = _c1;
+        _c1 = _ctx & 0xFF;
+        _ctx = 1;
+        _runMask = (_c1 == _c2) ? 0x100 : 0;
+    }
+}
+
+static Predictor* checkPredictor(Predictor* predictor)
+{
+    if (predictor == nullptr) throw std::invalid_argument("Invalid null predictor parameter");
+    if (dynamic_cast<CMPredictor*>(predictor) == nullptr) throw std::invalid_argument("Binary entropy codec: only the CM predictor has a device kernel");
+    return predictor;
+}
+
+BinaryEntropyEncoder::BinaryEntropyEncoder(OutputBitStream& obs, Predictor* predictor, bool deallocate)
+    : DeviceEntropyEncoder(obs, KNZ_E_CM), _predictor(checkPredictor(predictor)), _deallocate(deallocate) {}
+
+BinaryEntropyDecoder::BinaryEntropyDecoder(InputBitStream& ibs, Predictor* predictor, bool deallocate)
+    : DeviceEntropyDecoder(ibs, KNZ_E_CM), _predictor(checkPredictor(predictor)), _deallocate(deallocate) {}
+
 static const struct { const char* name; short type; } ENAMES[] = {
     {"NONE", 0}, {"HUFFMAN", 1}, {"FPAQ", 2}, {"RANGE", 4}, {"ANS0", 5}, {"CM", 6}, {"TPAQ", 7}, {"ANS1", 8}, {"TPAQX", 9} };
 
@@ -1080,7 +1135,7 @@ short EntropyEncoderFactory::getType(const char* str)
     throw std::invalid_argument("Unsupported entropy codec type: '" + name + "'");
 }
 
-EntropyEncoder* EntropyEncoderFactory::newEncoder(OutputBitStream& obs, Context&, short entropyType)
+EntropyEncoder* EntropyEncoderFactory::newEncoder(OutputBitStream& obs, Context& ctx, short entropyType)
 {
     switch (entropyType) {
     case HUFFMAN_TYPE: return new HuffmanEncoder(obs);
@@ -1088,6 +1143,7 @@ EntropyEncoder* EntropyEncoderFactory::newEncoder(OutputBitStream& obs, Context&
     case ANS1_TYPE: return new ANSRangeEncoder(obs, 1);
     case FPAQ_TYPE: return new FPAQEncoder(obs);
     case RANGE_TYPE: return new RangeEncoder(obs);
+    case CM_TYPE: return new BinaryEntropyEncoder(obs, new CMPredictor(&ctx));           // EntropyEncoderFactory.hpp:81
     case NONE_TYPE: return new NullEntropyEncoder(obs);
     default: throw std::invalid_argument(std::string("Entropy codec '") + getName(entropyType) + "' has no device kernel");
     }
@@ -1101,6 +1157,7 @@ EntropyDecoder* EntropyDecoderFactory::newDecoder(InputBitStream& ibs, Context& 
     case EntropyEncoderFactory::ANS1_TYPE: return new ANSRangeDecoder(ibs, 1);
     case EntropyEncoderFactory::FPAQ_TYPE: return new FPAQDecoder(ibs);
     case EntropyEncoderFactory::RANGE_TYPE: return new RangeDecoder(ibs);
+    case EntropyEncoderFactory::CM_TYPE: return new BinaryEntropyDecoder(ibs, new CMPredictor(&ctx));      // EntropyDecoderFactory.hpp:83
     case EntropyEncoderFactory::NONE_TYPE: return new NullEntropyDecoder(ibs);
     default: throw std::invalid_argument(std::string("Entropy codec '") + getName(entropyType) + "' has no device kernel");
     }
@@ -1589,6 +1646,16 @@ void CompressedOutputStream::submit(Lane& ln)
     std::unique_ptr<GateHold> gateOwner(gate);
     std::chrono::steady_clock::time_point tk0 = std::chrono::steady_clock::now();
     if (_hosted && n == 0) p.transform_type = 0;             // (the empty last batch: end marker only; the device call checks the chain before it looks at the size)
+    // CM: knz_hip_encode_bound is a first tier (include/knz_hip.h); a batch that does not fit it is encoded once more into the second
+    auto secondTier = [&](const std::function<int()>& call) -> int {
+        int rc = call();
+        if (rc == KNZ_ERR_WRITE_FILE && _entropyType == KNZ_E_CM) {
+            const size_t cap2 = cap + 32 * n;
+            g_devPool.put(c, ln.dOut, ln.dOutCap); ln.dOut = nullptr; ln.dOutCap = 0; ln.dOut = g_devPool.get(c, cap2, &ln.dOutCap);
+            rc = call();
+        }
+        return rc;
+    };
     if (_hosted && n > 0) {
         // host stages first (the original bytes are still in the lane's staging buffer), then the block in its new length to the device
         if (n > size_t(_blockSize)) throw IOException("a chain with host stages takes one block per call", Error::ERR_PROCESS_BLOCK);
@@ -1601,11 +1668,11 @@ void CompressedOutputStream::submit(Lane& ln)
         hs.applied_mask = r.applied;
         hs.reserved = uint32_t(r.dataType);
         if (r.applied) devCheck(c, knz_hip_memcpy_h2d(c, ln.dIn, r.data, size_t(r.len)), "h2d");
-        devCheck(c, knz_hip_encode_block_hosted(c, &p, &hs, static_cast<const uint8_t*>(ln.dIn), size_t(r.len), pro.bytes.empty() ? nullptr : pro.bytes.data(), uint32_t(pro.nbits),
-                                                ln.firstBlock, ln.last ? 1 : 0, static_cast<uint8_t*>(ln.dOut), ln.dOutCap, &bits), "encode block");
+        devCheck(c, secondTier([&] { return knz_hip_encode_block_hosted(c, &p, &hs, static_cast<const uint8_t*>(ln.dIn), size_t(r.len), pro.bytes.empty() ? nullptr : pro.bytes.data(), uint32_t(pro.nbits),
+                                                                        ln.firstBlock, ln.last ? 1 : 0, static_cast<uint8_t*>(ln.dOut), ln.dOutCap, &bits); }), "encode block");
     } else
-    devCheck(c, knz_hip_encode_blocks(c, &p, static_cast<const uint8_t*>(ln.dIn), n, pro.bytes.empty() ? nullptr : pro.bytes.data(), uint32_t(pro.nbits),
-                                      ln.firstBlock, ln.last ? 1 : 0, static_cast<uint8_t*>(ln.dOut), ln.dOutCap, &bits), "encode blocks");
+    devCheck(c, secondTier([&] { return knz_hip_encode_blocks(c, &p, static_cast<const uint8_t*>(ln.dIn), n, pro.bytes.empty() ? nullptr : pro.bytes.data(), uint32_t(pro.nbits),
+                                                              ln.firstBlock, ln.last ? 1 : 0, static_cast<uint8_t*>(ln.dOut), ln.dOutCap, &bits); }), "encode blocks");
     gateOwner.reset();
     const double tlKern = hostTimeline() ? msSince(_t0) : 0;
     _tns[4] += uint64_t(std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tk0).count());

@@ -4,12 +4,12 @@
 //   kanzi_amd_cli -c -i FILE [-o FILE.knz] [-t TRANSFORMS] [-e ENTROPY] [-l LEVEL] [-b SIZE] [-j JOBS] [-x | -x32 | -x64] [-f]
 //   kanzi_amd_cli -d -i FILE.knz [-o FILE] [-j JOBS] [--from=N] [--to=N] [-f]
 //
-// -e takes NONE, HUFFMAN, ANS0, ANS1, FPAQ and RANGE. Levels 0, 1, 5 and 6 are in (5 and 6: TEXT and UTF on the host in front of the device chain, host/text_codec.cpp).
+// -e takes NONE, HUFFMAN, ANS0, ANS1, FPAQ, RANGE and CM. Levels 0, 1, 5 and 6 are in (5 and 6: TEXT and UTF on the host in front of the device chain, host/text_codec.cpp).
 // What it does not do (and says so instead of guessing): directories, stdin/stdout, `-y` info, levels whose chains need the
-// reference's CPU-only transforms (EXE, DNA, ROLZ) or entropy coders (CM, TPAQ), or LZ / LZX behind PACK or MM (the device LZ
+// reference's CPU-only transforms (EXE, DNA, ROLZ) or entropy coders (TPAQ, TPAQX), or LZ / LZX behind PACK or MM (the device LZ
 // stages do not read the data type those leave, which level 3 needs): levels 2-4 and 7-9. PACK, MM and LZP themselves run on the
-// device (-t, LZP in any position behind the host stages); level 7 (LZP+TEXT+UTF+BWT+LZP / CM) still needs the CM coder and a host
-// stage behind a device stage.
+// device (-t, LZP in any position behind the host stages); level 7 (LZP+TEXT+UTF+BWT+LZP / CM) still needs a host stage behind a
+// device stage (its coder, CM, runs on the device).
 // Files written here are byte-identical to `kanzi -c` with the same -t/-e/-b/-x/-j, and either tool reads the other's files
 // (tests/test_host_stub.py, tests/test_gpu_host_api.py).
 #include <cstdio>

@@ -85,8 +85,18 @@ class DeviceRunEncoder:
         d_in, d_out = self.bufs.get("in", len(data) + 64), self.bufs.get("out", cap)
         if data:
             ctx.h2d(d_in, data)
-        bits = ctx.encode_blocks(self.p, d_in, len(data), d_out, cap, prologue=hdr, prologue_bits=hb, first_block=first_block,
-                                 finish=1 if finish else 0)
+        hipapi = importlib.import_module("kanzi_amd.hipapi")
+        try:
+            bits = ctx.encode_blocks(self.p, d_in, len(data), d_out, cap, prologue=hdr, prologue_bits=hb, first_block=first_block,
+                                     finish=1 if finish else 0)
+        except hipapi.KnzError as e:
+            # CM: knz_hip_encode_bound is a first tier (include/knz_hip.h); the second holds whatever the format can write
+            if e.code != 12 or self.p.entropy_type != hipapi.E_CM:
+                raise
+            cap += 32 * len(data)
+            d_out = self.bufs.get("out", cap)
+            bits = ctx.encode_blocks(self.p, d_in, len(data), d_out, cap, prologue=hdr, prologue_bits=hb, first_block=first_block,
+                                     finish=1 if finish else 0)
         return ctx.d2h(d_out, (bits + 7) // 8), bits
 
 
