@@ -174,6 +174,7 @@ __global__ __launch_bounds__(64) void k_assemble(const ChunkDesc* __restrict__ d
     }
     const ChunkDesc& cd = desc[slot];
     pos += cd.relBit;
+    const u64 chunkPos = pos;
     // hdr bits
     wave_copy_bits(out, pos, hdrBase + (size_t)slot * hdrStride, cd.hdrBits);
     pos += cd.hdrBits;
@@ -184,6 +185,11 @@ __global__ __launch_bounds__(64) void k_assemble(const ChunkDesc* __restrict__ d
         pos += cd.pieceBits[k];
     }
     if (lane == 0) lane_put_bytes(out, pos, cd.trailer, cd.trailerLen);
+    if (cd.aux >> 31) {                             // RANGE chunk with a wide frequency: the reference's unmasked writes (common.hpp)
+        __threadfence();
+        __syncthreads();
+        if (lane == 0) range_wide_spill(out, chunkPos, (fp.framing ? (u64)bi.hdrBits : 0ull) + cd.relBit, cd);
+    }
 }
 
 __global__ void k_put_prologue(u32* out, const u8* prologue, u32 bits)

@@ -33,12 +33,16 @@ struct BlockView {
 struct ChunkDesc {
     u32 hdrBits;
     u32 midLen;          // bytes
-    u32 mid[6];          // up to 24 inline bytes, memory order
+    u32 mid[6];          // up to 24 inline bytes, memory order. A RANGE chunk with aux bit 31 has midLen 0 and keeps three words here:
+                         // [0] bit offset in the header of the group log size that exceeds 4 bits (0xFFFFFFFF: none), [1] that log size,
+                         // [2] the number of 28-bit units (range.hip; read by range_wide_spill below)
     u32 nPieces;
     u32 pieceBits[4];
     u32 trailerLen;      // bytes
     u32 trailer[2];      // up to 8 inline bytes, memory order
-    u32 aux;             // codec specific (alphabet size)
+    u32 aux;             // codec specific below bit 31 (an alphabet size; RANGE adds its log range from bit 16). Every coder sets it for every
+                         // slot it emits, and bit 31 belongs to k_assemble: set, the chunk is a RANGE chunk with a wide frequency whose
+                         // unmasked bits it adds (range_wide_spill). No other coder may set it or leave aux unwritten.
     const u8* piecePtr[4];
     u64 relBit;          // bit offset of this chunk inside the block's entropy payload (k_block_sum)
     u64 totalBits;
@@ -212,6 +216,29 @@ __device__ __forceinline__ void or_bits_mem(u32* memWords, u64 pos, u64 value, u
         pos += take;
         n -= take;
     }
+}
+
+// A RANGE chunk whose normalised frequencies do not fit 16 bits (ChunkDesc::aux bit 31; range.hip, k_range_encode_wide). The reference's
+// writeBits(value, count) does not mask its value while the field lies inside the current 64-bit word of the block's own bit stream
+// (DefaultOutputBitStream.hpp:102-105): bits of the value above `count` are ORed into the bits written just before the field, as far
+// back as that word goes. Such a chunk has three kinds of oversized values: the log size of the wide frequency's group (32 in 4 bits),
+// the top four bits of `low` in every unit of 28 bits, and those of the final 60 bits. `absStart` is the chunk's first bit in `out`,
+// `p0` the same position counted from the start of the block's bit stream (its mode byte), which is what the words are aligned to.
+constexpr u32 RANGE_WIDE_NIB = 32768;      // byte offset of the per-write top bits inside the chunk's payload staging
+__device__ inline void range_wide_spill(u32* out, u64 absStart, u64 p0, const ChunkDesc& cd)
+{
+    auto spill = [&](u64 off, u32 count, u32 extra) {        // extra: the value's bits above count, bit t belongs at position -1 - t
+        const u32 m = (u32)((p0 + off) & 63);
+        if (count >= 64 - m) return;                          // the field ends the word or crosses it: masked, or shifted out
+        for (u32 t = 0; t < 4 && t < m; t++)
+            if ((extra >> t) & 1) or_bits_mem(out, absStart + off - 1 - t, 1, 1);
+    };
+    if (cd.mid[0] != 0xFFFFFFFFu) spill(cd.mid[0], 4, cd.mid[1] >> 4);
+    const u8* nib = cd.piecePtr[0] + RANGE_WIDE_NIB;
+    const u32 units = cd.mid[2];
+    u64 off = cd.hdrBits;
+    for (u32 u = 0; u < units; u++, off += 28) spill(off, 28, nib[u]);
+    spill(off, 60, nib[units]);
 }
 
 // --- launch helpers (host) ---

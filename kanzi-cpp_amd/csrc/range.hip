@@ -91,17 +91,36 @@ __global__ __launch_bounds__(64) void k_range_stats(BlockView view, const u32* _
     const u32 hdrWordsUsed = (pos + 31) >> 5;
     for (u32 i = lane; i < hdrWordsUsed; i += 64) hdrOut[i] = bswap32(hdrw[i]);
 
+    // A frequency that does not fit 16 bits: the normalisation's last line wrapped below zero (EntropyUtils.cpp:243; a short chunk at a low
+    // log range whose many rare symbols were raised to 1). Nobody can read such a chunk, the reference included, but it writes one, with
+    // 64-bit products and unmasked fields: k_range_encode_wide and range_wide_spill (common.hpp) write the same bits.
+    int wk = -1;
+#pragma unroll
+    for (int k = 0; k < 4; k++) if (f[k] > 0xFFFFu) wk = k;
+    const bool wide = asz > 1 && __ballot(wk >= 0) != 0;
+    if (wide && wk >= 0) {
+        // position and value of the log size of this symbol's group, when it does not fit its 4 bits
+        const u32 r = rankBase + (u32)__popc(present & ((1u << wk) - 1u));
+        const u32 chk = (asz >= 64) ? 8u : 6u, nGroups = (asz - 1 + chk - 1) / chk;
+        cd->mid[0] = 0xFFFFFFFFu; cd->mid[1] = 0;
+        if (r >= 1 && grpMax[(r - 1) / chk] >= 16) {
+            const u32 last = nGroups - 1, cntLast = asz - (1 + last * chk);
+            const u32 groupsBits = grpOff[last] + 4 + cntLast * grpMax[last];
+            cd->mid[0] = pos - groupsBits + grpOff[(r - 1) / chk];
+            cd->mid[1] = grpMax[(r - 1) / chk];
+        }
+    }
     if (asz > 1) {
-        // cumulative frequencies in symbol order (RangeEncoder.cpp:71-77), as the normalisation left them
+        // cumulative frequencies in symbol order (RangeEncoder.cpp:71-77), as the normalisation left them (wide: the frequencies alone)
         const u32 lsum = f[0] + f[1] + f[2] + f[3];
         const u32 lincl = wave_incl_scan(lsum);
         u32 cum = lincl - lsum;
         u32* out = cumFreq + (size_t)slot * 256;
 #pragma unroll
-        for (int k = 0; k < 4; k++) { out[4 * lane + k] = cum | (f[k] << 16); cum += f[k]; }
+        for (int k = 0; k < 4; k++) { out[4 * lane + k] = wide ? f[k] : (cum | (f[k] << 16)); cum += f[k]; }
     }
     if (lane == 0) {
-        cd->hdrBits = pos; cd->midLen = 0; cd->trailerLen = 0; cd->nPieces = 0; cd->aux = asz | (lr << 16);
+        cd->hdrBits = pos; cd->midLen = 0; cd->trailerLen = 0; cd->nPieces = 0; cd->aux = asz | (lr << 16) | (wide ? 0x80000000u : 0u);
     }
 }
 
@@ -140,7 +159,7 @@ __global__ __launch_bounds__(64) void k_range_encode(BlockView view, int maxChun
         const u32 start = (u32)ci * RANGE_CHUNK;
         if (start < len) {
             const u32 aux = desc[slot].aux;
-            if ((aux & 0xFFFF) > 1) {                // (0: raw copy block; 1: one symbol, the header is all)
+            if ((aux & 0xFFFF) > 1 && !(aux >> 31)) {   // (0: raw copy block; 1: one symbol, the header is all; bit 31: k_range_encode_wide)
                 act = true;
                 lr = aux >> 16;
                 n = (len - start < RANGE_CHUNK) ? (len - start) : RANGE_CHUNK;
@@ -234,6 +253,68 @@ __global__ __launch_bounds__(64) void k_range_encode(BlockView view, int maxChun
         ChunkDesc* cd = desc + slotBase + lane;
         cd->nPieces = 1; cd->pieceBits[0] = 32 * wc + nacc; cd->piecePtr[0] = reinterpret_cast<const u8*>(pay);
     }
+}
+
+// A chunk with a wide frequency (k_range_stats), one lane per chunk: RangeEncoder::encodeByte as it stands, in 64-bit cumulative
+// frequencies and products that wrap. The payload staging holds the units as the bit stream will (the top four bits of every value
+// masked off), those top bits per write at RANGE_WIDE_NIB for range_wide_spill, and the cumulative table. The renormalisation loop
+// has no bound of two turns here (a product may wrap to a range of 0, on which the reference never ends): it stops at RANGE_WIDE_UNITS.
+constexpr u32 RANGE_WIDE_UNITS = (RANGE_WIDE_NIB * 8 - 64) / 28;
+constexpr u32 RANGE_WIDE_CUM = 2 * RANGE_WIDE_NIB;
+static_assert(RANGE_WIDE_UNITS + 1 <= RANGE_WIDE_NIB && RANGE_WIDE_CUM + 257 * 8 <= RANGE_PAY_BYTES && (HDR_BYTES + RANGE_WIDE_CUM) % 8 == 0, "wide staging");
+__global__ __launch_bounds__(64) void k_range_encode_wide(BlockView view, int maxChunks, int nSlots, ChunkDesc* __restrict__ desc,
+                                                          const u32* __restrict__ cumFreq, u8* __restrict__ tmp)
+{
+    const int slot = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (slot >= nSlots) return;
+    const int b = slot / maxChunks;
+    const int ci = slot - b * maxChunks;
+    const u32 len = view.len[b];
+    const u32 start = (u32)ci * RANGE_CHUNK;
+    if (start >= len) return;
+    ChunkDesc* cd = desc + slot;
+    const u32 aux = cd->aux;
+    if (!(aux >> 31)) return;
+    const u32 lr = (aux >> 16) & 0xFF;
+    const u32 n = (len - start < RANGE_CHUNK) ? (len - start) : RANGE_CHUNK;
+    const u8* blk = view.ptr[b] + start;
+    u8* pay = tmp + (size_t)slot * RANGE_STRIDE + HDR_BYTES;
+    u32* payw = reinterpret_cast<u32*>(pay);
+    u8* nib = pay + RANGE_WIDE_NIB;
+    u64* cum = reinterpret_cast<u64*>(pay + RANGE_WIDE_CUM);
+    const u32* fr = cumFreq + (size_t)slot * 256;
+    u64 c = 0;
+    for (int i = 0; i < 256; i++) { cum[i] = c; c += fr[i]; }
+    cum[256] = c;
+    u64 low = 0, range = RANGE_TOP, acc = 0;
+    u32 nacc = 0, wc = 0, units = 0;
+    auto emit = [&](u32 v, u32 nb) {
+        acc = (acc << nb) | v;
+        nacc += nb;
+        if (nacc >= 32) { nacc -= 32; payw[wc++] = bswap32((u32)(acc >> nacc)); }
+    };
+    for (u32 i = 0; i < n && units < RANGE_WIDE_UNITS; i++) {
+        const u64 cf = cum[blk[i]], fq = cum[(u32)blk[i] + 1] - cf;
+        range >>= lr;
+        low += cf * range;
+        range *= fq;
+        while (units < RANGE_WIDE_UNITS) {
+            if (((low ^ (low + range)) & RANGE_MASK) != 0) {
+                if (range > RANGE_BOTTOM) break;
+                range = (0 - low) & RANGE_BOTTOM;
+            }
+            emit((u32)(low >> 32) & 0x0FFFFFFFu, 28);
+            nib[units++] = (u8)(low >> 60);
+            range <<= 28;
+            low <<= 28;
+        }
+    }
+    emit((u32)(low >> 32) & 0x0FFFFFFFu, 28);                           // 60 bits of low
+    emit((u32)low, 32);
+    nib[units] = (u8)(low >> 60);
+    if (nacc) payw[wc] = bswap32((u32)(acc << (32 - nacc)));
+    cd->mid[2] = units;
+    cd->nPieces = 1; cd->pieceBits[0] = 28 * units + 60; cd->piecePtr[0] = pay;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -458,6 +539,7 @@ void launch_range_encode(hipStream_t s, BlockView view, const u32* origLen, u32 
     const int nSlots = nBlocks * maxChunks;
     { KScope ks_("k_range_stats"); hipLaunchKernelGGL(k_range_stats, dim3(nSlots), dim3(64), 0, s, view, origLen, copyThreshold, maxChunks, desc, cumFreq, tmp); }
     { KScope ks_("k_range_encode"); hipLaunchKernelGGL(k_range_encode, dim3((nSlots + RCH - 1) / RCH), dim3(64), 0, s, view, maxChunks, nSlots, desc, cumFreq, tmp); }
+    { KScope ks_("k_range_encode_wide"); hipLaunchKernelGGL(k_range_encode_wide, dim3((nSlots + 63) / 64), dim3(64), 0, s, view, maxChunks, nSlots, desc, cumFreq, tmp); }
 }
 
 void launch_range_decode(hipStream_t s, BitSrc src, DecBlock* blocks, int nBlocks, u8* const* outPtr, int framing)

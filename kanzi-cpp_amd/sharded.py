@@ -70,12 +70,12 @@ class _DeviceBuffers:
 class DeviceRunEncoder:
     """Encodes a run of blocks on this rank's GPU (no CPU fallback)."""
 
-    def __init__(self, device, transform, entropy, block_size, jobs=1, orig_size=0, headerless=False):
+    def __init__(self, device, transform, entropy, block_size, jobs=1, orig_size=0, headerless=False, checksum=0):
         hipapi = importlib.import_module("kanzi_amd.hipapi")
         framing = importlib.import_module("kanzi_amd.framing")
         self.ctx = hipapi.Context(device)
-        self.p = self.ctx.params(transform, entropy, block_size, 0, jobs)
-        self.header = (b"", 0) if headerless else framing.make_header(self.p.entropy_type, self.p.transform_type, block_size, 0, orig_size)
+        self.p = self.ctx.params(transform, entropy, block_size, checksum, jobs)
+        self.header = (b"", 0) if headerless else framing.make_header(self.p.entropy_type, self.p.transform_type, block_size, checksum, orig_size)
         self.bufs = _DeviceBuffers(self.ctx)
 
     def __call__(self, data, first_block, with_header, finish):

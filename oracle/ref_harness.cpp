@@ -102,6 +102,31 @@ int ref_transform(const char* name, int forward, const uint8_t* in, int n, int s
     }
 }
 
+// Forward only, with the Context's data type set before (0 = UNDEFINED leaves it unset) and read back afterwards: what a stage such as
+// PACK learns about the block and leaves for the stages behind it.
+int ref_transform_dt(const char* name, const uint8_t* in, int n, uint8_t* out, int dstCap, int* outLen, int* dataType)
+{
+    try {
+        Context ctx;
+        ctx.putInt("bsVersion", 6);
+        ctx.putInt("size", n);
+        if (*dataType != 0) ctx.putInt("dataType", *dataType);
+        uint64 t = TransformFactory<byte>::getType(name);
+        TransformSequence<byte>* seq = TransformFactory<byte>::newTransform(ctx, t);
+        std::vector<byte> src(size_t(n > 0 ? n : 1));
+        memcpy(src.data(), in, size_t(n));
+        SliceArray<byte> sa1(src.data(), int(src.size()), 0);
+        SliceArray<byte> sa2(reinterpret_cast<byte*>(out), dstCap, 0);
+        const bool res = seq->forward(sa1, sa2, n);
+        *outLen = sa2._index;
+        *dataType = ctx.getInt("dataType", 0);
+        delete seq;
+        return res ? 1 : 0;
+    } catch (const std::exception&) {
+        return -1;
+    }
+}
+
 // SBRT with an explicit mode (1 MTF, 2 RANK, 3 TIMESTAMP): TIMESTAMP has no factory id.
 int ref_sbrt(int mode, int forward, const uint8_t* in, int n, uint8_t* out, int dstCap, int* outLen)
 {

@@ -55,14 +55,22 @@ int main(int argc, char** argv)
             u8* tb = reinterpret_cast<u8*>((reinterpret_cast<uintptr_t>(tmp.data()) + 255) & ~(uintptr_t)255);
             launch_range_encode(nullptr, view, &olen, count /* copy threshold */, 1, maxChunks, desc.data(), cumFreq.data(), tb);
             u64 nbits = 0;
+            std::vector<u64> chunkBit(maxChunks);
             for (int ci = 0; ci < maxChunks; ci++) {
                 const ChunkDesc& cd = desc[ci];
+                chunkBit[ci] = nbits;
                 put_bits(out, nbits, tb + (size_t)ci * RANGE_STRIDE, cd.hdrBits);
                 for (u32 k = 0; k < cd.nPieces; k++) {
                     if (cd.pieceBits[k] > 8u * RANGE_PAY_BYTES) { fprintf(stderr, "piece of %u bits exceeds the staging region\n", cd.pieceBits[k]); return 1; }
                     put_bits(out, nbits, cd.piecePtr[k], cd.pieceBits[k]);
                 }
             }
+            // chunks with a wide frequency: the reference's unmasked writes, as k_assemble adds them (the stream starts at bit 0 here)
+            std::vector<u32> words((out.size() + 3) / 4 + 1, 0);
+            memcpy(words.data(), out.data(), out.size());
+            for (int ci = 0; ci < maxChunks; ci++)
+                if (desc[ci].aux >> 31) range_wide_spill(words.data(), chunkBit[ci], chunkBit[ci], desc[ci]);
+            memcpy(out.data(), words.data(), out.size());
             res[1] = (u32)nbits; res[2] = (u32)out.size();
         } else {
             // the stream in a buffer of exactly the words the kernel may touch (the last, partial word included), so that AddressSanitizer sees a read past it

@@ -198,6 +198,15 @@ class Ref:
                                   (entropy or "").encode(), C.byref(ol), C.byref(sk))
         return ok, C.string_at(out, ol.value), sk.value
 
+    def forward_dt(self, name, data, dst_cap, data_type=0):
+        """Forward with the Context's data type preset (0: unset): (ok, bytes, data type afterwards)."""
+        self.L.ref_transform_dt.restype = C.c_int
+        self.L.ref_transform_dt.argtypes = [C.c_char_p, u8p, C.c_int, u8p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        out = (C.c_uint8 * (max(dst_cap, len(data)) + 2048))()
+        ol, dt = C.c_int(0), C.c_int(data_type)
+        ok = self.L.ref_transform_dt(name.encode(), _buf(data), len(data), out, dst_cap, C.byref(ol), C.byref(dt))
+        return ok, C.string_at(out, ol.value), dt.value
+
     def inverse(self, name, data, dst_cap, skip=0, src_cap=0):
         out = (C.c_uint8 * (dst_cap + 64))()
         ol = C.c_int(0)

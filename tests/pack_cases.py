@@ -87,7 +87,22 @@ def make(recipe):
         return make(recipe[3])[:n]
     if kind == "concat":
         return b"".join(make(r) for r in recipe[3])
+    if kind == "onehdr":
+        # a one-symbol header with a chosen size field, random bytes behind it
+        d = bytearray(make(["random", n, seed]))
+        d[0] = 255
+        d[2:6] = int(recipe[3]).to_bytes(4, "little")
+        return bytes(d)
     raise ValueError(kind)
+
+
+def overwrite(fwd, seed, k):
+    """A forward output with k of its first 64 bytes overwritten (the "overwrite" recipes of DAMAGED: [kind, 0, seed, source recipe, k])."""
+    r = _rng(seed)
+    d = bytearray(fwd)
+    for _ in range(k):
+        d[int(r.integers(0, min(64, len(d))))] = int(r.integers(0, 256))
+    return bytes(d)
 
 
 STAGE = [
@@ -97,7 +112,13 @@ STAGE = [
     ["text", 100001, 8], ["text", 100000, 9], ["text", 1 << 20, 10], ["phantom", 65537, 11],
     ["alpha", 300000, 12, 40],
     ["text", 1023, 13], ["random", 50000, 14], ["random16", 50000, 15], ["alpha", 200000, 16, 200],
+    # more than 256 chunks of 4,096 parse positions, so that k_pk_f_parse_scan turns its loop twice and carries the token count and the
+    # state over: n - 1 = 256 * 4096 + 1 and + 2 (the parse stops on the last byte in one and not in the other), one chunk more; and
+    # forward outputs above 256 chunks, so that k_pk_i_scan carries its offset over: 40 symbols, text, and a block of 4 MiB + 3
+    ["text", 1048578, 60], ["text", 1048579, 60], ["text", 1052678, 61],
+    ["alpha", 1500000, 62, 40], ["text", 2200001, 63], ["alpha", (4 << 20) + 3, 64, 100],
 ]
+LARGE = 1 << 20         # records above this are the ones added for the loops over the chunk table
 
 # reference forward outputs cut short (the inverse reads them as they are): [recipe, length]
 TRUNCATED = [
@@ -118,6 +139,38 @@ INVERSE = [
     ["hdr", 5000, 22, [[0, 20], [1, 0]]], ["hdr", 5001, 23, [[0, 200], [1, 1]]], ["hdr", 3000, 24, [[0, 250], [7, 1]]],
     ["hdr", 3001, 25, [[0, 253], [4, 3]]], ["hdr", 64, 26, [[0, 255], [2, 100], [3, 0], [4, 0], [5, 0]]],
 ]
+
+# damaged inverse inputs (at most 100). Header-shaped random bytes: every mode's first byte with the adjust byte of that mode (src[1] in
+# the digram mode, src[1 + n] behind the n symbols of a packing mode) at 0 to 5; one-symbol headers by their size field; the reference's
+# forward outputs with 1 to 4 of their first 64 bytes overwritten (the test takes the forward output from the emulated kernels, whose
+# bytes test 1 has compared, and applies overwrite())
+def _damaged():
+    out = []
+    seed = 300
+    for n0 in (15, 16, 17, 100, 239, 240, 243, 244, 251, 252, 254):
+        pos = 1 if n0 < 240 else 1 + 256 - n0
+        for adjust in range(6):
+            # (two lengths above a chunk of 4,096 payload bytes among them)
+            out.append(["hdr", 9001 if adjust == 1 and n0 in (100, 244) else 800 + (seed * 131) % 1500, seed, [[0, n0], [pos, adjust]]])
+            seed += 1
+    for size in (0, 1, 65536, (1 << 31) - 1, 1 << 31, (1 << 32) - 1):
+        out.append(["onehdr", 6 + seed % 50, seed, size])
+        seed += 1
+    srcs = [["alpha", 4099, 3, 4], ["alpha", 5002, 6, 16], ["alpha", 70001, 7, 12], ["text", 100001, 8], ["phantom", 65537, 11],
+            ["alpha", 5001, 5, 5], ["one", 5000, 65]]
+    for i in range(28):
+        out.append(["overwrite", 0, seed, srcs[i % len(srcs)], 1 + i % 4])
+        seed += 1
+    return out
+
+
+# one ACGT block under every preset data type: MULTIMEDIA, UTF8, EXE and BIN are refused, UNDEFINED becomes DNA, TEXT stays
+PRESET_BLOCK = ["alpha", 8192, 4, 4]
+PRESET_TYPES = [2, 3, 7, 8, 0, 1]
+
+DAMAGED = _damaged()
+DAMAGED_CAP_MIN = 1 << 17       # room for the one-symbol header of 65,536 bytes
+
 
 # one batch whose blocks have different data types: text, WAV (MULTIMEDIA preset: PACK refuses), BMP, random, DNA, a short tail
 # and blocks that start with a RIFF, BMP, PGM, ELF or PNG magic over text or a small alphabet (MULTIMEDIA, EXE and BIN presets)

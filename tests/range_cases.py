@@ -13,6 +13,13 @@ def make(r):
     if kind == "mid":                 # a coded chunk, a constant chunk, a coded tail: the decoder steps over a chunk without payload
         _, seed, tail = r
         return make(["alpha", 32768, seed, 256]) + bytes([0x41]) * 32768 + make(["geom", tail, seed + 1, 30])
+    if kind == "wide":                # 280 bytes, 255 values: see WIDE
+        _, seed = r
+        g = np.random.default_rng(seed)
+        vals = g.permutation(256)[1:]
+        counts = np.ones(255, dtype=np.int64)
+        counts[0] += 9; counts[1] += 7; counts[2] += 3; counts[3:9] += 1
+        return g.permutation(np.repeat(vals, counts)).astype(np.uint8).tobytes()
     if kind == "cat":                 # pieces back to back
         return b"".join(make(p) for p in r[1:])
     return vectors.make(tuple(r))
@@ -47,6 +54,17 @@ STREAMS = (
 # a chunk of random bytes on which the encoder cuts the range back to the next 2^16 border at least once (found with range_model.Stats
 # by tools/make_range_golden.py --find-underflow)
 UNDERFLOW = ["rand", 32768, 10]
+
+# A chunk on which the reference's normalisation ends below zero: shorter than 512 bytes (log range 8), 255 values with counts 10, 8, 4,
+# six times 2 and 246 times 1. The scaled frequencies sum to 278; five rounds take 12 off the three that exceed 2, and the largest,
+# by then 4, gets 4 - 10 = 0xFFFFFFFA (EntropyUtils.cpp:243). The reference writes the chunk and cannot read it; its bytes carry what
+# its unmasked writeBits and its 64-bit products leave, which depends on where the chunk lies in the 64-bit words of the block's bit
+# stream. Alone (by the seed the wide symbol is the first of the alphabet, whose frequency is not written, or a later one), behind a
+# chunk of 32,768 bytes whose length in bits moves it. (Only the last chunk of a block can be this short.)
+WIDE = [["wide", s] for s in range(1, 7)] + [["cat", ["geom", 32768, 200 + s, 12 + 9 * s], ["wide", 10 + s]] for s in range(8)]
+# (recipe, block size, checksum bits, jobs): the chunk inside a framed stream, behind block headers of different lengths
+WIDE_STREAMS = [(["wide", 30], 65536, 0, 1), (["wide", 31], 65536, 32, 2), (["wide", 32], 1024, 64, 1),
+                (["cat", ["text", 65536, 8], ["geom", 32768, 211, 25], ["wide", 34]], 65536, 32, 3)]
 
 # whole chains in front of the coder; the last one runs TEXT and UTF on the host
 CHAINS = [

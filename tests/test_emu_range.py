@@ -1,6 +1,8 @@
 """RANGE kernels on the CPU: kanzi-cpp_amd/csrc/range.hip compiled as plain C++ against the fiber emulation in tools/hipemu, compared
 with tests/range_model.py (which tests/test_range_model.py pins to the reference's streams). Test infrastructure only: the product
 runs the real kernels (tests/test_gpu_range.py)."""
+import hashlib
+import json
 import os
 import struct
 import subprocess
@@ -105,3 +107,24 @@ def test_range_decode_of_damaged_input_emulated(tmp_path):
             assert err == 0 and len(out) < count
         else:
             assert err == 13, (count, bits)
+
+
+def test_range_wide_frequency_emulated(tmp_path):
+    """Chunks on which the reference's normalisation wraps a frequency to 0xFFFFFFFA (range_cases.WIDE): nobody can read them, but the
+    reference writes them, with 64-bit cumulative products and with writeBits fields that are not masked inside a 64-bit word.
+    k_range_stats marks such a chunk, k_range_encode_wide codes it and range_wide_spill adds the unmasked bits: the reference's bits
+    (tests/golden/range.json, "wide"), alone and behind a chunk whose length puts it at 8 different positions in its word."""
+    recs = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "range.json")))["wide"]["stage"]
+    assert len(recs) == len(range_cases.WIDE) and len({r["bits"] % 64 for r in recs}) >= 8 and not any(r["ref_decodes"] for r in recs)
+    blocks = [range_cases.make(r["recipe"]) for r in recs]
+    for r, b in zip(recs, blocks):
+        assert hashlib.md5(b).hexdigest() == r["input_md5"], r["recipe"]
+    exe = build("range_emu", tmp_path, extra=["-fsanitize=address", "-g", "-fno-omit-frame-pointer"])
+    for order in ("0", "2"):
+        got = run_cases(exe, tmp_path, [(1, 0, 0, 0, b) for b in blocks], order)
+        for r, (err, bits, enc) in zip(recs, got):
+            assert bits == r["bits"] and hashlib.md5(enc).hexdigest() == r["enc_md5"], (r["recipe"], order)
+        # the decoder kernel refuses what the reference refuses
+        back = run_cases(exe, tmp_path, [(0, len(b), 0, bits, enc) for b, (_, bits, enc) in zip(blocks, got)], order)
+        for r, b, (err, _, out) in zip(recs, blocks, back):
+            assert err != 0 or out != b, r["recipe"]

@@ -758,3 +758,32 @@ def test_randomised_soak(hip):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "tools", "gpu_soak.py"), "5", "25"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+def test_randomised_soak_newer_stages(hip):
+    """The same soak drawn over the first-generation tables plus BWTS, PACK, MM and LZP chains (alone, mixed with older stages, two
+    of them in one chain), the coders RANGE and CM and four input kinds these stages accept (tools/gpu_soak.py, mode `newer`):
+    every job count, checksum width and block size from 1 KiB to 1 MiB against the reference build's stream (oracle/_ref, which
+    build() makes and which travels with the tree), which the device must write and read. A process and a budget of its own.
+    The floor of 10 newer-stage cases keeps the test from passing on nothing, a missing reference build included; streams the
+    reference writes and cannot read itself (RANGE on incompressible blocks: 3 of 360 on the reference alone) may be 1 in 20.
+
+    What this draw found (seed 6, its third case: LZP+BWTS+MTFT+ZRLT / RANGE, 280 bytes with 255 values in front of the coder):
+    a short chunk on which the reference's frequency normalisation wraps below zero. Neither side can read it, but the bytes
+    differed; the RANGE encoder now writes the reference's (k_range_encode_wide, range_wide_spill), and
+    tests/test_gpu_range.py pins the case by itself."""
+    import re
+    import subprocess
+    import sys
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "tools", "gpu_soak.py"), "6", "15", "newer"], capture_output=True, text=True, timeout=300)
+    print(r.stdout[-600:])
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    m = re.search(r"newer stages (\d+); of which undecodable by the reference too: (\d+); skipped for want of the reference build: (\d+)", r.stdout)
+    assert m, r.stdout[-500:]
+    newer, refbug, skipped = (int(g) for g in m.groups())
+    first = int(re.search(r"first generation (\d+)", r.stdout).group(1))
+    assert skipped == 0, "no reference build (oracle/_ref) to compare the newer stages with: " + r.stdout[-500:]
+    assert newer >= 10, r.stdout[-500:]
+    assert 20 * refbug <= newer + first, r.stdout[-500:]

@@ -262,3 +262,44 @@ def test_cpp_range_mirror():
     exe = os.environ.get("KNZ_TEST_RANGE_MIRROR_EXE") or os.path.join(knzlib.ROOT, "tests", "cpp", "range_mirror_test")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "OK" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+
+
+def test_wide_frequency_chunks_are_the_references(hip):
+    """A short chunk with a nearly full alphabet on which the reference's normalisation wraps a frequency below zero (range_cases.WIDE;
+    found by tools/gpu_soak.py): the reference writes a chunk that it cannot read, and the device writes the same bits -- per stage, and
+    inside framed streams whose block headers (checksums of 0, 32 and 64 bits) put the chunk at different positions of the block's
+    64-bit words -- and refuses to read them as the reference does."""
+    hipapi = importlib.import_module("kanzi_amd.hipapi")
+    for rec in GOLDEN["wide"]["stage"]:
+        d = _input(dict(rec, name=str(rec["recipe"])))
+        enc, bits = hip.entropy_encode("RANGE", d)
+        assert bits == rec["bits"] and md5(enc) == rec["enc_md5"], rec["recipe"]
+        assert not rec["ref_decodes"]
+        try:
+            dec, out, _ = hip.entropy_decode("RANGE", enc, len(d))
+            assert not (dec == len(d) and out == d), rec["recipe"]
+        except hipapi.KnzError:
+            pass
+    for rec in GOLDEN["wide"]["streams"]:
+        d = _input(dict(rec, name=str(rec["recipe"])))
+        bs = rec["block_size"]
+        p = hip.params("NONE", "RANGE", bs, rec["checksum"], jobs=rec["jobs"])
+        cap = hip.encode_bound(p, len(d)) + 64
+        d_in, d_out, d_dec = hip.malloc(len(d) + 64), hip.malloc(cap), hip.malloc(len(d) + 2 * bs + 64)
+        try:
+            hip.h2d(d_in, d)
+            bits = hip.encode_blocks(p, d_in, len(d), d_out, cap)
+            enc = hip.d2h(d_out, (bits + 7) // 8)
+            assert len(enc) == rec["stream_len"] and md5(enc) == rec["stream_md5"], rec["recipe"]
+            assert not rec["ref_decodes"]
+            with pytest.raises(hipapi.KnzError):
+                hip.decode_blocks(p, d_out, bits, 0, d_dec, len(d) + bs)
+        finally:
+            hip.free(d_in)
+            hip.free(d_out)
+            hip.free(d_dec)
+    # the context is still usable
+    d = range_cases.make(["text", 70000, 4])
+    enc, bits = hip.entropy_encode("RANGE", d)
+    dec, out, used = hip.entropy_decode("RANGE", enc, len(d))
+    assert dec == len(d) and out == d and used == bits

@@ -11,6 +11,9 @@ budget = float(sys.argv[2]) if len(sys.argv) > 2 else 300.0
 tmp = pathlib.Path(tempfile.mkdtemp())
 runs = [("huff_emu", ["6", "5"]), ("ans0_emu", ["6"]), ("ans1_emu", ["6"]), ("fpaq_emu", ["6"]), ("bwt_inv_emu", ["6", "5"]), ("lz_emu", ["6", "5"]),
         ("lzx_emu", ["6"]), ("srt_emu", ["6"]), ("zrlt_emu", ["6"]), ("mtft_emu", ["6"]), ("rlt_emu", ["6"]), ("rank_emu", ["6"])]
+# pack_emu (like mm_emu) is not in the list: these drivers take a file of plain blocks, encode them with the oracle and damage the result
+# by EMU_CORRUPT themselves. The oracle has no PACK, and pack_emu reads (direction, capacity, data type, bytes) cases whose expected
+# results come from the reference build; its damaged inputs are the seeded records of tests/golden/pack.json (tests/test_emu_pack.py).
 c = knzlib.corpus()
 with ThreadPoolExecutor(max_workers=6) as pool:
     exes = dict(zip([n for n, _ in runs], pool.map(lambda n: T.build(n, tmp, extra=["-fsanitize=address", "-g", "-fno-omit-frame-pointer"]), [n for n, _ in runs])))

@@ -1,9 +1,14 @@
 """Writes tests/golden/pack.json from the reference build in oracle/_ref (build() makes it where the reference sources exist).
 
-Per-stage records: the recipe (tests/pack_cases.py), the reference's PACK forward result (ok flag, md5, the bytes in full when short) and
-the result of its inverse on the forward output; inverse records: the reference's inverse of arbitrary bytes and of its own forward
-outputs cut short. Stream records: the md5 of the reference's headerless stream for each chain of pack_cases.STREAM_CHAINS, and of
-its .knz for the chains of pack_cases.HOSTED (TEXT / UTF on the host in front of PACK). The GPU tests read only this file.
+Per-stage records: the recipe (tests/pack_cases.py), the reference's PACK forward result (ok flag, md5, the bytes in full when
+short, the Context's data type afterwards) and the result of its inverse on the forward output.
+Preset records: the forward result of one ACGT block under every data type of pack_cases.PRESET_TYPES.
+Inverse records: the reference's inverse of arbitrary bytes and of its own forward outputs cut short.
+Damaged records (pack_cases.DAMAGED): the reference's inverse of seeded header-shaped bytes and of its forward outputs with a few
+header bytes overwritten. Every capacity is at least the input's length: below that TransformSequence::inverse refuses before
+AliasCodec is asked, and the record would hold the sequence's verdict.
+Stream records: the md5 of the reference's headerless stream for each chain of pack_cases.STREAM_CHAINS, and of its .knz for the
+chains of pack_cases.HOSTED (TEXT / UTF on the host in front of PACK). The tests read only this file.
     python tools/make_pack_golden.py
 """
 import hashlib
@@ -25,12 +30,15 @@ def md5(b):
 
 def main():
     ref = knzlib.Ref()
-    out = {"stage": [], "inverse": [], "truncated": [], "streams": [], "hosted": []}
+    out = {"stage": [], "inverse": [], "truncated": [], "presets": [], "damaged": [], "streams": [], "hosted": []}
     for r in pack_cases.STAGE:
         d = pack_cases.make(r)
         cap = len(d) + 1024
         ok, fwd, _ = ref.forward("PACK", d, cap)
-        rec = {"recipe": r, "input_md5": md5(d), "cap": cap, "ok": int(ok == 1), "fwd_len": len(fwd), "fwd_md5": md5(fwd)}
+        ok2, fwd2, dt_after = ref.forward_dt("PACK", d, cap)
+        assert ok2 == ok and (ok != 1 or fwd2 == fwd), r
+        rec = {"recipe": r, "input_md5": md5(d), "cap": cap, "ok": int(ok == 1), "fwd_len": len(fwd), "fwd_md5": md5(fwd),
+               "dt_after": dt_after}
         if len(fwd) <= SHORT:
             rec["fwd_hex"] = fwd.hex()
         if ok == 1:
@@ -50,6 +58,27 @@ def main():
             ok, inv = ref.inverse("PACK", d, cap)
             out["truncated"].append({"recipe": r, "cut": cut, "input_md5": md5(d), "cap": cap, "ok": int(ok == 1),
                                      "inv_md5": md5(inv) if ok == 1 else None})
+    d = pack_cases.make(pack_cases.PRESET_BLOCK)
+    for dt in pack_cases.PRESET_TYPES:
+        ok, fwd, dt_after = ref.forward_dt("PACK", d, len(d) + 1024, dt)
+        out["presets"].append({"dt": dt, "ok": int(ok == 1), "dt_after": dt_after, "fwd_md5": md5(fwd) if ok == 1 else None})
+    assert len(pack_cases.DAMAGED) <= 100
+    for r in pack_cases.DAMAGED:
+        if r[0] == "overwrite":
+            src = pack_cases.make(r[3])
+            ok, fwd, _ = ref.forward("PACK", src, len(src) + 1024)
+            assert ok == 1, r
+            d = pack_cases.overwrite(fwd, r[2], r[4])
+        else:
+            d = pack_cases.make(r)
+        cap = max(4 * len(d) + 64, pack_cases.DAMAGED_CAP_MIN)
+        assert cap >= len(d)
+        ok, inv = ref.inverse("PACK", d, cap)
+        out["damaged"].append({"recipe": r, "input_md5": md5(d), "cap": cap, "ok": int(ok == 1), "inv_len": len(inv) if ok == 1 else 0,
+                               "inv_md5": md5(inv) if ok == 1 else None})
+    n_acc = sum(r["ok"] for r in out["damaged"])
+    assert 2 * n_acc >= len(out["damaged"]), (n_acc, len(out["damaged"]))     # tests/test_emu_pack.py asks for at least half
+    print("damaged:", len(out["damaged"]), "records,", n_acc, "accepted by the reference")
     for chain, entropy, bs, ck, r in pack_cases.HOSTED:
         d = pack_cases.make(r)
         rc, enc = ref.compress(d, chain, entropy, bs, jobs=1, checksum=ck, orig_size=0)

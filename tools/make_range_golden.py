@@ -1,7 +1,9 @@
-"""Writes tests/golden/range.json from the reference's command line (oracle/_ref/kanzi, which build() makes where the reference sources
-exist): for every case of tests/range_cases.py the input recipe, the stream header and the length and md5 of what
-`kanzi -c -t CHAIN -e RANGE -b SIZE -j 1` writes, from a file (the header carries the input's size) and from standard input (it carries
-none: what a writer that cannot know the size, such as the C API's compressor, has to produce). The tests read only this file.
+"""Writes tests/golden/range.json from the reference's command line (oracle/_ref/kanzi, which build() makes where the reference
+sources exist): for every case of tests/range_cases.py the input recipe, the stream header and the length and md5 of what
+`kanzi -c -t CHAIN -e RANGE -b SIZE -j 1` writes, from a file (the header carries the input's size) and from standard input (it
+carries none: what a writer that cannot know the size, such as the C API's compressor, has to produce).
+The `wide` section holds the chunks with a wrapped frequency (range_cases.WIDE, WIDE_STREAMS), per stage and framed, from the
+reference build's library (knzlib.Ref). The tests read only this file.
     python tools/make_range_golden.py [--find-underflow]
 """
 import hashlib
@@ -52,6 +54,26 @@ def record(name, chain, recipe, bs, checksum):
             "unsized_len": len(unsized), "unsized_md5": md5(unsized)}
 
 
+def wide_records():
+    """The chunks with a wrapped frequency (range_cases.WIDE, WIDE_STREAMS) from the reference build's library: per stage, and framed."""
+    ref = knzlib.Ref()
+    stage, streams = [], []
+    for r in range_cases.WIDE:
+        d = range_cases.make(r)
+        enc, bits = ref.entropy_encode("RANGE", d)
+        rc, back = ref.entropy_decode("RANGE", enc, len(d))
+        stage.append({"recipe": r, "n": len(d), "input_md5": md5(d), "bits": bits, "enc_md5": md5(enc), "ref_decodes": int(rc >= 0 and back == d)})
+    for r, bs, ck, jobs in range_cases.WIDE_STREAMS:
+        d = range_cases.make(r)
+        rc, enc = ref.compress(d, "NONE", "RANGE", bs, jobs=jobs, checksum=ck, headerless=1)
+        assert rc == 0, r
+        rc1, full = ref.compress(d, "NONE", "RANGE", bs, jobs=jobs, checksum=ck, orig_size=len(d))
+        rc2, back = ref.decompress(full, len(d) + bs, jobs=jobs)
+        streams.append({"recipe": r, "block_size": bs, "checksum": ck, "jobs": jobs, "n": len(d), "input_md5": md5(d),
+                        "stream_len": len(enc), "stream_md5": md5(enc), "ref_decodes": int(rc1 == 0 and rc2 == 0 and back == d)})
+    return {"stage": stage, "streams": streams}
+
+
 def find_underflow():
     for seed in range(1, 200):
         st = range_model.Stats()
@@ -69,7 +91,8 @@ def main():
         knzlib.ensure_ref()
     out = {"streams": [record(n, "NONE", r, bs, ck) for n, r, bs, ck in range_cases.STREAMS],
            "chains": [record(c, c, r, bs, ck) for c, r, bs, ck in range_cases.CHAINS],
-           "hosted": [record(c, c, r, bs, ck) for c, r, bs, ck in range_cases.HOSTED]}
+           "hosted": [record(c, c, r, bs, ck) for c, r, bs, ck in range_cases.HOSTED],
+           "wide": wide_records()}
     path = os.path.join(ROOT, "tests", "golden", "range.json")
     with open(path, "w") as f:
         json.dump(out, f, indent=1)
