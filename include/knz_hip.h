@@ -30,7 +30,8 @@ extern "C" {
 enum { KNZ_E_NONE = 0, KNZ_E_HUFFMAN = 1, KNZ_E_FPAQ = 2, KNZ_E_RANGE = 4, KNZ_E_ANS0 = 5, KNZ_E_CM = 6, KNZ_E_ANS1 = 8 };
 enum { KNZ_T_NONE = 0, KNZ_T_BWT = 1, KNZ_T_BWTS = 2, KNZ_T_LZ = 3, KNZ_T_RLT = 5, KNZ_T_ZRLT = 6, KNZ_T_MTFT = 7, KNZ_T_RANK = 8, KNZ_T_SRT = 13, KNZ_T_LZP = 14, KNZ_T_MM = 15, KNZ_T_LZX = 16, KNZ_T_PACK = 18,
        KNZ_T_TIMESTAMP = 64 /* SBRT's third mode: no kanzi id, never part of a chain; per-stage entry points only */,
-       KNZ_T_TEXT = 10, KNZ_T_UTF = 17 /* stages that run on the HOST in front of the device chain: knz_hip_encode_block_hosted / _decode_ */ };
+       KNZ_T_UTF = 17 /* a device stage in any position; also accepted among the host's leading stages (below) */,
+       KNZ_T_TEXT = 10 /* runs on the HOST in front of the device chain: knz_hip_encode_block_hosted / _decode_ */ };
 
 /* kanzi error codes surfaced for data errors (src/Error.hpp:26-48) */
 enum { KNZ_ERR_BLOCK_SIZE = 2, KNZ_ERR_INVALID_CODEC = 3, KNZ_ERR_READ_FILE = 11, KNZ_ERR_WRITE_FILE = 12,
@@ -110,12 +111,15 @@ KNZ_API int knz_hip_decode_blocks(knz_ctx* ctx, const knz_params* p, const uint8
  * Chains whose first stages run on the host (the reference's level presets 5 and 6: TEXT + UTF in front of BWT + RANK / SRT + ZRLT,
  * app/BlockCompressor.cpp:583-591). The host applies those stages to ONE block (they change its length by a different amount per block)
  * and hands over what TransformSequence::forward would have left for the next stage (transform/TransformSequence.hpp:88-162):
- *   stages        how many leading stages of p->transform_type the host owns (each KNZ_T_TEXT or KNZ_T_UTF)
+ *   stages        how many leading stages of p->transform_type the host owns (each KNZ_T_TEXT or KNZ_T_UTF). TEXT has no device
+ *                 version, so the host owns the chain up to its last leading TEXT; a UTF in front of that TEXT has to run on the host
+ *                 too ("UTF+TEXT+...": stages = 2), a UTF behind it is a device stage like any other ("TEXT+UTF+...": stages = 1 is
+ *                 what the stream classes pass; stages = 2 with UTF applied by the caller still works)
  *   applied_mask  bit i set = stage i succeeded (its skip flag is clear, and it counts as a buffer swap for the capacities the
  *                 device stages see); clear = the stage refused the block and the block went on unchanged
  *   orig_len      length of the block before any stage (decides copy blocks and the buffer sizes of the reference)
  *   reserved      the data type the host stages left in the block's Context (Global::DataType: 0 UNDEFINED, 1 TEXT, 2 MULTIMEDIA,
- *                 3 EXE, 4 NUMERIC, 5 BASE64, 6 DNA, 7 BIN, 8 UTF8, 9 SMALL_ALPHABET); the device stages that read it (PACK, MM) start
+ *                 3 EXE, 4 NUMERIC, 5 BASE64, 6 DNA, 7 BIN, 8 UTF8, 9 SMALL_ALPHABET); the device stages that read it (UTF, PACK, MM) start
  *                 from it. 0 when the caller does not track it; values above 9 count as 0
  *   checksum      XXHash32 / 64 of the ORIGINAL block when p->checksum_bits != 0 (the device only ever sees the transformed bytes)
  * d_in holds the n bytes the host stages left. Everything else as knz_hip_encode_blocks with exactly one block; the block header
@@ -162,6 +166,7 @@ KNZ_API int knz_hip_entropy_decode_v(knz_ctx* ctx, int entropy_type, int bs_vers
  *   KNZ_T_LZP   LZPCodec             transform/LZCodec.cpp:771-879,881-992
  *   KNZ_T_PACK  AliasCodec           transform/AliasCodec.cpp:38-209,211-371
  *   KNZ_T_MM    FSDCodec             transform/FSDCodec.cpp:103-291,293-386
+ *   KNZ_T_UTF   UTFCodec             transform/UTFCodec.cpp:48-204,206-298 (+ validate :303-422, pack / unpack UTFCodec.hpp:71-154)
  * (the inverse of LZ/LZX expects what the reference expects: two readable bytes behind `in + n`,
  * LZCodec.cpp:486-490; the library stages the input itself, so callers need not pad). */
 KNZ_API int knz_hip_transform_forward(knz_ctx* ctx, int transform_type, const uint8_t* in, int32_t n,
@@ -171,7 +176,10 @@ KNZ_API int knz_hip_transform_inverse(knz_ctx* ctx, int transform_type, const ui
 /* The forward stage with the "dataType" entry of the block's Context (Global::DataType, 0 UNDEFINED .. 9 SMALL_ALPHABET, as in
  * knz_host_stages.reserved): *data_type goes in, and comes back as the stage left it. PACK refuses MULTIMEDIA, UTF8, EXE and
  * BIN and sets detectSimpleType's result on an UNDEFINED block; MM takes UNDEFINED, MULTIMEDIA and BIN blocks only and leaves
- * MULTIMEDIA once it has found a distance, or detectSimpleType's result of its samples when it has not; RLT refuses DNA, BASE64 and UTF8; the other stages ignore it.
+ * MULTIMEDIA once it has found a distance, or detectSimpleType's result of its samples when it has not; RLT refuses DNA, BASE64 and UTF8;
+ * UTF takes UNDEFINED (it validates the block first) and UTF8 (it does not) and leaves UTF8 once validation has passed or been skipped,
+ * also on a block it then refuses (too many symbols, a broken third byte, no gain); any other type makes it refuse and stays; the other
+ * stages ignore it.
  * knz_hip_transform_forward is this call with a fresh Context (UNDEFINED). */
 KNZ_API int knz_hip_transform_forward_dt(knz_ctx* ctx, int transform_type, const uint8_t* in, int32_t n, uint8_t* out,
                                          int32_t dst_cap, int entropy_type, int32_t* data_type, int32_t* out_len, int32_t* ok);
@@ -220,6 +228,11 @@ KNZ_API int knz_hip_get_kernel_times(knz_ctx* ctx, knz_kernel_time* out, int cap
  * batch size, 1024 / 4096 force it), "mtf_chain" (1: MTFT forward ranks by the byte-serial kernel of rounds 2-4).
  * Returns 0, or -1 for an unknown name. No knob changes a result. */
 KNZ_API int knz_hip_tune(const char* name, int value);
+
+/* 1 when this library runs transform id `transform_type` as a device stage (in a chain and through the per-stage entry points), else 0.
+ * libkanzi_amd.so asks it for KNZ_T_UTF to decide where UTF runs: against a device library without the stage, or from before this entry
+ * point existed (it binds the symbol weakly), UTF stays among the host's leading stages as it used to. */
+KNZ_API int knz_hip_transform_supported(int transform_type);
 
 /* Test hook: q[i] = floor(d[i] / r[i]) by the RANGE decoder's reciprocal-based divide (host arrays; every pair must satisfy what the
  * decoder has checked before it divides: r >= 1 and d < r * 2^15). */

@@ -601,6 +601,14 @@ static const XfInfo XF[] = {
     { .id = KNZ_T_LZP, .ws = "lzpScratch",
       .fwd = { .wsBytes = lzp_scratch_bytes, .launch = [](const StageCall& k) { launch_lzp_forward(k.s, k.st, k.ws); return 0; } },
       .inv = { .wsBytes = lzp_scratch_bytes, .launch = [](const StageCall& k) { launch_lzp_inverse(k.s, k.st, k.ws); return 0; } } },
+    // (UTFCodec; it reads the data type -- preset from the block's magic, or what TEXT left on the host, encode_impl -- and writes UTF8,
+    // which LZ and LZX treat like UNDEFINED (LZCodec.cpp:182-191). The refusal of LZ / LZX behind a stage that sets the type is kept for
+    // UTF all the same: a block UTF refuses keeps its preset type, which the device LZ stages do not read. Scratch per lane like LZP's, so
+    // the inverse runs in decode lanes. Behind the hosted prefix (TEXT) it is a device stage like any other, parse_chain)
+    { .id = KNZ_T_UTF, .ws = "utfScratch",
+      .fwd = { .wsBytes = utf_scratch_bytes, .launch = [](const StageCall& k) { launch_utf_forward(k.s, k.st, k.ws); return 0; } },
+      .inv = { .wsBytes = utf_scratch_bytes, .launch = [](const StageCall& k) { launch_utf_inverse(k.s, k.st, k.ws); return 0; } },
+      .setsType = true },
 };
 
 static const XfInfo* xf_info(int t) { for (const XfInfo& x : XF) if (x.id == t) return &x; return nullptr; }
@@ -1136,6 +1144,7 @@ static int decode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, uint64_
                 XfStage st = xf_stage(w, nb, (u32)S, p->entropy_type);
                 st.bsVersion = bsVersion;
                 st.maxCap = std::max(capMid, capFinal);
+                st.capModel = framing ? capMid : 0;
                 if (int r = run_stage(c, sp, *ch.xf[i], false, st, lane)) return r;
                 launch_seq_inv_commit(sp, w.a, blk, nb, i, ch.tok[i]);
             }
@@ -1330,6 +1339,8 @@ static int transform_host(Ctx* c, int t, int forward, const uint8_t* in, int32_t
     }
     return 0;
 }
+
+int knz_hip_transform_supported(int transform_type) { return xf_info(transform_type) != nullptr ? 1 : 0; }
 
 int knz_hip_transform_forward(knz_ctx* ctx, int transform_type, const uint8_t* in, int32_t n, uint8_t* out, int32_t dst_cap,
                               int entropy_type, int32_t* out_len, int32_t* ok)

@@ -72,7 +72,10 @@ struct XfStage {
     int entropyType;         // stream entropy id (RLT escape choice)
     int bsVersion = 6;       // bitstream version the blocks come from (inverse only: BWT block header of versions below 6)
     u32 maxCap = 0;          // upper bound of cap[] when the host knows one (inverse stages that size scratch by their output)
-    u8* dtype = nullptr;     // per-block Global::DataType (0 = UNDEFINED) read and written by PACK and MM; nullptr: a fresh context per block
+    u32 capModel = 0;        // inverse: the capacity of the reference's buffer where cap[] is smaller (the last inverse stage of a stream writes
+                             // into the caller's buffer, one block size per block, while the reference decodes into a buffer with slack):
+                             // UTF, whose verdict depends on the capacity, judges by max(cap, capModel) and writes within cap. 0: cap[] is all
+    u8* dtype = nullptr;     // per-block Global::DataType (0 = UNDEFINED) read and written by PACK, MM and UTF; nullptr: a fresh context per block
 };
 
 // zrlt_mtft.hip
@@ -112,6 +115,12 @@ size_t mm_scratch_bytes(int nBlocks, u32 maxLen);
 void launch_lzp_forward(hipStream_t s, const XfStage& st, void* scratch);
 void launch_lzp_inverse(hipStream_t s, const XfStage& st, void* scratch);
 size_t lzp_scratch_bytes(int nBlocks, u32 maxLen);
+
+// utf.hip (UTFCodec; scratch: utf_scratch_bytes(nBlocks, maxLen) bytes, about 1.8 MiB per block plus len / 4; reads and writes
+// XfStage::dtype like PACK; no host synchronisation)
+void launch_utf_forward(hipStream_t s, const XfStage& st, void* scratch);
+void launch_utf_inverse(hipStream_t s, const XfStage& st, void* scratch);
+size_t utf_scratch_bytes(int nBlocks, u32 maxLen);
 
 // fpaq.hip (probs: fpaq_probs_bytes(nBlocks, S) bytes of scratch, S = upper bound of the block lengths)
 void launch_fpaq_encode(hipStream_t s, BlockView view, const u32* origLen, u32 copyThreshold, int nBlocks, int maxChunks, ChunkDesc* desc, u8* tmp, u64 tmpStride,

@@ -12,14 +12,14 @@ LIB_PATH = os.path.join(_HERE, "libknz_hip.so")
 
 E_NONE, E_HUFFMAN, E_FPAQ, E_RANGE, E_ANS0, E_CM, E_ANS1 = 0, 1, 2, 4, 5, 6, 8
 ENTROPY_IDS = {"NONE": 0, "HUFFMAN": 1, "FPAQ": 2, "RANGE": 4, "ANS0": 5, "CM": 6, "ANS1": 8}
-TRANSFORM_IDS = {"NONE": 0, "BWT": 1, "BWTS": 2, "LZ": 3, "RLT": 5, "ZRLT": 6, "MTFT": 7, "RANK": 8, "SRT": 13, "LZP": 14, "MM": 15, "LZX": 16, "PACK": 18, "TIMESTAMP": 64}
+TRANSFORM_IDS = {"NONE": 0, "BWT": 1, "BWTS": 2, "LZ": 3, "RLT": 5, "ZRLT": 6, "MTFT": 7, "RANK": 8, "SRT": 13, "LZP": 14, "MM": 15, "LZX": 16, "UTF": 17, "PACK": 18, "TIMESTAMP": 64}
 
 SYMBOLS = [
     "knz_hip_device_count", "knz_hip_create", "knz_hip_destroy", "knz_hip_last_error", "knz_hip_encode_bound",
     "knz_hip_encode_blocks", "knz_hip_decode_blocks", "knz_hip_entropy_encode", "knz_hip_entropy_decode",
     "knz_hip_transform_forward", "knz_hip_transform_forward_dt", "knz_hip_transform_inverse", "knz_hip_malloc", "knz_hip_free",
     "knz_hip_memcpy_h2d", "knz_hip_memcpy_d2h", "knz_hip_sync", "knz_hip_memcpy_h2d_async", "knz_hip_memcpy_d2h_async", "knz_hip_copy_wait", "knz_hip_host_alloc", "knz_hip_host_free", "knz_hip_set_profiling", "knz_hip_get_kernel_times",
-    "knz_hip_tune", "knz_hip_shift_bits", "knz_hip_encode_block_hosted", "knz_hip_decode_block_hosted",
+    "knz_hip_tune", "knz_hip_transform_supported", "knz_hip_shift_bits", "knz_hip_encode_block_hosted", "knz_hip_decode_block_hosted",
     "knz_hip_entropy_decode_v", "knz_hip_transform_inverse_v", "knz_hip_range_divide",
 ]
 

@@ -753,11 +753,11 @@ bool UTFCodec::inverse(SliceArray<byte>& src, SliceArray<byte>& dst, int length)
     return ok;
 }
 
-// Leading stages of a chain that run on the host. TEXT / UTF anywhere else in a chain has no place to run: refused.
 // Chains the device runs far faster than one host thread copies memory (entropy coders alone, the byte transforms: tens of GB/s):
 // the staging copies of such a stream are spread over the helper threads. With a sorting or matching stage in the chain (BWT, LZ,
 // LZX, LZP; SRT / RANK are chains per block) the device is what a batch waits for and the extra threads only got in the way (measured,
 // config 3 end to end: 2.94-3.14 GB/s with the copies on the caller's thread, 2.72-2.94 with four threads; config 2: 3.1 -> 3.9).
+// TEXT runs on the host; UTF on the device is a dozen passes over the block and a sort, nothing one thread's copies keep up with.
 static bool chainIsHostBound(uint64 ttype)
 {
     for (int i = 0; i < 8; i++) {
@@ -767,17 +767,29 @@ static bool chainIsHostBound(uint64 ttype)
     return true;
 }
 
+// Whether the device library this one is bound to runs UTF as a device stage. The entry point is bound weakly: a device library from
+// before UTF moved to the device, or one without the stage, does not have it or answers 0, and UTF then stays a host stage.
+extern "C" int knz_hip_transform_supported(int transform_type) __attribute__((weak));
+static bool deviceRunsUtf() { return knz_hip_transform_supported != nullptr && knz_hip_transform_supported(KNZ_T_UTF) != 0; }
+
+// Leading stages of a chain that run on the host: the leading run of TEXT / UTF stages up to and including its last TEXT (TEXT is the
+// only stage without a device version; a UTF in front of it has to run where it runs). Every UTF behind that prefix is a device stage,
+// in any position: "UTF+..." has no hosted stage and is batched, "TEXT+UTF+..." runs TEXT here and UTF on the device (from the data
+// type TEXT left, knz_host_stages.reserved), "UTF+TEXT+..." runs both here. TEXT behind a device stage has no place to run: refused.
+// Bound to a device library without the UTF stage, UTF is a host stage like TEXT: the whole leading run, and refused anywhere else.
 static int hostedStagesOf(uint64 ttype, int ids[8])
 {
+    const bool utfOnDevice = deviceRunsUtf();
     int n = 0, k = 0;
-    bool device = false;
+    bool leading = true;
     for (int i = 0; i < 8; i++) {
         const int t = int((ttype >> (42 - 6 * i)) & 63);
         if (t == 0) continue;
         ids[k++] = t;
-        const bool host = (t == KNZ_T_TEXT || t == KNZ_T_UTF);
-        if (host && device) throw std::invalid_argument("TEXT / UTF behind a device transform is not supported");
-        if (host) n++; else device = true;
+        if (t != KNZ_T_TEXT && t != KNZ_T_UTF) leading = false;
+        if (t != KNZ_T_TEXT && (utfOnDevice || t != KNZ_T_UTF)) continue;
+        if (!leading) throw std::invalid_argument(utfOnDevice ? "TEXT behind a device transform is not supported" : "TEXT / UTF behind a device transform is not supported");
+        n = k;
     }
     return n;
 }
@@ -1410,8 +1422,8 @@ void CompressedOutputStream::init(int tasks, const std::string& entropy, const s
     if (e && atoi(e) > 0) _batchBlocks = atoi(e);
     // one device call takes at most 2 GiB of input (32-bit positions on the device side)
     { const int64_t lim = (int64_t(1) << 31) / int64_t(blockSize) - 1; if (_batchBlocks > lim) _batchBlocks = int(lim < 1 ? 1 : lim); }
-    // chains that start with TEXT / UTF (the level presets 5 and 6): those stages run on the host, block by block, and every block
-    // goes to the device on its own (its length after them differs from block to block)
+    // chains with TEXT in their leading TEXT / UTF stages (the level presets 5 and 6): those stages run on the host, block by block, and
+    // every block goes to the device on its own (its length after them differs from block to block)
     _hosted = hostedStagesOf(_transformType, _hostIds);
     if (_hosted) _batchBlocks = 1;
     _blockId = 0;
