@@ -113,6 +113,7 @@ enum FwdCounter : u32 {
     CNT_STAT_MAJ_MEMBERS = 20,
     CNT_STAT_ASLEEP = 21,        // medium groups k_bwt_f_med_sleep kept out of the gather (counted among the ones above as well)
     CNT_STAT_ASLEEP_MEMBERS = 22,
+    CNT_RUN_TILES = 23,          // tiles of the run round's direct placement (device side only: k_bwt_f_run_tile_starts' scan)
     CNT_ROUND_SLOTS = 24,
     CNT_PROBE_SLOTS = 2,         // slots 0-1 (CNT_SMALL_LEFT, CNT_MED): what the probe zeroes, recounts and reads back
     CNT_LONGEST_BLOCK = 32,      // longest block the transform applies to (k_bwt_bases)
@@ -2128,6 +2129,9 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_fallback(FwdView v, const uin
 // generated run by run in that order and sorted, stably, on (class, hi(R)) alone -- three passes over 8-byte elements for 24 key
 // bits, where the pair sort took six passes over 12-byte elements: the order of equal (class, hi) is the order of the runs, i.e.
 // T. What k_bwt_f_large_flags / _place want -- the full key and the position per slot -- is rebuilt from the run table.
+// That is the order of work of a batch with a run longer than RUN_DIRECT_LMAX and of the knob bwt_run_sort. Every other batch sorts the
+// runs the same way and then writes each member's record straight to its slot, which three counts over the runs give ("the members placed
+// directly" below: k_bwt_f_run_seg_marks .. k_bwt_f_run_emit in place of k_bwt_f_run_members, the member sort and k_bwt_f_run_expand).
 
 // class of a run-group byte: classTab[block * 256 + byte] = index of the group's descriptor
 __global__ __launch_bounds__(256) void k_bwt_f_run_classes(BwtView bv, FwdView v, const uint2* __restrict__ runList, u32 nRun, u32* __restrict__ classTab)
@@ -2237,6 +2241,233 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_expand(const u64* __restrict_
     keys[j] = (ch << kbits) | T;
     vals[j] = sE[k] - Rr;
     Rout[j] = Rr;
+}
+
+// ---- the members placed directly (no sort of the members at all) ---------------------------------------------------------------
+// The member sort above only transposes a ragged matrix. The sorted runs fall into segments of equal (class, direction); the sorted
+// members of a segment are its columns R, ascending for "below" and descending for "above", and column R holds the runs with L >= R
+// in run order. So the slot of member (run k, R) is
+//   (members in front of the segment: moff of its first run) + (members of the columns in front of R) + #{earlier runs of the segment with L >= R},
+// three counts over the runs. A segment is cut into tiles of RUN_TILE consecutive runs (most segments are one partly filled tile; one
+// per block -- byte 0 of the stand-in -- has tens of thousands of runs), a tile into rows of 64 runs, one wave each:
+//   k_bwt_f_run_seg_marks, max scan      first run of the segment of every run
+//   k_bwt_f_run_tile_marks, sum scan,
+//   k_bwt_f_run_tile_starts              the tiles [tileStart[t], tileStart[t + 1]) in run order, their number in CNT_RUN_TILES
+//   k_bwt_f_run_tile_counts              tiles of segments of several tiles: colTab[tile][R] = #{runs of the tile with L >= R}
+//   k_bwt_f_run_tile_scan                per such segment and column: colTab[tile][R] = column offset of R + runs of the tiles in front
+//   k_bwt_f_run_emit                     per tile: the same counts per row in LDS, RUN_CH columns at a time; a wave then walks the columns
+//                                        of its row, ranks the runs that are still alive with a ballot and writes their records
+// Every loop is bounded by a count known when the kernel starts (runs of the tile, RUN_DIRECT_LMAX columns, tiles of the batch); nothing
+// waits for another workgroup. The host launches one workgroup per tile there CAN be (segments + runs / RUN_TILE), the ones past
+// CNT_RUN_TILES leave at once: no read-back. Runs longer than RUN_DIRECT_LMAX (a block of one byte: one run, one member per position)
+// send the batch through the member sort above: the tables are sized by that bound, and a column costs a wave one step however few of
+// its runs reach it.
+constexpr u32 RUN_TILE = 1024;                       // runs per tile (16 rows of 64)
+constexpr u32 RUN_ROWS = RUN_TILE / 64;
+constexpr u32 RUN_DIRECT_LMAX = 1023;                // longest run the direct path takes
+constexpr u32 RUN_COLS = RUN_DIRECT_LMAX + 1;        // columns of a tile's row in colTab (column R at index R)
+constexpr u32 RUN_CH = 256;                          // columns k_bwt_f_run_emit counts at a time
+static_assert(RUN_COLS == 4 * 256 && RUN_CH == 256 && RUN_ROWS % 4 == 0, "the kernels below map columns and rows to 256 threads");
+// slots of colTab: a tile of RUN_TILE runs holds exactly one multiple of RUN_TILE, the last, shorter tile of a segment of several
+// tiles follows a full one of its segment
+static inline size_t run_tile_slots(size_t maxRuns) { return 2 * (maxRuns / RUN_TILE + 2); }
+
+struct RunTile { u32 k0, k1, a, slot; bool first, last, multi; };
+__device__ __forceinline__ RunTile run_tile(const u32* __restrict__ tileStart, const u32* __restrict__ segStart, u32 nRuns, u32 t)
+{
+    RunTile r;
+    r.k0 = tileStart[t]; r.k1 = tileStart[t + 1]; r.a = segStart[r.k0];
+    r.first = r.k0 == r.a;
+    r.last = r.k1 >= nRuns || segStart[r.k1] == r.k1;
+    r.multi = !(r.first && r.last);
+    r.slot = (r.k1 - r.k0 == RUN_TILE) ? 2u * ((r.k0 + RUN_TILE - 1) / RUN_TILE) : (r.k0 >= RUN_TILE ? 2u * ((r.k0 - 1) / RUN_TILE) + 1u : 1u);
+    return r;
+}
+
+__global__ __launch_bounds__(256) void k_bwt_f_run_seg_marks(const u64* __restrict__ sKey, u32 nRuns, int kbits, u32* __restrict__ segMark)
+{
+    const u32 k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= nRuns) return;
+    segMark[k] = (k > 0 && (sKey[k] >> kbits) == (sKey[k - 1] >> kbits)) ? 0u : k;     // (a running maximum makes it the segment's first run)
+}
+
+__global__ __launch_bounds__(256) void k_bwt_f_run_tile_marks(const u32* __restrict__ segStart, u32 nRuns, u32* __restrict__ tileMark)
+{
+    const u32 k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= nRuns) return;
+    tileMark[k] = ((k - segStart[k]) % RUN_TILE == 0) ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void k_bwt_f_run_tile_starts(const u32* __restrict__ segStart, const u32* __restrict__ tileIdx, u32 nRuns, u32* __restrict__ tileStart)
+{
+    const u32 k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= nRuns) return;
+    const bool mark = (k - segStart[k]) % RUN_TILE == 0;
+    const u32 t = tileIdx[k];
+    if (mark) tileStart[t] = k;
+    if (k + 1 == nRuns) tileStart[t + (mark ? 1u : 0u)] = nRuns;         // (the end of the last tile)
+}
+
+// tiles of segments of several tiles: colTab[slot][R] = #{runs of the tile with L >= R}
+__global__ __launch_bounds__(256) void k_bwt_f_run_tile_counts(const u32* __restrict__ tileStart, const u32* __restrict__ segStart, const u32* __restrict__ rcnt, u32 nRuns,
+                                                               const u32* __restrict__ nTilesDev, u32 nsym, u32* __restrict__ colTab)
+{
+    __shared__ u32 hist[RUN_COLS];
+    __shared__ u32 wsum[4];
+    const u32 t = blockIdx.x, tid = threadIdx.x;
+    if (t >= *nTilesDev) return;
+    const RunTile T = run_tile(tileStart, segStart, nRuns, t);
+    if (!T.multi) return;
+    for (u32 i = tid; i < RUN_COLS; i += 256) hist[i] = 0;
+    __syncthreads();
+    for (u32 k = T.k0 + tid; k < T.k1; k += 256) { const u32 L = rcnt[k] + nsym - 1u; atomicAdd(&hist[L < RUN_DIRECT_LMAX ? L : RUN_DIRECT_LMAX], 1u); }
+    __syncthreads();
+    u32 x[4], acc = 0;
+#pragma unroll
+    for (u32 i = 0; i < 4; i++) { x[i] = hist[4 * tid + i]; acc += x[i]; }
+    u32 tot;
+    const u32 incl = prims::sc_block_incl<prims::SCAN_SUM_EXCL>(acc, wsum, &tot);
+    u32 ge = tot - (incl - acc);                                         // runs with L >= 4 tid
+    u32* row = colTab + (size_t)T.slot * RUN_COLS;
+#pragma unroll
+    for (u32 i = 0; i < 4; i++) { row[4 * tid + i] = ge; ge -= x[i]; }
+}
+
+// the first tile of a segment of several tiles, for all of them: colTab[slot][R] = (members of the segment's columns in front of R) +
+// (runs with L >= R of the segment's tiles in front of this one)
+__global__ __launch_bounds__(256) void k_bwt_f_run_tile_scan(const u32* __restrict__ tileStart, const u32* __restrict__ segStart, const u64* __restrict__ sKey, u32 nRuns,
+                                                             const u32* __restrict__ nTilesDev, u32 nsym, int kbits, u32* __restrict__ colTab)
+{
+    __shared__ u32 wsum[4];
+    const u32 t0 = blockIdx.x, tid = threadIdx.x, nT = *nTilesDev;
+    if (t0 >= nT) return;
+    const RunTile T0 = run_tile(tileStart, segStart, nRuns, t0);
+    if (!T0.multi || !T0.first) return;
+    const bool above = ((sKey[T0.a] >> kbits) & 1ull) != 0;
+    u32 A[4] = { 0, 0, 0, 0 };                                           // column R = tid + 256 c: runs of the segment with L >= R
+    for (u32 t = t0; t < nT; t++) {
+        const RunTile T = run_tile(tileStart, segStart, nRuns, t);
+        const u32* row = colTab + (size_t)T.slot * RUN_COLS;
+#pragma unroll
+        for (u32 c = 0; c < 4; c++) A[c] += row[tid + 256 * c];
+        if (T.last) break;
+    }
+    u32 P[4], carry = 0;                                                 // members of the columns up to R
+#pragma unroll
+    for (u32 c = 0; c < 4; c++) {
+        if (tid + 256 * c < nsym) A[c] = 0;                              // (no such column)
+        u32 tot;
+        P[c] = carry + prims::sc_block_incl<prims::SCAN_SUM_EXCL>(A[c], wsum, &tot);
+        carry += tot;
+    }
+    u32 run[4];
+#pragma unroll
+    for (u32 c = 0; c < 4; c++) run[c] = above ? carry - P[c] : P[c] - A[c];
+    for (u32 t = t0; t < nT; t++) {
+        const RunTile T = run_tile(tileStart, segStart, nRuns, t);
+        u32* row = colTab + (size_t)T.slot * RUN_COLS;
+#pragma unroll
+        for (u32 c = 0; c < 4; c++) { const u32 x = row[tid + 256 * c]; row[tid + 256 * c] = run[c]; run[c] += x; }
+        if (T.last) break;
+    }
+}
+
+// one workgroup per tile, a wave per row of 64 runs: rk[j] = [class | hi(R) | T], rv[j] = position, Rout[j] = R for every member of the tile
+__global__ __launch_bounds__(256) void k_bwt_f_run_emit(const u32* __restrict__ tileStart, const u32* __restrict__ segStart, const u32* __restrict__ rcnt,
+                                                        const u32* __restrict__ moff, const u64* __restrict__ sKey, const u32* __restrict__ sE, u32 nRuns, u32 M,
+                                                        const u32* __restrict__ nTilesDev, const u32* __restrict__ colTab, u32 nsym, int kbits, int hbits,
+                                                        u64* __restrict__ keys, u32* __restrict__ vals, u32* __restrict__ Rout)
+{
+    __shared__ u32 cnt[RUN_ROWS][RUN_CH];                                // runs of the row with L >= c0 + r, then the same of the rows in front
+    __shared__ u32 colBase[RUN_CH];                                      // where column c0 + r of this tile starts in the segment
+    __shared__ u32 wsum[4];
+    __shared__ u32 sLmax;
+    const u32 t = blockIdx.x, tid = threadIdx.x;
+    if (t >= *nTilesDev) return;
+    const int lane = lane_id();
+    const u32 wave = tid >> 6;
+    const RunTile T = run_tile(tileStart, segStart, nRuns, t);
+    const u32 nRows = (T.k1 - T.k0 + 63) / 64;
+    const u32 segBase = moff[T.a];
+    const u32 tileMembers = (T.k1 < nRuns ? moff[T.k1] : M) - moff[T.k0];     // (the segment's, when the tile is all of it)
+    const bool above = ((sKey[T.k0] >> kbits) & 1ull) != 0;
+    const u64 hiAll = (1ull << hbits) - 1ull;
+    // my runs: wave w has the rows w, w + 4, ...
+    u32 Lr[RUN_ROWS / 4], rowMax[RUN_ROWS / 4], e[RUN_ROWS / 4];
+    u64 kb[RUN_ROWS / 4];
+    u32 lmax = 0;
+    if (tid == 0) sLmax = 0;
+#pragma unroll
+    for (u32 q = 0; q < RUN_ROWS / 4; q++) {
+        const u32 k = T.k0 + (wave + 4 * q) * 64 + (u32)lane;
+        Lr[q] = 0; e[q] = 0; kb[q] = 0;
+        if (k < T.k1) {
+            const u64 key = sKey[k];
+            Lr[q] = rcnt[k] + nsym - 1u;
+            if (Lr[q] > RUN_DIRECT_LMAX) Lr[q] = RUN_DIRECT_LMAX;        // (the host sends no such batch here)
+            e[q] = sE[k];
+            kb[q] = ((key >> (kbits + 1)) << (hbits + kbits)) | (key & ((1ull << kbits) - 1ull));
+        }
+        rowMax[q] = wave_max(Lr[q]);
+        lmax = rowMax[q] > lmax ? rowMax[q] : lmax;
+    }
+    __syncthreads();
+    if (lane == 0) atomicMax(&sLmax, lmax);
+    __syncthreads();
+    const u32 Lmax = sLmax;
+    u32 carry = 0;                                                       // members of the columns below c0 (a segment of one tile)
+    for (u32 c0 = nsym; c0 <= Lmax; c0 += RUN_CH) {
+        for (u32 i = tid; i < nRows * RUN_CH; i += 256) (&cnt[0][0])[i] = 0;
+        __syncthreads();
+#pragma unroll
+        for (u32 q = 0; q < RUN_ROWS / 4; q++)
+            if (Lr[q] >= c0) atomicAdd(&cnt[wave + 4 * q][Lr[q] - c0 < RUN_CH ? Lr[q] - c0 : RUN_CH - 1], 1u);
+        __syncthreads();
+        // per row: counts of L -> counts of L >= column
+#pragma unroll
+        for (u32 q = 0; q < RUN_ROWS / 4; q++) {
+            const u32 row = wave + 4 * q;
+            if (row >= nRows) break;
+            u32 x[4], acc = 0;
+#pragma unroll
+            for (u32 i = 0; i < 4; i++) { x[i] = cnt[row][4 * lane + i]; acc += x[i]; }
+            const u32 incl = wave_incl_scan(acc);
+            const u32 tot = (u32)__shfl((int)incl, 63, 64);
+            u32 ge = tot - (incl - acc);
+#pragma unroll
+            for (u32 i = 0; i < 4; i++) { cnt[row][4 * lane + i] = ge; ge -= x[i]; }
+        }
+        __syncthreads();
+        // per column: the rows in front, and the column's place in the segment
+        u32 colRuns = 0;
+        for (u32 row = 0; row < nRows; row++) { const u32 x = cnt[row][tid]; cnt[row][tid] = colRuns; colRuns += x; }
+        if (T.multi) {
+            colBase[tid] = (c0 + tid < RUN_COLS) ? colTab[(size_t)T.slot * RUN_COLS + c0 + tid] : 0u;
+        } else {
+            u32 tot;
+            const u32 P = carry + prims::sc_block_incl<prims::SCAN_SUM_EXCL>(colRuns, wsum, &tot);
+            colBase[tid] = above ? tileMembers - P : P - colRuns;
+            carry += tot;
+        }
+        __syncthreads();
+#pragma unroll
+        for (u32 q = 0; q < RUN_ROWS / 4; q++) {
+            const u32 row = wave + 4 * q;
+            if (row >= nRows) break;
+            const u32 Rend = rowMax[q] < c0 + RUN_CH - 1 ? rowMax[q] : c0 + RUN_CH - 1;
+            for (u32 R = c0; R <= Rend; R++) {
+                const bool alive = Lr[q] >= R;
+                const unsigned long long m = __ballot(alive);
+                const u32 j = segBase + colBase[R - c0] + cnt[row][R - c0] + (u32)__popcll(m & __lanemask_lt());
+                if (alive && j < M) {
+                    keys[j] = kb[q] | ((above ? hiAll - (u64)R : (u64)R) << kbits);
+                    vals[j] = e[q] - R;
+                    Rout[j] = R;
+                }
+            }
+        }
+        __syncthreads();
+    }
 }
 
 // ---- the run round's last step without index arrays: where a tie starts among the sorted members is ONE BIT per member (a ballot per
@@ -2440,16 +2671,17 @@ __global__ __launch_bounds__(256) void k_bwt_f_med_compact(uint2* __restrict__ s
 // knobs (tests, diagnostics): read from the environment once per process, or set through knz_hip_tune(). Each one forces, at test
 // sizes, a path that some inputs take by themselves (round-0 key length, no run round, the run groups' fall-back, the plain labels of
 // blocks above 256 MiB, the plain keys of blocks above 8 MiB, where the link step starts), or reports (stats).
-struct FwdTuning { int nsym; int noRunRound; int runFallback; int stats; int link; int plainLabels; int noPack; int noUnsplitSkip; int noGroupSleep; int noMediumFuse; };
+struct FwdTuning { int nsym; int noRunRound; int runFallback; int stats; int link; int plainLabels; int noPack; int noUnsplitSkip; int noGroupSleep; int noMediumFuse; int runSort; };
 static FwdTuning& fwd_tuning()
 {
     static FwdTuning t = [] {
-        FwdTuning x; x.nsym = 0; x.noRunRound = 0; x.runFallback = 0; x.stats = 0; x.link = 1; x.plainLabels = 0; x.noPack = 0; x.noUnsplitSkip = 0; x.noGroupSleep = 0; x.noMediumFuse = 0;     // link: 0 off, 1 on (from h = 32), n > 1: from h = n
+        FwdTuning x; x.nsym = 0; x.noRunRound = 0; x.runFallback = 0; x.stats = 0; x.link = 1; x.plainLabels = 0; x.noPack = 0; x.noUnsplitSkip = 0; x.noGroupSleep = 0; x.noMediumFuse = 0; x.runSort = 0;     // link: 0 off, 1 on (from h = 32), n > 1: from h = n
         if (getenv("KNZ_BWT_PLAIN_LABELS")) x.plainLabels = 1;
         if (getenv("KNZ_BWT_NO_PACK")) x.noPack = 1;
         if (getenv("KNZ_BWT_NO_UNSPLIT_SKIP")) x.noUnsplitSkip = 1;
         if (getenv("KNZ_BWT_NO_GROUP_SLEEP")) x.noGroupSleep = 1;
         if (getenv("KNZ_BWT_NO_MEDIUM_FUSE")) x.noMediumFuse = 1;
+        if (const char* e = getenv("KNZ_BWT_RUN_SORT")) x.runSort = atoi(e);
         if (const char* e = getenv("KNZ_BWT_LINK")) x.link = atoi(e);
         if (getenv("KNZ_BWT_STATS")) x.stats = 1;
         if (const char* e = getenv("KNZ_BWT_NSYM")) x.nsym = atoi(e);
@@ -2473,6 +2705,7 @@ int bwt_forward_tune(const char* key, int value)
     else if (!strcmp(key, "bwt_no_unsplit_skip")) t.noUnsplitSkip = value;      // medium groups whose keys are all equal stored and sorted like any other
     else if (!strcmp(key, "bwt_no_group_sleep")) t.noGroupSleep = value;        // every such group gathered in every round (no k_bwt_f_med_sleep, no records)
     else if (!strcmp(key, "bwt_no_medium_fuse")) t.noMediumFuse = value;        // medium groups through k_bwt_f_gather_desc and k_bwt_f_sort_medium on versioned labels too
+    else if (!strcmp(key, "bwt_run_sort")) t.runSort = value;                   // 1: the run round's members generated and sorted (k_bwt_f_run_members, _expand), not placed directly
     else return -1;
     return 0;
 }
@@ -2497,6 +2730,7 @@ struct FwdScratch {
     u32* classTab; u32* rbits; u32* rcount; u32* rprefix;
     u32* runPos; u32* runE; u32* runL; u32* sE; u32* rcnt; u32* moff;
     u64* runKeysA; u64* runKeysB; u64* sKey;
+    u32* runTileStart; u32* runColTab;      // direct placement of the members: first runs of the tiles, column tables of the segments of several tiles
     size_t maxRuns;
 };
 
@@ -2545,6 +2779,10 @@ static size_t fwd_carve(u8* p, int nBlocks, size_t total, FwdScratch* w, u32 VS)
     w->runPos = (u32*)take(4 * w->maxRuns); w->runE = (u32*)take(4 * w->maxRuns); w->runL = (u32*)take(4 * w->maxRuns);
     w->sE = (u32*)take(4 * w->maxRuns); w->rcnt = (u32*)take(4 * w->maxRuns); w->moff = (u32*)take(4 * w->maxRuns + 64);
     w->runKeysA = (u64*)take(8 * w->maxRuns); w->runKeysB = (u64*)take(8 * w->maxRuns); w->sKey = (u64*)take(8 * w->maxRuns);
+    // direct placement: a tile per RUN_TILE runs or segment (4 bytes each), and RUN_COLS counts for each of the at most 2 maxRuns / RUN_TILE
+    // tiles of segments of several tiles -- 8 * RUN_COLS / RUN_TILE = 8 bytes per run, 2 per byte of input, whatever the input holds
+    w->runTileStart = (u32*)take(4 * w->maxRuns + 64);
+    w->runColTab = (u32*)take(4ull * RUN_COLS * run_tile_slots(w->maxRuns));
     return (size_t)(q - p);
 }
 
@@ -2597,6 +2835,7 @@ struct FwdSort {
     u32 h = 1; int cur = 0;                                // offset of the doubling round; its lists w.med[cur], w.large[cur] (the next round's: cur ^ 1)
     u64 *keysFree, *keysFree2;                             // key buffers of the rounds (keysFree2: round 0's sorted keys until they are placed)
     bool medFuse = false;                                  // medium groups through k_bwt_f_medium_fused (versioned labels; knob bwt_no_medium_fuse)
+    bool runDirect = false;                                // the run round placed its members directly (k_bwt_f_run_emit; knob bwt_run_sort)
     u32 nMedLo = 0;                                        // descriptors of the lower size class among the nMed of the list
     u32 nRun, runElems, surv, nMed, nLarge, largeElems, survMembers;   // run groups of round 0 and their members; left: small groups (!= 0),
                                                                        // medium and large groups, large members, small members still tied
@@ -2758,13 +2997,35 @@ struct FwdSort {
           rkSorted = sort_one_segment<u64, false>(nRuns, w.runKeysA, w.runKeysB, nullptr, nullptr, idxBits, idxBits + kbits + 1 + rbits) ? w.runKeysB : w.runKeysA; }
         { KScope ks_("k_bwt_f_run_sorted"); hipLaunchKernelGGL(k_bwt_f_run_sorted, GRID1(nRuns), rkSorted, nRuns, idxBits, w.runE, w.runL, (u32)nsym, w.sE, w.sKey, w.rcnt); }
         { KScope ks_("k_bwt_f_scan_sum"); prims::launch_scan<prims::SCAN_SUM_EXCL>(s, w.rcnt, w.moff, nRuns, nullptr, w.scanTmp); }
-        { KScope ks_("k_bwt_f_run_members"); hipLaunchKernelGGL(k_bwt_f_run_members, dim3((runElems + 2047) / 2048), dim3(256), 0, s, w.moff, nRuns, runElems, w.sKey, kbits, hbits,
-                                                                (u32)nsym, keysFree); }
         u64* rk; u32* rv = w.valsA;
-        { KScope ks_("k_bwt_f_sort_members");
-          const int r = sort_one_segment<u64, false>(runElems, keysFree, keysFree2, nullptr, nullptr, 32, 32 + hbits + rbits);
-          rk = r ? keysFree : keysFree2;
-          hipLaunchKernelGGL(k_bwt_f_run_expand, GRID1(runElems), r ? keysFree2 : keysFree, runElems, w.sKey, w.sE, kbits, hbits, rk, rv, w.valsB); }
+        runDirect = !tune.runSort && hp[CNT_RUN_LONGEST] <= RUN_DIRECT_LMAX;
+        if (runDirect) {
+            // the members placed without a sort (k_bwt_f_run_emit): segments and tiles of the sorted runs, the column tables of the segments
+            // of several tiles, the records. The tables of the unsorted runs are free by now: runPos holds the segments' first runs, runE
+            // the tiles' numbers. One workgroup per tile there can be: a segment's last tile may be short, and there are two segments per class.
+            KScope ks_("k_bwt_f_run_direct");
+            u32* segStart = w.runPos; u32* tileIdx = w.runE;
+            const u32 maxTiles = (u32)std::min<u64>((u64)nRuns, 2ull * nRun + nRuns / RUN_TILE + 1);
+            hipLaunchKernelGGL(k_bwt_f_run_seg_marks, GRID1(nRuns), w.sKey, nRuns, kbits, segStart);
+            prims::launch_scan<prims::SCAN_MAX_INCL>(s, segStart, segStart, nRuns, nullptr, w.scanTmp);
+            hipLaunchKernelGGL(k_bwt_f_run_tile_marks, GRID1(nRuns), segStart, nRuns, tileIdx);
+            prims::launch_scan<prims::SCAN_SUM_EXCL>(s, tileIdx, tileIdx, nRuns, nullptr, w.scanTmp, w.counters + CNT_RUN_TILES);
+            hipLaunchKernelGGL(k_bwt_f_run_tile_starts, GRID1(nRuns), segStart, tileIdx, nRuns, w.runTileStart);
+            if (nRuns > RUN_TILE) {                                     // (no segment of several tiles otherwise)
+                hipLaunchKernelGGL(k_bwt_f_run_tile_counts, dim3(maxTiles), dim3(256), 0, s, w.runTileStart, segStart, w.rcnt, nRuns, w.counters + CNT_RUN_TILES, (u32)nsym, w.runColTab);
+                hipLaunchKernelGGL(k_bwt_f_run_tile_scan, dim3(maxTiles), dim3(256), 0, s, w.runTileStart, segStart, w.sKey, nRuns, w.counters + CNT_RUN_TILES, (u32)nsym, kbits, w.runColTab);
+            }
+            rk = keysFree;
+            hipLaunchKernelGGL(k_bwt_f_run_emit, dim3(maxTiles), dim3(256), 0, s, w.runTileStart, segStart, w.rcnt, w.moff, w.sKey, w.sE, nRuns, runElems, w.counters + CNT_RUN_TILES,
+                               w.runColTab, (u32)nsym, kbits, hbits, rk, rv, w.valsB);
+        } else {
+            { KScope ks_("k_bwt_f_run_members"); hipLaunchKernelGGL(k_bwt_f_run_members, dim3((runElems + 2047) / 2048), dim3(256), 0, s, w.moff, nRuns, runElems, w.sKey, kbits, hbits,
+                                                                    (u32)nsym, keysFree); }
+            KScope ks_("k_bwt_f_sort_members");
+            const int r = sort_one_segment<u64, false>(runElems, keysFree, keysFree2, nullptr, nullptr, 32, 32 + hbits + rbits);
+            rk = r ? keysFree : keysFree2;
+            hipLaunchKernelGGL(k_bwt_f_run_expand, GRID1(runElems), r ? keysFree2 : keysFree, runElems, w.sKey, w.sE, kbits, hbits, rk, rv, w.valsB);
+        }
         // ties among the sorted members as a bit map, heads and sizes per window of 2048 members (the bit map reuses the run-end map, which
         // nobody reads any more)
         u32* mbits = w.ebits; const u32 nWinM = (runElems + SM_WIN - 1) / SM_WIN;
@@ -2798,8 +3059,8 @@ struct FwdSort {
             if (fetch(0, CNT_MED_LO + 1)) return -1;                    // (the probe's two slots, and the class count that goes with CNT_MED)
             surv |= hp[CNT_SMALL_LEFT]; nMed += hp[CNT_MED]; nMedLo += hp[CNT_MED_LO];
         }
-        if (tune.stats) fprintf(stderr, "after round 0 (nsym %d, total %u): run groups %u (%u members); small left %u, medium %u, large %u (%u members)\n",
-                                nsym, total, nRun, runElems, surv, nMed, nLarge, largeElems);
+        if (tune.stats) fprintf(stderr, "after round 0 (nsym %d, total %u): run groups %u (%u members); small left %u, medium %u, large %u (%u members); run members placed directly %u, sorted %u\n",
+                                nsym, total, nRun, runElems, surv, nMed, nLarge, largeElems, (nRun && runDirect) ? runElems : 0u, (nRun && !runDirect) ? runElems : 0u);
         statT = std::chrono::steady_clock::now();
         return 0;
     }
