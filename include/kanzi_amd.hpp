@@ -376,25 +376,33 @@ public:
 // ---- entropy codecs on the device --------------------------------------------------------------
 class DeviceEntropyEncoder : public EntropyEncoder {
 public:
-    DeviceEntropyEncoder(OutputBitStream& obs, int type) : _obs(obs), _type(type) {}
+    DeviceEntropyEncoder(OutputBitStream& obs, int type) : _obs(obs), _type(type), _streamBlockSize(0), _size(-1) {}
     int encode(const byte block[], uint blkptr, uint len);
     OutputBitStream& getBitStream() const { return _obs; }
     void dispose() {}
+protected:
+    // TPAQ / TPAQX: the "blockSize" and "size" entries of the predictor's Context. The device sizes its tables by the block size and
+    // by the length of the buffer it is given, so encode() refuses a length other than `size` (-1: any)
+    void setSizes(int streamBlockSize, int size) { _streamBlockSize = streamBlockSize; _size = size; }
 private:
     OutputBitStream& _obs;
     int _type;
+    int _streamBlockSize, _size;
 };
 
 class DeviceEntropyDecoder : public EntropyDecoder {
 public:
-    DeviceEntropyDecoder(InputBitStream& ibs, int type, int bsVersion = 6) : _ibs(ibs), _type(type), _bsVersion(bsVersion) {}
+    DeviceEntropyDecoder(InputBitStream& ibs, int type, int bsVersion = 6) : _ibs(ibs), _type(type), _bsVersion(bsVersion), _streamBlockSize(0), _size(-1) {}
     int decode(byte block[], uint blkptr, uint len);
     InputBitStream& getBitStream() const { return _ibs; }
     void dispose() {}
+protected:
+    void setSizes(int streamBlockSize, int size) { _streamBlockSize = streamBlockSize; _size = size; }       // as DeviceEntropyEncoder
 private:
     InputBitStream& _ibs;
     int _type;
     int _bsVersion;
+    int _streamBlockSize, _size;
 };
 
 // Constructor parameters as in the reference (entropy/ANSRangeEncoder.hpp:48-51, ANSRangeDecoder.hpp:45-47,
@@ -433,7 +441,7 @@ public:
 // reference. The coder runs on the device (csrc/cm.hip) and starts from the predictor's initial state, as every caller of the reference
 // does; the object is not read. The device kernels hold the tables of bitstream version 6, which every stream path of the reference
 // passes in its Context: a CMPredictor built without a Context, or with "bsVersion" 7 or more, would stand for the other table
-// (counter2[*][16] = 65535) and is refused with std::invalid_argument. Only a CMPredictor has a device kernel behind it.
+// (counter2[*][16] = 65535) and is refused with std::invalid_argument. CMPredictor and TPAQPredictor (below) have device kernels behind them.
 class Predictor {
 public:
     virtual ~Predictor() {}
@@ -448,6 +456,22 @@ public:
 private:
     int _c1, _c2, _ctx, _runMask, _idx;
     std::vector<int> _counter1, _counter2;        // [256][257], [512][17]
+};
+// entropy/TPAQPredictor.hpp:60-132, :297-372: TPAQ (T = false) and TPAQX (T = true). The predictor runs on the device (csrc/tpaq.hip), which
+// builds it from the three Context entries kept here: "blockSize" (the stream's block size), "size" (the length of the block behind
+// the transforms; the block size when absent) and "bsVersion". As with CMPredictor, the device holds the predictor of bitstream
+// version 6 (masks of size - 1, sizes not rounded to powers of two): no Context, or "bsVersion" 7 or more, is refused with
+// std::invalid_argument. The object keeps no tables: update() and get() throw std::logic_error.
+template <bool T>
+class TPAQPredictor : public Predictor {
+public:
+    explicit TPAQPredictor(Context* pCtx = nullptr);
+    void update(int bit);
+    int get();
+    int blockSize() const { return _blockSize; }
+    int size() const { return _size; }
+private:
+    int _blockSize, _size;
 };
 class BinaryEntropyEncoder : public DeviceEntropyEncoder {
 public:

@@ -27,7 +27,7 @@ extern "C" {
 #define KNZ_API __attribute__((visibility("default")))
 
 /* kanzi ids: entropy (entropy/EntropyEncoderFactory.hpp:37-52) and transforms (transform/TransformFactory.hpp:49-73) */
-enum { KNZ_E_NONE = 0, KNZ_E_HUFFMAN = 1, KNZ_E_FPAQ = 2, KNZ_E_RANGE = 4, KNZ_E_ANS0 = 5, KNZ_E_CM = 6, KNZ_E_ANS1 = 8 };
+enum { KNZ_E_NONE = 0, KNZ_E_HUFFMAN = 1, KNZ_E_FPAQ = 2, KNZ_E_RANGE = 4, KNZ_E_ANS0 = 5, KNZ_E_CM = 6, KNZ_E_TPAQ = 7, KNZ_E_ANS1 = 8, KNZ_E_TPAQX = 9 };
 enum { KNZ_T_NONE = 0, KNZ_T_BWT = 1, KNZ_T_BWTS = 2, KNZ_T_LZ = 3, KNZ_T_RLT = 5, KNZ_T_ZRLT = 6, KNZ_T_MTFT = 7, KNZ_T_RANK = 8, KNZ_T_SRT = 13, KNZ_T_LZP = 14, KNZ_T_MM = 15, KNZ_T_LZX = 16, KNZ_T_PACK = 18,
        KNZ_T_TIMESTAMP = 64 /* SBRT's third mode: no kanzi id, never part of a chain; per-stage entry points only */,
        KNZ_T_UTF = 17 /* a device stage in any position; also accepted among the host's leading stages (below) */,
@@ -72,7 +72,8 @@ typedef struct {
  * KNZ_E_CM: nothing tighter than the format's own ceiling of 32 bytes per input byte is known for CM, so the value is a FIRST tier --
  * n + n / 8 plus framing, what the reference's own buffer starts at and what every input met so far stays below. An encode whose
  * stream does not fit out_cap fails with KNZ_ERR_WRITE_FILE (the message names the size needed) and leaves the context usable;
- * the second tier, knz_hip_encode_bound(p, n) + 32 * n, holds whatever the format can write. */
+ * the second tier, knz_hip_encode_bound(p, n) + 32 * n, holds whatever the format can write.
+ * KNZ_E_TPAQ, KNZ_E_TPAQX: the same coder behind another predictor; the same two tiers. */
 KNZ_API size_t knz_hip_encode_bound(const knz_params* p, size_t n);
 
 /*
@@ -152,6 +153,16 @@ KNZ_API int knz_hip_entropy_decode(knz_ctx* ctx, int entropy_type, const uint8_t
 KNZ_API int knz_hip_entropy_decode_v(knz_ctx* ctx, int entropy_type, int bs_version, const uint8_t* in, uint64_t in_bits,
                                      uint64_t start_bit, uint8_t* out, uint32_t n, int32_t* decoded,
                                      uint64_t* used_bits);
+
+/* The same two calls with the block size of the stream the buffer belongs to -- the "blockSize" entry of the Context that
+ * EntropyEncoderFactory / EntropyDecoderFactory hand to the predictor. KNZ_E_TPAQ and KNZ_E_TPAQX size their tables by it
+ * (entropy/TPAQPredictor.hpp:312-339) and by the buffer's own length n (the "size" entry), so the same bytes code differently in
+ * streams of different block sizes; the other coders ignore it. 0 = the buffer's own length rounded up to 16, which is what
+ * knz_hip_entropy_encode / _decode_v pass. */
+KNZ_API int knz_hip_entropy_encode_bs(knz_ctx* ctx, int entropy_type, uint32_t stream_block_size, const uint8_t* in, uint32_t n,
+                                      uint8_t* out, size_t out_cap, uint64_t* out_bits);
+KNZ_API int knz_hip_entropy_decode_bs(knz_ctx* ctx, int entropy_type, int bs_version, uint32_t stream_block_size, const uint8_t* in,
+                                      uint64_t in_bits, uint64_t start_bit, uint8_t* out, uint32_t n, int32_t* decoded, uint64_t* used_bits);
 
 /* Transform<byte>::forward / inverse for one buffer (src/Transform.hpp:38-45). dst_cap mirrors
  * SliceArray::_length - _index of the destination (it changes results for ZRLT/RLT; LZ/LZX refuse a
@@ -237,6 +248,11 @@ KNZ_API int knz_hip_transform_supported(int transform_type);
 /* Test hook: q[i] = floor(d[i] / r[i]) by the RANGE decoder's reciprocal-based divide (host arrays; every pair must satisfy what the
  * decoder has checked before it divides: r >= 1 and d < r * 2^15). */
 KNZ_API int knz_hip_range_divide(knz_ctx* ctx, const uint64_t* d, const uint64_t* r, uint32_t n, uint32_t* q);
+
+/* Test hook: the sizes the TPAQ (extra = 0) / TPAQX (extra = 1) predictor takes for a block of block_len bytes (behind the
+ * transforms) in a stream of block size stream_block_size, bitstream version 6: sizes[0..5] = bytes of the big states table, mixers,
+ * words of the position hash, bytes of the ring buffer, contexts of the first and of the second SSE map. Needs no context and no device. */
+KNZ_API int knz_hip_tpaq_params(uint32_t stream_block_size, uint32_t block_len, int extra, uint32_t sizes[6]);
 
 #ifdef __cplusplus
 }

@@ -165,7 +165,10 @@ static int count_transforms(uint64_t t, int* tok)
 }
 
 static bool host_stage_id(int t) { return t == KNZ_T_TEXT || t == KNZ_T_UTF; }
-static bool entropy_supported(int e) { return e == KNZ_E_NONE || e == KNZ_E_ANS0 || e == KNZ_E_ANS1 || e == KNZ_E_HUFFMAN || e == KNZ_E_FPAQ || e == KNZ_E_RANGE || e == KNZ_E_CM; }
+static bool entropy_supported(int e) { return e == KNZ_E_NONE || e == KNZ_E_ANS0 || e == KNZ_E_ANS1 || e == KNZ_E_HUFFMAN || e == KNZ_E_FPAQ || e == KNZ_E_RANGE || e == KNZ_E_CM || e == KNZ_E_TPAQ || e == KNZ_E_TPAQX; }
+// the coders behind BinaryEntropyEncoder: two-tier staging, one chunk rule (binary_coder.hpp)
+static bool binary_coder(int e) { return e == KNZ_E_CM || e == KNZ_E_TPAQ || e == KNZ_E_TPAQX; }
+static bool tpaq_coder(int e) { return e == KNZ_E_TPAQ || e == KNZ_E_TPAQX; }
 
 }  // namespace knz
 
@@ -274,7 +277,8 @@ size_t knz_hip_encode_bound(const knz_params* p, size_t n)
     // CM: no bound is proved below the format's 32 bytes per byte, so this is the FIRST tier, what the encoder stages a block at
     // (n + n / 8, cm.hip) plus var-ints and tails. An encode whose stream is longer fails with KNZ_ERR_WRITE_FILE and names the size;
     // 32 * n on top of this value always holds it (include/knz_hip.h).
-    if (p->entropy_type == KNZ_E_CM) bound = (cm_tier1_div() ? n / cm_tier1_div() : n + n / 8) + nb * 64 + nb * (size_t)CM_MAX_CHUNKS * 16 + 4096;
+    // (TPAQ and TPAQX: the same coder behind another predictor, the same two tiers)
+    if (binary_coder(p->entropy_type)) bound = (cm_tier1_div() ? n / cm_tier1_div() : n + n / 8) + nb * 64 + nb * (size_t)CM_MAX_CHUNKS * 16 + 4096;
     return bound;
 }
 
@@ -756,7 +760,7 @@ static int run_stage(Ctx* c, hipStream_t s, const XfInfo& x, bool forward, const
 // capsMode: 0 = reference stream buffers (jobs model), otherwise every destination capacity = capsMode (per-stage API)
 static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t n, const uint8_t* prologue,
                        uint32_t prologueBits, int framing, int finish, int64_t firstBlock, uint8_t* d_out, size_t outCap,
-                       uint64_t* outBits, const knz_host_stages* hs = nullptr)
+                       uint64_t* outBits, const knz_host_stages* hs = nullptr, u32 streamBlockSize = 0)
 {
     ProfInstall pi_(c);
     HIPCHK(c, hipSetDevice(c->device));
@@ -888,7 +892,11 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
     // ---- entropy stage
     const bool ans1 = (p->entropy_type == KNZ_E_ANS1);
     const bool rangeCoder = (p->entropy_type == KNZ_E_RANGE);
-    const bool cm = (p->entropy_type == KNZ_E_CM);
+    const bool cm = binary_coder(p->entropy_type);
+    const bool tpaq = tpaq_coder(p->entropy_type);
+    const int tpaqExtra = p->entropy_type == KNZ_E_TPAQX ? 1 : 0;
+    const u32 tpaqRbsz = streamBlockSize ? streamBlockSize : bs;      // the "blockSize" of the stream's Context (per-stage calls pass it)
+    void* d_tpaqTables = nullptr;
     // (CM: the chunk length depends on the block's own length, so a block is ONE chunk of the framing's arithmetic that owns
     // cm_max_chunks(S) slots; the slots a block does not use stay zero and add nothing)
     const u32 entChunk = (p->entropy_type == KNZ_E_FPAQ || ans1) ? (4u << 20) : rangeCoder ? RANGE_CHUNK : cm ? 0x80000000u : ENT_CHUNK;
@@ -935,6 +943,12 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
         if (int r = ws_get(c, "chunkTmp", (size_t)cStride * nBlocks, (void**)&d_tmp, s)) return r;
         if (int r = ws_get(c, "cmCtrl", cm_ctrl_bytes(nBlocks), &d_cmCtrl, s)) return r;
         // blocks that did not fit their staging are coded again into 32 n + 16 bytes each: workspace taken only then
+        if (tpaq) {
+            // the predictor's tables, for as many blocks as the budget lets run at once (tpaq.hip)
+            const size_t tb = tpaq_table_bytes(tpaqRbsz, (u32)S, tpaqExtra);
+            if (int r = ws_get(c, "tpaqTables", tb * (size_t)tpaq_slice_blocks(tb, nBlocks), &d_tpaqTables, s)) return r;
+            launch_tpaq_encode(s, tpaqExtra, view, d_origLen, framing ? 15u : 0u, nBlocks, maxChunks, d_desc, d_tmp, cStride, d_cmCtrl, d_tpaqTables, tpaqRbsz, (u32)S);
+        } else
         launch_cm_encode(s, view, d_origLen, framing ? 15u : 0u, nBlocks, maxChunks, d_desc, d_tmp, cStride, d_cmCtrl);
         d_cmMarked = static_cast<u32*>(d_cmCtrl);                 // how many blocks did not fit: read back with the total below
     } else {
@@ -965,9 +979,11 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
             g->rc = ws_get(g->c, "cmBig", bytes, &m, g->s);
             return g->rc ? nullptr : m;
         };
-        const int r = launch_cm_encode_again(s, view, d_origLen, framing ? 15u : 0u, nBlocks, maxChunks, d_desc, d_tmp, cm_stage_stride(S), d_cmMarked, bigAlloc, &big);
+        const int r = tpaq ? launch_tpaq_encode_again(s, tpaqExtra, view, d_origLen, framing ? 15u : 0u, nBlocks, maxChunks, d_desc, d_tmp, cm_stage_stride(S), d_cmMarked, bigAlloc, &big,
+                                                      d_tpaqTables, tpaqRbsz, (u32)S)
+                           : launch_cm_encode_again(s, view, d_origLen, framing ? 15u : 0u, nBlocks, maxChunks, d_desc, d_tmp, cm_stage_stride(S), d_cmMarked, bigAlloc, &big);
         if (r == -2) return big.rc;                               // (ws_get has said why)
-        if (r < 0) return fail(c, -1, "CM encode failed: %s", hipGetErrorString(hipGetLastError()));
+        if (r < 0) return fail(c, -1, "binary coder: encode failed: %s", hipGetErrorString(hipGetLastError()));
         launch_block_sum(s, d_desc, d_info, d_blockLen, nBlocks, maxChunks, entChunk, slotMul);
         launch_block_scan(s, d_info, d_blockLen, d_origLen, nBlocks, fp, d_total);
         HIPCHK(c, hipMemcpyAsync(h_total, d_total, sizeof(u64), hipMemcpyDeviceToHost, s));
@@ -1021,7 +1037,7 @@ struct WalkResultHost { u64 endBit; int64_t nBlocks; int32_t ended; int32_t erro
 
 static int decode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, uint64_t inBits, uint64_t startBit, int64_t maxBlocks,
                        int framing, u32 rawLen, uint8_t* d_out, size_t outCap, uint64_t* outBytes, uint64_t* endBit,
-                       int64_t* blocksDone, int32_t* rawDecoded, uint64_t* usedBits, int nHosted = 0, uint32_t* skipOut = nullptr, uint64_t* sumOut = nullptr)
+                       int64_t* blocksDone, int32_t* rawDecoded, uint64_t* usedBits, int nHosted = 0, uint32_t* skipOut = nullptr, uint64_t* sumOut = nullptr, u32 streamBlockSize = 0)
 {
     ProfInstall pi_(c);
     HIPCHK(c, hipSetDevice(c->device));
@@ -1130,6 +1146,14 @@ static int decode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, uint64_
             launch_range_decode(sp, src, blk, nb, w.d_entDst, framing);
         } else if (p->entropy_type == KNZ_E_CM) {
             launch_cm_decode(sp, src, blk, nb, w.d_entDst);
+        } else if (tpaq_coder(p->entropy_type)) {
+            // the predictor's tables, per lane, for as many blocks as the budget lets run at once; a valid block is at most S bytes
+            const int extra = p->entropy_type == KNZ_E_TPAQX ? 1 : 0;
+            const u32 rbsz = streamBlockSize ? streamBlockSize : bs;
+            const size_t tb = tpaq_table_bytes(rbsz, (u32)S, extra);
+            void* d_tables;
+            if (int r = ws_get(c, lane_ws("tpaqTables", lane), tb * (size_t)tpaq_slice_blocks(tb, nb), &d_tables, sp)) return r;
+            launch_tpaq_decode(sp, extra, src, blk, nb, w.d_entDst, d_tables, rbsz, (u32)S);
         } else {
             launch_none_decode(sp, src, blk, nb, w.d_entDst);
         }
@@ -1211,8 +1235,15 @@ int knz_hip_decode_block_hosted(knz_ctx* ctx, const knz_params* p, int32_t host_
 int knz_hip_entropy_encode(knz_ctx* ctx, int entropy_type, const uint8_t* in, uint32_t n, uint8_t* out, size_t out_cap,
                            uint64_t* out_bits)
 {
+    return knz_hip_entropy_encode_bs(ctx, entropy_type, 0, in, n, out, out_cap, out_bits);
+}
+
+int knz_hip_entropy_encode_bs(knz_ctx* ctx, int entropy_type, uint32_t stream_block_size, const uint8_t* in, uint32_t n, uint8_t* out, size_t out_cap,
+                              uint64_t* out_bits)
+{
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     CTX_LOCK(c);
+    if (stream_block_size > (1u << 30)) return fail(c, KNZ_ERR_INVALID_PARAM, "invalid block size %u", stream_block_size);
     if (n == 0) { *out_bits = 0; return 0; }
     knz_params p; memset(&p, 0, sizeof(p));
     p.entropy_type = entropy_type; p.block_size = (int32_t)((n + 15) & ~15u); p.transform_type = 0;
@@ -1222,12 +1253,12 @@ int knz_hip_entropy_encode(knz_ctx* ctx, int entropy_type, const uint8_t* in, ui
     if (int r = ws_get(c, "stageOut", cap, (void**)&d_out, c->stream)) return r;
     HIPCHK(c, hipMemcpyAsync(d_in, in, n, hipMemcpyHostToDevice, c->stream));
     u64 bits = 0;
-    int r = encode_impl(c, &p, d_in, n, nullptr, 0, 0, 0, 0, d_out, cap, &bits);
-    if (r == KNZ_ERR_WRITE_FILE && entropy_type == KNZ_E_CM) {
-        // the bound of CM is its first tier (knz_hip_encode_bound): the second holds whatever the format can write
+    int r = encode_impl(c, &p, d_in, n, nullptr, 0, 0, 0, 0, d_out, cap, &bits, nullptr, stream_block_size);
+    if (r == KNZ_ERR_WRITE_FILE && binary_coder(entropy_type)) {
+        // the bound of the binary coders is their first tier (knz_hip_encode_bound): the second holds whatever the format can write
         const size_t cap2 = cap + 32 * (size_t)n;
         if (int r2 = ws_get(c, "stageOut", cap2, (void**)&d_out, c->stream)) return r2;
-        r = encode_impl(c, &p, d_in, n, nullptr, 0, 0, 0, 0, d_out, cap2, &bits);
+        r = encode_impl(c, &p, d_in, n, nullptr, 0, 0, 0, 0, d_out, cap2, &bits, nullptr, stream_block_size);
     }
     if (r) return r;
     const size_t bytes = (size_t)((bits + 7) >> 3);
@@ -1247,8 +1278,15 @@ int knz_hip_entropy_decode(knz_ctx* ctx, int entropy_type, const uint8_t* in, ui
 int knz_hip_entropy_decode_v(knz_ctx* ctx, int entropy_type, int bs_version, const uint8_t* in, uint64_t in_bits, uint64_t start_bit,
                              uint8_t* out, uint32_t n, int32_t* decoded, uint64_t* used_bits)
 {
+    return knz_hip_entropy_decode_bs(ctx, entropy_type, bs_version, 0, in, in_bits, start_bit, out, n, decoded, used_bits);
+}
+
+int knz_hip_entropy_decode_bs(knz_ctx* ctx, int entropy_type, int bs_version, uint32_t stream_block_size, const uint8_t* in, uint64_t in_bits,
+                              uint64_t start_bit, uint8_t* out, uint32_t n, int32_t* decoded, uint64_t* used_bits)
+{
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     CTX_LOCK(c);
+    if (stream_block_size > (1u << 30)) return fail(c, KNZ_ERR_INVALID_PARAM, "invalid block size %u", stream_block_size);
     if (bs_version < 0 || bs_version > 6) return fail(c, KNZ_ERR_STREAM_VERSION, "cannot read bitstream version %d", bs_version);   // (as knz_hip_transform_inverse_v)
     if (n == 0) { *decoded = 0; if (used_bits) *used_bits = 0; return 0; }
     knz_params p; memset(&p, 0, sizeof(p));
@@ -1259,11 +1297,19 @@ int knz_hip_entropy_decode_v(knz_ctx* ctx, int entropy_type, int bs_version, con
     if (int r = ws_get(c, "stageOut", (size_t)n + 64, (void**)&d_out, c->stream)) return r;
     HIPCHK(c, hipMemcpyAsync(d_in, in, inBytes, hipMemcpyHostToDevice, c->stream));
     u64 ob = 0;
-    if (int r = decode_impl(c, &p, d_in, in_bits, start_bit, 1, 0, n, d_out, n, &ob, nullptr, nullptr, decoded, used_bits)) return r;
+    if (int r = decode_impl(c, &p, d_in, in_bits, start_bit, 1, 0, n, d_out, n, &ob, nullptr, nullptr, decoded, used_bits, 0, nullptr, nullptr, stream_block_size)) return r;
     if (*decoded == (int32_t)n) {
         HIPCHK(c, hipMemcpyAsync(out, d_out, n, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
+    return 0;
+}
+
+int knz_hip_tpaq_params(uint32_t stream_block_size, uint32_t block_len, int extra, uint32_t sizes[6])
+{
+    if (sizes == nullptr || (extra != 0 && extra != 1)) return KNZ_ERR_INVALID_PARAM;
+    const TpaqSizes z = tpaq_params(stream_block_size, block_len, extra);
+    sizes[0] = z.states; sizes[1] = z.mixers; sizes[2] = z.hash; sizes[3] = z.buffer; sizes[4] = z.sse0; sizes[5] = z.sse1;
     return 0;
 }
 

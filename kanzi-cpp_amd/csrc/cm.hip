@@ -5,6 +5,9 @@
 // BinaryEntropyDecoder.hpp:68-89 (decodeBit). Every stream path of the reference builds the predictor with a Context of bitstream
 // version 6, so counter2[*][16] starts at 65536; the 65535 of version 7 and up is not built here (api.hip refuses that version).
 //
+// The coder itself -- chunk rule, interval chain, payload units, chunk tail -- is binary_coder.hpp, shared with tpaq.hip; this file is the
+// predictor, the two kernels that instantiate the coder with it, and the staging protocol's host side.
+//
 // Format: a block of `count` bytes is coded in chunks of max(count, 64) bytes -- one chunk -- unless that is CM_BIG_BLOCK (64 MiB) or
 // more: then a chunk is count >> 3 bytes, or count >> 4 when count / 8 is itself CM_BIG_BLOCK or more (8-9 or 16-17 chunks). A chunk
 // is: var-int payload byte count, payload, 56 bits of low | 0xFFFFFF. Predictor and interval carry across chunks. The decoder reads
@@ -33,44 +36,20 @@
 // what it reads back anyway, so the common path has no synchronisation of its own.
 #include "common.hpp"
 #include "stages.hpp"
-#include "binary_tail.hpp"
+#include "binary_coder.hpp"
 
 #include <stdlib.h>
 #include <vector>
 
 namespace knz {
 
-#ifdef KNZ_EMU_CM_BIG_BLOCK        // CPU emulation tests only: a low threshold, to cross chunk borders with small inputs
-constexpr u32 CM_BIG_BLOCK = KNZ_EMU_CM_BIG_BLOCK;
-#else
-constexpr u32 CM_BIG_BLOCK = 1u << 26;
-#endif
-static_assert(CM_BIG_BLOCK >= 256, "a big block has at least 16 bytes per chunk");
-constexpr u64 CM_TOP = 0x00FFFFFFFFFFFFFFull;
-constexpr u64 CM_MASK32 = 0x00000000FFFFFFFFull;
-constexpr u64 CM_MASK56 = 0x00FFFFFFFFFFFFFFull;
-
 struct CmTables {
     u16 c1[256 * 257];
     u16 c2[512 * 16];
     u32 c2top[512];
 };
-constexpr u32 CM_RING_WORDS = 512;            // a tile of 64 bytes is 512 bits, a bit leaves at most one word
 static_assert(sizeof(CmTables) == 150016, "16-bit cells, cell 16 of counter2 apart");
 static_assert(sizeof(CmTables) + 4 * CM_RING_WORDS + 64 <= KNZ_LDS_BYTES, "the predictor of a block lives in the LDS of one workgroup");
-
-__host__ __device__ __forceinline__ u32 cm_chunk_len(u32 count)
-{
-    u32 length = count < 64 ? 64u : count;
-    if (length >= CM_BIG_BLOCK) length = (length / 8 < CM_BIG_BLOCK) ? count >> 3 : count >> 4;
-    return length;
-}
-
-// The first staging of a block of n bytes. div != 0 (tests only, cm_tier1_div): n / div + 64 bytes, so that the second pass is taken.
-__host__ __device__ __forceinline__ u64 cm_stage1(u64 n, u32 div)
-{
-    return div ? n / div + 64 : n + n / 8 + 64;
-}
 
 // KNZ_CM_TIER1_DIV=d (a debugging aid like KNZ_POISON_WS, read on every call so that a test can set it): the first tier -- the
 // encoder's first staging and what knz_hip_encode_bound returns for CM -- becomes n / d, so that blocks that do not compress take the
@@ -85,9 +64,6 @@ u32 cm_tier1_div()
     return v > 0 ? (u32)v : 0u;
 #endif
 }
-
-__device__ __forceinline__ u32 cm_rl(u32 v, u32 l) { return (u32)__builtin_amdgcn_readlane((int)v, (int)l); }
-__device__ __forceinline__ u32 cm_uni(u32 v) { return (u32)__builtin_amdgcn_readfirstlane((int)v); }
 
 __device__ __forceinline__ void cm_init(CmTables& t, int lane)
 {
@@ -139,6 +115,16 @@ __device__ __forceinline__ void cm_update(CmTables& t, CmCtx& s, const CmCells& 
     }
 }
 
+// The predictor as binary_coder.hpp takes it
+struct CmPred {
+    CmTables& t;
+    CmCtx s;
+    CmCells cells;
+    __device__ __forceinline__ explicit CmPred(CmTables& tables) : t(tables) { s.c1 = 0; s.c2 = 0; s.ctx = 1; s.runMask = 0; }
+    __device__ __forceinline__ u32 get() { return cm_get(t, s, cells); }
+    __device__ __forceinline__ void update(bool one) { cm_update(t, s, cells, one); }
+};
+
 // ------------------------------------------------------------------------------------------------
 // encoder: one wave per block
 // ------------------------------------------------------------------------------------------------
@@ -157,67 +143,16 @@ __global__ __launch_bounds__(64) void k_cm_encode(BlockView view, const u32* __r
     ChunkDesc* cds = desc + (size_t)b * maxChunks;
     if (pass == 1 && ctrl[1 + b] != 1) return;
     if (origLen[b] <= copyThreshold) {
-        // copy block: entropy type forced to NONE (io/CompressedOutputStream.cpp:691-695)
-        if (lane == 0) {
-            ChunkDesc& cd = cds[0];
-            cd.hdrBits = 0; cd.midLen = 0; cd.trailerLen = 0; cd.aux = 0;
-            cd.nPieces = 1; cd.pieceBits[0] = 8 * count; cd.piecePtr[0] = blk;
-        }
+        if (lane == 0) binary_copy_desc(cds[0], blk, count);
         return;
     }
     cm_init(t, lane);
     __syncthreads();
     u8* buf = pass ? big + bigOff[b] : tmp + (size_t)b * tmpStride;
     const u64 cap = pass ? 32ull * count + 16 : cm_stage1(count, tier1Div);
-    const u32 length = cm_chunk_len(count);
-    CmCtx s; s.c1 = 0; s.c2 = 0; s.ctx = 1; s.runMask = 0;
-    u64 low = 0, high = CM_TOP;
-    u64 index = 0;                                  // bytes of the block's staging in use; a chunk's payload starts where the last one ended
-    u32 startChunk = 0;
-    int ci = 0;
-    bool full = false;
-    while (startChunk < count && !full) {
-        const u32 chunkSize = (length < count - startChunk) ? length : count - startChunk;
-        const u32 endChunk = startChunk + chunkSize;
-        const u64 index0 = index;
-        u32 nByte = 0;
-        { const u32 i = startChunk + (u32)lane; if (i < endChunk) nByte = blk[i]; }
-        for (u32 i0 = startChunk; i0 < endChunk && !full; i0 += 64) {
-            const u32 byte = nByte;
-            { const u32 i = i0 + 64 + (u32)lane; nByte = 0; if (i < endChunk) nByte = blk[i]; }
-            const u32 nb = (endChunk - i0 < 64) ? endChunk - i0 : 64;
-            u32 cnt = 0;
-            for (u32 l = 0; l < nb && !full; l++) {
-                const u32 bv = cm_rl(byte, l);
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    CmCells cells;
-                    const u64 pred = cm_get(t, s, cells);
-                    const bool one = (bv >> (7 - k)) & 1u;
-                    const u64 mid = low + ((((high - low) >> 4) * pred) >> 8);
-                    high = one ? mid : high;
-                    low = one ? low : mid + 1;
-                    cm_update(t, s, cells, one);
-                    const u64 x = low ^ high;
-                    if ((((u32)(x >> 32)) | ((u32)x >> 24)) == 0) {  // top 32 of the 56 bits agree: they leave
-                        if (index + 4ull * cnt + 4 > cap) { full = true; break; }
-                        if (lane == 0) ring[cnt] = (u32)(high >> 24);
-                        cnt++;
-                        low <<= 32;
-                        high = (high << 32) | CM_MASK32;
-                    }
-                }
-            }
-            __syncthreads();
-            if (!full) for (u32 qd = (u32)lane; qd < cnt; qd += 64) reinterpret_cast<u32*>(buf + index)[qd] = bswap32(ring[qd]);
-            __syncthreads();
-            index += 4ull * cnt;
-        }
-        if (!full && lane == 0) binary_desc_finish(cds[ci], (u32)(index - index0), buf + index0, low);
-        startChunk = endChunk;
-        ci++;
-    }
-    // (pass 1 cannot fill its staging: a bit leaves at most one unit, 32 bytes per input byte; the check above only guards the memory)
+    CmPred pr(t);
+    const bool full = binary_encode_block(pr, blk, count, buf, cap, cds, ring, lane);
+    // (pass 1 cannot fill its staging: a bit leaves at most one unit, 32 bytes per input byte; the check only guards the memory)
     if (full && pass == 0 && lane == 0) { ctrl[1 + b] = 1; atomicAdd(&ctrl[0], 1u); }
 }
 
@@ -230,95 +165,14 @@ __global__ __launch_bounds__(64) void k_cm_decode(BitSrc src, DecBlock* __restri
     const int b = blockIdx.x;
     const int lane = lane_id();
     DecBlock& db = blocks[b];
-    if (db.error) return;
-    BitSrc s = src;
-    {
-        const u64 end = db.payloadBit + ((db.bits + 7) & ~7ull);
-        s.limitBits = end < src.limitBits ? end : src.limitBits;      // never past the caller's in_bits
-    }
-    const u64 limit = s.limitBits;
-    u64 pos = db.entropyBit;
-    const u32 count = db.preLen;
+    BitSrc s;
     u8* block = outPtr[b];
-    if (db.copyBlock) {
-        const bool bad = pos + 8ull * count > limit;
-        if (!bad) for (u32 i = (u32)lane; i < count; i += 64) block[i] = (u8)peek_bits(s, pos + 8ull * i, 8);
-        if (lane == 0) { if (bad) db.error = KNZ_ERR_PROCESS_BLOCK; db.usedBits = bad ? (limit - db.entropyBit) : 8ull * count; }
-        return;
-    }
+    if (binary_decode_head(src, db, s, block, lane)) return;
+    u64 pos = db.entropyBit;
     cm_init(t, lane);
     __syncthreads();
-    const u64 lastWord = ((src.nBytes + 3) >> 2) - 1;
-    const u32 length = cm_chunk_len(count);
-    CmCtx cs; cs.c1 = 0; cs.c2 = 0; cs.ctx = 1; cs.runMask = 0;
-    u64 low = 0, high = CM_TOP, current = 0;
-    u32 startChunk = 0;
-    bool fail = false;
-    while (startChunk < count && !fail) {
-        const u32 chunkSize = (length < count - startChunk) ? length : count - startChunk;
-        const u32 endChunk = startChunk + chunkSize;
-        int err = 0;
-        const u32 szBytes = take_varint(s, pos, err);
-        if (err) { fail = true; break; }
-        {
-            const u64 most = ((u64)chunkSize << 5) < 0x1FFFFFFFull ? ((u64)chunkSize << 5) : 0x1FFFFFFFull;      // BinaryEntropyDecoder.cpp:98-101
-            if (szBytes > most) { fail = true; break; }
-        }
-        current = ((u64)take_bits(s, pos, 24, err) << 32) | take_bits(s, pos, 32, err);
-        if (err || pos + 8ull * szBytes > limit) { fail = true; pos = limit; break; }
-        const u64 payBit = pos;
-        pos += 8ull * szBytes;
-        // payload as 32-bit units in stream order, unit u = bits [payBit + 32 u, + 32): window = 64 units, one per lane
-        const u64 wbase = payBit >> 5;
-        const u32 sh = (u32)(payBit & 31);
-        auto loadWin = [&](u32 unit0) -> u32 {
-            const u64 w = wbase + unit0 + (u32)lane;
-            const u32 a = bswap32(src.words[w < lastWord ? w : lastWord]);
-            const u32 c = bswap32(src.words[w + 1 < lastWord ? w + 1 : lastWord]);
-            return sh ? ((a << sh) | (c >> (32 - sh))) : a;
-        };
-        u32 winBase = 0;
-        u32 winCur = loadWin(0), winNext = loadWin(64);
-        u32 index = 0;
-        for (u32 i0 = startChunk; i0 < endChunk && !fail; i0 += 64) {
-            const u32 nb = (endChunk - i0 < 64) ? endChunk - i0 : 64;
-            u32 myByte = 0;
-            for (u32 l = 0; l < nb; l++) {
-                u32 val8 = 0;
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    CmCells cells;
-                    const u64 pred = cm_get(t, cs, cells);
-                    const u64 split = ((((high - low) >> 4) * pred) >> 8) + low;
-                    const bool one = split >= current;
-                    high = one ? split : high;
-                    low = one ? low : split + 1;
-                    cm_update(t, cs, cells, one);
-                    val8 = 2 * val8 + (one ? 1u : 0u);
-                    const u64 x = low ^ high;
-                    if ((((u32)(x >> 32)) | ((u32)x >> 24)) == 0) {
-                        low = (low << 32) & CM_MASK56;
-                        high = ((high << 32) | CM_MASK32) & CM_MASK56;
-                        if (index + 4 > szBytes) {
-                            // the reference would read behind its payload here: no stream it writes does that
-                            current = (current << 32) & CM_MASK56;
-                            index = szBytes + 1;
-                        } else {
-                            const u32 u = index >> 2;
-                            if (u - winBase >= 64) { winCur = winNext; winBase += 64; winNext = loadWin(winBase + 64); }
-                            const u64 val = cm_rl(winCur, (u - winBase) & 63);
-                            current = ((current << 32) | val) & CM_MASK56;
-                            index += 4;
-                        }
-                    }
-                }
-                if ((u32)lane == l) myByte = val8;
-                if (index > szBytes) { fail = true; break; }
-            }
-            if ((u32)lane < nb && !fail) block[i0 + (u32)lane] = (u8)myByte;
-        }
-        startChunk = endChunk;
-    }
+    CmPred pr(t);
+    const bool fail = binary_decode_block(pr, src, s, pos, db.preLen, block, lane);
     if (lane == 0) {
         if (fail) db.error = KNZ_ERR_PROCESS_BLOCK;
         db.usedBits = pos - db.entropyBit;
@@ -339,13 +193,13 @@ void launch_cm_encode(hipStream_t s, BlockView view, const u32* origLen, u32 cop
                                                     (u8*)nullptr, (const u64*)nullptr, 0, cm_tier1_div()); }
 }
 
-// The rare path: the caller has read the first word of ctrlMem back (with whatever else it reads back behind the encoder) and found it
-// non-zero. Reads the marks and the lengths back, asks for the second staging and codes the marked blocks again.
-int launch_cm_encode_again(hipStream_t s, BlockView view, const u32* origLen, u32 copyThreshold, int nBlocks, int maxChunks, ChunkDesc* desc,
-                           u8* tmp, u64 tmpStride, void* ctrlMem, CmBigAlloc bigAlloc, void* user)
+// What both binary coders do before their second pass: read the marks and the lengths back (the stream is synchronised), lay the marked
+// blocks out in a second staging of 32 n + 16 bytes each that bigAlloc gives, and put the offsets behind the marks. Returns the
+// number of marked blocks, -1 for a HIP error, -2 when bigAlloc failed.
+int binary_again_prepare(hipStream_t s, BlockView view, int nBlocks, void* ctrlMem, CmBigAlloc bigAlloc, void* user, u64** bigOffOut, u8** bigOut)
 {
     u32* ctrl = reinterpret_cast<u32*>(ctrlMem);
-    u64* bigOff = reinterpret_cast<u64*>(reinterpret_cast<u8*>(ctrlMem) + (4 * ((size_t)nBlocks + 1) + 7) / 8 * 8);
+    u64* bigOff = *bigOffOut = reinterpret_cast<u64*>(reinterpret_cast<u8*>(ctrlMem) + (4 * ((size_t)nBlocks + 1) + 7) / 8 * 8);
     std::vector<u32> flags((size_t)nBlocks), lens((size_t)nBlocks);
     if (hipMemcpyAsync(flags.data(), ctrl + 1, 4 * (size_t)nBlocks, hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
     if (hipMemcpyAsync(lens.data(), view.len, 4 * (size_t)nBlocks, hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
@@ -359,9 +213,22 @@ int launch_cm_encode_again(hipStream_t s, BlockView view, const u32* origLen, u3
         off[b] = total;
         total += (32ull * lens[b] + 16 + 255) & ~255ull;
     }
-    u8* big = bigAlloc ? reinterpret_cast<u8*>(bigAlloc(user, (size_t)total)) : nullptr;
+    u8* big = *bigOut = bigAlloc ? reinterpret_cast<u8*>(bigAlloc(user, (size_t)total)) : nullptr;
     if (big == nullptr) return -2;
     if (hipMemcpyAsync(bigOff, off.data(), 8 * (size_t)nBlocks, hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return -1;
+    return marked;
+}
+
+// The rare path: the caller has read the first word of ctrlMem back (with whatever else it reads back behind the encoder) and found it
+// non-zero. Reads the marks and the lengths back, asks for the second staging and codes the marked blocks again.
+int launch_cm_encode_again(hipStream_t s, BlockView view, const u32* origLen, u32 copyThreshold, int nBlocks, int maxChunks, ChunkDesc* desc,
+                           u8* tmp, u64 tmpStride, void* ctrlMem, CmBigAlloc bigAlloc, void* user)
+{
+    u32* ctrl = reinterpret_cast<u32*>(ctrlMem);
+    u64* bigOff = nullptr;
+    u8* big = nullptr;
+    const int marked = binary_again_prepare(s, view, nBlocks, ctrlMem, bigAlloc, user, &bigOff, &big);
+    if (marked < 0) return marked;
     { KScope ks_("k_cm_encode"); hipLaunchKernelGGL(k_cm_encode, dim3(nBlocks), dim3(64), 0, s, view, origLen, copyThreshold, maxChunks, desc, tmp, tmpStride, ctrl,
                                                     big, (const u64*)bigOff, 1, 0u); }
     return marked;

@@ -147,6 +147,23 @@ int launch_cm_encode_again(hipStream_t s, BlockView view, const u32* origLen, u3
                            u8* tmp, u64 tmpStride, void* ctrlMem, CmBigAlloc bigAlloc, void* user);
 void launch_cm_decode(hipStream_t s, BitSrc src, DecBlock* blocks, int nBlocks, u8* const* outPtr);
 
+int binary_again_prepare(hipStream_t s, BlockView view, int nBlocks, void* ctrlMem, CmBigAlloc bigAlloc, void* user, u64** bigOffOut, u8** bigOut);
+
+// tpaq.hip (TPAQ, entropy id 7, extra = 0; TPAQX, id 9, extra = 1). Slots, staging, ctrlMem and the second pass as CM's (cm_max_chunks,
+// cm_stage_stride, cm_ctrl_bytes). The predictor's tables live in `tables`: tpaq_table_bytes(rbsz, abszMax, extra) bytes for each of
+// tpaq_slice_blocks(that, nBlocks) blocks; rbsz is the stream's block size, abszMax the longest block (after the transforms) that the
+// batch can hold. The launchers zero the tables on the stream and run the batch in slices of that many blocks.
+struct TpaqSizes { u32 states, mixers, hash, buffer, sse0, sse1; };
+TpaqSizes tpaq_params(u32 rbsz, u32 absz, int extra);       // the format's sizes (tests: knz_hip_tpaq_params)
+u32 tpaq_states_log();                                      // 0, or the k of KNZ_TPAQ_STATES_LOG (tests)
+size_t tpaq_table_bytes(u32 rbsz, u32 abszMax, int extra);
+int tpaq_slice_blocks(size_t tableBytes, int nBlocks);      // KNZ_TPAQ_TABLES_MAX: bytes of tables in use at once (default 16 GiB)
+void launch_tpaq_encode(hipStream_t s, int extra, BlockView view, const u32* origLen, u32 copyThreshold, int nBlocks, int maxChunks, ChunkDesc* desc,
+                        u8* tmp, u64 tmpStride, void* ctrlMem, void* tables, u32 rbsz, u32 abszMax);
+int launch_tpaq_encode_again(hipStream_t s, int extra, BlockView view, const u32* origLen, u32 copyThreshold, int nBlocks, int maxChunks, ChunkDesc* desc,
+                             u8* tmp, u64 tmpStride, void* ctrlMem, CmBigAlloc bigAlloc, void* user, void* tables, u32 rbsz, u32 abszMax);
+void launch_tpaq_decode(hipStream_t s, int extra, BitSrc src, DecBlock* blocks, int nBlocks, u8* const* outPtr, void* tables, u32 rbsz, u32 abszMax);
+
 void launch_srt_forward(hipStream_t s, const XfStage& st);          // scratch: srt_scratch_u32(nBlocks, maxLen) words
 size_t srt_scratch_u32(int nBlocks, u32 maxLen);
 void launch_srt_inverse(hipStream_t s, const XfStage& st);          // scratch: srt_inverse_scratch_u32(nBlocks, maxLen) words

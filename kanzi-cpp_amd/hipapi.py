@@ -10,8 +10,9 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libknz_hip.so")
 
-E_NONE, E_HUFFMAN, E_FPAQ, E_RANGE, E_ANS0, E_CM, E_ANS1 = 0, 1, 2, 4, 5, 6, 8
-ENTROPY_IDS = {"NONE": 0, "HUFFMAN": 1, "FPAQ": 2, "RANGE": 4, "ANS0": 5, "CM": 6, "ANS1": 8}
+E_NONE, E_HUFFMAN, E_FPAQ, E_RANGE, E_ANS0, E_CM, E_TPAQ, E_ANS1, E_TPAQX = 0, 1, 2, 4, 5, 6, 7, 8, 9
+BINARY_CODERS = (E_CM, E_TPAQ, E_TPAQX)          # knz_hip_encode_bound is a first tier for these (include/knz_hip.h)
+ENTROPY_IDS = {"NONE": 0, "HUFFMAN": 1, "FPAQ": 2, "RANGE": 4, "ANS0": 5, "CM": 6, "TPAQ": 7, "ANS1": 8, "TPAQX": 9}
 TRANSFORM_IDS = {"NONE": 0, "BWT": 1, "BWTS": 2, "LZ": 3, "RLT": 5, "ZRLT": 6, "MTFT": 7, "RANK": 8, "SRT": 13, "LZP": 14, "MM": 15, "LZX": 16, "UTF": 17, "PACK": 18, "TIMESTAMP": 64}
 
 SYMBOLS = [
@@ -21,6 +22,7 @@ SYMBOLS = [
     "knz_hip_memcpy_h2d", "knz_hip_memcpy_d2h", "knz_hip_sync", "knz_hip_memcpy_h2d_async", "knz_hip_memcpy_d2h_async", "knz_hip_copy_wait", "knz_hip_host_alloc", "knz_hip_host_free", "knz_hip_set_profiling", "knz_hip_get_kernel_times",
     "knz_hip_tune", "knz_hip_transform_supported", "knz_hip_shift_bits", "knz_hip_encode_block_hosted", "knz_hip_decode_block_hosted",
     "knz_hip_entropy_decode_v", "knz_hip_transform_inverse_v", "knz_hip_range_divide",
+    "knz_hip_entropy_encode_bs", "knz_hip_entropy_decode_bs", "knz_hip_tpaq_params",
 ]
 
 
@@ -97,6 +99,10 @@ def lib():
         L.knz_hip_tune.argtypes = [C.c_char_p, C.c_int]
         L.knz_hip_shift_bits.argtypes = [vp, u8p, C.c_uint64, C.c_uint32, u8p]
         L.knz_hip_range_divide.argtypes = [vp, vp, vp, C.c_uint32, vp]
+        L.knz_hip_entropy_encode_bs.argtypes = [vp, C.c_int, C.c_uint32, C.c_char_p, C.c_uint32, u8p, sz, C.POINTER(C.c_uint64)]
+        L.knz_hip_entropy_decode_bs.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, C.c_char_p, C.c_uint64, C.c_uint64, u8p, C.c_uint32,
+                                                C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
+        L.knz_hip_tpaq_params.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint32)]
         _lib = L
     return _lib
 
@@ -175,22 +181,24 @@ class Context:
         return ob.value, eb.value, nb.value
 
     # ---- per-stage API on host buffers
-    def entropy_encode(self, entropy, data):
+    def entropy_encode(self, entropy, data, stream_block_size=0):
+        """stream_block_size: the block size of the stream the buffer belongs to (TPAQ and TPAQX size their tables by it); 0 = the
+        buffer's own length."""
         e = ENTROPY_IDS[entropy.upper()]
-        # (RANGE: up to 28 bits per byte and a bit; CM: the format's ceiling of 32 bytes per byte -- knz_hip_encode_bound)
-        cap = (34 if e == E_CM else 4 if e == E_RANGE else 2) * len(data) + 65536
+        # (RANGE: up to 28 bits per byte and a bit; CM, TPAQ, TPAQX: the format's ceiling of 32 bytes per byte -- knz_hip_encode_bound)
+        cap = (34 if e in BINARY_CODERS else 4 if e == E_RANGE else 2) * len(data) + 65536
         out = (C.c_uint8 * cap)()
         bits = C.c_uint64(0)
-        self._chk(self.L.knz_hip_entropy_encode(self.h, e, data, len(data), out, cap, C.byref(bits)))
+        self._chk(self.L.knz_hip_entropy_encode_bs(self.h, e, stream_block_size, data, len(data), out, cap, C.byref(bits)))
         return C.string_at(out, (bits.value + 7) // 8), bits.value
 
-    def entropy_decode(self, entropy, enc, n, start_bit=0, in_bits=None, bs_version=0):
+    def entropy_decode(self, entropy, enc, n, start_bit=0, in_bits=None, bs_version=0, stream_block_size=0):
         e = ENTROPY_IDS[entropy.upper()]
         out = (C.c_uint8 * max(1, n))()
         dec, used = C.c_int32(0), C.c_uint64(0)
         if in_bits is None:
             in_bits = 8 * len(enc)
-        self._chk(self.L.knz_hip_entropy_decode_v(self.h, e, bs_version, enc, in_bits, start_bit, out, n, C.byref(dec), C.byref(used)))
+        self._chk(self.L.knz_hip_entropy_decode_bs(self.h, e, bs_version, stream_block_size, enc, in_bits, start_bit, out, n, C.byref(dec), C.byref(used)))
         return dec.value, C.string_at(out, n), used.value
 
     def transform_forward(self, transform, data, dst_cap, entropy=None):
@@ -233,3 +241,13 @@ class Context:
         arr = (KernelTime * 256)()
         n = self.L.knz_hip_get_kernel_times(self.h, arr, 256)
         return [(arr[i].name.decode(), arr[i].ms, arr[i].launches) for i in range(n)]
+
+
+def tpaq_params(stream_block_size, block_len, extra):
+    """(states bytes, mixers, hash words, buffer bytes, contexts of the first and of the second SSE map) of the TPAQ (extra 0) / TPAQX
+    (extra 1) predictor: the library's own restatement of the format's sizing, for tests. Needs no device."""
+    out = (C.c_uint32 * 6)()
+    rc = lib().knz_hip_tpaq_params(stream_block_size, block_len, extra, out)
+    if rc != 0:
+        raise KnzError(rc, "knz_hip_tpaq_params")
+    return tuple(out)

@@ -11,7 +11,7 @@ enum { DT_UNDEFINED = 0, DT_TEXT, DT_MULTIMEDIA, DT_EXE, DT_NUMERIC, DT_BASE64, 
 uint32_t magicOf(const uint8_t* p);                        // Magic::getType: 4 readable bytes
 int presetDataType(const uint8_t* block, int n);          // io/CompressedOutputStream.cpp:724-733
 
-// variant 1 / 2 = TextCodec1 / TextCodec2. forward: false = the stage is skipped (the block goes on unchanged), *dataType is updated either way.
+// variant 1 / 2 = TextCodec1 / TextCodec2; 3 = TextCodec1 with the hash map doubled (entropy coder TPAQX, TextCodec.cpp:539). forward: false = the stage is skipped (the block goes on unchanged), *dataType is updated either way.
 // blockSize is the STREAM's block size (it sizes the hash map, hence decides which words collide), not the block's length.
 bool textForward(int variant, const uint8_t* src, int count, uint8_t* dst, int dstCap, int blockSize, int bsVersion, int* dataType, int* outLen);
 bool textInverse(int variant, const uint8_t* src, int count, uint8_t* dst, int dstCap, int blockSize, int bsVersion, int* outLen);

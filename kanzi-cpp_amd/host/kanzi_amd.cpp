@@ -695,6 +695,7 @@ template class TransformSequence<byte>;
 TextCodec::TextCodec(Context& ctx) : _ctx(&ctx)
 {
     _variant = ctx.getInt("textcodec", 1);
+    if (_variant == 1 && ctx.has("entropy") && ctx.getString("entropy") == "TPAQX") _variant = 3;       // TextCodec.cpp:539
     _blockSize = ctx.getInt("blockSize", 0);
     _bsVersion = ctx.getInt("bsVersion", 6);
 }
@@ -844,7 +845,7 @@ static uint64 hostChecksum(const uint8_t* d, int length, int bits)
     return h ^ (h >> 32);
 }
 
-static int textVariantOfEntropy(int etype) { return (etype == 0 || etype == 1 || etype == 4 || etype == 5) ? 2 : 1; }      // NONE, HUFFMAN, RANGE, ANS0
+static int textVariantOfEntropy(int etype) { return (etype == 0 || etype == 1 || etype == 4 || etype == 5) ? 2 : etype == 9 ? 3 : 1; }      // NONE, HUFFMAN, RANGE, ANS0; TPAQX (host_stages.hpp)
 
 // the host stages of one block, in chain order: data ends up in `a` or `b`; returns the buffer that holds it
 struct HostedResult { const uint8_t* data; int len; uint32_t applied; int dataType; };
@@ -971,6 +972,26 @@ template class TransformFactory<byte>;
 // ------------------------------------------------------------------------------------------------
 // entropy codecs
 // ------------------------------------------------------------------------------------------------
+static bool isBinaryCoder(int type) { return type == KNZ_E_CM || type == KNZ_E_TPAQ || type == KNZ_E_TPAQX; }
+
+// The per-stage calls that carry the stream's block size are bound weakly: a device library from before they existed (such as the CPU
+// stand-in the host layer is tested against) lacks them. Only TPAQ and TPAQX read the block size, and such a library has neither.
+#pragma weak knz_hip_entropy_encode_bs
+#pragma weak knz_hip_entropy_decode_bs
+static int entropyEncodeBs(knz_ctx* c, int type, uint32_t sbs, const uint8_t* in, uint32_t n, uint8_t* out, size_t cap, uint64_t* bits)
+{
+    if (knz_hip_entropy_encode_bs != nullptr) return knz_hip_entropy_encode_bs(c, type, sbs, in, n, out, cap, bits);
+    if (type == KNZ_E_TPAQ || type == KNZ_E_TPAQX) throw std::invalid_argument("this device library has no TPAQ / TPAQX coder");
+    return knz_hip_entropy_encode(c, type, in, n, out, cap, bits);
+}
+static int entropyDecodeBs(knz_ctx* c, int type, int ver, uint32_t sbs, const uint8_t* in, uint64_t inBits, uint64_t startBit, uint8_t* out, uint32_t n,
+                           int32_t* decoded, uint64_t* used)
+{
+    if (knz_hip_entropy_decode_bs != nullptr) return knz_hip_entropy_decode_bs(c, type, ver, sbs, in, inBits, startBit, out, n, decoded, used);
+    if (type == KNZ_E_TPAQ || type == KNZ_E_TPAQX) throw std::invalid_argument("this device library has no TPAQ / TPAQX coder");
+    return knz_hip_entropy_decode_v(c, type, ver, in, inBits, startBit, out, n, decoded, used);
+}
+
 int DeviceEntropyEncoder::encode(const byte block[], uint blkptr, uint len)
 {
     if (len == 0) return 0;
@@ -979,14 +1000,15 @@ int DeviceEntropyEncoder::encode(const byte block[], uint blkptr, uint len)
     memset(&p, 0, sizeof(p));
     p.entropy_type = _type;
     p.block_size = int32_t((len + 15) & ~15u);
+    if (_size >= 0 && uint(_size) != len) throw std::invalid_argument("TPAQ: the device sizes the predictor by the length it is given, which differs from the Context's \"size\"");
     const size_t cap = knz_hip_encode_bound(&p, len) + 64;
     std::vector<byte> out(cap);
     uint64_t bits = 0;
-    int rc = knz_hip_entropy_encode(c, _type, &block[blkptr], len, out.data(), cap, &bits);
-    if (rc == KNZ_ERR_WRITE_FILE && _type == KNZ_E_CM) {
-        // CM's bound is a first tier (include/knz_hip.h); the second holds whatever the format can write
+    int rc = entropyEncodeBs(c, _type, uint32_t(_streamBlockSize), &block[blkptr], len, out.data(), cap, &bits);
+    if (rc == KNZ_ERR_WRITE_FILE && isBinaryCoder(_type)) {
+        // the bound of CM, TPAQ and TPAQX is a first tier (include/knz_hip.h); the second holds whatever the format can write
         out.resize(cap + 32 * size_t(len));
-        rc = knz_hip_entropy_encode(c, _type, &block[blkptr], len, out.data(), out.size(), &bits);
+        rc = entropyEncodeBs(c, _type, uint32_t(_streamBlockSize), &block[blkptr], len, out.data(), out.size(), &bits);
     }
     devCheck(c, rc, "entropy encode");
     uint64 done = 0;
@@ -1002,6 +1024,8 @@ int DeviceEntropyDecoder::decode(byte block[], uint blkptr, uint len)
 {
     if (len == 0) return 0;
     knz_ctx* c = deviceContext();
+    if (_size >= 0 && uint(_size) != len) throw std::invalid_argument("TPAQ: the device sizes the predictor by the length it is given, which differs from the Context's \"size\"");
+    const uint32_t sbs = uint32_t(_streamBlockSize);
     int32_t decoded = 0;
     uint64_t used = 0;
     const int ver = (_bsVersion == 0) ? 1 : _bsVersion;     // a declared version 0 is an old layout (knz_params.bs_version: 0 = unset)
@@ -1013,10 +1037,10 @@ int DeviceEntropyDecoder::decode(byte block[], uint blkptr, uint len)
         const uint64 bound = 8 * (2ull * len + (uint64(len) / 16384 + 2) * 640 + (_type == KNZ_E_ANS1 ? (uint64(len) / (4u << 20) + 1) * 256 * 576 : 0) + 4096);
         const byte* data; uint64 startBit, endBit;
         dibs->peekAhead(bound, &data, &startBit, &endBit);
-        devCheck(c, knz_hip_entropy_decode_v(c, _type, ver, data, endBit, startBit, &block[blkptr], len, &decoded, &used), "entropy decode");
+        devCheck(c, entropyDecodeBs(c, _type, ver, sbs, data, endBit, startBit, &block[blkptr], len, &decoded, &used), "entropy decode");
         if (decoded != int32_t(len) && endBit - startBit >= bound) {
             dibs->peekRemaining(&data, &startBit, &endBit);
-            devCheck(c, knz_hip_entropy_decode_v(c, _type, ver, data, endBit, startBit, &block[blkptr], len, &decoded, &used), "entropy decode");
+            devCheck(c, entropyDecodeBs(c, _type, ver, sbs, data, endBit, startBit, &block[blkptr], len, &decoded, &used), "entropy decode");
         }
         if (decoded == int32_t(len)) dibs->skip(used);
         return int(decoded);
@@ -1025,7 +1049,7 @@ int DeviceEntropyDecoder::decode(byte block[], uint blkptr, uint len)
     // only ONE decode() per stream is possible through such an object; DefaultInputBitStream has no such limit
     std::vector<byte> rest;
     try { while (_ibs.hasMoreToRead()) rest.push_back(byte(_ibs.readBits(8))); } catch (const BitStreamException&) {}
-    devCheck(c, knz_hip_entropy_decode_v(c, _type, ver, rest.data(), uint64(rest.size()) * 8, 0, &block[blkptr], len, &decoded, &used), "entropy decode");
+    devCheck(c, entropyDecodeBs(c, _type, ver, sbs, rest.data(), uint64(rest.size()) * 8, 0, &block[blkptr], len, &decoded, &used), "entropy decode");
     return int(decoded);
 }
 
@@ -1117,18 +1141,48 @@ void CMPredictor::update(int bit)
     }
 }
 
-static Predictor* checkPredictor(Predictor* predictor)
+// entropy/TPAQPredictor.hpp:297-343
+template <bool T>
+TPAQPredictor<T>::TPAQPredictor(Context* pCtx) : _blockSize(0), _size(0)
+{
+    if (pCtx == nullptr) throw std::invalid_argument("TPAQ predictor: without a Context the reference builds the predictor of bitstream version 7, which has no device kernel");
+    if (pCtx->getInt("bsVersion", 7) >= 7) throw std::invalid_argument("TPAQ predictor: the predictor of bitstream version 7 and up has no device kernel");
+    _blockSize = pCtx->getInt("blockSize", 32768);
+    _size = pCtx->getInt("size", _blockSize);
+    if (_blockSize < 1 || _blockSize > (1 << 30) || _size < 0) throw std::invalid_argument("TPAQ predictor: invalid block size or size");
+}
+template <bool T> void TPAQPredictor<T>::update(int) { throw std::logic_error("TPAQ predictor: the tables live on the device; use it through BinaryEntropyEncoder / BinaryEntropyDecoder"); }
+template <bool T> int TPAQPredictor<T>::get() { throw std::logic_error("TPAQ predictor: the tables live on the device; use it through BinaryEntropyEncoder / BinaryEntropyDecoder"); }
+template class TPAQPredictor<false>;
+template class TPAQPredictor<true>;
+
+// the entropy id behind a predictor; *blockSize and *size for the predictors that are sized by their Context (-1: not sized)
+static int checkPredictor(Predictor* predictor, int* blockSize, int* size)
 {
     if (predictor == nullptr) throw std::invalid_argument("Invalid null predictor parameter");
-    if (dynamic_cast<CMPredictor*>(predictor) == nullptr) throw std::invalid_argument("Binary entropy codec: only the CM predictor has a device kernel");
-    return predictor;
+    *blockSize = 0; *size = -1;
+    if (dynamic_cast<CMPredictor*>(predictor) != nullptr) return KNZ_E_CM;
+    if (TPAQPredictor<false>* t = dynamic_cast<TPAQPredictor<false>*>(predictor)) { *blockSize = t->blockSize(); *size = t->size(); return KNZ_E_TPAQ; }
+    if (TPAQPredictor<true>* t = dynamic_cast<TPAQPredictor<true>*>(predictor)) { *blockSize = t->blockSize(); *size = t->size(); return KNZ_E_TPAQX; }
+    throw std::invalid_argument("Binary entropy codec: only the CM, TPAQ and TPAQX predictors have a device kernel");
 }
+static int predictorType(Predictor* predictor) { int a, b; return checkPredictor(predictor, &a, &b); }
 
 BinaryEntropyEncoder::BinaryEntropyEncoder(OutputBitStream& obs, Predictor* predictor, bool deallocate)
-    : DeviceEntropyEncoder(obs, KNZ_E_CM), _predictor(checkPredictor(predictor)), _deallocate(deallocate) {}
+    : DeviceEntropyEncoder(obs, predictorType(predictor)), _predictor(predictor), _deallocate(deallocate)
+{
+    int bs, size;
+    checkPredictor(predictor, &bs, &size);
+    setSizes(bs, size);
+}
 
 BinaryEntropyDecoder::BinaryEntropyDecoder(InputBitStream& ibs, Predictor* predictor, bool deallocate)
-    : DeviceEntropyDecoder(ibs, KNZ_E_CM), _predictor(checkPredictor(predictor)), _deallocate(deallocate) {}
+    : DeviceEntropyDecoder(ibs, predictorType(predictor)), _predictor(predictor), _deallocate(deallocate)
+{
+    int bs, size;
+    checkPredictor(predictor, &bs, &size);
+    setSizes(bs, size);
+}
 
 static const struct { const char* name; short type; } ENAMES[] = {
     {"NONE", 0}, {"HUFFMAN", 1}, {"FPAQ", 2}, {"RANGE", 4}, {"ANS0", 5}, {"CM", 6}, {"TPAQ", 7}, {"ANS1", 8}, {"TPAQX", 9} };
@@ -1156,6 +1210,8 @@ EntropyEncoder* EntropyEncoderFactory::newEncoder(OutputBitStream& obs, Context&
     case FPAQ_TYPE: return new FPAQEncoder(obs);
     case RANGE_TYPE: return new RangeEncoder(obs);
     case CM_TYPE: return new BinaryEntropyEncoder(obs, new CMPredictor(&ctx));           // EntropyEncoderFactory.hpp:81
+    case TPAQ_TYPE: return new BinaryEntropyEncoder(obs, new TPAQPredictor<false>(&ctx));      // :84
+    case TPAQX_TYPE: return new BinaryEntropyEncoder(obs, new TPAQPredictor<true>(&ctx));      // :87
     case NONE_TYPE: return new NullEntropyEncoder(obs);
     default: throw std::invalid_argument(std::string("Entropy codec '") + getName(entropyType) + "' has no device kernel");
     }
@@ -1170,6 +1226,8 @@ EntropyDecoder* EntropyDecoderFactory::newDecoder(InputBitStream& ibs, Context& 
     case EntropyEncoderFactory::FPAQ_TYPE: return new FPAQDecoder(ibs);
     case EntropyEncoderFactory::RANGE_TYPE: return new RangeDecoder(ibs);
     case EntropyEncoderFactory::CM_TYPE: return new BinaryEntropyDecoder(ibs, new CMPredictor(&ctx));      // EntropyDecoderFactory.hpp:83
+    case EntropyEncoderFactory::TPAQ_TYPE: return new BinaryEntropyDecoder(ibs, new TPAQPredictor<false>(&ctx));
+    case EntropyEncoderFactory::TPAQX_TYPE: return new BinaryEntropyDecoder(ibs, new TPAQPredictor<true>(&ctx));
     case EntropyEncoderFactory::NONE_TYPE: return new NullEntropyDecoder(ibs);
     default: throw std::invalid_argument(std::string("Entropy codec '") + getName(entropyType) + "' has no device kernel");
     }
@@ -1658,10 +1716,10 @@ void CompressedOutputStream::submit(Lane& ln)
     std::unique_ptr<GateHold> gateOwner(gate);
     std::chrono::steady_clock::time_point tk0 = std::chrono::steady_clock::now();
     if (_hosted && n == 0) p.transform_type = 0;             // (the empty last batch: end marker only; the device call checks the chain before it looks at the size)
-    // CM: knz_hip_encode_bound is a first tier (include/knz_hip.h); a batch that does not fit it is encoded once more into the second
+    // CM, TPAQ, TPAQX: knz_hip_encode_bound is a first tier (include/knz_hip.h); a batch that does not fit it is encoded once more into the second
     auto secondTier = [&](const std::function<int()>& call) -> int {
         int rc = call();
-        if (rc == KNZ_ERR_WRITE_FILE && _entropyType == KNZ_E_CM) {
+        if (rc == KNZ_ERR_WRITE_FILE && isBinaryCoder(_entropyType)) {
             const size_t cap2 = cap + 32 * n;
             g_devPool.put(c, ln.dOut, ln.dOutCap); ln.dOut = nullptr; ln.dOutCap = 0; ln.dOut = g_devPool.get(c, cap2, &ln.dOutCap);
             rc = call();

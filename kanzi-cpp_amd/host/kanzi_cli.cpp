@@ -4,12 +4,13 @@
 //   kanzi_amd_cli -c -i FILE [-o FILE.knz] [-t TRANSFORMS] [-e ENTROPY] [-l LEVEL] [-b SIZE] [-j JOBS] [-x | -x32 | -x64] [-f]
 //   kanzi_amd_cli -d -i FILE.knz [-o FILE] [-j JOBS] [--from=N] [--to=N] [-f]
 //
-// -e takes NONE, HUFFMAN, ANS0, ANS1, FPAQ, RANGE and CM. Levels 0, 1, 5 and 6 are in (5 and 6: TEXT on the host in front of the device chain, host/text_codec.cpp; UTF behind it runs on the device).
+// -e takes NONE, HUFFMAN, ANS0, ANS1, FPAQ, RANGE, CM, TPAQ and TPAQX (every entropy coder of the reference). Levels 0, 1, 5 and 6 are in (5 and 6: TEXT on the host in front of the device chain, host/text_codec.cpp; UTF behind it runs on the device).
 // What it does not do (and says so instead of guessing): directories, stdin/stdout, `-y` info, levels whose chains need the
-// reference's CPU-only transforms (EXE, DNA, ROLZ) or entropy coders (TPAQ, TPAQX), or LZ / LZX behind PACK or MM (the device LZ
+// reference's CPU-only transforms (EXE, DNA, ROLZ), or LZ / LZX behind PACK or MM (the device LZ
 // stages do not read the data type those leave, which level 3 needs): levels 2-4 and 7-9. PACK, MM, LZP and UTF themselves run on the
 // device (-t, in any position behind the host stage: -t LZP+UTF+BWT+RANK+ZRLT works); level 7 (LZP+TEXT+UTF+BWT+LZP / CM) has LZP, UTF, BWT
-// and CM on the device and waits for one thing only: TEXT, the last host stage, behind a device stage.
+// and CM on the device and waits for one thing only: TEXT, the last host stage, behind a device stage. Levels 8 and 9 (TPAQ / TPAQX,
+// which run on the device) wait for EXE and DNA.
 // Files written here are byte-identical to `kanzi -c` with the same -t/-e/-b/-x/-j, and either tool reads the other's files
 // (tests/test_host_stub.py, tests/test_gpu_host_api.py).
 #include <cstdio>
@@ -85,7 +86,7 @@ int main(int argc, char** argv)
         else if (level == 1) { transform = "LZX"; entropy = "NONE"; }
         else if (level == 5) { transform = "TEXT+UTF+BWT+RANK+ZRLT"; entropy = "ANS0"; }      // TEXT runs on the host, the rest on the device
         else if (level == 6) { transform = "TEXT+UTF+BWT+SRT+ZRLT"; entropy = "FPAQ"; if (!blockGiven) block = 8 << 20; }      // (BlockCompressor.cpp:121-124: 8 MiB blocks by default)
-        else { fprintf(stderr, "level %d needs transforms or entropy coders that only exist in the CPU reference (EXE/DNA/ROLZ, CM/TPAQ), LZX behind PACK / MM (level 3) or TEXT behind LZP (level 7); use -t/-e\n", level); return Error::ERR_INVALID_CODEC; }
+        else { fprintf(stderr, "level %d needs transforms that only exist in the CPU reference (EXE/DNA/ROLZ: levels 2, 4, 8, 9), LZX behind PACK / MM (level 3) or TEXT behind LZP (level 7); use -t/-e\n", level); return Error::ERR_INVALID_CODEC; }
     }
     if (transform.empty()) transform = "NONE";
     if (entropy.empty()) entropy = "NONE";

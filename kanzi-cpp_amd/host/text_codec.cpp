@@ -313,7 +313,7 @@ struct Enc2 {
 };
 
 template <class E>
-static bool wordsForward(const uint8_t* src, int count, uint8_t* dst, int dstCap, int blockSize, int& dataType, int& outLen)
+static bool wordsForward(const uint8_t* src, int count, uint8_t* dst, int dstCap, int blockSize, int& dataType, int& outLen, int extraLog = 0)
 {
     outLen = 0;
     if (dstCap < count) return false;
@@ -321,7 +321,7 @@ static bool wordsForward(const uint8_t* src, int count, uint8_t* dst, int dstCap
     const uint8_t flags = blockFlags(src, count, E::strict);
     if (flags & F_NOT_TEXT) { dataType = flags & F_TYPE; return false; }
     dataType = DT_TEXT;
-    Dictionary dict(E::logSlots(blockSize), count, E::escapes);
+    Dictionary dict(E::logSlots(blockSize) + extraLog, count, E::escapes);
     const int8_t* cls = charClasses();
     const int end = count, room = count, roomRef = room - E::slack();
     const bool crlf = (flags & F_CRLF) != 0;
@@ -380,11 +380,11 @@ static bool wordsForward(const uint8_t* src, int count, uint8_t* dst, int dstCap
 }
 
 template <class E>
-static bool wordsInverse(const uint8_t* src, int count, uint8_t* dst, int dstCap, int blockSize, int bsVersion, int& outLen)
+static bool wordsInverse(const uint8_t* src, int count, uint8_t* dst, int dstCap, int blockSize, int bsVersion, int& outLen, int extraLog = 0)
 {
     outLen = 0;
     if (count < 2) return false;
-    Dictionary dict(E::logSlots(blockSize), dstCap, E::escapes);
+    Dictionary dict(E::logSlots(blockSize) + extraLog, dstCap, E::escapes);
     const int8_t* cls = charClasses();
     const bool crlf = (src[0] & F_CRLF) != 0;
     const bool oldIndexes = !E::escapes && bsVersion < 6;
@@ -492,9 +492,11 @@ bool textForward(int variant, const uint8_t* src, int count, uint8_t* dst, int d
     *outLen = 0;
     if (count == 0) return true;
     if (count < 1024 || count > (1 << 30)) return false;
-    const bool ok = (variant == 1) ? wordsForward<Enc1>(src, count, dst, dstCap, blockSize, *dataType, *outLen)
-                                   : wordsForward<Enc2>(src, count, dst, dstCap, blockSize, *dataType, *outLen);
-    if (ok && bsVersion >= 7) { if (variant == 1) dst[0] &= uint8_t(~F_CODEC2); else dst[0] |= F_CODEC2; }
+    // (variant 3: TextCodec1 with the hash map doubled, which the reference builds when the entropy coder is TPAQX, TextCodec.cpp:539)
+    const bool one = variant == 1 || variant == 3;
+    const bool ok = one ? wordsForward<Enc1>(src, count, dst, dstCap, blockSize, *dataType, *outLen, variant == 3 ? 1 : 0)
+                        : wordsForward<Enc2>(src, count, dst, dstCap, blockSize, *dataType, *outLen);
+    if (ok && bsVersion >= 7) { if (one) dst[0] &= uint8_t(~F_CODEC2); else dst[0] |= F_CODEC2; }
     return ok;
 }
 
@@ -503,16 +505,16 @@ bool textInverse(int variant, const uint8_t* src, int count, uint8_t* dst, int d
     *outLen = 0;
     if (count == 0) return true;
     if (count > (1 << 30) || count < 2) return false;
-    if (bsVersion >= 7) variant = (src[0] & F_CODEC2) ? 2 : 1;
-    return (variant == 1) ? wordsInverse<Enc1>(src, count, dst, dstCap, blockSize, bsVersion, *outLen)
-                          : wordsInverse<Enc2>(src, count, dst, dstCap, blockSize, bsVersion, *outLen);
+    if (bsVersion >= 7) variant = (src[0] & F_CODEC2) ? 2 : (variant == 3 ? 3 : 1);
+    return (variant == 1 || variant == 3) ? wordsInverse<Enc1>(src, count, dst, dstCap, blockSize, bsVersion, *outLen, variant == 3 ? 1 : 0)
+                                          : wordsInverse<Enc2>(src, count, dst, dstCap, blockSize, bsVersion, *outLen);
 }
 
 int textVariantFor(const char* entropy)
 {
     std::string e(entropy ? entropy : "");
     for (char& ch : e) ch = char(toupper(ch));
-    return (e == "NONE" || e == "ANS0" || e == "HUFFMAN" || e == "RANGE") ? 2 : 1;
+    return (e == "NONE" || e == "ANS0" || e == "HUFFMAN" || e == "RANGE") ? 2 : e == "TPAQX" ? 3 : 1;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -90,8 +90,8 @@ class DeviceRunEncoder:
             bits = ctx.encode_blocks(self.p, d_in, len(data), d_out, cap, prologue=hdr, prologue_bits=hb, first_block=first_block,
                                      finish=1 if finish else 0)
         except hipapi.KnzError as e:
-            # CM: knz_hip_encode_bound is a first tier (include/knz_hip.h); the second holds whatever the format can write
-            if e.code != 12 or self.p.entropy_type != hipapi.E_CM:
+            # CM, TPAQ, TPAQX: knz_hip_encode_bound is a first tier (include/knz_hip.h); the second holds whatever the format can write
+            if e.code != 12 or self.p.entropy_type not in hipapi.BINARY_CODERS:
                 raise
             cap += 32 * len(data)
             d_out = self.bufs.get("out", cap)
