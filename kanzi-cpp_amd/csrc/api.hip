@@ -613,6 +613,13 @@ static const XfInfo XF[] = {
       .fwd = { .wsBytes = utf_scratch_bytes, .launch = [](const StageCall& k) { launch_utf_forward(k.s, k.st, k.ws); return 0; } },
       .inv = { .wsBytes = utf_scratch_bytes, .launch = [](const StageCall& k) { launch_utf_inverse(k.s, k.st, k.ws); return 0; } },
       .setsType = true },
+    // (ROLZCodec2; it reads the data type -- EXE and DNA change its key and its minimum match -- and writes detectSimpleType's verdict
+    // where it found none, which RLT behind it reads. About 8.3 MiB of tables per block that runs at once, per lane like LZP's, so the
+    // inverse runs in decode lanes. ROLZ proper, id 11, codes its streams with ANS coders of its own and has no kernel)
+    { .id = KNZ_T_ROLZX, .ws = "rolzxScratch",
+      .fwd = { .wsBytes = rolzx_scratch_bytes, .launch = [](const StageCall& k) { launch_rolzx_forward(k.s, k.st, k.ws); return 0; } },
+      .inv = { .wsBytes = rolzx_scratch_bytes, .launch = [](const StageCall& k) { launch_rolzx_inverse(k.s, k.st, k.ws); return 0; } },
+      .setsType = true },
 };
 
 static const XfInfo* xf_info(int t) { for (const XfInfo& x : XF) if (x.id == t) return &x; return nullptr; }

@@ -75,7 +75,7 @@ struct XfStage {
     u32 capModel = 0;        // inverse: the capacity of the reference's buffer where cap[] is smaller (the last inverse stage of a stream writes
                              // into the caller's buffer, one block size per block, while the reference decodes into a buffer with slack):
                              // UTF, whose verdict depends on the capacity, judges by max(cap, capModel) and writes within cap. 0: cap[] is all
-    u8* dtype = nullptr;     // per-block Global::DataType (0 = UNDEFINED) read and written by PACK, MM and UTF; nullptr: a fresh context per block
+    u8* dtype = nullptr;     // per-block Global::DataType (0 = UNDEFINED) read and written by PACK, MM, UTF and ROLZX; nullptr: a fresh context per block
 };
 
 // zrlt_mtft.hip
@@ -115,6 +115,13 @@ size_t mm_scratch_bytes(int nBlocks, u32 maxLen);
 void launch_lzp_forward(hipStream_t s, const XfStage& st, void* scratch);
 void launch_lzp_inverse(hipStream_t s, const XfStage& st, void* scratch);
 size_t lzp_scratch_bytes(int nBlocks, u32 maxLen);
+
+// rolzx.hip (ROLZCodec2; scratch: rolzx_scratch_bytes(nBlocks, maxLen) bytes, about 8.3 MiB of tables for each block that runs at once,
+// bounded by KNZ_ROLZX_TABLES_MAX: the launchers run a larger batch in slices and the kernels clear the tables; reads XfStage::dtype
+// and writes detectSimpleType's verdict like PACK; no host synchronisation)
+void launch_rolzx_forward(hipStream_t s, const XfStage& st, void* scratch);
+void launch_rolzx_inverse(hipStream_t s, const XfStage& st, void* scratch);
+size_t rolzx_scratch_bytes(int nBlocks, u32 maxLen);
 
 // utf.hip (UTFCodec; scratch: utf_scratch_bytes(nBlocks, maxLen) bytes, about 1.8 MiB per block plus len / 4; reads and writes
 // XfStage::dtype like PACK; no host synchronisation)

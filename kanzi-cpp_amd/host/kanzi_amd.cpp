@@ -530,6 +530,39 @@ static int lzTypeFromContext(Context& ctx)
 
 LZCodec::LZCodec(Context& ctx) : DeviceTransform(lzTypeFromContext(ctx), &ctx) {}
 
+// ROLZCodec.cpp:40-50
+static int rolzTypeFromContext(Context* ctx)
+{
+    if (ctx == nullptr || ctx->getString("transform", "NONE").find("ROLZX") == std::string::npos)
+        throw std::invalid_argument("ROLZ has no device kernel (only ROLZX, which a chain has to name, runs on the device)");
+    return KNZ_T_ROLZX;
+}
+
+ROLZCodec::ROLZCodec(uint) : DeviceTransform(rolzTypeFromContext(nullptr), nullptr), _ctx(nullptr) {}
+
+ROLZCodec::ROLZCodec(Context& ctx) : DeviceTransform(rolzTypeFromContext(&ctx), &ctx), _ctx(&ctx) {}
+
+bool ROLZCodec::forward(SliceArray<byte>& src, SliceArray<byte>& dst, int length)
+{
+    if (length == 0) return true;
+    if (!SliceArray<byte>::isValid(src)) throw std::invalid_argument("ROLZ codec: Invalid input block");
+    if (!SliceArray<byte>::isValid(dst)) throw std::invalid_argument("ROLZ codec: Invalid output block");
+    if ((length < 0) || (length > src._length - src._index)) return false;
+    if (src._array == dst._array) return false;
+    if (&knz_hip_transform_forward_dt == nullptr) throw std::runtime_error("the device library has no ROLZX stage");
+    int32_t dt = _ctx->getInt("dataType", hoststage::DT_UNDEFINED);
+    if (dt < 0 || dt > 9) dt = hoststage::DT_UNDEFINED;
+    knz_ctx* c = deviceContext();
+    int32_t outLen = 0, ok = 0;
+    devCheck(c, knz_hip_transform_forward_dt(c, _type, src._array + src._index, length, dst._array + dst._index,
+                                             dst._length - dst._index, _entropy, &dt, &outLen, &ok), "transform forward");
+    if (dt != hoststage::DT_UNDEFINED) _ctx->putInt("dataType", dt);          // ROLZCodec.cpp:935-936
+    if (!ok) return false;
+    src._index += length;
+    dst._index += outLen;
+    return true;
+}
+
 static int sbrtType(int mode)
 {
     if ((mode != SBRT::MODE_MTF) && (mode != SBRT::MODE_RANK) && (mode != SBRT::MODE_TIMESTAMP)) throw std::invalid_argument("Invalid mode parameter");
@@ -756,14 +789,14 @@ bool UTFCodec::inverse(SliceArray<byte>& src, SliceArray<byte>& dst, int length)
 
 // Chains the device runs far faster than one host thread copies memory (entropy coders alone, the byte transforms: tens of GB/s):
 // the staging copies of such a stream are spread over the helper threads. With a sorting or matching stage in the chain (BWT, LZ,
-// LZX, LZP; SRT / RANK are chains per block) the device is what a batch waits for and the extra threads only got in the way (measured,
+// LZX, LZP, ROLZX; SRT / RANK are chains per block) the device is what a batch waits for and the extra threads only got in the way (measured,
 // config 3 end to end: 2.94-3.14 GB/s with the copies on the caller's thread, 2.72-2.94 with four threads; config 2: 3.1 -> 3.9).
 // TEXT runs on the host; UTF on the device is a dozen passes over the block and a sort, nothing one thread's copies keep up with.
 static bool chainIsHostBound(uint64 ttype)
 {
     for (int i = 0; i < 8; i++) {
         const int t = int((ttype >> (42 - 6 * i)) & 63);
-        if (t == KNZ_T_BWT || t == KNZ_T_BWTS || t == KNZ_T_LZ || t == KNZ_T_LZX || t == KNZ_T_LZP || t == KNZ_T_SRT || t == KNZ_T_RANK || t == KNZ_T_TEXT || t == KNZ_T_UTF) return false;
+        if (t == KNZ_T_BWT || t == KNZ_T_BWTS || t == KNZ_T_LZ || t == KNZ_T_LZX || t == KNZ_T_LZP || t == KNZ_T_ROLZX || t == KNZ_T_SRT || t == KNZ_T_RANK || t == KNZ_T_TEXT || t == KNZ_T_UTF) return false;
     }
     return true;
 }
@@ -948,6 +981,8 @@ TransformSequence<T>* TransformFactory<T>::newTransform(Context& ctx, uint64 fun
             case LZ_TYPE: ctx.putInt("lz", LZ_TYPE); transforms[nbtr++] = new LZCodec(ctx); break;
             case LZX_TYPE: ctx.putInt("lz", LZX_TYPE); transforms[nbtr++] = new LZCodec(ctx); break;
             case LZP_TYPE: ctx.putInt("lz", LZP_TYPE); transforms[nbtr++] = new LZCodec(ctx); break;
+            case ROLZX_TYPE: transforms[nbtr++] = new ROLZCodec(ctx); break;      // (the context's "transform" has to name ROLZX, as in the reference)
+            case ROLZ_TYPE: throw std::invalid_argument("ROLZ has no device kernel (ROLZX has one)");
             case DICT_TYPE:
                 ctx.putInt("textcodec", hoststage::textVariantFor(ctx.has("entropy") ? ctx.getString("entropy").c_str() : ""));
                 transforms[nbtr++] = new TextCodec(ctx);

@@ -7,12 +7,14 @@
 // -e takes NONE, HUFFMAN, ANS0, ANS1, FPAQ, RANGE, CM, TPAQ and TPAQX (every entropy coder of the reference). Levels 0, 1, 5 and 6 are in (5 and 6: TEXT on the host in front of the device chain, host/text_codec.cpp; UTF behind it runs on the device).
 // What it does not do (and says so instead of guessing): directories, stdin/stdout, `-y` info, levels whose chains need the
 // reference's CPU-only transforms (EXE, DNA, ROLZ), or LZ / LZX behind PACK or MM (the device LZ
-// stages do not read the data type those leave, which level 3 needs): levels 2-4 and 7-9. PACK, MM, LZP and UTF themselves run on the
-// device (-t, in any position behind the host stage: -t LZP+UTF+BWT+RANK+ZRLT works); level 7 (LZP+TEXT+UTF+BWT+LZP / CM) has LZP, UTF, BWT
+// stages do not read the data type those leave, which level 3 needs): levels 2-4 and 7-9. PACK, MM, LZP, UTF and ROLZX themselves run on the
+// device (ROLZ proper, id 11, does not and is refused by name; -t, in any position behind the host stage: -t LZP+UTF+BWT+RANK+ZRLT works); level 7 (LZP+TEXT+UTF+BWT+LZP / CM) has LZP, UTF, BWT
 // and CM on the device and waits for one thing only: TEXT, the last host stage, behind a device stage. Levels 8 and 9 (TPAQ / TPAQX,
 // which run on the device) wait for EXE and DNA.
 // Files written here are byte-identical to `kanzi -c` with the same -t/-e/-b/-x/-j, and either tool reads the other's files
 // (tests/test_host_stub.py, tests/test_gpu_host_api.py).
+#include <algorithm>
+#include <cctype>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -90,6 +92,13 @@ int main(int argc, char** argv)
     }
     if (transform.empty()) transform = "NONE";
     if (entropy.empty()) entropy = "NONE";
+    for (size_t at = 0; mode == "c" && at <= transform.size();) {          // ROLZ (ROLZCodec1) has no device kernel; ROLZX has
+        const size_t plus = std::min(transform.find('+', at), transform.size());
+        std::string tok = transform.substr(at, plus - at);
+        for (char& ch : tok) ch = char(toupper((unsigned char)ch));
+        if (tok == "ROLZ") { fprintf(stderr, "the ROLZ transform only exists in the CPU reference (ROLZX runs on the device: -t ROLZX)\n"); return Error::ERR_INVALID_CODEC; }
+        at = plus + 1;
+    }
     if (out.empty()) {
         if (mode == "c") out = in + ".knz";
         else out = (in.size() > 4 && in.compare(in.size() - 4, 4, ".knz") == 0) ? in.substr(0, in.size() - 4) : in + ".bak";

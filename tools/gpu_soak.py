@@ -4,7 +4,7 @@ device decode of the expected stream (developer tool).   usage: gpu_soak.py SEED
 first (the default; tests/test_gpu_parity.py::test_randomised_soak): the 16 chains and 5 coders of the first generation, expected
 streams from the C oracle.
 
-newer (test_randomised_soak_newer_stages): the same draw over those tables plus the chains of NEWER_CHAINS (BWTS, PACK, MM and LZP
+newer (test_randomised_soak_newer_stages): the same draw over those tables plus the chains of NEWER_CHAINS (BWTS, PACK, MM, LZP and ROLZX
 alone, in front of and behind first-generation stages, and two of them in one chain) and the coders RANGE and CM. A case whose chain
 and coder the oracle knows stays on the oracle; any other takes its expected stream from the reference build (knzlib.Ref,
 oracle/_ref/libkanzi_ref.so) with the same jobs and checksum, and where that build is absent the case is skipped and counted. The
@@ -29,7 +29,8 @@ CHAINS = ["NONE", "BWT", "BWT+MTFT+ZRLT", "BWT+SRT+ZRLT", "BWT+MTFT", "RLT", "ZR
 ENTS = ["NONE", "ANS0", "ANS1", "HUFFMAN", "FPAQ"]
 KINDS = ["text", "mixed", "rand", "runs", "sparse", "small_alpha"]
 NEWER_CHAINS = ["BWTS", "BWTS+MTFT+ZRLT", "BWTS+SRT+ZRLT", "PACK", "PACK+BWT+MTFT+ZRLT", "PACK+RLT", "PACK+MM", "MM", "MM+PACK", "MM+RLT",
-                "MM+BWT+MTFT+ZRLT", "LZP", "LZP+BWT+RANK+ZRLT", "BWT+LZP", "LZP+LZX", "LZP+BWTS+MTFT+ZRLT", "PACK+LZP", "LZP+BWT+LZP"]
+                "MM+BWT+MTFT+ZRLT", "LZP", "LZP+BWT+RANK+ZRLT", "BWT+LZP", "LZP+LZX", "LZP+BWTS+MTFT+ZRLT", "PACK+LZP", "LZP+BWT+LZP",
+                "ROLZX", "PACK+ROLZX", "ROLZX+RLT", "MM+ROLZX", "ROLZX+BWT+RANK+ZRLT"]
 NEWER_ENTS = ["RANGE", "CM"]
 NEWER_KINDS = ["walk", "alpha12", "acgt", "repeats"]
 CM_MAX = 65536
