@@ -662,6 +662,20 @@ static int seq_required(const Chain& ch, int n)
     return req;
 }
 
+// stride of a chain's two workspaces for blocks of n bytes. The chain's bound is what the reference gives the task's "buffer", and a
+// stage in even position may fill it: ZRLT in front writes up to requiredSize for a block without zeros, more than its own
+// getMaxEncodedLength. The stage behind it writes into the task's "data" (256 KiB or more, encode_impl) and asks for its own bound over
+// that longer input (LZP: n + n / 64, ROLZX and SRT: n + 1024, MM: n + n / 16), so with two stages or more the stride is the chain's
+// bound of the chain's bound. A capacity is cut to the stride (k_seq_fwd_prepare); cut to the bound alone, ZRLT+LZP, ZRLT+ROLZX,
+// ZRLT+SRT and ZRLT+MM refused blocks in second position that the reference transforms (tests/test_gpu_pairs.py).
+static int seq_stride(const Chain& ch, int n)
+{
+    int stages = 0;
+    for (int i = 0; i < ch.n; i++) stages += ch.tok[i] != KNZ_T_NONE;
+    const int req = seq_required(ch, n);
+    return stages < 2 ? req : seq_required(ch, req);
+}
+
 static size_t chain_scratch_u32(const Chain& ch, bool forward, int nBlocks, u32 maxLen)
 {
     size_t most = 0;
@@ -814,7 +828,7 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
     if (int r = ws_get(c, "origLen", sizeof(u32) * nBlocks, (void**)&d_origLen, s)) return r;
     if (int r = ws_get(c, "info", sizeof(BlockInfo) * nBlocks, (void**)&d_info, s)) return r;
     const int maxIn = (int)((n < bs) ? n : bs);
-    const int required = seq_required(ch, maxIn);
+    const int required = seq_stride(ch, maxIn);
     const u64 S = ((u64)required + 255) & ~255ull;
     bool realStages = false, wantType = false;              // (wantType: a device stage reads the per-block data type)
     for (int i = 0; i < nTok; i++) { realStages |= ch.tok[i] != KNZ_T_NONE; wantType |= ch.xf[i] && ch.xf[i]->setsType; }
@@ -1088,7 +1102,7 @@ static int decode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, uint64_
 
     // workspace stride: large enough for every valid preTransformLength of this chain
     const u32 unit = framing ? bs : rawLen;
-    const int required = seq_required(ch, (int)unit);     // (the whole chain sizes the buffers, as in the encoder: a UTF stage adds 8 KiB of room)
+    const int required = seq_stride(ch, (int)unit);       // (the whole chain sizes the buffers, as in the encoder: a UTF stage adds 8 KiB of room)
     const u64 S = ((u64)required + 255) & ~255ull;
     const u32 maxPre = (u32)S;
     const int maxChunks = (int)((S + ENT_CHUNK - 1) / ENT_CHUNK);

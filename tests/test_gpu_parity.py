@@ -761,8 +761,8 @@ def test_randomised_soak(hip):
 
 
 def test_randomised_soak_newer_stages(hip):
-    """The same soak drawn over the first-generation tables plus BWTS, PACK, MM and LZP chains (alone, mixed with older stages, two
-    of them in one chain), the coders RANGE and CM and four input kinds these stages accept (tools/gpu_soak.py, mode `newer`):
+    """The same soak drawn over the first-generation tables plus BWTS, PACK, MM, LZP, ROLZX and UTF chains (alone, mixed with older
+    stages, two of them in one chain), the coders RANGE, CM, TPAQ and TPAQX and five input kinds these stages accept (tools/gpu_soak.py, mode `newer`):
     every job count, checksum width and block size from 1 KiB to 1 MiB against the reference build's stream (oracle/_ref, which
     build() makes and which travels with the tree), which the device must write and read. A process and a budget of its own.
     The floor of 10 newer-stage cases keeps the test from passing on nothing, a missing reference build included; streams the

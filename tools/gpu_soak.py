@@ -4,22 +4,25 @@ device decode of the expected stream (developer tool).   usage: gpu_soak.py SEED
 first (the default; tests/test_gpu_parity.py::test_randomised_soak): the 16 chains and 5 coders of the first generation, expected
 streams from the C oracle.
 
-newer (test_randomised_soak_newer_stages): the same draw over those tables plus the chains of NEWER_CHAINS (BWTS, PACK, MM, LZP and ROLZX
-alone, in front of and behind first-generation stages, and two of them in one chain) and the coders RANGE and CM. A case whose chain
+newer (test_randomised_soak_newer_stages): the same draw over those tables plus the chains of NEWER_CHAINS (BWTS, PACK, MM, LZP, ROLZX and
+UTF alone, in front of and behind first-generation stages, and two of them in one chain) and the coders RANGE, CM, TPAQ and TPAQX. A case whose chain
 and coder the oracle knows stays on the oracle; any other takes its expected stream from the reference build (knzlib.Ref,
 oracle/_ref/libkanzi_ref.so) with the same jobs and checksum, and where that build is absent the case is skipped and counted. The
-input kinds grow by four that the newer stages accept at every block size from 4,096 up (checked with Ref.forward at 4,096, 65,536,
+input kinds grow by five that the newer stages accept: four at every block size from 4,096 up (checked with Ref.forward at 4,096, 65,536,
 262,144 and 1 MiB): `walk` (a bounded random walk: MM, and PACK in its digram mode), `alpha12` and `acgt` (12 skewed symbols and
-ACGT: PACK's digram and 2-bit modes) and `repeats` (corpus.repeats, text with copied spans of 1 KiB and more: LZP, and PACK). Of the
+ACGT: PACK's digram and 2-bit modes) and `repeats` (corpus.repeats, text with copied spans of 1 KiB and more: LZP, and PACK), and
+`utf8` (utf_cases.utf8, code points of one byte and more, cut wherever a block ends: UTF). Of the
 older kinds MM also takes `runs`, LZP `mixed`, `runs` and `sparse`, PACK `text` and `small_alpha` at all four sizes.
-CM and FPAQ code one block per wave at 2.85 us per byte: n is capped at 65,536 for CM and at 300,000 for FPAQ.
+CM, TPAQ, TPAQX and FPAQ code one block per wave (CM at 2.85 us per byte): n is capped at 65,536 for CM, TPAQ and TPAQX
+and at 300,000 for FPAQ. The three binary coders get the output buffer of their second tier (knz_hip_encode_bound is their first).
 
 Left out in both: BWT+ZRLT and BWT+RLT+ZRLT, and chains that start with ZRLT / RLT / SRT on `rand`; LZ and LZX
-behind PACK or MM (the device refuses those chains by design); EXE, TEXT, UTF and the other host-side stages; TPAQ; block sizes above
-1 MiB (the per-stage tests and tests/test_emu_pack.py hold the larger blocks)."""
+behind PACK, MM, UTF or ROLZX (the device refuses to write those chains by design; tests/test_gpu_pairs.py has it read the
+reference's); EXE, TEXT and the other host-side stages; block sizes above 1 MiB (the per-stage tests and tests/test_emu_pack.py hold
+the larger blocks). Every ordered pair of the device transforms, which this draw only samples, is in tests/test_gpu_pairs.py."""
 import sys, os, time, importlib
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
-import knzlib, vectors
+import knzlib, vectors, utf_cases
 import numpy as np
 
 # chains whose even-indexed stages cannot expand into the caller's buffer (see DESIGN.md section 4)
@@ -30,9 +33,11 @@ ENTS = ["NONE", "ANS0", "ANS1", "HUFFMAN", "FPAQ"]
 KINDS = ["text", "mixed", "rand", "runs", "sparse", "small_alpha"]
 NEWER_CHAINS = ["BWTS", "BWTS+MTFT+ZRLT", "BWTS+SRT+ZRLT", "PACK", "PACK+BWT+MTFT+ZRLT", "PACK+RLT", "PACK+MM", "MM", "MM+PACK", "MM+RLT",
                 "MM+BWT+MTFT+ZRLT", "LZP", "LZP+BWT+RANK+ZRLT", "BWT+LZP", "LZP+LZX", "LZP+BWTS+MTFT+ZRLT", "PACK+LZP", "LZP+BWT+LZP",
-                "ROLZX", "PACK+ROLZX", "ROLZX+RLT", "MM+ROLZX", "ROLZX+BWT+RANK+ZRLT"]
-NEWER_ENTS = ["RANGE", "CM"]
-NEWER_KINDS = ["walk", "alpha12", "acgt", "repeats"]
+                "ROLZX", "PACK+ROLZX", "ROLZX+RLT", "MM+ROLZX", "ROLZX+BWT+RANK+ZRLT",
+                "UTF", "UTF+BWT+RANK+ZRLT", "LZP+UTF+BWT+LZP", "UTF+PACK+RLT", "UTF+ROLZX"]
+NEWER_ENTS = ["RANGE", "CM", "TPAQ", "TPAQX"]
+NEWER_KINDS = ["walk", "alpha12", "acgt", "repeats", "utf8"]
+BINARY_ENTS = ("CM", "TPAQ", "TPAQX")
 CM_MAX = 65536
 FPAQ_MAX = 300000
 
@@ -62,6 +67,8 @@ def gen(kind, n, rng):
         return np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, n)].tobytes()
     if kind == "repeats":
         return knzlib.corpus().repeats(n, int(rng.integers(1, 1000)))
+    if kind == "utf8":
+        return utf_cases.utf8(n, int(rng.integers(1, 1000)))
     return bytes((rng.integers(0, 3, n, dtype=np.uint8) * 37 + 65).astype(np.uint8))
 
 
@@ -69,10 +76,10 @@ def draw(rng, chains, ents, kinds):
     """One case: (chain, coder, block size, length, kind, jobs, checksum)."""
     chain = chains[int(rng.integers(0, len(chains)))]
     ent = ents[int(rng.integers(0, len(ents)))]
-    bs = int(rng.choice([1024, 4096, 65536, 262144, 1 << 20])) if ent not in ("FPAQ", "CM") and "SRT" not in chain else int(rng.choice([1024, 4096, 65536]))
+    bs = int(rng.choice([1024, 4096, 65536, 262144, 1 << 20])) if ent not in ("FPAQ",) + BINARY_ENTS and "SRT" not in chain else int(rng.choice([1024, 4096, 65536]))
     n = int(rng.integers(0, 6 * bs + 7)) if bs <= 65536 else int(rng.integers(bs // 2, 3 * bs))
     if ent == "FPAQ": n = min(n, FPAQ_MAX)
-    if ent == "CM": n = min(n, CM_MAX)
+    if ent in BINARY_ENTS: n = min(n, CM_MAX)
     kind = kinds[int(rng.integers(0, len(kinds)))]
     jobs = int(rng.choice([1, 2, 3, 8]))
     ck = int(rng.choice([0, 0, 32, 64]))
@@ -127,6 +134,7 @@ def main():
         rc, ref = exp.stream(d, chain, ent, bs, jobs, ck)
         p = ctx.params(chain, ent, bs, ck, jobs=jobs)
         cap = ctx.encode_bound(p, len(d)) + 64
+        if ent in BINARY_ENTS: cap += 32 * len(d)            # knz_hip_encode_bound is these coders' first tier (include/knz_hip.h)
         d_in = ctx.malloc(len(d) + 64); d_out = ctx.malloc(cap)
         ctx.h2d(d_in, d)
         ok = dok = False
