@@ -28,7 +28,7 @@ extern "C" {
 
 /* kanzi ids: entropy (entropy/EntropyEncoderFactory.hpp:37-52) and transforms (transform/TransformFactory.hpp:49-73) */
 enum { KNZ_E_NONE = 0, KNZ_E_HUFFMAN = 1, KNZ_E_FPAQ = 2, KNZ_E_RANGE = 4, KNZ_E_ANS0 = 5, KNZ_E_CM = 6, KNZ_E_TPAQ = 7, KNZ_E_ANS1 = 8, KNZ_E_TPAQX = 9 };
-enum { KNZ_T_NONE = 0, KNZ_T_BWT = 1, KNZ_T_BWTS = 2, KNZ_T_LZ = 3, KNZ_T_RLT = 5, KNZ_T_ZRLT = 6, KNZ_T_MTFT = 7, KNZ_T_RANK = 8, KNZ_T_ROLZX = 12, KNZ_T_SRT = 13, KNZ_T_LZP = 14, KNZ_T_MM = 15, KNZ_T_LZX = 16, KNZ_T_PACK = 18,
+enum { KNZ_T_NONE = 0, KNZ_T_BWT = 1, KNZ_T_BWTS = 2, KNZ_T_LZ = 3, KNZ_T_RLT = 5, KNZ_T_ZRLT = 6, KNZ_T_MTFT = 7, KNZ_T_RANK = 8, KNZ_T_EXE = 9, KNZ_T_ROLZX = 12, KNZ_T_SRT = 13, KNZ_T_LZP = 14, KNZ_T_MM = 15, KNZ_T_LZX = 16, KNZ_T_PACK = 18,
        KNZ_T_TIMESTAMP = 64 /* SBRT's third mode: no kanzi id, never part of a chain; per-stage entry points only */,
        KNZ_T_UTF = 17 /* a device stage in any position; also accepted among the host's leading stages (below) */,
        KNZ_T_TEXT = 10 /* runs on the HOST in front of the device chain: knz_hip_encode_block_hosted / _decode_ */ };
@@ -176,6 +176,7 @@ KNZ_API int knz_hip_entropy_decode_bs(knz_ctx* ctx, int entropy_type, int bs_ver
  *   KNZ_T_LZ / KNZ_T_LZX   LZCodec -> LZXCodec<false> / LZXCodec<true>   transform/LZCodec.cpp:119-456,470-640
  *   KNZ_T_LZP   LZPCodec             transform/LZCodec.cpp:771-879,881-992
  *   KNZ_T_ROLZX ROLZCodec -> ROLZCodec2   transform/ROLZCodec.cpp:52-96,862-1109 (+ ROLZEncoder / ROLZDecoder :681-820, ROLZCodec.hpp:311-365)
+ *   KNZ_T_EXE   EXECodec             transform/EXECodec.cpp:63-312,314-518 (+ detectType :520-625, parseHeader :627-849)
  *   KNZ_T_PACK  AliasCodec           transform/AliasCodec.cpp:38-209,211-371
  *   KNZ_T_MM    FSDCodec             transform/FSDCodec.cpp:103-291,293-386
  *   KNZ_T_UTF   UTFCodec             transform/UTFCodec.cpp:48-204,206-298 (+ validate :303-422, pack / unpack UTFCodec.hpp:71-154)
@@ -192,7 +193,10 @@ KNZ_API int knz_hip_transform_inverse(knz_ctx* ctx, int transform_type, const ui
  * UTF takes UNDEFINED (it validates the block first) and UTF8 (it does not) and leaves UTF8 once validation has passed or been skipped,
  * also on a block it then refuses (too many symbols, a broken third byte, no gain); any other type makes it refuse and stays; ROLZX
  * takes every type (EXE: keys 3 bytes back; DNA: hashed 8-byte keys, matches of 7 and more) and sets detectSimpleType's result of the
- * whole block on an UNDEFINED one; the other stages ignore it.
+ * whole block on an UNDEFINED one; EXE takes UNDEFINED, EXE and BIN blocks of 4,096 bytes and more, leaves EXE on a block it rewrites,
+ * overwrites the type with what its detection found (UNDEFINED included) on a block that detection rejects, and leaves it alone on a
+ * block it refuses for another reason (the gates; fewer than 16 rewritten addresses; more than 2 % of growth). EXE is the only stage
+ * that produces the type EXE, which ROLZX reads and PACK refuses. The other stages ignore the type.
  * knz_hip_transform_forward is this call with a fresh Context (UNDEFINED). */
 KNZ_API int knz_hip_transform_forward_dt(knz_ctx* ctx, int transform_type, const uint8_t* in, int32_t n, uint8_t* out,
                                          int32_t dst_cap, int entropy_type, int32_t* data_type, int32_t* out_len, int32_t* ok);

@@ -620,6 +620,14 @@ static const XfInfo XF[] = {
       .fwd = { .wsBytes = rolzx_scratch_bytes, .launch = [](const StageCall& k) { launch_rolzx_forward(k.s, k.st, k.ws); return 0; } },
       .inv = { .wsBytes = rolzx_scratch_bytes, .launch = [](const StageCall& k) { launch_rolzx_inverse(k.s, k.st, k.ws); return 0; } },
       .setsType = true },
+    // (EXECodec; it reads the data type -- preset from the block's magic: ELF, PE and Mach-O blocks come as EXE -- and writes EXE on a
+    // block it rewrites, or what its detection found on a block that detection rejects: ROLZX behind it keys EXE blocks 3 bytes back,
+    // PACK behind it refuses them. Scratch per lane like LZP's, so the inverse runs in decode lanes. Its verdict on the way back
+    // depends on the capacity, so the last inverse stage of a stream judges by XfStage::capModel as UTF does)
+    { .id = KNZ_T_EXE, .ws = "exeScratch",
+      .fwd = { .wsBytes = exe_scratch_bytes, .launch = [](const StageCall& k) { launch_exe_forward(k.s, k.st, k.ws); return 0; } },
+      .inv = { .wsBytes = exe_scratch_bytes, .launch = [](const StageCall& k) { launch_exe_inverse(k.s, k.st, k.ws); return 0; } },
+      .setsType = true },
 };
 
 static const XfInfo* xf_info(int t) { for (const XfInfo& x : XF) if (x.id == t) return &x; return nullptr; }

@@ -14,6 +14,7 @@ inline int knz_max_encoded_len(int t, int n)
     case KNZ_T_LZ: case KNZ_T_LZX: return ((n <= 1024) ? n + 16 : n + n / 64) + 2;     // LZCodec.hpp:91-95
     case KNZ_T_LZP: return (n <= 1024) ? n + 16 : n + n / 64;                           // LZCodec.hpp:158-161
     case KNZ_T_ROLZX: return n + (n < 32768 ? 1024 : n >> 5);                          // ROLZCodec.hpp:168-173
+    case KNZ_T_EXE: return (n <= 256) ? n + 32 : n + n / 8;                            // EXECodec.hpp:96-100
     case KNZ_T_UTF: return n + 8192;                                                   // UTFCodec.hpp:53
     default: return n;
     }

@@ -74,8 +74,8 @@ struct XfStage {
     u32 maxCap = 0;          // upper bound of cap[] when the host knows one (inverse stages that size scratch by their output)
     u32 capModel = 0;        // inverse: the capacity of the reference's buffer where cap[] is smaller (the last inverse stage of a stream writes
                              // into the caller's buffer, one block size per block, while the reference decodes into a buffer with slack):
-                             // UTF, whose verdict depends on the capacity, judges by max(cap, capModel) and writes within cap. 0: cap[] is all
-    u8* dtype = nullptr;     // per-block Global::DataType (0 = UNDEFINED) read and written by PACK, MM, UTF and ROLZX; nullptr: a fresh context per block
+                             // UTF and EXE, whose verdicts depend on the capacity, judge by max(cap, capModel) and write within cap. 0: cap[] is all
+    u8* dtype = nullptr;     // per-block Global::DataType (0 = UNDEFINED) read and written by PACK, MM, UTF, ROLZX and EXE; nullptr: a fresh context per block
 };
 
 // zrlt_mtft.hip
@@ -128,6 +128,12 @@ size_t rolzx_scratch_bytes(int nBlocks, u32 maxLen);
 void launch_utf_forward(hipStream_t s, const XfStage& st, void* scratch);
 void launch_utf_inverse(hipStream_t s, const XfStage& st, void* scratch);
 size_t utf_scratch_bytes(int nBlocks, u32 maxLen);
+
+// exe.hip (EXECodec; scratch: exe_scratch_bytes(nBlocks, maxLen) bytes, about 1 KiB per block plus len / 4; reads and writes
+// XfStage::dtype; the inverse judges by max(cap, capModel) like UTF's; no host synchronisation)
+void launch_exe_forward(hipStream_t s, const XfStage& st, void* scratch);
+void launch_exe_inverse(hipStream_t s, const XfStage& st, void* scratch);
+size_t exe_scratch_bytes(int nBlocks, u32 maxLen);
 
 // fpaq.hip (probs: fpaq_probs_bytes(nBlocks, S) bytes of scratch, S = upper bound of the block lengths)
 void launch_fpaq_encode(hipStream_t s, BlockView view, const u32* origLen, u32 copyThreshold, int nBlocks, int maxChunks, ChunkDesc* desc, u8* tmp, u64 tmpStride,

@@ -563,6 +563,28 @@ bool ROLZCodec::forward(SliceArray<byte>& src, SliceArray<byte>& dst, int length
     return true;
 }
 
+bool EXECodec::forward(SliceArray<byte>& src, SliceArray<byte>& dst, int length)
+{
+    if (_ctx == nullptr) return DeviceTransform::forward(src, dst, length);
+    if (length == 0) return true;
+    if (!SliceArray<byte>::isValid(src)) throw std::invalid_argument("EXECodec: Invalid input block");
+    if (!SliceArray<byte>::isValid(dst)) throw std::invalid_argument("EXECodec: Invalid output block");
+    if ((length < 0) || (length > src._length - src._index)) return false;
+    if (src._array == dst._array) return false;
+    if (&knz_hip_transform_forward_dt == nullptr) throw std::runtime_error("the device library has no EXE stage");
+    const int32_t dtIn = _ctx->getInt("dataType", hoststage::DT_UNDEFINED);
+    int32_t dt = (dtIn < 0 || dtIn > 9) ? hoststage::DT_UNDEFINED : dtIn;
+    knz_ctx* c = deviceContext();
+    int32_t outLen = 0, ok = 0;
+    devCheck(c, knz_hip_transform_forward_dt(c, _type, src._array + src._index, length, dst._array + dst._index,
+                                             dst._length - dst._index, _entropy, &dt, &outLen, &ok), "transform forward");
+    if (dt != dtIn) _ctx->putInt("dataType", dt);         // (a NOT_EXE verdict overwrites the type, with UNDEFINED too: EXECodec.cpp:91-95)
+    if (!ok) return false;
+    src._index += length;
+    dst._index += outLen;
+    return true;
+}
+
 static int sbrtType(int mode)
 {
     if ((mode != SBRT::MODE_MTF) && (mode != SBRT::MODE_RANK) && (mode != SBRT::MODE_TIMESTAMP)) throw std::invalid_argument("Invalid mode parameter");
@@ -792,6 +814,7 @@ bool UTFCodec::inverse(SliceArray<byte>& src, SliceArray<byte>& dst, int length)
 // LZX, LZP, ROLZX; SRT / RANK are chains per block) the device is what a batch waits for and the extra threads only got in the way (measured,
 // config 3 end to end: 2.94-3.14 GB/s with the copies on the caller's thread, 2.72-2.94 with four threads; config 2: 3.1 -> 3.9).
 // TEXT runs on the host; UTF on the device is a dozen passes over the block and a sort, nothing one thread's copies keep up with.
+// EXE is a few passes of byte-level parsing with no sort and no search, so it counts with the byte transforms (not measured end to end).
 static bool chainIsHostBound(uint64 ttype)
 {
     for (int i = 0; i < 8; i++) {
@@ -982,6 +1005,7 @@ TransformSequence<T>* TransformFactory<T>::newTransform(Context& ctx, uint64 fun
             case LZX_TYPE: ctx.putInt("lz", LZX_TYPE); transforms[nbtr++] = new LZCodec(ctx); break;
             case LZP_TYPE: ctx.putInt("lz", LZP_TYPE); transforms[nbtr++] = new LZCodec(ctx); break;
             case ROLZX_TYPE: transforms[nbtr++] = new ROLZCodec(ctx); break;      // (the context's "transform" has to name ROLZX, as in the reference)
+            case EXE_TYPE: transforms[nbtr++] = new EXECodec(ctx); break;
             case ROLZ_TYPE: throw std::invalid_argument("ROLZ has no device kernel (ROLZX has one)");
             case DICT_TYPE:
                 ctx.putInt("textcodec", hoststage::textVariantFor(ctx.has("entropy") ? ctx.getString("entropy").c_str() : ""));

@@ -6,11 +6,11 @@
 //
 // -e takes NONE, HUFFMAN, ANS0, ANS1, FPAQ, RANGE, CM, TPAQ and TPAQX (every entropy coder of the reference). Levels 0, 1, 5 and 6 are in (5 and 6: TEXT on the host in front of the device chain, host/text_codec.cpp; UTF behind it runs on the device).
 // What it does not do (and says so instead of guessing): directories, stdin/stdout, `-y` info, levels whose chains need the
-// reference's CPU-only transforms (EXE, DNA, ROLZ), or LZ / LZX behind PACK or MM (the device LZ
-// stages do not read the data type those leave, which level 3 needs): levels 2-4 and 7-9. PACK, MM, LZP, UTF and ROLZX themselves run on the
+// reference's CPU-only transforms (DNA, ROLZ), or LZ / LZX behind EXE, PACK or MM (the device LZ
+// stages do not read the data type those leave, which level 3 needs): levels 2-4 and 7-9. EXE, PACK, MM, LZP, UTF and ROLZX themselves run on the
 // device (ROLZ proper, id 11, does not and is refused by name; -t, in any position behind the host stage: -t LZP+UTF+BWT+RANK+ZRLT works); level 7 (LZP+TEXT+UTF+BWT+LZP / CM) has LZP, UTF, BWT
-// and CM on the device and waits for one thing only: TEXT, the last host stage, behind a device stage. Levels 8 and 9 (TPAQ / TPAQX,
-// which run on the device) wait for EXE and DNA.
+// and CM on the device and waits for one thing only: TEXT, the last host stage, behind a device stage. Levels 8 and 9
+// (EXE+RLT+TEXT+UTF+DNA / TPAQ, TPAQX: EXE, RLT, UTF and the coders run on the device) wait for TEXT behind a device stage and for DNA.
 // Files written here are byte-identical to `kanzi -c` with the same -t/-e/-b/-x/-j, and either tool reads the other's files
 // (tests/test_host_stub.py, tests/test_gpu_host_api.py).
 #include <algorithm>
@@ -88,7 +88,7 @@ int main(int argc, char** argv)
         else if (level == 1) { transform = "LZX"; entropy = "NONE"; }
         else if (level == 5) { transform = "TEXT+UTF+BWT+RANK+ZRLT"; entropy = "ANS0"; }      // TEXT runs on the host, the rest on the device
         else if (level == 6) { transform = "TEXT+UTF+BWT+SRT+ZRLT"; entropy = "FPAQ"; if (!blockGiven) block = 8 << 20; }      // (BlockCompressor.cpp:121-124: 8 MiB blocks by default)
-        else { fprintf(stderr, "level %d needs transforms that only exist in the CPU reference (EXE/DNA/ROLZ: levels 2, 4, 8, 9), LZX behind PACK / MM (level 3) or TEXT behind LZP (level 7); use -t/-e\n", level); return Error::ERR_INVALID_CODEC; }
+        else { fprintf(stderr, "level %d needs transforms that only exist in the CPU reference (DNA / ROLZ: levels 2, 4, 8, 9), LZX behind PACK / MM (level 3) or TEXT behind a device stage (levels 7, 8, 9); use -t/-e\n", level); return Error::ERR_INVALID_CODEC; }
     }
     if (transform.empty()) transform = "NONE";
     if (entropy.empty()) entropy = "NONE";
