@@ -268,11 +268,12 @@ public:
     bool inverse(SliceArray<byte>& src, SliceArray<byte>& dst, int length);
 };
 // transform/AliasCodec.hpp: PACK, getMaxEncodedLength = n + 1024. forward() reads the Context's "dataType" and writes back what
-// the stage left there (knz_hip_transform_forward_dt), as AliasCodec.cpp:46-72 does.
+// the stage left there (knz_hip_transform_forward_dt), as AliasCodec.cpp:46-72 does. With the Context entry "packOnlyDNA" (which
+// TransformFactory sets for DNA, id 19) it is the DNA transform: blocks that are not DNA are refused (AliasCodec.cpp:34, :66, :93).
 class AliasCodec : public DeviceTransform {
 public:
     AliasCodec() : DeviceTransform(KNZ_T_PACK, nullptr), _ctx(nullptr) {}
-    explicit AliasCodec(Context& ctx) : DeviceTransform(KNZ_T_PACK, &ctx), _ctx(&ctx) {}
+    explicit AliasCodec(Context& ctx) : DeviceTransform(ctx.getInt("packOnlyDNA", 0) != 0 ? KNZ_T_DNA : KNZ_T_PACK, &ctx), _ctx(&ctx) {}
     bool forward(SliceArray<byte>& src, SliceArray<byte>& dst, int length);
 private:
     Context* _ctx;

@@ -28,10 +28,10 @@ extern "C" {
 
 /* kanzi ids: entropy (entropy/EntropyEncoderFactory.hpp:37-52) and transforms (transform/TransformFactory.hpp:49-73) */
 enum { KNZ_E_NONE = 0, KNZ_E_HUFFMAN = 1, KNZ_E_FPAQ = 2, KNZ_E_RANGE = 4, KNZ_E_ANS0 = 5, KNZ_E_CM = 6, KNZ_E_TPAQ = 7, KNZ_E_ANS1 = 8, KNZ_E_TPAQX = 9 };
-enum { KNZ_T_NONE = 0, KNZ_T_BWT = 1, KNZ_T_BWTS = 2, KNZ_T_LZ = 3, KNZ_T_RLT = 5, KNZ_T_ZRLT = 6, KNZ_T_MTFT = 7, KNZ_T_RANK = 8, KNZ_T_EXE = 9, KNZ_T_ROLZX = 12, KNZ_T_SRT = 13, KNZ_T_LZP = 14, KNZ_T_MM = 15, KNZ_T_LZX = 16, KNZ_T_PACK = 18,
+enum { KNZ_T_NONE = 0, KNZ_T_BWT = 1, KNZ_T_BWTS = 2, KNZ_T_LZ = 3, KNZ_T_RLT = 5, KNZ_T_ZRLT = 6, KNZ_T_MTFT = 7, KNZ_T_RANK = 8, KNZ_T_EXE = 9, KNZ_T_ROLZX = 12, KNZ_T_SRT = 13, KNZ_T_LZP = 14, KNZ_T_MM = 15, KNZ_T_LZX = 16, KNZ_T_PACK = 18, KNZ_T_DNA = 19 /* PACK that takes DNA blocks only */,
        KNZ_T_TIMESTAMP = 64 /* SBRT's third mode: no kanzi id, never part of a chain; per-stage entry points only */,
        KNZ_T_UTF = 17 /* a device stage in any position; also accepted among the host's leading stages (below) */,
-       KNZ_T_TEXT = 10 /* runs on the HOST in front of the device chain: knz_hip_encode_block_hosted / _decode_ */ };
+       KNZ_T_TEXT = 10 /* a device stage in any position; also accepted among the host's leading stages (below) */ };
 
 /* kanzi error codes surfaced for data errors (src/Error.hpp:26-48) */
 enum { KNZ_ERR_BLOCK_SIZE = 2, KNZ_ERR_INVALID_CODEC = 3, KNZ_ERR_READ_FILE = 11, KNZ_ERR_WRITE_FILE = 12,
@@ -112,8 +112,9 @@ KNZ_API int knz_hip_decode_blocks(knz_ctx* ctx, const knz_params* p, const uint8
  * Chains whose first stages run on the host (the reference's level presets 5 and 6: TEXT + UTF in front of BWT + RANK / SRT + ZRLT,
  * app/BlockCompressor.cpp:583-591). The host applies those stages to ONE block (they change its length by a different amount per block)
  * and hands over what TransformSequence::forward would have left for the next stage (transform/TransformSequence.hpp:88-162):
- *   stages        how many leading stages of p->transform_type the host owns (each KNZ_T_TEXT or KNZ_T_UTF). TEXT has no device
- *                 version, so the host owns the chain up to its last leading TEXT; a UTF in front of that TEXT has to run on the host
+ *   stages        how many leading stages of p->transform_type the host owns (each KNZ_T_TEXT or KNZ_T_UTF). TEXT is a device stage
+ *                 as well (knz_hip_transform_supported(KNZ_T_TEXT) = 1 since it is), so this entry point is for callers that want TEXT
+ *                 on the host; they own the chain up to its last leading TEXT, and a UTF in front of that TEXT has to run on the host
  *                 too ("UTF+TEXT+...": stages = 2), a UTF behind it is a device stage like any other ("TEXT+UTF+...": stages = 1 is
  *                 what the stream classes pass; stages = 2 with UTF applied by the caller still works)
  *   applied_mask  bit i set = stage i succeeded (its skip flag is clear, and it counts as a buffer swap for the capacities the
@@ -178,8 +179,13 @@ KNZ_API int knz_hip_entropy_decode_bs(knz_ctx* ctx, int entropy_type, int bs_ver
  *   KNZ_T_ROLZX ROLZCodec -> ROLZCodec2   transform/ROLZCodec.cpp:52-96,862-1109 (+ ROLZEncoder / ROLZDecoder :681-820, ROLZCodec.hpp:311-365)
  *   KNZ_T_EXE   EXECodec             transform/EXECodec.cpp:63-312,314-518 (+ detectType :520-625, parseHeader :627-849)
  *   KNZ_T_PACK  AliasCodec           transform/AliasCodec.cpp:38-209,211-371
+ *   KNZ_T_DNA   AliasCodec with packOnlyDNA = 1 (TransformFactory.hpp:293-294): the forward refuses a preset type other than UNDEFINED
+ *               or DNA (AliasCodec.cpp:66) and a block whose detection does not say DNA (:93); the inverse is PACK's
  *   KNZ_T_MM    FSDCodec             transform/FSDCodec.cpp:103-291,293-386
  *   KNZ_T_UTF   UTFCodec             transform/UTFCodec.cpp:48-204,206-298 (+ validate :303-422, pack / unpack UTFCodec.hpp:71-154)
+ *   KNZ_T_TEXT  TextCodec -> TextCodec1 / TextCodec2   transform/TextCodec.cpp:520-1015,1017-1581 (+ statistics :213-425); entropy_type
+ *               picks the encoding as TransformFactory.hpp:225-242 does (NONE, HUFFMAN, RANGE, ANS0: TextCodec2; TPAQX: TextCodec1 with
+ *               a doubled hash map; anything else and -1: TextCodec1); the stream's block size is 0 here (knz_hip_transform_forward_bs)
  * (the inverse of LZ/LZX expects what the reference expects: two readable bytes behind `in + n`,
  * LZCodec.cpp:486-490; the library stages the input itself, so callers need not pad). */
 KNZ_API int knz_hip_transform_forward(knz_ctx* ctx, int transform_type, const uint8_t* in, int32_t n,
@@ -196,7 +202,9 @@ KNZ_API int knz_hip_transform_inverse(knz_ctx* ctx, int transform_type, const ui
  * whole block on an UNDEFINED one; EXE takes UNDEFINED, EXE and BIN blocks of 4,096 bytes and more, leaves EXE on a block it rewrites,
  * overwrites the type with what its detection found (UNDEFINED included) on a block that detection rejects, and leaves it alone on a
  * block it refuses for another reason (the gates; fewer than 16 rewritten addresses; more than 2 % of growth). EXE is the only stage
- * that produces the type EXE, which ROLZX reads and PACK refuses. The other stages ignore the type.
+ * that produces the type EXE, which ROLZX reads and PACK refuses; TEXT takes UNDEFINED, TEXT and BIN blocks of 1,024 bytes and more,
+ * leaves TEXT on a block its statistics call text (also when the encoding then outgrows the block) and the type they found -- DNA,
+ * NUMERIC, BASE64, BIN, SMALL_ALPHABET, UTF8 or UNDEFINED -- on one they do not. The other stages ignore the type.
  * knz_hip_transform_forward is this call with a fresh Context (UNDEFINED). */
 KNZ_API int knz_hip_transform_forward_dt(knz_ctx* ctx, int transform_type, const uint8_t* in, int32_t n, uint8_t* out,
                                          int32_t dst_cap, int entropy_type, int32_t* data_type, int32_t* out_len, int32_t* ok);
@@ -205,6 +213,14 @@ KNZ_API int knz_hip_transform_forward_dt(knz_ctx* ctx, int transform_type, const
  * classes take from the "bsVersion" entry of their Context. */
 KNZ_API int knz_hip_transform_inverse_v(knz_ctx* ctx, int transform_type, int bs_version, const uint8_t* in, int32_t n,
                                         uint8_t* out, int32_t dst_cap, int32_t* out_len, int32_t* ok);
+
+/* The two calls with the block size of the stream the block belongs to (the "blockSize" entry of the Context) and, on the way back,
+ * the stream's entropy id: TEXT sizes its hash map by the block size (TextCodec.cpp:533-541, 1030-1035; 0 = 8,192 slots) and picks its
+ * encoding by the entropy id in both directions. The other stages ignore both. */
+KNZ_API int knz_hip_transform_forward_bs(knz_ctx* ctx, int transform_type, uint32_t stream_block_size, const uint8_t* in, int32_t n,
+                                         uint8_t* out, int32_t dst_cap, int entropy_type, int32_t* data_type, int32_t* out_len, int32_t* ok);
+KNZ_API int knz_hip_transform_inverse_bs(knz_ctx* ctx, int transform_type, int bs_version, uint32_t stream_block_size, int entropy_type,
+                                         const uint8_t* in, int32_t n, uint8_t* out, int32_t dst_cap, int32_t* out_len, int32_t* ok);
 
 /* Device-memory helpers so that non-HIP hosts (ctypes, cgo, JNI) can stage data. */
 KNZ_API int knz_hip_malloc(knz_ctx* ctx, size_t bytes, void** d_ptr);

@@ -509,6 +509,7 @@ enum Split { NO_SPLIT, SPLIT_QUEUED, SPLIT_THREADS };
 struct XfDir {
     size_t (*scratchU32)(int nBlocks, u32 maxLen);   // words of the chain's shared stage scratch (XfStage::scratchU32), or nullptr
     size_t (*wsBytes)(int nBlocks, u32 maxLen);      // bytes of the stage's own scratch XfInfo::ws, or nullptr
+    size_t (*wsBytesOf)(const XfStage&);             // the same for a stage whose scratch depends on more of the stage record (TEXT)
     int (*launch)(const StageCall&);
     Split split;
 };
@@ -595,6 +596,13 @@ static const XfInfo XF[] = {
       .fwd = { .wsBytes = pack_scratch_bytes, .launch = [](const StageCall& k) { launch_pack_forward(k.s, k.st, k.ws); return 0; } },
       .inv = { .wsBytes = pack_scratch_bytes, .launch = [](const StageCall& k) { launch_pack_inverse(k.s, k.st, k.ws); return 0; } },
       .setsType = true },
+    // (DNA, id 19: AliasCodec with the Context entry packOnlyDNA, TransformFactory.hpp:293-294. PACK's launchers; the forward refuses a
+    // preset type other than UNDEFINED or DNA and a block whose detection does not say DNA, after it wrote what detection found. The
+    // inverse is PACK's)
+    { .id = KNZ_T_DNA, .ws = "packScratch",
+      .fwd = { .wsBytes = pack_scratch_bytes, .launch = [](const StageCall& k) { XfStage st = k.st; st.onlyDNA = 1; launch_pack_forward(k.s, st, k.ws); return 0; } },
+      .inv = { .wsBytes = pack_scratch_bytes, .launch = [](const StageCall& k) { launch_pack_inverse(k.s, k.st, k.ws); return 0; } },
+      .setsType = true },
     // (FSDCodec; it leaves MULTIMEDIA or detectSimpleType's verdict on the blocks it looks at, which RLT behind it reads)
     { .id = KNZ_T_MM, .ws = "mmScratch",
       .fwd = { .wsBytes = mm_scratch_bytes, .launch = [](const StageCall& k) { launch_mm_forward(k.s, k.st, k.ws); return 0; } },
@@ -627,6 +635,17 @@ static const XfInfo XF[] = {
     { .id = KNZ_T_EXE, .ws = "exeScratch",
       .fwd = { .wsBytes = exe_scratch_bytes, .launch = [](const StageCall& k) { launch_exe_forward(k.s, k.st, k.ws); return 0; } },
       .inv = { .wsBytes = exe_scratch_bytes, .launch = [](const StageCall& k) { launch_exe_inverse(k.s, k.st, k.ws); return 0; } },
+      .setsType = true },
+    // (TextCodec, in the encoding the stream's entropy coder asks for; it reads the data type -- UNDEFINED, TEXT and BIN blocks are looked
+    // at -- and writes TEXT, or the type its statistics found on a block that is no text, which UTF, PACK and ROLZX behind it read. Its
+    // hash map is sized by the stream's block size (XfStage::blockSize), so its scratch is; per lane like LZP's, so the inverse runs in
+    // decode lanes, and the last inverse stage of a stream judges by XfStage::capModel as UTF does. In front of a chain it may still run
+    // on the host: knz_hip_encode_block_hosted)
+    { .id = KNZ_T_TEXT, .ws = "textScratch",
+      .fwd = { .wsBytesOf = [](const XfStage& st) { return text_scratch_bytes(st.nBlocks, st.maxLen, st.blockSize); },
+               .launch = [](const StageCall& k) { launch_text_forward(k.s, k.st, k.ws); return 0; } },
+      .inv = { .wsBytesOf = [](const XfStage& st) { return text_scratch_bytes(st.nBlocks, st.maxLen, st.blockSize); },
+               .launch = [](const StageCall& k) { launch_text_inverse(k.s, k.st, k.ws); return 0; } },
       .setsType = true },
 };
 
@@ -777,8 +796,8 @@ static int run_stage(Ctx* c, hipStream_t s, const XfInfo& x, bool forward, const
     return fork_join(c, s, parts, d.split == SPLIT_THREADS,
                      [&](int k, hipStream_t q) { return d.launch({ c, q, part[k], ws[k], bytes[k], lane_pinned(c, at(k)) }); },
                      [&](int k, hipStream_t q) {
-                         if (d.wsBytes == nullptr) return 0;
-                         bytes[k] = d.wsBytes(part[k].nBlocks, st.maxLen);
+                         if (d.wsBytes == nullptr && d.wsBytesOf == nullptr) return 0;
+                         bytes[k] = d.wsBytesOf ? d.wsBytesOf(part[k]) : d.wsBytes(part[k].nBlocks, st.maxLen);
                          return ws_get(c, lane_ws(x.ws, at(k)), bytes[k], &ws[k], q);
                      });
 }
@@ -909,6 +928,7 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
         }
         XfStage st = xf_stage(w, nBlocks, (u32)S, p->entropy_type);
         st.dtype = wantType ? w.a.dtype : nullptr;
+        st.blockSize = streamBlockSize ? streamBlockSize : (framing ? bs : 0u);
         if (int r = run_stage(c, s, *ch.xf[i], true, st)) return r;
         launch_seq_fwd_commit(s, w.a, nBlocks, i);
     }
@@ -1198,6 +1218,7 @@ static int decode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, uint64_
                 st.bsVersion = bsVersion;
                 st.maxCap = std::max(capMid, capFinal);
                 st.capModel = framing ? capMid : 0;
+                st.blockSize = streamBlockSize ? streamBlockSize : (framing ? bs : 0u);
                 if (int r = run_stage(c, sp, *ch.xf[i], false, st, lane)) return r;
                 launch_seq_inv_commit(sp, w.a, blk, nb, i, ch.tok[i]);
             }
@@ -1362,7 +1383,7 @@ int knz_hip_range_divide(knz_ctx* ctx, const uint64_t* d, const uint64_t* r, uin
 }
 
 static int transform_host(Ctx* c, int t, int forward, const uint8_t* in, int32_t n, uint8_t* out, int32_t dstCap, int etype,
-                          int32_t* outLen, int32_t* ok, int bsVersion = 6, int32_t* dataType = nullptr)
+                          int32_t* outLen, int32_t* ok, int bsVersion = 6, int32_t* dataType = nullptr, u32 streamBlockSize = 0)
 {
     CTX_LOCK(c);
     ProfInstall pi_(c);
@@ -1391,6 +1412,7 @@ static int transform_host(Ctx* c, int t, int forward, const uint8_t* in, int32_t
     XfStage st = xf_stage(w, 1, (u32)n, etype);
     st.maxCap = (u32)dstCap;
     st.bsVersion = bsVersion;
+    st.blockSize = streamBlockSize;
     u8 hdt = 0;
     if (dataType) {
         if (*dataType < 0 || *dataType > 9) return fail(c, KNZ_ERR_INVALID_PARAM, "data type %d out of range", *dataType);
@@ -1444,6 +1466,23 @@ int knz_hip_transform_inverse_v(knz_ctx* ctx, int transform_type, int bs_version
     const int v = (bs_version == 0) ? 6 : bs_version;
     if (v < 0 || v > 6) return fail(c, KNZ_ERR_STREAM_VERSION, "cannot read bitstream version %d", v);
     return transform_host(c, transform_type, 0, in, n, out, dst_cap, -1, out_len, ok, v);
+}
+
+int knz_hip_transform_forward_bs(knz_ctx* ctx, int transform_type, uint32_t stream_block_size, const uint8_t* in, int32_t n, uint8_t* out,
+                                 int32_t dst_cap, int entropy_type, int32_t* data_type, int32_t* out_len, int32_t* ok)
+{
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!data_type) return fail(c, KNZ_ERR_INVALID_PARAM, "no data type");
+    return transform_host(c, transform_type, 1, in, n, out, dst_cap, entropy_type, out_len, ok, 6, data_type, stream_block_size);
+}
+
+int knz_hip_transform_inverse_bs(knz_ctx* ctx, int transform_type, int bs_version, uint32_t stream_block_size, int entropy_type,
+                                 const uint8_t* in, int32_t n, uint8_t* out, int32_t dst_cap, int32_t* out_len, int32_t* ok)
+{
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    const int v = (bs_version == 0) ? 6 : bs_version;
+    if (v < 0 || v > 6) return fail(c, KNZ_ERR_STREAM_VERSION, "cannot read bitstream version %d", v);
+    return transform_host(c, transform_type, 0, in, n, out, dst_cap, entropy_type, out_len, ok, v, nullptr, stream_block_size);
 }
 
 }  // extern "C"

@@ -8,7 +8,7 @@ inline int knz_max_encoded_len(int t, int n)
     switch (t) {
     case KNZ_T_BWT: return n + 33;                                                     // BWTBlockCodec.hpp:47-50
     case KNZ_T_SRT: return n + 1024;                                                   // SRT.hpp:38
-    case KNZ_T_PACK: return n + 1024;                                                  // AliasCodec.hpp:52-55
+    case KNZ_T_PACK: case KNZ_T_DNA: return n + 1024;                                                  // AliasCodec.hpp:52-55
     case KNZ_T_MM: return n + (n < 1024 ? 64 : n >> 4);                                // FSDCodec.hpp:45-48
     case KNZ_T_RLT: return (n <= 512) ? n + 32 : n;                                    // RLT.hpp:43
     case KNZ_T_LZ: case KNZ_T_LZX: return ((n <= 1024) ? n + 16 : n + n / 64) + 2;     // LZCodec.hpp:91-95

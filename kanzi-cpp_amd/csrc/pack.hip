@@ -136,6 +136,7 @@ __global__ __launch_bounds__(PK_T) void k_pk_f_init(XfStage st, u32* scratch, si
     if (st.dtype) {
         const int dt = st.dtype[b];
         if (dt == DT_MULTIMEDIA || dt == DT_UTF8 || dt == DT_EXE || dt == DT_BIN) mode = PK_NONE;
+        if (st.onlyDNA && dt != DT_UNDEFINED && dt != DT_DNA) mode = PK_NONE;                   // AliasCodec.cpp:66 (the DNA transform)
     }
     info->mode = mode;
     info->ok = 0;
@@ -187,8 +188,10 @@ __global__ __launch_bounds__(PK_T) void k_pk_f_decide(XfStage st, u32* scratch, 
             if (dt == DT_UNDEFINED) {
                 dt = pk_simple_type(n, f0);
                 if (st.dtype && dt != DT_UNDEFINED) st.dtype[b] = (u8)dt;
+                if (st.onlyDNA && dt != DT_DNA) mode = PK_NONE;                                 // AliasCodec.cpp:93: the type is written first
             }
-            if (nAbsent == 255) mode = PK_ONE;
+            if (mode == PK_NONE) ;
+            else if (nAbsent == 255) mode = PK_ONE;
             else if (nAbsent >= 252) mode = PK_BITS2;
             else if (nAbsent >= 240) mode = PK_BITS4;
         }

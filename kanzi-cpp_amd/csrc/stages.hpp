@@ -75,7 +75,9 @@ struct XfStage {
     u32 capModel = 0;        // inverse: the capacity of the reference's buffer where cap[] is smaller (the last inverse stage of a stream writes
                              // into the caller's buffer, one block size per block, while the reference decodes into a buffer with slack):
                              // UTF and EXE, whose verdicts depend on the capacity, judge by max(cap, capModel) and write within cap. 0: cap[] is all
-    u8* dtype = nullptr;     // per-block Global::DataType (0 = UNDEFINED) read and written by PACK, MM, UTF, ROLZX and EXE; nullptr: a fresh context per block
+    u8* dtype = nullptr;     // per-block Global::DataType (0 = UNDEFINED) read and written by PACK, MM, UTF, ROLZX, EXE and TEXT; nullptr: a fresh context per block
+    u32 onlyDNA = 0;         // PACK forward as the DNA transform (AliasCodec with packOnlyDNA): blocks that are not DNA are refused
+    u32 blockSize = 0;       // the stream's block size (the "blockSize" of the reference's Context): TEXT sizes its hash map by it. 0: none given
 };
 
 // zrlt_mtft.hip
@@ -134,6 +136,14 @@ size_t utf_scratch_bytes(int nBlocks, u32 maxLen);
 void launch_exe_forward(hipStream_t s, const XfStage& st, void* scratch);
 void launch_exe_inverse(hipStream_t s, const XfStage& st, void* scratch);
 size_t exe_scratch_bytes(int nBlocks, u32 maxLen);
+
+// text.hip (TextCodec, both word-index encodings, chosen by XfStage::entropyType; scratch: text_scratch_bytes(nBlocks, maxLen, blockSize)
+// bytes -- a hash map sized by the stream's block size, up to 2^19 entries and two words per possible word for each block that runs at
+// once, bounded by KNZ_TEXT_TABLES_MAX: the launchers run a larger batch in slices and clear the tables on the stream; reads and
+// writes XfStage::dtype; the inverse judges by max(cap, capModel) like UTF's; no host synchronisation)
+void launch_text_forward(hipStream_t s, const XfStage& st, void* scratch);
+void launch_text_inverse(hipStream_t s, const XfStage& st, void* scratch);
+size_t text_scratch_bytes(int nBlocks, u32 maxLen, u32 blockSize);
 
 // fpaq.hip (probs: fpaq_probs_bytes(nBlocks, S) bytes of scratch, S = upper bound of the block lengths)
 void launch_fpaq_encode(hipStream_t s, BlockView view, const u32* origLen, u32 copyThreshold, int nBlocks, int maxChunks, ChunkDesc* desc, u8* tmp, u64 tmpStride,

@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libknz_hip.so")
 E_NONE, E_HUFFMAN, E_FPAQ, E_RANGE, E_ANS0, E_CM, E_TPAQ, E_ANS1, E_TPAQX = 0, 1, 2, 4, 5, 6, 7, 8, 9
 BINARY_CODERS = (E_CM, E_TPAQ, E_TPAQX)          # knz_hip_encode_bound is a first tier for these (include/knz_hip.h)
 ENTROPY_IDS = {"NONE": 0, "HUFFMAN": 1, "FPAQ": 2, "RANGE": 4, "ANS0": 5, "CM": 6, "TPAQ": 7, "ANS1": 8, "TPAQX": 9}
-TRANSFORM_IDS = {"NONE": 0, "BWT": 1, "BWTS": 2, "LZ": 3, "RLT": 5, "ZRLT": 6, "MTFT": 7, "RANK": 8, "EXE": 9, "ROLZX": 12, "SRT": 13, "LZP": 14, "MM": 15, "LZX": 16, "UTF": 17, "PACK": 18, "TIMESTAMP": 64}
+TRANSFORM_IDS = {"NONE": 0, "BWT": 1, "BWTS": 2, "LZ": 3, "RLT": 5, "ZRLT": 6, "MTFT": 7, "RANK": 8, "EXE": 9, "TEXT": 10, "ROLZX": 12, "SRT": 13, "LZP": 14, "MM": 15, "LZX": 16, "UTF": 17, "PACK": 18, "DNA": 19, "TIMESTAMP": 64}
 
 SYMBOLS = [
     "knz_hip_device_count", "knz_hip_create", "knz_hip_destroy", "knz_hip_last_error", "knz_hip_encode_bound",
@@ -23,6 +23,7 @@ SYMBOLS = [
     "knz_hip_tune", "knz_hip_transform_supported", "knz_hip_shift_bits", "knz_hip_encode_block_hosted", "knz_hip_decode_block_hosted",
     "knz_hip_entropy_decode_v", "knz_hip_transform_inverse_v", "knz_hip_range_divide",
     "knz_hip_entropy_encode_bs", "knz_hip_entropy_decode_bs", "knz_hip_tpaq_params",
+    "knz_hip_transform_forward_bs", "knz_hip_transform_inverse_bs",
 ]
 
 
@@ -89,6 +90,10 @@ def lib():
                                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.knz_hip_transform_forward_dt.argtypes = [vp, C.c_int, C.c_char_p, C.c_int32, u8p, C.c_int32, C.c_int,
                                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.knz_hip_transform_forward_bs.argtypes = [vp, C.c_int, C.c_uint32, C.c_char_p, C.c_int32, u8p, C.c_int32, C.c_int,
+                                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.knz_hip_transform_inverse_bs.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_char_p, C.c_int32, u8p, C.c_int32,
+                                                   C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.knz_hip_malloc.argtypes = [vp, sz, C.POINTER(vp)]
         L.knz_hip_free.argtypes = [vp, vp]
         L.knz_hip_memcpy_h2d.argtypes = [vp, vp, C.c_char_p, sz]
@@ -217,6 +222,24 @@ class Context:
         e = ENTROPY_IDS[entropy.upper()] if entropy else -1
         self._chk(self.L.knz_hip_transform_forward_dt(self.h, t, data, len(data), out, dst_cap, e, C.byref(dt), C.byref(ol), C.byref(ok)))
         return ok.value, C.string_at(out, ol.value), dt.value
+
+    def transform_forward_bs(self, transform, data, dst_cap, data_type, entropy, stream_block_size):
+        """transform_forward_dt with the block size of the stream the block belongs to (TEXT sizes its hash map by it)."""
+        t = TRANSFORM_IDS[transform.upper()]
+        out = (C.c_uint8 * (max(dst_cap, len(data)) + 2048))()
+        ol, ok, dt = C.c_int32(0), C.c_int32(0), C.c_int32(data_type)
+        e = ENTROPY_IDS[entropy.upper()] if entropy else -1
+        self._chk(self.L.knz_hip_transform_forward_bs(self.h, t, stream_block_size, data, len(data), out, dst_cap, e, C.byref(dt), C.byref(ol), C.byref(ok)))
+        return ok.value, C.string_at(out, ol.value), dt.value
+
+    def transform_inverse_bs(self, transform, data, dst_cap, entropy, stream_block_size, bs_version=0):
+        """The inverse stage with the stream's entropy coder and block size (TEXT reads both)."""
+        t = TRANSFORM_IDS[transform.upper()]
+        out = (C.c_uint8 * (dst_cap + 64))()
+        ol, ok = C.c_int32(0), C.c_int32(0)
+        e = ENTROPY_IDS[entropy.upper()] if entropy else -1
+        self._chk(self.L.knz_hip_transform_inverse_bs(self.h, t, bs_version, stream_block_size, e, data, len(data), out, dst_cap, C.byref(ol), C.byref(ok)))
+        return ok.value, C.string_at(out, ol.value)
 
     def transform_inverse(self, transform, data, dst_cap, bs_version=0):
         t = TRANSFORM_IDS[transform.upper()]

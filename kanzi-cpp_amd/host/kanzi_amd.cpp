@@ -829,25 +829,41 @@ static bool chainIsHostBound(uint64 ttype)
 extern "C" int knz_hip_transform_supported(int transform_type) __attribute__((weak));
 static bool deviceRunsUtf() { return knz_hip_transform_supported != nullptr && knz_hip_transform_supported(KNZ_T_UTF) != 0; }
 
-// Leading stages of a chain that run on the host: the leading run of TEXT / UTF stages up to and including its last TEXT (TEXT is the
-// only stage without a device version; a UTF in front of it has to run where it runs). Every UTF behind that prefix is a device stage,
-// in any position: "UTF+..." has no hosted stage and is batched, "TEXT+UTF+..." runs TEXT here and UTF on the device (from the data
-// type TEXT left, knz_host_stages.reserved), "UTF+TEXT+..." runs both here. TEXT behind a device stage has no place to run: refused.
-// Bound to a device library without the UTF stage, UTF is a host stage like TEXT: the whole leading run, and refused anywhere else.
-static int hostedStagesOf(uint64 ttype, int ids[8])
+// Whether TEXT runs as a device stage: the device library has it (an older one answers 0 and nothing changes), and KNZ_HOST_TEXT=1 (read
+// once) does not ask for the host path of before, which is there for A/B runs.
+static int hostTextKnob() { static const int v = getenv("KNZ_HOST_TEXT") != nullptr ? atoi(getenv("KNZ_HOST_TEXT")) : -1; return v; }
+static bool deviceRunsText() { return hostTextKnob() <= 0 && deviceRunsUtf() && knz_hip_transform_supported(KNZ_T_TEXT) != 0; }
+// Whether a chain whose TEXT stages all lead it is decoded on the device too. The device's forward pass is parallel but for the walk
+// over the words; its inverse is one wave per block and, measured end to end on streams of levels 5 and 6, no faster than
+// hoststage::textInverse behind the device chain ("TEXT on the device"): such streams are decoded as before unless
+// KNZ_HOST_TEXT=0 asks for the device. TEXT behind a device stage has no host path and is decoded on the device.
+static bool deviceDecodesLeadingText() { return hostTextKnob() == 0; }
+
+// Leading stages of a chain that run on the host. With TEXT on the device there are none when encoding: a chain with TEXT in any position
+// is batched like any other (decoding: deviceDecodesLeadingText above). One exception: the device refuses LZ / LZX behind a stage that sets the data type, which TEXT does, so a chain whose
+// TEXT stages all lead it and that has LZ or LZX further on keeps the hosted path below (it works there, and goes on working).
+// The hosted path: the leading run of TEXT / UTF stages up to and including its last TEXT runs here (a UTF in front of a TEXT has to run
+// where it runs). Every UTF behind that prefix is a device stage, in any position: "UTF+..." has no hosted stage and is batched,
+// "TEXT+UTF+..." runs TEXT here and UTF on the device (from the data type TEXT left, knz_host_stages.reserved), "UTF+TEXT+..." runs both
+// here. TEXT behind a device stage has no place to run there: refused. Bound to a device library without the UTF stage, UTF is a host
+// stage like TEXT: the whole leading run, and refused anywhere else.
+static int hostedStagesOf(uint64 ttype, int ids[8], bool decoding)
 {
     const bool utfOnDevice = deviceRunsUtf();
     int n = 0, k = 0;
-    bool leading = true;
+    bool leading = true, textBehind = false, lz = false;
     for (int i = 0; i < 8; i++) {
         const int t = int((ttype >> (42 - 6 * i)) & 63);
         if (t == 0) continue;
         ids[k++] = t;
         if (t != KNZ_T_TEXT && t != KNZ_T_UTF) leading = false;
+        if (t == KNZ_T_LZ || t == KNZ_T_LZX) lz = true;
         if (t != KNZ_T_TEXT && (utfOnDevice || t != KNZ_T_UTF)) continue;
-        if (!leading) throw std::invalid_argument(utfOnDevice ? "TEXT behind a device transform is not supported" : "TEXT / UTF behind a device transform is not supported");
+        if (!leading) { textBehind = true; continue; }
         n = k;
     }
+    if (deviceRunsText() && (textBehind || (!lz && (!decoding || n == 0 || deviceDecodesLeadingText())))) return 0;
+    if (textBehind) throw std::invalid_argument(utfOnDevice ? "TEXT behind a device transform is not supported" : "TEXT / UTF behind a device transform is not supported");
     return n;
 }
 
@@ -995,6 +1011,7 @@ TransformSequence<T>* TransformFactory<T>::newTransform(Context& ctx, uint64 fun
             case BWT_TYPE: transforms[nbtr++] = new BWTBlockCodec(ctx); break;
             case BWTS_TYPE: transforms[nbtr++] = new BWTS(ctx); break;
             case PACK_TYPE: transforms[nbtr++] = new AliasCodec(ctx); break;
+            case DNA_TYPE: ctx.putInt("packOnlyDNA", 1); transforms[nbtr++] = new AliasCodec(ctx); break;      // (TransformFactory.hpp:293-294)
             case MM_TYPE: transforms[nbtr++] = new FSDCodec(ctx); break;
             case MTFT_TYPE: transforms[nbtr++] = new SBRT(SBRT::MODE_MTF, ctx); break;
             case RANK_TYPE: transforms[nbtr++] = new SBRT(SBRT::MODE_RANK, ctx); break;
@@ -1539,9 +1556,10 @@ void CompressedOutputStream::init(int tasks, const std::string& entropy, const s
     if (e && atoi(e) > 0) _batchBlocks = atoi(e);
     // one device call takes at most 2 GiB of input (32-bit positions on the device side)
     { const int64_t lim = (int64_t(1) << 31) / int64_t(blockSize) - 1; if (_batchBlocks > lim) _batchBlocks = int(lim < 1 ? 1 : lim); }
-    // chains with TEXT in their leading TEXT / UTF stages (the level presets 5 and 6): those stages run on the host, block by block, and
+    // chains with TEXT go to the device in batches like any other (hostedStagesOf gives 0). Where it gives more -- a device library
+    // without TEXT, KNZ_HOST_TEXT=1, or LZ / LZX behind a leading TEXT -- those leading stages run on the host, block by block, and
     // every block goes to the device on its own (its length after them differs from block to block)
-    _hosted = hostedStagesOf(_transformType, _hostIds);
+    _hosted = hostedStagesOf(_transformType, _hostIds, false);
     if (_hosted) _batchBlocks = 1;
     _blockId = 0;
     _pendingByte = 0; _pendingBits = 0; _written = 0;
@@ -1928,7 +1946,7 @@ void CompressedInputStream::init(int tasks, const std::string& entropy, const st
         if ((blockSize < 1024) || (blockSize > 1024 * 1024 * 1024) || ((blockSize & -16) != blockSize)) throw std::invalid_argument("Invalid block size");
         _entropyType = EntropyEncoderFactory::getType(entropy.c_str());
         _transformType = TransformFactory<byte>::getType(transform.c_str());
-        _hosted = hostedStagesOf(_transformType, _hostIds);
+        _hosted = hostedStagesOf(_transformType, _hostIds, true);
         _spreadCopies = chainIsHostBound(_transformType);
     }
     _batchBlocks = std::max(tasks, 64);               // clamped to 256 MiB / 2 GiB once the block size is known
@@ -2028,7 +2046,7 @@ void CompressedInputStream::readHeader()
     _entropyType = short(get(5));
     try { EntropyEncoderFactory::getName(_entropyType); } catch (const std::invalid_argument&) { throw IOException("Invalid bitstream, unknown entropy type", Error::ERR_INVALID_CODEC); }
     _transformType = get(48);
-    _hosted = hostedStagesOf(_transformType, _hostIds);
+    _hosted = hostedStagesOf(_transformType, _hostIds, true);
     _spreadCopies = chainIsHostBound(_transformType);
     try { TransformFactory<byte>::getName(_transformType); } catch (const std::invalid_argument&) { throw IOException("Invalid bitstream, unknown transform type", Error::ERR_INVALID_CODEC); }
     _blockSize = int(get(28) << 4);

@@ -4,13 +4,11 @@
 //   kanzi_amd_cli -c -i FILE [-o FILE.knz] [-t TRANSFORMS] [-e ENTROPY] [-l LEVEL] [-b SIZE] [-j JOBS] [-x | -x32 | -x64] [-f]
 //   kanzi_amd_cli -d -i FILE.knz [-o FILE] [-j JOBS] [--from=N] [--to=N] [-f]
 //
-// -e takes NONE, HUFFMAN, ANS0, ANS1, FPAQ, RANGE, CM, TPAQ and TPAQX (every entropy coder of the reference). Levels 0, 1, 5 and 6 are in (5 and 6: TEXT on the host in front of the device chain, host/text_codec.cpp; UTF behind it runs on the device).
-// What it does not do (and says so instead of guessing): directories, stdin/stdout, `-y` info, levels whose chains need the
-// reference's CPU-only transforms (DNA, ROLZ), or LZ / LZX behind EXE, PACK or MM (the device LZ
-// stages do not read the data type those leave, which level 3 needs): levels 2-4 and 7-9. EXE, PACK, MM, LZP, UTF and ROLZX themselves run on the
-// device (ROLZ proper, id 11, does not and is refused by name; -t, in any position behind the host stage: -t LZP+UTF+BWT+RANK+ZRLT works); level 7 (LZP+TEXT+UTF+BWT+LZP / CM) has LZP, UTF, BWT
-// and CM on the device and waits for one thing only: TEXT, the last host stage, behind a device stage. Levels 8 and 9
-// (EXE+RLT+TEXT+UTF+DNA / TPAQ, TPAQX: EXE, RLT, UTF and the coders run on the device) wait for TEXT behind a device stage and for DNA.
+// -e takes NONE, HUFFMAN, ANS0, ANS1, FPAQ, RANGE, CM, TPAQ and TPAQX (every entropy coder of the reference). Levels 0, 1 and 5 to 9 are in (TEXT and UTF run on the device like every other stage, csrc/text.hip; KNZ_HOST_TEXT=1 puts a leading TEXT back on the host, host/text_codec.cpp).
+// Levels 7, 8 and 9 are in as well (LZP+TEXT+UTF+BWT+LZP / CM; EXE+RLT+TEXT+UTF+DNA / TPAQ and TPAQX), with the reference's default blocks of 16, 16 and 32 MiB.
+// What it does not do (and says so instead of guessing): directories, stdin/stdout, `-y` info, levels whose chains need ROLZ proper
+// (id 11, refused by name) or LZ / LZX behind a stage that sets the data type (the device LZ stages do not read it): levels 2, 3 and 4.
+// EXE, PACK, DNA, MM, LZP, UTF, TEXT and ROLZX run on the device, -t takes them in any position.
 // Files written here are byte-identical to `kanzi -c` with the same -t/-e/-b/-x/-j, and either tool reads the other's files
 // (tests/test_host_stub.py, tests/test_gpu_host_api.py).
 #include <algorithm>
@@ -44,7 +42,7 @@ static long long parseSize(const std::string& v)
 static int usage(const char* msg)
 {
     if (msg) fprintf(stderr, "%s\n", msg);
-    fprintf(stderr, "usage: kanzi_amd_cli -c|-d -i FILE [-o FILE] [-t TRANSFORMS] [-e ENTROPY] [-l 0|1|5|6] [-b SIZE] [-j JOBS] [-x|-x32|-x64] [--from=N] [--to=N] [-f]\n");
+    fprintf(stderr, "usage: kanzi_amd_cli -c|-d -i FILE [-o FILE] [-t TRANSFORMS] [-e ENTROPY] [-l 0|1|5|6|7|8|9] [-b SIZE] [-j JOBS] [-x|-x32|-x64] [--from=N] [--to=N] [-f]\n");
     return Error::ERR_MISSING_PARAM;
 }
 
@@ -86,9 +84,12 @@ int main(int argc, char** argv)
         // BlockCompressor.cpp:556-613
         if (level == 0) { transform = "NONE"; entropy = "NONE"; }
         else if (level == 1) { transform = "LZX"; entropy = "NONE"; }
-        else if (level == 5) { transform = "TEXT+UTF+BWT+RANK+ZRLT"; entropy = "ANS0"; }      // TEXT runs on the host, the rest on the device
+        else if (level == 5) { transform = "TEXT+UTF+BWT+RANK+ZRLT"; entropy = "ANS0"; }      // (every stage on the device)
         else if (level == 6) { transform = "TEXT+UTF+BWT+SRT+ZRLT"; entropy = "FPAQ"; if (!blockGiven) block = 8 << 20; }      // (BlockCompressor.cpp:121-124: 8 MiB blocks by default)
-        else { fprintf(stderr, "level %d needs transforms that only exist in the CPU reference (DNA / ROLZ: levels 2, 4, 8, 9), LZX behind PACK / MM (level 3) or TEXT behind a device stage (levels 7, 8, 9); use -t/-e\n", level); return Error::ERR_INVALID_CODEC; }
+        else if (level == 7) { transform = "LZP+TEXT+UTF+BWT+LZP"; entropy = "CM"; if (!blockGiven) block = 16 << 20; }      // (BlockCompressor.cpp:125-128: 16 MiB blocks by default)
+        else if (level == 8) { transform = "EXE+RLT+TEXT+UTF+DNA"; entropy = "TPAQ"; if (!blockGiven) block = 16 << 20; }
+        else if (level == 9) { transform = "EXE+RLT+TEXT+UTF+DNA"; entropy = "TPAQX"; if (!blockGiven) block = 32 << 20; }
+        else { fprintf(stderr, "level %d needs ROLZ, which only exists in the CPU reference (levels 2, 4), or LZ / LZX behind a stage that sets the data type (levels 2, 3); use -t/-e\n", level); return Error::ERR_INVALID_CODEC; }
     }
     if (transform.empty()) transform = "NONE";
     if (entropy.empty()) entropy = "NONE";
