@@ -19,7 +19,7 @@
 //     * medium groups (257..8192) are (start, length) descriptors (found through staging slots, no atomics); one workgroup sorts a
 //       group in LDS: majority-key split or a stable LSD radix sort (8-bit digits, ranking by ballot matching inside a wave),
 //     * a group whose majority key is its OWN label (a periodic stretch whose period divides h) is finished in one round by pointer
-//       jumping along its chains (k_bwt_f_super),
+//       jumping along its chains (med_chain_round inside k_bwt_f_medium_fused; k_bwt_f_super where the groups are listed),
 //     * large groups go through one global radix sort of (descriptor index, key) pairs.
 //   A round sorts on the labels as they stood when it began (a refined head read beside an unrefined one would order two suffixes that
 //   are still equal): the keys of medium and large groups are gathered by kernels of their own before anything moves; the small groups
@@ -96,7 +96,7 @@ enum FwdCounter : u32 {
     CNT_RUN = 4,                 // run groups (round 0)
     CNT_RUN_MEMBERS = 5,         // their members
     CNT_RUN_LONGEST = 6,         // longest run (run round)
-    CNT_SUPER = 7,               // groups listed for the chain round (k_bwt_f_super)
+    CNT_SUPER = 7,               // groups that take the chain round (listed: k_bwt_f_super reads it)
     CNT_RUNS = 8,                // runs of run-group bytes (run round)
     CNT_MED_LO = 9,              // medium descriptors of the lower size class, up to MED_LO_CAP members (k_bwt_f_med_compact)
     CNT_STAT_SMALL = 10,         // small members worked on (knob bwt_stats)
@@ -1173,6 +1173,17 @@ __global__ __launch_bounds__(256) void k_bwt_f_med_sleep(FwdView v, uint2* __res
     }
 }
 
+// threadIdx.x as a value the optimiser cannot trace to threadIdx.x: nothing computed from it is merged with, or hoisted to, code outside
+// the function that asks for it (no instruction is emitted)
+__device__ __forceinline__ int local_tid()
+{
+    int t = (int)threadIdx.x;
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(KNZ_EMU)
+    asm volatile("" : "+v"(t));
+#endif
+    return t;
+}
+
 // LDS of one sorting workgroup of THREADS threads: up to ROWS elements per thread
 template <int THREADS, int ROWS>
 struct MedLds {
@@ -1277,7 +1288,10 @@ template <int THREADS, int ROWS>
 __device__ __forceinline__ void med_write_back(MedLds<THREADS, ROWS>& L, const FwdView& v, u32 gs, u32 n, uint2* __restrict__ medNext, uint2* __restrict__ largeNext)
 {
     constexpr u32 CAP = (u32)ROWS * THREADS;
-    const int tid = (int)threadIdx.x, lane = tid & 63;
+    // (the thread's index, hidden from the optimiser: what it derives from it per row here -- word, bit, masks, slots -- is then computed
+    // where it is used. Otherwise all of it is hoisted out of the caller's loop over the groups and lives in registers through every other
+    // phase of that loop: k_bwt_f_medium_fused<512, 16> spilled 92 B per lane for it, and <256, 8> began to once the chain round ran there)
+    const int tid = local_tid(), lane = tid & 63;
     // ---- subgroup boundaries of the sorted keys as a bit map in LDS + per-word summaries
     const int nWords = (int)((n + 31) >> 5);
     if (tid < (int)(CAP / 32)) {
@@ -1416,12 +1430,167 @@ __device__ __forceinline__ void med_majority_write_back(MedLds<THREADS, ROWS>& L
     if (__ballot(surv != 0) != 0 && (tid & 63) == 0) v.counters[CNT_SMALL_LEFT] = 1;
 }
 
+// The chain round (see k_bwt_f_super, whose sort this is, key for key) on a group that is in LDS already: oK / oV [0, n) = keys and
+// positions in position order, m = the group's own label as a key, link = the offset the keys were gathered at. It needs no LDS beyond
+// the group's own, because what it adds is never live together with what it replaces:
+//   - a member's link and chain length are one word, (successor's index | steps << 16), and take the place of its position in oV once every
+//     binary search has read the positions (the links wait in registers for that); the final re-gather reads the positions from SA, which
+//     nothing has written yet;
+//   - a member whose key is m has its successor in the group, so the chain ends are at most the others, n - c <= n / 2 <= CAP / 2 of them.
+//     Their (key, index) pairs are sorted in the lower halves of oK / oV -- the keys pass through oV's upper half, since oK is read until
+//     every member knows on which side of m its end's key lies -- and the ends' ranks, one word per member index, fill the two upper halves.
+// A thread keeps one word per member throughout: end's index | chain length << 16 | (end's key below m) << 31, then the sort key, then the
+// position. Returns false, with oK / oV untouched, when the ends would not fit half the capacity (members with key m whose successor is not
+// in the group: that would be a group out of position order); the caller then refines the group the ordinary way. Returns true with
+// the group sorted in oK / oV (positions) for med_write_back. Entered and left with the workgroup in step.
+template <int THREADS, int ROWS>
+__device__ __forceinline__ bool med_chain_round(MedLds<THREADS, ROWS>& L, const FwdView& v, u32 gs, u32 n, u32 m, u32 link, int npass)
+{
+    constexpr u32 CAP = (u32)ROWS * THREADS, HALF = CAP / 2;
+    static_assert(CAP <= 0x2000u, "index and chain length of a member: 13 bits each");
+    __shared__ u32 sEnds, sAt, sCmax, sMoved[2];
+    const int tid = (int)threadIdx.x, lane = tid & 63;
+    const unsigned long long ltMask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    if (tid == 0) { sEnds = 0; sAt = 0; sCmax = 0; }
+    __syncthreads();
+    u32 w[ROWS];
+    // ---- chain links: the member `link` further on (first index with position >= target)
+    {
+        u32 nE = 0;
+#pragma unroll
+        for (int r = 0; r < ROWS; r++) {
+            const u32 i = (u32)tid + (u32)r * THREADS;
+            w[r] = i;
+            if (i < n) {
+                bool found = false;
+                if (L.oK[i] == m) {
+                    const u32 target = L.oV[i] + link;
+                    u32 lo = i + 1, hi = n;
+                    if (lo < n && L.oV[lo] == target) hi = lo;     // (inside a stretch whose period is the link the next member is the one: no search)
+                    while (lo < hi) { const u32 mid = (lo + hi) >> 1; if (L.oV[mid] < target) lo = mid + 1; else hi = mid; }
+                    if (lo < n && L.oV[lo] == target) { w[r] = lo | (1u << 16); found = true; }
+                }
+                nE += found ? 0u : 1u;
+            }
+        }
+        nE = wave_sum(nE);
+        if (lane == 0 && nE) atomicAdd(&sEnds, nE);
+    }
+    __syncthreads();
+    const u32 nEnds = sEnds;
+    if (nEnds > HALF) return false;                        // (uniform; the next call's reset of sEnds lies behind the caller's barriers)
+#pragma unroll
+    for (int r = 0; r < ROWS; r++) { const u32 i = (u32)tid + (u32)r * THREADS; if (i < n) L.oV[i] = w[r]; }
+    __syncthreads();
+    // ---- pointer jumping: chain end and chain length of every member (until no link moves any more)
+    for (u32 span = 1, it = 0; span < n; span <<= 1, it ^= 1) {
+        bool moved = false;
+#pragma unroll
+        for (int r = 0; r < ROWS; r++) {
+            const u32 i = (u32)tid + (u32)r * THREADS;
+            if (i < n) {
+                // (two hops a pass: the reach triples, and a pass is two barriers of all waves)
+                const u32 wi = L.oV[i], j = wi & 0xFFFFu, wj = L.oV[j], k = wj & 0xFFFFu, wk = L.oV[k];
+                w[r] = (wk & 0xFFFFu) | (((wi >> 16) + (wj >> 16) + (wk >> 16)) << 16);
+                moved = moved || ((wk & 0xFFFFu) != k);
+            }
+        }
+        if (tid == 0) sMoved[it] = 0;                              // (two flags in turn: the other one may still be read by a slow thread)
+        __syncthreads();
+        if (moved) sMoved[it] = 1;
+#pragma unroll
+        for (int r = 0; r < ROWS; r++) { const u32 i = (u32)tid + (u32)r * THREADS; if (i < n) L.oV[i] = w[r]; }
+        __syncthreads();
+        if (!sMoved[it]) break;
+    }
+    // (w = what oV holds for the thread's members, and nobody reads oV any more)
+    // ---- the side of every member's end; the chain ends compacted (any order): indexes to oV [0, nEnds), keys to oV [HALF, HALF + nEnds)
+    {
+        u32 cm = 0;
+#pragma unroll
+        for (int r = 0; r < ROWS; r++) {
+            const u32 i = (u32)tid + (u32)r * THREADS;
+            const bool in = i < n;
+            const u32 cc = w[r] >> 16;
+            const u32 tail = in ? L.oK[w[r] & 0xFFFFu] : m;
+            if (in && tail < m) w[r] |= 0x80000000u;
+            cm = (in && cc > cm) ? cc : cm;
+            const bool isEnd = in && cc == 0;
+            const unsigned long long bal = __ballot(isEnd);
+            u32 base0 = 0;
+            if (lane == 0 && bal) base0 = atomicAdd(&sAt, (u32)__popcll(bal));
+            base0 = (u32)__shfl((int)base0, 0, 64);
+            if (isEnd) { const u32 at = base0 + (u32)__popcll(bal & ltMask); L.oV[at] = i; L.oV[HALF + at] = tail; }
+        }
+        cm = wave_max(cm);
+        if (lane == 0 && cm) atomicMax(&sCmax, cm);
+    }
+    __syncthreads();
+    for (u32 j = (u32)tid; j < nEnds; j += THREADS) L.oK[j] = L.oV[HALF + j];
+    __syncthreads();
+    // (the members' words wait in the upper halves while the ends are sorted, by index like the ranks that replace them, so that the
+    // sort's registers do not come on top of them)
+#pragma unroll
+    for (int r = 0; r < ROWS; r++) { const u32 i = (u32)tid + (u32)r * THREADS; if (r < ROWS / 2) L.oK[HALF + i] = w[r]; else L.oV[i] = w[r]; }      // (i < HALF in the first half of the rows)
+    // ---- the ends sorted by key
+    if (nEnds <= (u32)THREADS) {
+        u32 kk = 0, vv = 0, at = 0;
+        if ((u32)tid < nEnds) {
+            kk = L.oK[tid]; vv = L.oV[tid];
+            for (u32 j = 0; j < nEnds; j++) { const u32 kj = L.oK[j]; at += (kj < kk || (kj == kk && j < (u32)tid)) ? 1u : 0u; }
+        }
+        __syncthreads();
+        if ((u32)tid < nEnds) { L.oK[at] = kk; L.oV[at] = vv; }
+        __syncthreads();
+    } else {
+        med_radix_sort<THREADS, ROWS>(L, nEnds, npass);
+    }
+#pragma unroll
+    for (int r = 0; r < ROWS; r++) { const u32 i = (u32)tid + (u32)r * THREADS; w[r] = (r < ROWS / 2) ? L.oK[HALF + i] : L.oV[i]; }
+    __syncthreads();
+    // rank of an end's key = first index with that key, kept by the end's index: [0, HALF) in oK's upper half, [HALF, CAP) in oV's
+    for (u32 j = (u32)tid; j < nEnds; j += THREADS) {
+        const u32 key = L.oK[j];
+        u32 lo = 0, hi = j;
+        while (lo < hi) { const u32 mid = (lo + hi) >> 1; if (L.oK[mid] < key) lo = mid + 1; else hi = mid; }
+        const u32 e = L.oV[j];
+        if (e < HALF) L.oK[HALF + e] = lo; else L.oV[e] = lo;
+    }
+    __syncthreads();
+    // ---- one sort of all members on (chain length or its mirror, rank of the end's key), as wide as the longest chain and the ends ask for
+    const u32 cmax = sCmax;
+    const u32 trBits = bitlen_u32(nEnds ? nEnds - 1 : 0), hiBits = bitlen_u32(2u * cmax + 1u);
+#pragma unroll
+    for (int r = 0; r < ROWS; r++) {
+        const u32 i = (u32)tid + (u32)r * THREADS;
+        if (i < n) {
+            const u32 e = w[r] & 0xFFFFu, cc = (w[r] >> 16) & 0x7FFFu;
+            const u32 hiKey = (w[r] >> 31) ? cc : (2u * cmax + 1u - cc);
+            w[r] = (hiKey << trBits) | (e < HALF ? L.oK[HALF + e] : L.oV[e]);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < ROWS; r++) { const u32 i = (u32)tid + (u32)r * THREADS; if (i < n) { L.oK[i] = w[r]; L.oV[i] = i; } }
+    __syncthreads();
+    med_radix_sort<THREADS, ROWS>(L, n, (int)((hiBits + trBits + 7) / 8));
+#pragma unroll
+    for (int r = 0; r < ROWS; r++) { const u32 i = (u32)tid + (u32)r * THREADS; if (i < n) w[r] = v.SA[gs + L.oV[i]]; }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < ROWS; r++) { const u32 i = (u32)tid + (u32)r * THREADS; if (i < n) L.oV[i] = w[r]; }
+    __syncthreads();
+    return true;
+}
+
 // The refinement of one group whose keys and positions are in LDS (oK / oV [0, n), position order; the workgroup in step behind the
-// stores): chain-round listing, majority split or radix sort, write-back. info = (block base, the members' label). storeKeys: the keys
-// are nowhere but in LDS (k_bwt_f_medium_fused), so a group listed for the chain round, which reads them from K, stores them there first.
+// stores): chain round, majority split or radix sort, write-back. info = (block base, the members' label). A group whose majority looks at
+// the group itself takes the chain round: in place (med_chain_round; chainLink = the offset its keys were gathered at, from
+// k_bwt_f_medium_fused) or, chainLink == 0, listed for k_bwt_f_super. storeKeys: the keys are nowhere but in LDS (k_bwt_f_medium_fused), so
+// a group listed for the chain round, which reads them from K, stores them there first.
 // Left with the workgroup in step.
 template <int THREADS, int ROWS, bool STATS>
-__device__ __forceinline__ void med_sort_group(MedLds<THREADS, ROWS>& L, const FwdView& v, u32 gs, u32 n, uint2 info, int npass, bool storeKeys,
+__device__ __forceinline__ void med_sort_group(MedLds<THREADS, ROWS>& L, const FwdView& v, u32 gs, u32 n, uint2 info, int npass, bool storeKeys, u32 chainLink,
                                                uint2* __restrict__ medNext, uint2* __restrict__ largeNext, uint4* __restrict__ superList)
 {
     constexpr int WAVES = THREADS / 64;
@@ -1434,15 +1603,20 @@ __device__ __forceinline__ void med_sort_group(MedLds<THREADS, ROWS>& L, const F
     u32 c = 0;
     for (u32 i = (u32)tid; i < n; i += THREADS) c += (L.oK[i] == m) ? 1u : 0u;
     c = med_block_sum(L, c);
+    bool chained = false;
     if (c < n && 2 * c >= n && n <= SUPER_CAP && m == info.y - info.x + 1u) {
-        // the majority looks at the group itself (a periodic stretch whose period divides h): k_bwt_f_super finishes it in one round
-        if (tid == 0) { const u32 at = atomicAdd(&v.counters[CNT_SUPER], 1u); superList[at] = make_uint4(gs, n, info.x, info.y); }
-        if (storeKeys) for (u32 i = (u32)tid; i < n; i += THREADS) v.K[gs + i] = L.oK[i];
-        __syncthreads();
-        return;
+        // the majority looks at the group itself (a periodic stretch whose period divides h): the chain round finishes it in one round
+        if (chainLink == 0u) {
+            if (tid == 0) { const u32 at = atomicAdd(&v.counters[CNT_SUPER], 1u); superList[at] = make_uint4(gs, n, info.x, info.y); }
+            if (storeKeys) for (u32 i = (u32)tid; i < n; i += THREADS) v.K[gs + i] = L.oK[i];
+            __syncthreads();
+            return;
+        }
+        chained = med_chain_round<THREADS, ROWS>(L, v, gs, n, m, chainLink, npass);
+        if (chained && tid == 0) atomicAdd(&v.counters[CNT_SUPER], 1u);
     }
     if (STATS && tid == 0 && c == n) { atomicAdd(&v.counters[CNT_STAT_UNSPLIT], 1u); atomicAdd(&v.counters[CNT_STAT_UNSPLIT_MEMBERS], n); }
-    if (c < n) {
+    if (c < n && !chained) {
         if (2 * c >= n) {
             // ---- stable split: [others (nOth)][members with key m (c)]
             const int R = (int)((n + THREADS - 1) / THREADS);
@@ -1562,7 +1736,7 @@ __global__ __launch_bounds__(THREADS, (THREADS >= 1024 ? 4 : THREADS / 128)) voi
             for (int r = 0; r < ROWS; r++) { const u32 i = (u32)tid + (u32)r * THREADS; if (i < n) { L.oK[i] = k[r]; L.oV[i] = p[r]; } }
         }
         __syncthreads();
-        med_sort_group<THREADS, ROWS, STATS>(L, v, gs, n, info, npass, false, medNext, largeNext, superList);
+        med_sort_group<THREADS, ROWS, STATS>(L, v, gs, n, info, npass, false, 0u, medNext, largeNext, superList);
     }
 }
 
@@ -1575,7 +1749,7 @@ __global__ __launch_bounds__(THREADS, (THREADS >= 1024 ? 4 : THREADS / 128)) voi
 // the chain round) and nothing through descInfo. skip == 0 (knob bwt_no_unsplit_skip): every group is sorted.
 template <int THREADS, int ROWS, bool STATS>
 __global__ __launch_bounds__(THREADS, 4) void k_bwt_f_medium_fused(FwdView v, const uint2* __restrict__ desc, const u32* __restrict__ classIdx, u32 nClass, u32 h, int npass,
-                                                               int skip, uint2* __restrict__ medNext, uint2* __restrict__ largeNext, uint4* __restrict__ superList)
+                                                               int skip, int chainList, uint2* __restrict__ medNext, uint2* __restrict__ largeNext, uint4* __restrict__ superList)
 {
     constexpr u32 CAP = (u32)ROWS * THREADS;
     __shared__ MedLds<THREADS, ROWS> L;
@@ -1627,7 +1801,7 @@ __global__ __launch_bounds__(THREADS, 4) void k_bwt_f_medium_fused(FwdView v, co
         for (int r = 0; r < ROWS; r++) { const u32 i = (u32)tid + (u32)r * THREADS; if (i < n) { L.oK[i] = key[r]; L.oV[i] = gp[r]; } }
         __syncthreads();
         if (tid == 0) sDiff = 0;                            // (every thread has read it; the barriers of the sort lie in front of the next group's verdict)
-        med_sort_group<THREADS, ROWS, STATS>(L, v, gs, n, make_uint2(bb, lab), npass, true, medNext, largeNext, superList);
+        med_sort_group<THREADS, ROWS, STATS>(L, v, gs, n, make_uint2(bb, lab), npass, true, chainList ? 0u : off, medNext, largeNext, superList);
     }
 }
 
@@ -2671,17 +2845,18 @@ __global__ __launch_bounds__(256) void k_bwt_f_med_compact(uint2* __restrict__ s
 // knobs (tests, diagnostics): read from the environment once per process, or set through knz_hip_tune(). Each one forces, at test
 // sizes, a path that some inputs take by themselves (round-0 key length, no run round, the run groups' fall-back, the plain labels of
 // blocks above 256 MiB, the plain keys of blocks above 8 MiB, where the link step starts), or reports (stats).
-struct FwdTuning { int nsym; int noRunRound; int runFallback; int stats; int link; int plainLabels; int noPack; int noUnsplitSkip; int noGroupSleep; int noMediumFuse; int runSort; };
+struct FwdTuning { int nsym; int noRunRound; int runFallback; int stats; int link; int plainLabels; int noPack; int noUnsplitSkip; int noGroupSleep; int noMediumFuse; int runSort; int chainList; };
 static FwdTuning& fwd_tuning()
 {
     static FwdTuning t = [] {
-        FwdTuning x; x.nsym = 0; x.noRunRound = 0; x.runFallback = 0; x.stats = 0; x.link = 1; x.plainLabels = 0; x.noPack = 0; x.noUnsplitSkip = 0; x.noGroupSleep = 0; x.noMediumFuse = 0; x.runSort = 0;     // link: 0 off, 1 on (from h = 32), n > 1: from h = n
+        FwdTuning x; x.nsym = 0; x.noRunRound = 0; x.runFallback = 0; x.stats = 0; x.link = 1; x.plainLabels = 0; x.noPack = 0; x.noUnsplitSkip = 0; x.noGroupSleep = 0; x.noMediumFuse = 0; x.runSort = 0; x.chainList = 0;     // link: 0 off, 1 on (from h = 32), n > 1: from h = n
         if (getenv("KNZ_BWT_PLAIN_LABELS")) x.plainLabels = 1;
         if (getenv("KNZ_BWT_NO_PACK")) x.noPack = 1;
         if (getenv("KNZ_BWT_NO_UNSPLIT_SKIP")) x.noUnsplitSkip = 1;
         if (getenv("KNZ_BWT_NO_GROUP_SLEEP")) x.noGroupSleep = 1;
         if (getenv("KNZ_BWT_NO_MEDIUM_FUSE")) x.noMediumFuse = 1;
         if (const char* e = getenv("KNZ_BWT_RUN_SORT")) x.runSort = atoi(e);
+        if (const char* e = getenv("KNZ_BWT_CHAIN_LIST")) x.chainList = atoi(e);
         if (const char* e = getenv("KNZ_BWT_LINK")) x.link = atoi(e);
         if (getenv("KNZ_BWT_STATS")) x.stats = 1;
         if (const char* e = getenv("KNZ_BWT_NSYM")) x.nsym = atoi(e);
@@ -2706,6 +2881,7 @@ int bwt_forward_tune(const char* key, int value)
     else if (!strcmp(key, "bwt_no_group_sleep")) t.noGroupSleep = value;        // every such group gathered in every round (no k_bwt_f_med_sleep, no records)
     else if (!strcmp(key, "bwt_no_medium_fuse")) t.noMediumFuse = value;        // medium groups through k_bwt_f_gather_desc and k_bwt_f_sort_medium on versioned labels too
     else if (!strcmp(key, "bwt_run_sort")) t.runSort = value;                   // 1: the run round's members generated and sorted (k_bwt_f_run_members, _expand), not placed directly
+    else if (!strcmp(key, "bwt_chain_list")) t.chainList = value;               // 1: k_bwt_f_medium_fused lists the chain round's groups for k_bwt_f_super (keys through K), not in place
     else return -1;
     return 0;
 }
@@ -3106,15 +3282,16 @@ struct FwdSort {
             const auto fuse256 = tune.stats ? k_bwt_f_medium_fused<256, 8, true> : k_bwt_f_medium_fused<256, 8, false>;
             const auto fuse512 = tune.stats ? k_bwt_f_medium_fused<512, 16, true> : k_bwt_f_medium_fused<512, 16, false>;
             // (whole multiples of 8 workgroups, one eighth of a class per XCD; four and two workgroups per CU at once)
-            if (nMedLo) hipLaunchKernelGGL(fuse256, dim3(std::min<u32>((nMedLo + 7) / 8 * 8, 2048)), dim3(256), 0, s, v, w.med[cur], w.medIdxLo, nMedLo, h, npass, skip, w.med[nxt], w.large[nxt], w.superList);
-            if (nMedHi) hipLaunchKernelGGL(fuse512, dim3(std::min<u32>((nMedHi + 7) / 8 * 8, 1024)), dim3(512), 0, s, v, w.med[cur], w.medIdxHi, nMedHi, h, npass, skip, w.med[nxt], w.large[nxt], w.superList);
+            if (nMedLo) hipLaunchKernelGGL(fuse256, dim3(std::min<u32>((nMedLo + 7) / 8 * 8, 2048)), dim3(256), 0, s, v, w.med[cur], w.medIdxLo, nMedLo, h, npass, skip, tune.chainList ? 1 : 0, w.med[nxt], w.large[nxt], w.superList);
+            if (nMedHi) hipLaunchKernelGGL(fuse512, dim3(std::min<u32>((nMedHi + 7) / 8 * 8, 1024)), dim3(512), 0, s, v, w.med[cur], w.medIdxHi, nMedHi, h, npass, skip, tune.chainList ? 1 : 0, w.med[nxt], w.large[nxt], w.superList);
         } else { KScope ks_("k_bwt_f_sort_medium"); const dim3 gridM(std::min<u32>(nMed, 8192));
           const auto sort256 = tune.stats ? k_bwt_f_sort_medium<256, 8, true> : k_bwt_f_sort_medium<256, 8, false>;
           const auto sort512 = tune.stats ? k_bwt_f_sort_medium<512, 16, true> : k_bwt_f_sort_medium<512, 16, false>;
           hipLaunchKernelGGL(sort256, gridM, dim3(256), 0, s, v, w.med[cur], nMed, npass, SM_G, w.med[nxt], w.large[nxt], w.descInfo, w.superList);
           hipLaunchKernelGGL(sort512, gridM, dim3(512), 0, s, v, w.med[cur], nMed, npass, MED_LO_CAP, w.med[nxt], w.large[nxt], w.descInfo, w.superList); }
-        // groups whose majority looks at the group itself (sort_medium has listed them; the kernel reads the count itself)
-        { KScope ks_("k_bwt_f_super"); hipLaunchKernelGGL(k_bwt_f_super, dim3(std::min<u32>(nMed, 512)), dim3(1024), 0, s, v, w.superList, h, npass, w.med[nxt], w.large[nxt]); }
+        // groups whose majority looks at the group itself, where sort_medium has listed them (the kernel reads the count itself);
+        // k_bwt_f_medium_fused finishes them in place (knob bwt_chain_list: lists them)
+        if (!medFuse || tune.chainList) { KScope ks_("k_bwt_f_super"); hipLaunchKernelGGL(k_bwt_f_super, dim3(std::min<u32>(nMed, 512)), dim3(1024), 0, s, v, w.superList, h, npass, w.med[nxt], w.large[nxt]); }
     }
     // large groups: (descriptor index, key) pairs, KEY = u32 where kbits + lbits bits fit. The keys are gathered before any kernel of the
     // round changes a label; the sort and the placement come after the small and medium groups.
