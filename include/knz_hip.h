@@ -271,6 +271,27 @@ KNZ_API int knz_hip_transform_supported(int transform_type);
  * decoder has checked before it divides: r >= 1 and d < r * 2^15). */
 KNZ_API int knz_hip_range_divide(knz_ctx* ctx, const uint64_t* d, const uint64_t* r, uint32_t n, uint32_t* q);
 
+/* Test hooks: the device-wide primitives of csrc/prims.hpp by themselves (prefix scans over 32-bit words, segmented stable LSD radix sort).
+ * out[0..3] = keys per radix tile (RS_TILE), tiles per group of the column scan (RS_GROUP), words per scan tile (SC_TILE), passes the
+ * one-read sort counts ahead (RS_MAXPASS): the sizes at which the kernels change path. Needs no context and no device. */
+KNZ_API int knz_hip_prims_info(uint32_t out[4]);
+/* op 0: d_out[i] = d_in[0] + .. + d_in[i-1] (wraps at 32 bits), 1: max of d_in[0..i], 2: min of d_in[0..i], for i < n, where
+ * n = min(n_max, *d_n) when d_n (a device word) is given and n_max when it is NULL. d_in and d_out are device arrays of n_max words,
+ * 16-byte aligned, and may be the same array; words of d_out from n on are left alone. d_total (device word, or NULL; op 0 only) receives
+ * the sum of the n words -- 0 when *d_n is 0. n_max = 0 launches nothing and writes nothing. The scan's scratch is allocated by the call, which
+ * runs on the context's stream and returns when the result is there. */
+KNZ_API int knz_hip_prims_scan(knz_ctx* ctx, int op, const uint32_t* d_in, uint32_t* d_out, size_t n_max, const uint32_t* d_n, uint32_t* d_total);
+/* Sorts every segment [d_seg_base[g], d_seg_base[g + 1]) (g < n_seg; d_seg_base[0] = 0, ascending, no segment longer than max_seg_len)
+ * of the keys (key_bytes 4 or 8) stably on key bits [lo_bit, hi_bit), and moves d_vals (32-bit; NULL when has_val = 0) along.
+ * one_read 1: one kernel per pass that learns the counts of the tiles in front of it by look-back (fails when the knob "rs_onesweep" is 0),
+ * 0: a counting kernel, a column scan and a scatter per pass. keep 0: prims::rs_sort on a copy of the input; 1: prims::rs_sort_keep, which
+ * reads the caller's arrays directly and must leave them as they are. The result always lands in d_keys_out / d_vals_out (no overlap with the
+ * input). The call allocates the sort's workspace (exactly rs_ws_bytes of the key count and n_seg) and its ping-pong arrays with 4 KiB of
+ * a fixed byte pattern in front of and behind each, and returns an error when a byte of a pattern has changed. It runs on the context's
+ * stream and returns when the result is there. */
+KNZ_API int knz_hip_prims_sort(knz_ctx* ctx, int key_bytes, int has_val, int keep, int one_read, const void* d_keys, const uint32_t* d_vals,
+                               const uint32_t* d_seg_base, int n_seg, size_t max_seg_len, int lo_bit, int hi_bit, void* d_keys_out, uint32_t* d_vals_out);
+
 /* Test hook: the sizes the TPAQ (extra = 0) / TPAQX (extra = 1) predictor takes for a block of block_len bytes (behind the
  * transforms) in a stream of block size stream_block_size, bitstream version 6: sizes[0..5] = bytes of the big states table, mixers,
  * words of the position hash, bytes of the ring buffer, contexts of the first and of the second SSE map. Needs no context and no device. */

@@ -1382,6 +1382,35 @@ int knz_hip_range_divide(knz_ctx* ctx, const uint64_t* d, const uint64_t* r, uin
     return 0;
 }
 
+int knz_hip_prims_info(uint32_t out[4])
+{
+    if (out == nullptr) return KNZ_ERR_INVALID_PARAM;
+    prims_probe_info(out);
+    return 0;
+}
+
+int knz_hip_prims_scan(knz_ctx* ctx, int op, const uint32_t* d_in, uint32_t* d_out, size_t n_max, const uint32_t* d_n, uint32_t* d_total)
+{
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    CTX_LOCK(c);
+    HIPCHK(c, hipSetDevice(c->device));
+    char msg[256] = { 0 };
+    const int r = prims_probe_scan(c->stream, op, d_in, d_out, n_max, d_n, d_total, msg, sizeof(msg));
+    return r ? fail(c, r, "knz_hip_prims_scan: %s", msg) : 0;
+}
+
+int knz_hip_prims_sort(knz_ctx* ctx, int key_bytes, int has_val, int keep, int one_read, const void* d_keys, const uint32_t* d_vals,
+                       const uint32_t* d_seg_base, int n_seg, size_t max_seg_len, int lo_bit, int hi_bit, void* d_keys_out, uint32_t* d_vals_out)
+{
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    CTX_LOCK(c);
+    HIPCHK(c, hipSetDevice(c->device));
+    char msg[256] = { 0 };
+    const int r = prims_probe_sort(c->stream, key_bytes, has_val, keep, one_read, d_keys, d_vals, d_seg_base, n_seg, max_seg_len, lo_bit, hi_bit,
+                                   d_keys_out, d_vals_out, msg, sizeof(msg));
+    return r ? fail(c, r, "knz_hip_prims_sort: %s", msg) : 0;
+}
+
 static int transform_host(Ctx* c, int t, int forward, const uint8_t* in, int32_t n, uint8_t* out, int32_t dstCap, int etype,
                           int32_t* outLen, int32_t* ok, int bsVersion = 6, int32_t* dataType = nullptr, u32 streamBlockSize = 0)
 {

@@ -3,7 +3,7 @@
 // the LZ match finder. Every size a kernel needs can be read from device memory (`nDev`, `base[]`), so that a sequence of
 // launches does not need the host to read a counter back in between.
 //
-// Sort pass = four launches: tile histograms (one row of 256 counters per tile of 4096 keys, coalesced), a column scan
+// Sort pass = four launches: tile histograms (one row of 256 counters per tile of RS_TILE keys, coalesced), a column scan
 // of the rows in two levels (inside groups of RS_GROUP tiles, then over the groups and the digits), and the scatter:
 // the tile's keys are ranked inside the workgroup (ballot matching inside a wave, rows in order; per-wave digit counters
 // scanned in (digit, wave) order), staged through LDS in sorted order and written out as runs of consecutive addresses.
@@ -78,12 +78,13 @@ __global__ __launch_bounds__(256) void k_scan_reduce(const u32* __restrict__ in,
 // one workgroup of 256 threads scans a short array in place (exclusive for the sum, which is what the tiles need as their
 // carry; for max / min the carry of tile t is the inclusive result of tile t-1, i.e. also "exclusive")
 template <int OP>
-__global__ __launch_bounds__(256) void k_scan_carries(u32* __restrict__ partial, u32 nMax, const u32* __restrict__ nDev)
+__global__ __launch_bounds__(256) void k_scan_carries(u32* __restrict__ partial, u32 nMax, const u32* __restrict__ nDev, u32* __restrict__ totalOut)
 {
     __shared__ u32 wsum[4];
     __shared__ u32 inclAll[256];
     const u32 n = nDev ? (*nDev < nMax ? *nDev : nMax) : nMax;
     const u32 nT = (n + SC_TILE - 1) / SC_TILE;
+    if (n == 0 && totalOut != nullptr && threadIdx.x == 0) *totalOut = 0;      // no tile of k_scan_apply runs: the empty sum is written here
     u32 carry = sc_ident<OP>();
     for (u32 c0 = 0; c0 < nT; c0 += 256 * 16) {
         u32 x[16];
@@ -152,8 +153,10 @@ __global__ __launch_bounds__(256) void k_scan_apply(const u32* __restrict__ in, 
 
 static inline size_t scan_tmp_bytes(size_t nMax) { return (((nMax + SC_TILE - 1) / SC_TILE) * 4 + 255 + 256) & ~(size_t)255; }
 
-// out[i] = scan of in[0..i) (sum) or in[0..i] (max / min); in == out allowed; both 16-byte aligned. n = min(nMax, *nDev) when nDev
-// is given. totalOut (optional, sum only): the sum of all n values.
+// out[i] = scan of in[0..i) (sum) or in[0..i] (max / min) for i < n; in == out allowed; both 16-byte aligned. n = min(nMax, *nDev) when
+// nDev is given (a device word, read by the kernels), else nMax. Words of out from n on are left as they are. Sums wrap at 32 bits.
+// totalOut (optional, sum only): the sum of all n values, also when *nDev is 0 -- out is untouched then and *totalOut = 0. nMax == 0
+// launches nothing and writes nothing, *totalOut included: a caller that passes a host-side 0 knows the total.
 template <int OP>
 static inline void launch_scan(hipStream_t s, const u32* in, u32* out, size_t nMax, const u32* nDev, void* tmp, u32* totalOut = nullptr)
 {
@@ -162,7 +165,7 @@ static inline void launch_scan(hipStream_t s, const u32* in, u32* out, size_t nM
     const u32 nT = (u32)((nMax + SC_TILE - 1) / SC_TILE);
     const u32 grid = nT < 4096 ? nT : 4096;
     hipLaunchKernelGGL((k_scan_reduce<OP>), dim3(grid), dim3(256), 0, s, in, (u32)nMax, nDev, partial);
-    hipLaunchKernelGGL((k_scan_carries<OP>), dim3(1), dim3(256), 0, s, partial, (u32)nMax, nDev);
+    hipLaunchKernelGGL((k_scan_carries<OP>), dim3(1), dim3(256), 0, s, partial, (u32)nMax, nDev, totalOut);
     hipLaunchKernelGGL((k_scan_apply<OP>), dim3(grid), dim3(256), 0, s, in, out, (u32)nMax, nDev, partial, totalOut);
 }
 
@@ -612,7 +615,8 @@ static inline void rs_launch_pass(hipStream_t s, const RsWs& w, SRC src, const u
 }
 
 // knob "rs_onesweep" (KNZ_RS_ONESWEEP): 1 = the one-read passes where a sort's passes are known ahead (default), 0 = count + scatter
-static inline std::atomic<int>& rs_onesweep_knob()
+// (inline, not static: ONE value for every translation unit of the library, so that knz_hip_tune reaches the sorts of all stages)
+inline std::atomic<int>& rs_onesweep_knob()
 {
     static std::atomic<int> v{ getenv("KNZ_RS_ONESWEEP") ? atoi(getenv("KNZ_RS_ONESWEEP")) : 1 };
     return v;
@@ -668,11 +672,11 @@ static inline int rs_sort(hipStream_t s, const RsWs& w, KEY* ka, KEY* kb, u32* v
 // The same with the input left untouched: the first pass reads (kin, vin), the others move between (kb, vb) and (kc, vc).
 // Returns 0 when the result is in (kb, vb), 1 when in (kc, vc).
 template <class KEY, bool HAS_VAL>
-static inline int rs_sort_keep(hipStream_t s, const RsWs& w, const KEY* kin, const u32* vin, KEY* kb, KEY* kc, u32* vb, u32* vc, size_t maxSegLen, int loBit, int hiBit)
+static inline int rs_sort_keep(hipStream_t s, const RsWs& w, const KEY* kin, const u32* vin, KEY* kb, KEY* kc, u32* vb, u32* vc, size_t maxSegLen, int loBit, int hiBit, bool oneRead = true)
 {
     int cur = -1;                                            // -1: input, 0: b, 1: c
     const int nPass = (hiBit - loBit + 7) / 8;
-    const bool os = rs_onesweep_knob().load() != 0 && nPass >= 1 && nPass <= RS_MAXPASS && maxSegLen < (size_t)RS_VAL_MASK;
+    const bool os = oneRead && rs_onesweep_knob().load() != 0 && nPass >= 1 && nPass <= RS_MAXPASS && maxSegLen < (size_t)RS_VAL_MASK;
     if (os) {
         DigitOfKey<KEY> src; src.keys = kin; src.shift = loBit; src.mask = 255u;
         const int rem = hiBit - loBit - 8 * (nPass - 1);

@@ -58,6 +58,12 @@ void launch_range_encode(hipStream_t s, BlockView view, const u32* origLen, u32 
 void launch_range_decode(hipStream_t s, BitSrc src, DecBlock* blocks, int nBlocks, u8* const* outPtr, int framing);
 void launch_range_div_probe(hipStream_t s, const u64* d, const u64* r, u32 n, u32* q);      // range_div on n pairs (tests)
 
+// prims_probe.hip (tests: the scans and the radix sort of prims.hpp by themselves; 0, or a code for the C ABI with its message in err)
+void prims_probe_info(u32 out[4]);
+int prims_probe_scan(hipStream_t s, int op, const u32* in, u32* out, size_t nMax, const u32* nDev, u32* totalOut, char* err, size_t errCap);
+int prims_probe_sort(hipStream_t s, int keyBytes, int hasVal, int keep, int oneRead, const void* keys, const u32* vals, const u32* segBase, int nSeg,
+                     size_t maxSegLen, int loBit, int hiBit, void* keysOut, u32* valsOut, char* err, size_t errCap);
+
 // One transform stage over a batch (all arrays are device arrays indexed by block).
 struct XfStage {
     const u8* const* src;

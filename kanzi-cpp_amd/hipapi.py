@@ -24,6 +24,7 @@ SYMBOLS = [
     "knz_hip_entropy_decode_v", "knz_hip_transform_inverse_v", "knz_hip_range_divide",
     "knz_hip_entropy_encode_bs", "knz_hip_entropy_decode_bs", "knz_hip_tpaq_params",
     "knz_hip_transform_forward_bs", "knz_hip_transform_inverse_bs",
+    "knz_hip_prims_info", "knz_hip_prims_scan", "knz_hip_prims_sort",
 ]
 
 
@@ -108,6 +109,9 @@ def lib():
         L.knz_hip_entropy_decode_bs.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, C.c_char_p, C.c_uint64, C.c_uint64, u8p, C.c_uint32,
                                                 C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
         L.knz_hip_tpaq_params.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint32)]
+        L.knz_hip_prims_info.argtypes = [C.POINTER(C.c_uint32)]
+        L.knz_hip_prims_scan.argtypes = [vp, C.c_int, vp, vp, sz, vp, vp]
+        L.knz_hip_prims_sort.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, sz, C.c_int, C.c_int, vp, vp]
         _lib = L
     return _lib
 
@@ -256,6 +260,17 @@ class Context:
         self._chk(self.L.knz_hip_range_divide(self.h, d.ctypes.data, r.ctypes.data, len(d), q.ctypes.data))
         return q
 
+    # ---- test hooks of csrc/prims.hpp, on device pointers (0 / None = absent)
+    def prims_scan(self, op, d_in, d_out, n_max, d_n=None, d_total=None):
+        """op 0: exclusive sum, 1: inclusive max, 2: inclusive min over min(n_max, *d_n) 32-bit words; d_in may equal d_out."""
+        self._chk(self.L.knz_hip_prims_scan(self.h, op, C.c_void_p(d_in), C.c_void_p(d_out), n_max, C.c_void_p(d_n or None), C.c_void_p(d_total or None)))
+
+    def prims_sort(self, key_bytes, has_val, keep, one_read, d_keys, d_vals, d_seg_base, n_seg, max_seg_len, lo_bit, hi_bit, d_keys_out, d_vals_out):
+        """Stable sort of every segment on key bits [lo_bit, hi_bit) into d_keys_out / d_vals_out; raises when a guard byte around the
+        sort's own buffers has changed."""
+        self._chk(self.L.knz_hip_prims_sort(self.h, key_bytes, int(has_val), int(keep), int(one_read), C.c_void_p(d_keys), C.c_void_p(d_vals or None),
+                                            C.c_void_p(d_seg_base), n_seg, max_seg_len, lo_bit, hi_bit, C.c_void_p(d_keys_out), C.c_void_p(d_vals_out or None)))
+
     # ---- profiling
     def set_profiling(self, on):
         self.L.knz_hip_set_profiling(self.h, 1 if on else 0)
@@ -264,6 +279,16 @@ class Context:
         arr = (KernelTime * 256)()
         n = self.L.knz_hip_get_kernel_times(self.h, arr, 256)
         return [(arr[i].name.decode(), arr[i].ms, arr[i].launches) for i in range(n)]
+
+
+def prims_info():
+    """(RS_TILE, RS_GROUP, SC_TILE, RS_MAXPASS) of csrc/prims.hpp: keys per radix tile, tiles per group of the column scan, words per scan
+    tile, passes the one-read sort counts ahead. Needs no device."""
+    out = (C.c_uint32 * 4)()
+    rc = lib().knz_hip_prims_info(out)
+    if rc != 0:
+        raise KnzError(rc, "knz_hip_prims_info")
+    return tuple(out)
 
 
 def tpaq_params(stream_block_size, block_len, extra):

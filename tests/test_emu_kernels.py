@@ -37,7 +37,9 @@ def write_case(path, blocks):
 def test_device_primitives_emulated(tmp_path):
     """csrc/prims.hpp -- the hand-written prefix scans and the segmented stable LSD radix sort that replaced rocPRIM -- against
     std::stable_sort / plain loops: u32 and u64 keys, with and without values, partial digits, empty / tiny / ragged segments,
-    constant and low-entropy digits (the one-digit fast path of the counting kernel), sizes from device memory."""
+    constant and low-entropy digits (the one-digit fast path of the counting kernel), sizes from device memory (0 among them), scans
+    in place, rs_sort_keep, and -- in every run below, on both paths -- segments of more than RS_GROUP tiles (the second level of the
+    column scan). The same primitives on the GPU: tests/test_gpu_prims.py."""
     exe = build("prims_emu", tmp_path)
     # the passes read their keys once (k_rs_hist_all + k_rs_onesweep: tiles learn their predecessors' counts by look-back; tiles are handed
     # out by a ticket counter, so any workgroup order will do -- HIPEMU_ORDER=2 is a permutation) or twice (k_rs_count + k_rs_scatter, KNZ_RS_ONESWEEP=0)
