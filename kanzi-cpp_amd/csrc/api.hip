@@ -248,6 +248,9 @@ int knz_hip_tune(const char* name, int value)
     if (!strcmp(name, "mtf_chain")) return mtft_tune_chain(value);
     if (!strcmp(name, "lz_serial_decode")) { lz_serial_decode(value ? 1 : 0); return 0; }
     if (!strcmp(name, "bwt_split")) { bwt_split_knob().store(value < 1 ? 1 : (value > 4 ? 4 : value)); return 0; }
+    if (!strcmp(name, "bwt_inv_jump_all")) return bwt_inverse_tune(0, value);
+    if (!strcmp(name, "bwt_inv_ruler_log")) return bwt_inverse_tune(1, value);
+    if (!strcmp(name, "bwt_inv_wide")) return bwt_inverse_tune(2, value);
     return bwt_forward_tune(name, value);
 }
 

@@ -16,6 +16,8 @@
 #include "stages.hpp"
 #include "bwt_common.hpp"
 
+#include <atomic>
+#include <cstdlib>
 #include <cstring>
 #include <algorithm>
 #include "prims.hpp"
@@ -34,7 +36,7 @@ struct BwtHdr { u32 n; u32 hdr; u32 pIdx; u32 okFlag; };
 struct InvInfo { u32 total; u32 nWords; u32 count; u32 dyn; u32 pad[4]; };      // device-resident sizes: no host read-back in this stage
 
 template <bool OLD>
-__global__ void k_bwt_i_header(BwtView v, BwtHdr* __restrict__ hd, u32* __restrict__ base, u8* __restrict__ ok, u32* __restrict__ newLen, InvInfo* __restrict__ info)
+__global__ void k_bwt_i_header(BwtView v, BwtHdr* __restrict__ hd, u32* __restrict__ base, u8* __restrict__ ok, u32* __restrict__ newLen, InvInfo* __restrict__ info, u32 wide)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     u32 sum = 0;
@@ -111,7 +113,8 @@ __global__ void k_bwt_i_header(BwtView v, BwtHdr* __restrict__ hd, u32* __restri
     info->total = sum; info->nWords = (sum + 31) / 32; info->count = 0; info->dyn = 0;
     u32 longest = 0;
     for (int b = 0; b < v.nBlocks; b++) if (hd[b].okFlag && hd[b].n > longest) longest = hd[b].n;
-    info->pad[2] = longest;                          // (decides the width of the link records: inv_narrow)
+    // (decides the width of the link records: inv_narrow; knob "bwt_inv_wide": reported as a block no 4-byte record holds)
+    info->pad[2] = wide ? 0xFFFFFFFFu : longest;
 }
 
 // Link records (round 6). A record is the next node, "the next node is a splitter" and the node's symbol. With positions relative to the
@@ -119,7 +122,7 @@ __global__ void k_bwt_i_header(BwtView v, BwtHdr* __restrict__ hd, u32* __restri
 // sort scatters, half the working set of the walk), 8-byte words otherwise. The stage has no host read-back, so both forms of the two
 // kernels are launched and the one the batch's longest block (InvInfo::pad[2]) does not ask for returns at once.
 constexpr u32 INV_NARROW_MAX = 1u << 23;
-__device__ __forceinline__ bool inv_narrow(const InvInfo* info) { return info->pad[2] <= INV_NARROW_MAX; }
+__host__ __device__ __forceinline__ bool inv_narrow(const InvInfo* info) { return info->pad[2] <= INV_NARROW_MAX; }
 template <class REC> struct InvRec;
 template <> struct InvRec<u64> {
     static __device__ __forceinline__ u64 make(u32 nx, u32 bb, bool split, u32 sym) { (void)bb; return (u64)nx | (split ? 0x80000000ull : 0ull) | ((u64)sym << 32); }
@@ -629,6 +632,24 @@ size_t bwt_inverse_scratch_bytes(int nBlocks, u32 VS, size_t total)
     return inv_carve(nullptr, nBlocks, VS, total, &w) + 4096;
 }
 
+// knobs (knz_hip_tune; the environment gives the initial values): "bwt_inv_jump_all" (KNZ_BWT_I_JUMP_ALL; 1: pointer jumping over all rows,
+// rounds 3-4, instead of the rulers), "bwt_inv_ruler_log" (KNZ_BWT_I_RULER_LOG; one row in 2^k is a ruler, 2..8, anything else means 3),
+// "bwt_inv_wide" (KNZ_BWT_I_WIDE; 1: the 8-byte link records whatever the longest block is)
+static int env_int(const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; }
+static u32 ruler_log_of(int v) { return (v >= 2 && v <= 8) ? (u32)v : 3u; }
+static std::atomic<int>& inv_jump_all_knob() { static std::atomic<int> v(env_int("KNZ_BWT_I_JUMP_ALL") != 0 ? 1 : 0); return v; }
+static std::atomic<int>& inv_ruler_log_knob() { static std::atomic<int> v((int)ruler_log_of(env_int("KNZ_BWT_I_RULER_LOG"))); return v; }
+static std::atomic<int>& inv_wide_knob() { static std::atomic<int> v(env_int("KNZ_BWT_I_WIDE") != 0 ? 1 : 0); return v; }
+
+int bwt_inverse_tune(int knob, int value)
+{
+    if (knob == 0) inv_jump_all_knob().store(value ? 1 : 0);
+    else if (knob == 1) inv_ruler_log_knob().store((int)ruler_log_of(value));
+    else if (knob == 2) inv_wide_knob().store(value ? 1 : 0);
+    else return -1;
+    return 0;
+}
+
 int launch_bwt_inverse(hipStream_t s, const XfStage& st, void* scratch, size_t scratchBytes, u32* h_pinned)
 {
     (void)h_pinned;
@@ -642,8 +663,9 @@ int launch_bwt_inverse(hipStream_t s, const XfStage& st, void* scratch, size_t s
     // no size is read back: every grid is sized by the upper bound (blocks x longest block), the kernels take the sizes from `info`
     {
         KScope ks_("k_bwt_i_header");
-        if (st.bsVersion < 6) hipLaunchKernelGGL(k_bwt_i_header<true>, dim3(1), dim3(64), 0, s, v, w.hd, w.base, st.ok, st.newLen, w.info);
-        else hipLaunchKernelGGL(k_bwt_i_header<false>, dim3(1), dim3(64), 0, s, v, w.hd, w.base, st.ok, st.newLen, w.info);
+        const u32 wide = inv_wide_knob().load() ? 1u : 0u;
+        if (st.bsVersion < 6) hipLaunchKernelGGL(k_bwt_i_header<true>, dim3(1), dim3(64), 0, s, v, w.hd, w.base, st.ok, st.newLen, w.info, wide);
+        else hipLaunchKernelGGL(k_bwt_i_header<false>, dim3(1), dim3(64), 0, s, v, w.hd, w.base, st.ok, st.newLen, w.info, wide);
     }
     { KScope ks_("k_bwt_i_tiny"); hipLaunchKernelGGL(k_bwt_i_tiny, dim3((st.nBlocks + 63) / 64), dim3(64), 0, s, v, w.hd); }
     const dim3 gridT((unsigned)perTiles, st.nBlocks);
@@ -664,7 +686,7 @@ int launch_bwt_inverse(hipStream_t s, const XfStage& st, void* scratch, size_t s
     u32* nA = w.nA; u32* nB = w.nB; u32* dA = w.dA; u32* dB = w.dB;
     // chains never leave a block: a chain has at most rows-per-block rows
     const u64 chainRows = (u64)v.VS / 48 + (u64)v.VS / ROW + 4096 + 3;
-    static const bool allRowsJump = getenv("KNZ_BWT_I_JUMP_ALL") != nullptr && atoi(getenv("KNZ_BWT_I_JUMP_ALL")) != 0;   // the ranking of rounds 3-4
+    const bool allRowsJump = inv_jump_all_knob().load() != 0;                    // the ranking of rounds 3-4
     if (allRowsJump) {
         for (u64 span = 1; span < chainRows; span <<= 1) {
             { KScope ks_("k_bwt_i_jump"); hipLaunchKernelGGL(k_bwt_i_jump, GRID1(w.maxRows), nA, dA, w.info, w.maxRows, nB, dB); }
@@ -677,7 +699,7 @@ int launch_bwt_inverse(hipStream_t s, const XfStage& st, void* scratch, size_t s
         u32* rbits = w.rbits; u32* rprefix = w.rprefix;
         const u32 rWords = (w.maxRows + 31) / 32;
         u32* nRulers = &w.info->pad[0];
-        static const u32 rlog = []() { const char* e = getenv("KNZ_BWT_I_RULER_LOG"); const int v = e ? atoi(e) : 0; return (v >= 2 && v <= 8) ? (u32)v : 3u; }();
+        const u32 rlog = ruler_log_of(inv_ruler_log_knob().load());
         hipLaunchKernelGGL(k_bwt_i_ruler_flags, GRID1(rWords), w.hd, w.base, w.rowNode, w.rowBlk, nA, w.info, w.maxRows, rbits, rprefix, rlog);
         prims::launch_scan<prims::SCAN_SUM_EXCL>(s, rprefix, rprefix, rWords, nullptr, w.scanTmp, nRulers);
         hipMemsetAsync(nB, 0xFF, 4 * (size_t)w.maxRows, s);                      // owner: none
@@ -694,6 +716,13 @@ int launch_bwt_inverse(hipStream_t s, const XfStage& st, void* scratch, size_t s
     { KScope ks_("k_bwt_i_place");
       const u32 wantWg = (w.maxRows + 8 * PLACE_U - 1) / (8 * PLACE_U);
       hipLaunchKernelGGL(k_bwt_i_place, dim3(std::max(1u, std::min(wantWg, 16384u))), dim3(256), 0, s, v, w.hd, w.rowBlk, dA, w.rowLen, w.rows, w.info, w.maxRows); }
+    if (g_prof != nullptr) {
+        // with the timing of kernels on (knz_hip_set_profiling; tests), the one place where the stage reads a size back: the width of the
+        // link records, which only the device knows, as an entry of its own among the kernel times
+        InvInfo hi;
+        if (hipMemcpyAsync(&hi, w.info, sizeof(hi), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return -1;
+        KScope ks_(inv_narrow(&hi) ? "bwt_i_records_4_byte" : "bwt_i_records_8_byte");
+    }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

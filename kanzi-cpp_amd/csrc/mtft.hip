@@ -792,9 +792,9 @@ static void mtft_forward_t(hipStream_t s, const XfStage& st)
     { KScope ks_("k_mtf_f_last"); hipLaunchKernelGGL((k_mtf_f_last<MT>), grid, dim3(64), 0, s, v, perTiles, tileLast); }
     { KScope ks_("k_mtf_f_scan"); hipLaunchKernelGGL((k_mtf_f_scan<MT>), dim3(nSeg, st.nBlocks), dim3(256), 0, s, tileLast, perTiles, segT, nSeg, st.len, segMax);
       hipLaunchKernelGGL(k_mtf_f_scan2, dim3(st.nBlocks), dim3(256), 0, s, segMax, nSeg); }
-    { KScope ks_("k_mtf_f_rank");
-      if (g_mtfChainKnob.load()) hipLaunchKernelGGL((k_mtf_f_rank<MT>), grid, dim3(64), 0, s, v, perTiles, tileLast, segT, nSeg, segMax);
-      else hipLaunchKernelGGL((k_mtf_f_rank_par<MT>), grid, dim3(64), 0, s, v, perTiles, tileLast, segT, nSeg, segMax); }
+    // (the chain kernels have names of their own among the kernel times: a test can tell that the knob took)
+    if (g_mtfChainKnob.load()) { KScope ks_("k_mtf_f_rank_chain"); hipLaunchKernelGGL((k_mtf_f_rank<MT>), grid, dim3(64), 0, s, v, perTiles, tileLast, segT, nSeg, segMax); }
+    else { KScope ks_("k_mtf_f_rank"); hipLaunchKernelGGL((k_mtf_f_rank_par<MT>), grid, dim3(64), 0, s, v, perTiles, tileLast, segT, nSeg, segMax); }
 }
 
 void launch_mtft_forward(hipStream_t s, const XfStage& st)
@@ -812,9 +812,8 @@ static void mtft_inverse_t(hipStream_t s, const XfStage& st)
     const u32 segT = mtf_seg_tiles((u32)perTiles), nSeg = ((u32)perTiles + segT - 1) / segT;
     u8* segPerm = tilePerm + (size_t)st.nBlocks * perTiles * 256;                  // nBlocks * nSeg * 256 bytes
     { KScope ks_("k_copy_ok"); hipLaunchKernelGGL(k_copy_ok, dim3((st.nBlocks + 255) / 256), dim3(256), 0, s, st.len, st.cap, st.nBlocks, st.ok, st.newLen); }
-    { KScope ks_("k_mtf_i_symbolic");
-      if (g_mtfChainKnob.load()) hipLaunchKernelGGL((k_mtf_i_symbolic<MT>), dim3(perTiles, st.nBlocks), dim3(64), 0, s, v, perTiles, tilePerm);
-      else hipLaunchKernelGGL((k_mtf_i_symbolic_par<MT>), dim3(perTiles, st.nBlocks), dim3(64), 0, s, v, perTiles, tilePerm); }
+    if (g_mtfChainKnob.load()) { KScope ks_("k_mtf_i_symbolic_chain"); hipLaunchKernelGGL((k_mtf_i_symbolic<MT>), dim3(perTiles, st.nBlocks), dim3(64), 0, s, v, perTiles, tilePerm); }
+    else { KScope ks_("k_mtf_i_symbolic"); hipLaunchKernelGGL((k_mtf_i_symbolic_par<MT>), dim3(perTiles, st.nBlocks), dim3(64), 0, s, v, perTiles, tilePerm); }
     { KScope ks_("k_mtf_i_compose"); hipLaunchKernelGGL((k_mtf_i_compose<MT>), dim3(nSeg, st.nBlocks), dim3(256), 0, s, tilePerm, perTiles, segT, nSeg, st.len, segPerm);
       hipLaunchKernelGGL(k_mtf_i_compose2, dim3(st.nBlocks), dim3(256), 0, s, segPerm, nSeg); }
     { KScope ks_("k_mtf_i_resolve"); hipLaunchKernelGGL((k_mtf_i_resolve<MT>), dim3(perTiles, st.nBlocks), dim3(256), 0, s, v, perTiles, tilePerm, segT, nSeg, segPerm); }

@@ -102,6 +102,7 @@ int launch_bwt_inverse(hipStream_t s, const XfStage& st, void* scratch, size_t s
 size_t bwt_forward_scratch_bytes(int nBlocks, u32 VS, size_t total);
 size_t bwt_inverse_scratch_bytes(int nBlocks, u32 VS, size_t total);
 int bwt_forward_tune(const char* key, int value);          // developer knobs of the suffix sort (knz_hip_tune)
+int bwt_inverse_tune(int knob, int value);                 // knz_hip_tune: 0 "bwt_inv_jump_all", 1 "bwt_inv_ruler_log", 2 "bwt_inv_wide"
 
 // bwts.hip (these synchronise the stream like the BWT stages; cap >= len is all a block needs, blocks below 2 bytes are copied)
 int launch_bwts_forward(hipStream_t s, const XfStage& st, void* scratch, size_t scratchBytes, u32* h_pinned);

@@ -2,6 +2,8 @@
 // fed with the oracle's forward BWT block codec output, must reproduce the input. Test infrastructure only.
 //   usage: bwt_inv_emu <case file> [bitstream version]   (binary: u32 nBlocks, then per block u32 len + bytes; a version below 6 selects
 //   the block header of BWTBlockCodec.cpp:140-164 on both sides)
+//          bwt_inv_emu <case file> <bitstream version> raw   the blocks are taken as they are, not encoded first (per block u32 len, u32
+//   destination capacity, bytes): encoded blocks with damaged headers. Prints "block <i> ok <0|1> len <n>" per block; nothing is compared here.
 #include "hip/hip_runtime.h"
 #include "../../kanzi-cpp_amd/csrc/bwt.hip"
 
@@ -20,15 +22,25 @@ int main(int argc, char** argv)
     if (argc < 2) return 2;
     const int bsVersion = argc > 2 ? atoi(argv[2]) : 6;
     knzo_set_bs_version(bsVersion);
+    const bool raw = argc > 3 && !strcmp(argv[3], "raw");
     FILE* f = fopen(argv[1], "rb");
     if (!f) return 2;
     u32 nBlocks = 0;
     if (fread(&nBlocks, 4, 1, f) != 1) return 2;
     std::vector<std::vector<u8>> plain(nBlocks), enc(nBlocks), out(nBlocks);
+    std::vector<u32> rawCap(nBlocks, 0);
     u32 maxLen = 1;
     for (u32 b = 0; b < nBlocks; b++) {
         u32 n = 0;
         if (fread(&n, 4, 1, f) != 1) return 2;
+        if (raw) {
+            if (fread(&rawCap[b], 4, 1, f) != 1) return 2;
+            enc[b].resize(n);
+            if (n && fread(enc[b].data(), 1, n, f) != n) return 2;
+            out[b].assign(rawCap[b], 0xEE);                       // (exactly the capacity: a byte behind it is the sanitizer's to report)
+            maxLen = std::max(maxLen, n);
+            continue;
+        }
         plain[b].resize(n);
         if (n && fread(plain[b].data(), 1, n, f) != n) return 2;
         enc[b].resize(n + 64);
@@ -43,7 +55,7 @@ int main(int argc, char** argv)
     std::vector<const u8*> src(nBlocks); std::vector<u8*> dst(nBlocks);
     std::vector<u32> len(nBlocks), cap(nBlocks), newLen(nBlocks, 0);
     std::vector<u8> ok(nBlocks, 0);
-    for (u32 b = 0; b < nBlocks; b++) { enc[b].reserve(enc[b].size() + 64); src[b] = enc[b].data(); dst[b] = out[b].data(); len[b] = (u32)enc[b].size(); cap[b] = (u32)plain[b].size() + 16; }
+    for (u32 b = 0; b < nBlocks; b++) { enc[b].reserve(enc[b].size() + 64); src[b] = enc[b].data(); dst[b] = out[b].data(); len[b] = (u32)enc[b].size(); cap[b] = raw ? rawCap[b] : (u32)plain[b].size() + 16; }
     XfStage st;
     st.src = src.data(); st.dst = dst.data(); st.len = len.data(); st.cap = cap.data(); st.ok = ok.data(); st.newLen = newLen.data();
     st.nBlocks = (int)nBlocks; st.maxLen = maxLen; st.scratchU32 = nullptr; st.entropyType = -1; st.bsVersion = bsVersion;
@@ -53,6 +65,7 @@ int main(int argc, char** argv)
     u32 pinned[64];
     const int rc = launch_bwt_inverse(nullptr, st, sc, bytes, pinned);
     if (rc != 0) { printf("FAIL launch rc=%d\n", rc); return 1; }
+    if (raw) { for (u32 b = 0; b < nBlocks; b++) printf("block %u ok %d len %u\n", b, ok[b], newLen[b]); return 0; }
     if (emu_corrupt_on()) { int no = 0; for (u32 b = 0; b < nBlocks; b++) no += !ok[b]; printf("damaged input: %d of %u blocks refused\n", no, nBlocks); return 0; }
     int bad = 0;
     for (u32 b = 0; b < nBlocks; b++) {

@@ -423,3 +423,58 @@ def test_decoders_survive_damaged_input_emulated(tmp_path):
         jobs = [(name, ver, seed) for name, versions in runs for ver in versions for seed in range(1, 5)]
         for job, r in pool.map(one, jobs):
             assert r.returncode == 0 and "AddressSanitizer" not in r.stderr, (job, r.stdout[-500:] + r.stderr[-3000:])
+    # the BWT blocks with damaged headers of tests/golden/first_gen_damage.json, taken as they are (the driver's "raw" mode), into
+    # destinations of exactly the capacity: what k_bwt_i_header decides is the fixture's decision (the reference's) and length
+    import first_gen_damage as fgd
+    recs = [r for r in fgd.load()[0] if r["stage"] == "BWT"]
+    raw = str(tmp_path / "bwt_raw.bin")
+    write_raw_case(raw, recs)
+    r = subprocess.run([exes["bwt_inv_emu"], raw, "6", "raw"], capture_output=True, text=True, timeout=900,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0:detect_stack_use_after_return=0"))
+    assert r.returncode == 0 and "AddressSanitizer" not in r.stderr, r.stdout[-500:] + r.stderr[-3000:]
+    check_raw_answers(r.stdout, recs)
+
+
+def write_raw_case(path, recs):
+    """Records of the damage fixture as a case file of blocks taken as they are: u32 count, then per block u32 len, u32 capacity, bytes."""
+    import first_gen_damage as fgd
+    oracle = knzlib.Oracle()
+    with open(path, "wb") as f:
+        f.write(struct.pack("<I", len(recs)))
+        for rec in recs:
+            b = fgd.block(oracle, rec)
+            f.write(struct.pack("<II", len(b), rec["cap"]))
+            f.write(b)
+
+
+def check_raw_answers(stdout, recs):
+    lines = [ln.split() for ln in stdout.splitlines() if ln.startswith("block ")]
+    assert len(lines) == len(recs)
+    for ln, rec in zip(lines, recs):
+        ok, length = int(ln[3]), int(ln[5])
+        assert ok == rec["ok"] and (not ok or length == rec["len"]), (rec, ok, length)
+
+
+def test_lz_decoders_on_damaged_fixture_blocks_emulated(tmp_path):
+    """The damaged LZ / LZX blocks of tests/golden/first_gen_damage.json through the data-parallel decoder (k_lz_i_pparse, k_lz_i_parse for
+    what it hands on) and the one-wave-per-block decoder (k_lz_inverse), built with AddressSanitizer: both give the oracle's decision,
+    length and bytes (tests/emu/lz_raw_emu.cpp compares), which are the fixture's. The same blocks on the device:
+    tests/test_gpu_lz_decoders.py."""
+    import first_gen_damage as fgd
+    exe = build("lz_raw_emu", tmp_path, extra=["-fsanitize=address", "-g", "-fno-omit-frame-pointer"])
+    groups = {}
+    for rec in fgd.load()[0]:
+        if rec["stage"] == "LZ":
+            groups.setdefault((rec["transform"], rec["input"][1]), []).append(rec)
+
+    def one(item):
+        (transform, name), recs = item
+        path = str(tmp_path / ("lz_%s_%s.bin" % (transform, name)))
+        write_raw_case(path, recs)
+        return item, subprocess.run([exe, path, str(knzlib.TTYPE[transform])], capture_output=True, text=True, timeout=900,
+                                    env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0:detect_stack_use_after_return=0"))
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=6) as pool:
+        for (key, recs), r in pool.map(one, sorted(groups.items())):
+            assert r.returncode == 0 and "AddressSanitizer" not in r.stderr, (key, r.stdout[-1500:] + r.stderr[-3000:])
+            check_raw_answers(r.stdout, recs)

@@ -286,6 +286,45 @@ def test_mtft_tile_sizes(hip, oracle):
         hipapi.lib().knz_hip_tune(b"mtf_tile", 0)
 
 
+def test_mtft_chain_kernels(hip, oracle):
+    """The byte-serial chain kernels of the MTFT (k_mtf_f_rank, k_mtf_i_symbolic: knob mtf_chain, KNZ_MTF_CHAIN) beside the data-parallel
+    ones, with both tile sizes: the reference's bytes in both directions on a lone block of 300,001 bytes and on a batch of blocks of
+    4,096 bytes with a short last one. The kernel times say which kernels ran (the chain kernels have names of their own there)."""
+    from kanzi_amd import hipapi
+    L = hipapi.lib()
+    d = vectors.make(("mixed", 300001, 6))
+    ok1, o1 = oracle.forward("MTFT", d, len(d) + 64, "ANS0")
+    assert ok1
+    batch = vectors.make(("mixed", 300001, 6))[200000:200000 + 9 * 4096 + 1234]
+    rc, want = oracle.compress(batch, "MTFT", "NONE", 4096, headerless=1)
+    assert rc == 0
+
+    def timed(call):
+        hip.set_profiling(True)
+        try:
+            r = call()
+            return r, {name for name, ms, launches in hip.kernel_times()}
+        finally:
+            hip.set_profiling(False)
+    try:
+        for chain in (0, 1):
+            fwd, inv = ("k_mtf_f_rank_chain", "k_mtf_i_symbolic_chain") if chain else ("k_mtf_f_rank", "k_mtf_i_symbolic")
+            other = {"k_mtf_f_rank_chain", "k_mtf_i_symbolic_chain", "k_mtf_f_rank", "k_mtf_i_symbolic"} - {fwd, inv}
+            for tile in (1024, 4096):
+                assert L.knz_hip_tune(b"mtf_chain", chain) == 0 and L.knz_hip_tune(b"mtf_tile", tile) == 0
+                (ok2, o2), ran = timed(lambda: hip.transform_forward("MTFT", d, len(d) + 64, "ANS0"))
+                assert ok2 and o1 == o2 and fwd in ran and not (other & ran), (chain, tile, ran)
+                (ok3, back), ran = timed(lambda: hip.transform_inverse("MTFT", o1, len(d)))
+                assert ok3 and back == d and inv in ran and not (other & ran), (chain, tile, ran)
+                (out, bits, hb), ran = timed(lambda: gpu_compress(hip, batch, "MTFT", "NONE", 4096, headerless=1))
+                assert out == want and fwd in ran and not (other & ran), (chain, tile, ran)
+                back, ran = timed(lambda: gpu_decompress(hip, want, "MTFT", "NONE", 4096, len(batch), 0))
+                assert back == batch and inv in ran and not (other & ran), (chain, tile, ran)
+    finally:
+        L.knz_hip_tune(b"mtf_chain", 0)
+        L.knz_hip_tune(b"mtf_tile", 0)
+
+
 def test_jobs_capacity_model(hip, oracle):
     # the reference's output depends on -j through buffer-slot capacities (SURVEY App. C #1)
     d = vectors.make(("mixed", 700001, 11))
@@ -500,6 +539,28 @@ def test_bwt_split_into_parts_gives_one_stream(hip, oracle):
                 back = gpu_decompress(hip, outs, rec["chain"], rec["entropy"], rec["block_size"], rec["n"], hbs, checksum=rec["checksum"])
                 assert back == ds, ("BWTS", parts, ranges)
     finally:
+        L.knz_hip_tune(b"bwt_split", 3)
+        L.knz_hip_tune(b"dec_parts", 3)
+
+
+@pytest.mark.parametrize("blocks", (4, 5))
+def test_bwt_parts_of_one_block_each(hip, oracle, blocks):
+    """bwt_part_min 1 with bwt_split 4: the BWT stages of a batch of four blocks run as four parts of one block each, of five blocks as an
+    uneven cut (2 + 1 + 1 + 1); by default a part has at least two blocks. The stream is the oracle's and decodes back, as one range
+    and as three (knob dec_parts)."""
+    L = importlib.import_module("kanzi_amd.hipapi").lib()
+    d = vectors.make(("mixed", 17 * 65536 + 12345, 41))[3 * 65536:(3 + blocks) * 65536]
+    rc, want = oracle.compress(d, "BWT+MTFT+ZRLT", "ANS0", 65536, headerless=1)
+    assert rc == 0
+    try:
+        assert L.knz_hip_tune(b"bwt_part_min", 1) == 0 and L.knz_hip_tune(b"bwt_split", 4) == 0
+        out, bits, hb = gpu_compress(hip, d, "BWT+MTFT+ZRLT", "ANS0", 65536, headerless=1)
+        assert out == want, blocks
+        for ranges in (1, 3):
+            assert L.knz_hip_tune(b"dec_parts", ranges) == 0
+            assert gpu_decompress(hip, want, "BWT+MTFT+ZRLT", "ANS0", 65536, len(d), 0) == d, (blocks, ranges)
+    finally:
+        L.knz_hip_tune(b"bwt_part_min", 2)
         L.knz_hip_tune(b"bwt_split", 3)
         L.knz_hip_tune(b"dec_parts", 3)
 

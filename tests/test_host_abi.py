@@ -95,3 +95,26 @@ def test_radix_tile_size_is_one_value_across_the_library():
         if any("prims::k_rs_" in n for n in names):
             t = {n for n in names if "rs_tile_tag<" in n}
             assert t == tags, (obj, t)
+
+
+def test_every_knob_is_documented_and_set_by_a_gpu_test():
+    """Every name knz_hip_tune accepts (the strcmp chains of csrc/api.hip and csrc/bwt_fwd.hip) is named in the comment of
+    include/knz_hip.h and set by at least one tests/test_gpu_*.py: a path behind a knob that no device test takes is a path the suite
+    does not know. An unknown name returns -1 (needs no device)."""
+    import glob
+    names = set()
+    for src in ("api.hip", "bwt_fwd.hip"):
+        text = open(os.path.join(knzlib.PKG, "csrc", src)).read()
+        body = text[text.index("int knz_hip_tune(" if src == "api.hip" else "int bwt_forward_tune("):]
+        body = body[:body.index("\n}\n")]
+        names |= set(re.findall(r'strcmp\(\w+, "(\w+)"\)', body))
+    assert len(names) >= 22 and {"bwt_inv_wide", "bwt_inv_jump_all", "bwt_inv_ruler_log", "lz_serial_decode", "bwt_nsym"} <= names, names
+    hdr = open(os.path.join(knzlib.ROOT, "include", "knz_hip.h")).read()
+    comment = hdr[hdr.index("/* Developer / test knobs"):hdr.index("KNZ_API int knz_hip_tune(")]
+    gpu_tests = "".join(open(f).read() for f in glob.glob(os.path.join(knzlib.ROOT, "tests", "test_gpu_*.py")))
+    for name in sorted(names):
+        assert '"%s"' % name in comment, "knob %s is missing from the comment in include/knz_hip.h" % name
+        assert 'b"%s"' % name in gpu_tests, "no tests/test_gpu_*.py sets the knob %s" % name
+    knzlib.load_pkg()
+    L = importlib.import_module("kanzi_amd.hipapi").lib()
+    assert L.knz_hip_tune(b"no_such_knob", 1) == -1 and L.knz_hip_tune(None, 1) == -1

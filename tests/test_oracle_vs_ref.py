@@ -1,5 +1,7 @@
 """Pins the oracle against the unmodified reference compiled into oracle/_ref (skipped where that
 build is absent). Randomised inputs beyond the committed golden vectors."""
+import hashlib
+
 import numpy as np
 import pytest
 
@@ -167,3 +169,84 @@ def test_chains_left_out_of_the_soak_have_no_reference_behaviour(ref):
         assert rc == 0, (t, e)
         rc2, back = ref.decompress(out, len(d))
         assert rc2 != 0 or back != d, (t, e, "the reference now decodes its own stream: put the chain back into the soak")
+
+
+def test_first_gen_damage_fixture_is_the_case_list_and_the_oracle_agrees(oracle):
+    """tests/golden/first_gen_damage.json (written by tests/golden/make_first_gen_damage.py from the reference build) holds exactly the
+    cases of tests/first_gen_damage.py, in their order, and the restatement in oracle/ gives every recorded decision, length and md5.
+    Needs no reference build: this is what ties the fixture the GPU tests read to the oracle they encode with."""
+    import first_gen_damage as fgd
+    cases, dropped = fgd.load()
+    have = {fgd.key(r) for r in cases} | {fgd.key(r) for r in dropped}
+    listed = [fgd.key(r) for r in fgd.enumerate_cases(oracle)]
+    assert len(have) == len(cases) + len(dropped) == len(listed) and have == set(listed)
+    assert [fgd.key(r) for r in cases] == [k for k in listed if k not in {fgd.key(r) for r in dropped}]
+    lz = [r for r in cases if r["stage"] == "LZ" and not r["intact"]]
+    accepted = sum(r["ok"] for r in lz)
+    assert 4 * accepted >= len(lz) and 4 * (len(lz) - accepted) >= len(lz), (accepted, len(lz))       # the draw tests both sides
+    for r in cases:
+        ok, out = oracle.inverse(r["transform"], fgd.block(oracle, r), r["cap"])
+        assert (1 if ok else 0) == r["ok"], r
+        if ok:
+            assert len(out) == r["len"] and (r["md5"] is None or hashlib.md5(out).hexdigest() == r["md5"]), r
+        if r["intact"] and r["ok"]:
+            assert out == fgd.plain(r), r
+
+
+def test_damaged_first_gen_blocks_match_reference(oracle, ref):
+    """The same cases against the reference build itself: the fixture is what the reference answers today, with two bytes behind an LZ
+    block (what its decoder asks for, LZCodec.cpp:486-490) and with 4 KiB of zeros."""
+    import first_gen_damage as fgd
+    cases, dropped = fgd.load()
+    n = 0
+    for r in cases:
+        if r["source"] != "reference":
+            assert r["cap"] < r["cut"], r                    # (a destination shorter than the input: the harness cannot be asked)
+            continue
+        blk = fgd.block(oracle, r)
+        for pad in ((2, 4096) if r["stage"] == "LZ" else (0,)):
+            ok, out = ref.inverse(r["transform"], blk, r["cap"], src_cap=len(blk) + pad)
+            assert (1 if ok == 1 else 0) == r["ok"], (r, pad)
+            if ok == 1:
+                assert len(out) == r["len"] and (r["md5"] is None or hashlib.md5(out).hexdigest() == r["md5"]), (r, pad)
+        n += 1
+    assert n >= 700
+
+
+def test_lzx_extensions_read_behind_the_block(oracle, ref):
+    """LZX, text(60000, 3), header byte 8 changed from 136 to 183 (nDist + 47): the length extensions start 47 bytes late, and the
+    decoder, which never looks for the end of the block when it reads one (readLength, LZCodec.hpp:212-225; the two guard bytes of
+    LZCodec.cpp:486-490 are all it asks for), reads the last of them behind the block. What it finds there decides: with zeros behind
+    the block -- what oracle/lz.c and the device's byte windows (LzByteWin) read there -- the reference accepts and returns the 59,983
+    bytes the oracle returns; with the two guard bytes alone it reads the heap, and refused when this was written. The case is
+    therefore not in the fixture (listed under "dropped" there); the restatement needed no change."""
+    import first_gen_damage as fgd
+    import lz_decoder_cases
+    d = lz_decoder_cases.blocks()["text"]
+    ok, enc = oracle.forward("LZX", d, lz_decoder_cases.forward_cap(len(d)))
+    assert ok and enc[8] == 136
+    blk = bytearray(enc); blk[8] = 183; blk = bytes(blk)
+    assert any(r["case"] == "nDist+47" for r in fgd.load()[1])
+    for cap in (len(d), len(d) + 64):
+        ok1, o1 = oracle.inverse("LZX", blk, cap)
+        ok2, o2 = ref.inverse("LZX", blk, cap, src_cap=len(blk) + 4096)
+        assert ok1 == 1 and ok2 == 1 and len(o1) == 59983 and o1 == o2
+
+
+def test_bwt_mode_byte_of_eight_one_byte_indexes(oracle, ref):
+    """BWT, text of 300 and of 5,000 bytes (seed 3), mode byte 13 (eight indexes of two bytes) changed to 12 (eight of one byte): the
+    header is 8 bytes shorter, the block n + 8 bytes, and every byte read as an index is in range. The reference accepts and returns
+    n + 8 bytes -- into a destination that holds them. BWT::inverse refuses a block longer than its destination (BWT.cpp:147-151), and
+    so does oracle/transforms.c: asked with a capacity of n the restatement refuses, which is where it seemed to disagree; the
+    reference's harness cannot be given less than the input's length (TransformSequence). With equal capacities the two agree on
+    decision, length and bytes at every capacity the harness takes."""
+    for n in (300, 5000):
+        d = vectors.make(("text", n, 3))
+        ok, enc = oracle.forward("BWT", d, len(d) + 64)
+        assert ok and enc[0] == 13 and len(enc) == n + 17
+        blk = bytes([12]) + enc[1:]
+        for cap in (len(enc), len(enc) + 64):
+            ok1, o1 = oracle.inverse("BWT", blk, cap)
+            ok2, o2 = ref.inverse("BWT", blk, cap)
+            assert ok1 == 1 and ok2 == 1 and len(o1) == n + 8 and o1 == o2, (n, cap)
+        assert oracle.inverse("BWT", blk, n + 8)[0] == 1 and oracle.inverse("BWT", blk, n + 7)[0] == 0 and oracle.inverse("BWT", blk, n)[0] == 0
