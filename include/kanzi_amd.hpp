@@ -243,6 +243,24 @@ size_t releaseIdleBuffers();
 knz_ctx* laneContext(int device, int index);
 void setDefaultDevice(int device);
 
+// ---- many small independent buffers, many per device call ---------------------------------------
+// Every input becomes a stream of its own -- the file `kanzi -c` writes for those bytes, the input's length stored in the header --
+// and every stream comes back by itself. The inputs are staged through the page-locked pool and go to the device many per call
+// (knz_hip_encode_streams / knz_hip_decode_streams: one batch of 24 MiB at a time, the stream classes' batch size; never more items,
+// blocks or bytes than a call takes), so that a thousand small files cost a handful of calls instead of a thousand. errors[i] is 0 or
+// the kanzi Error code of item i, whose output is then empty; the other items are not affected. `messages`, when given, receives one
+// text per item (empty where nothing failed). The pair cuts its work into calls by the device layer's limits (items, blocks, bytes,
+// blocks x longest block); a call that fails as a whole is repeated item by item, so that every item gets a verdict of its own. Against a device library without the two entry points (they are bound weakly), for chains whose leading
+// stages run on the host, for inputs beyond a call's limits and, on the way back, for streams without a stored size or of an old
+// bitstream version, an item goes through a CompressedOutputStream / CompressedInputStream of its own: the same bytes, one call each.
+// KNZ_STREAMS_BATCH=0 in the environment forces that path.
+struct ByteSpan { const byte* data; size_t size; };
+void compressMany(const std::vector<ByteSpan>& inputs, const std::string& entropy, const std::string& transform, int blockSize, int checksum, int jobs,
+                  std::vector<std::vector<byte>>& streams, std::vector<int>& errors, std::vector<std::string>* messages = nullptr);
+void decompressMany(const std::vector<ByteSpan>& streams, int jobs, std::vector<std::vector<byte>>& outputs, std::vector<int>& errors,
+                    std::vector<std::string>* messages = nullptr);
+bool deviceBatchesStreams();        // whether the pair above reaches the device many items per call
+
 // ---- transforms on the device ------------------------------------------------------------------
 class DeviceTransform : public Transform<byte> {
 public:

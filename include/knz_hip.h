@@ -138,6 +138,62 @@ KNZ_API int knz_hip_decode_block_hosted(knz_ctx* ctx, const knz_params* p, int32
                                         uint64_t start_bit, uint8_t* d_out, size_t out_cap, uint64_t* out_bytes, uint64_t* end_bit,
                                         uint32_t* skip_flags, uint64_t* checksum, int32_t* done);
 
+/*
+ * Many independent streams in one call. One call is one batch: the blocks of all items go through the stages together, and the number
+ * of kernel launches, host synchronisations and bus copies does not grow with the number of items (TPAQ's table slices excepted).
+ * An item is one stream: one input cut into blocks of p->block_size, framed by itself, block ids counted from 0.
+ *
+ * Limits of a call: at most KNZ_STREAMS_MAX_ITEMS items and KNZ_STREAMS_MAX_BLOCKS blocks; at most 2 GiB of input (encode), or of bytes
+ * the streams can decode to (decode: the sum over the items of min(out_cap, blocks found x block size)); blocks x the longest block of
+ * the call at most 2 GiB as well (the workspaces are that large: encode, the longest block of any item; decode, the largest
+ * min(out_cap, block size) -- so a thousand items of 1 KiB cost the same under a block size of 4 MiB as under one of 1 KiB, and one item
+ * of 4 MiB among them makes the call a thousand times 4 MiB); every in_off / out_off a multiple of 16, d_in and d_out 16-byte aligned.
+ * A caller with more splits its work into several calls; a call over a limit fails as a whole and says which.
+ */
+#define KNZ_STREAMS_MAX_ITEMS 65536
+#define KNZ_STREAMS_MAX_BLOCKS 65536
+typedef struct {
+    uint64_t in_off;        /* byte offset of the item in d_in, multiple of 16 */
+    uint64_t in_len;        /* encode: bytes of input; decode: bits of the stream, counted from in_off * 8 */
+    uint64_t start_bit;     /* decode: bit of the first block's length prefix, relative to in_off * 8 (behind the header) */
+    uint32_t prologue_off;  /* encode: where this item's prologue begins in the call's `prologues` host array */
+    uint32_t prologue_bits; /* encode: bits put first in the stream (the stream header, or 0); at most 200 bytes */
+    uint64_t out_off;       /* encode: OUT, byte offset of the stream in d_out (multiple of 16);
+                               decode: IN, byte offset where the item's bytes go (multiple of 16) */
+    uint64_t out_cap;       /* decode: IN, room at out_off */
+    uint64_t out_len;       /* OUT: encode = bits written, decode = bytes decoded */
+    int32_t  blocks;        /* OUT */
+    int32_t  error;         /* OUT: 0, or the kanzi Error code of this item */
+} knz_item;
+
+/* Bytes of d_out that knz_hip_encode_streams needs for these items (in_len and prologue_bits are read): the sum over the items of
+ * knz_hip_encode_bound(p, in_len) plus the prologue, each rounded up to 16. The binary coders' bound is their first tier here too. */
+KNZ_API size_t knz_hip_encode_streams_bound(const knz_params* p, const knz_item* items, size_t n_items);
+
+/*
+ * Item i becomes exactly the bytes that knz_hip_encode_blocks(d_in + in_off, in_len, prologues + prologue_off, prologue_bits,
+ * first_block_id = 0, finish, ...) writes: blocks of p->block_size, copy blocks, the per-block data type, checksums of the original
+ * bytes, the skip byte of chains of more than four stages, the capacities of p->jobs, the end marker. An empty item is its prologue
+ * plus the end marker. The streams lie in d_out back to back, each at a 16-byte boundary (out_off) with zero bytes up to the next, so
+ * that every one can be handed to knz_hip_decode_blocks where it lies; out_len is its length in bits, blocks its block count.
+ * *out_bytes = bytes of d_out in use. The call fails as a whole (nothing in `items` is then meaningful): a chain the device refuses,
+ * out_cap below knz_hip_encode_streams_bound, more than 2 GiB of input, too many items or blocks, a misaligned offset. Hosted leading
+ * stages (knz_host_stages) are not part of this call. `prologues` may be NULL when every prologue_bits is 0.
+ */
+KNZ_API int knz_hip_encode_streams(knz_ctx* ctx, const knz_params* p, const uint8_t* d_in, knz_item* items, size_t n_items,
+                                   const uint8_t* prologues, int finish, uint8_t* d_out, size_t out_cap, uint64_t* out_bytes);
+
+/*
+ * All items share p (the caller groups streams by header). For every item the blocks from start_bit to the end marker are decoded
+ * to d_out + out_off. Items are judged one by one: error is 0, a block's error code, KNZ_ERR_WRITE_FILE when out_cap is too small
+ * for the blocks the stream holds, KNZ_ERR_PROCESS_BLOCK for a short block that is not the last, KNZ_ERR_READ_FILE for damaged
+ * framing; out_len and blocks are the decoded bytes and the blocks found (0 bytes for an item with an error). A failing item leaves
+ * every other item as a call without it would, and writes nothing outside [out_off, out_off + out_cap). The ranges overlap for no two
+ * items and lie inside out_cap bytes of d_out. The return value is non-zero only for failures of the call itself.
+ */
+KNZ_API int knz_hip_decode_streams(knz_ctx* ctx, const knz_params* p, const uint8_t* d_in, knz_item* items, size_t n_items,
+                                   uint8_t* d_out, size_t out_cap);
+
 /* ---- per-stage entry points (host buffers in/out; used by the host mirror classes and tests) ---- */
 
 /* EntropyEncoder::encode for one buffer (entropy/EntropyEncoder.hpp:30-37). out receives the bits

@@ -808,10 +808,48 @@ static int run_stage(Ctx* c, hipStream_t s, const XfInfo& x, bool forward, const
 // ------------------------------------------------------------------------------------------------
 // encode
 // ------------------------------------------------------------------------------------------------
+// The workspaces of a batch of many streams are blocks x the stride of the longest block (two of them, seq_alloc). A caller that keeps
+// blocks x longest block below 2 GiB (the documented limit, include/knz_hip.h) stays below this whatever the chain adds to the stride.
+constexpr u64 STREAMS_MAX_WORK = (u64)1 << 32;
+
+// A batch of many streams as encode_impl takes it (knz_hip_encode_streams builds it): the blocks of all streams in stream order, block b
+// at d_in + inOff[b] with len[b] bytes, stream i owning the blocks [first[i], first[i + 1]). The d_* arrays are one upload.
+struct EncTab {
+    int nItems = 0, nBlocks = 0;
+    u32 maxLen = 0;                            // the longest block
+    std::vector<u32> first, len;               // host copies (the capacity model runs there)
+    const u64* d_inOff = nullptr; const u32* d_len = nullptr; const u32* d_itemOf = nullptr; const StreamEnc* d_st = nullptr; const u8* d_pro = nullptr;
+    StreamOut* d_res = nullptr; u64* d_excl = nullptr;
+    std::vector<StreamOut> res;                // OUT: where the streams lie
+};
+
+// The output of a batch of many streams behind the framing scan: room check, the one clearing of the range (padding included), prologues
+static int streams_place(Ctx* c, hipStream_t s, const EncTab* tab, uint8_t* d_out, size_t outCap, u64 totalBytes)
+{
+    if (totalBytes > outCap) return fail(c, KNZ_ERR_WRITE_FILE, "output buffer too small: need %zu have %zu", (size_t)totalBytes, outCap);
+    {
+        ProfScope ps(c, "memset_out");
+        if (totalBytes) HIPCHK(c, hipMemsetAsync(d_out, 0, (size_t)totalBytes, s));
+    }
+    launch_stream_prologues(s, reinterpret_cast<u32*>(d_out), tab->d_st, tab->d_res, tab->nItems, tab->d_pro);
+    return 0;
+}
+
+static int streams_results(Ctx* c, hipStream_t s, EncTab* tab)
+{
+    tab->res.resize((size_t)tab->nItems);
+    if (tab->nItems) HIPCHK(c, hipMemcpyAsync(tab->res.data(), tab->d_res, sizeof(StreamOut) * (size_t)tab->nItems, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
 // capsMode: 0 = reference stream buffers (jobs model), otherwise every destination capacity = capsMode (per-stage API)
+// tab: the batch holds many streams (n = all their bytes; prologue, prologueBits and firstBlock are unused: every stream has its own
+// prologue and counts its blocks from 0; *outBits = 8 * the bytes of d_out in use)
 static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t n, const uint8_t* prologue,
                        uint32_t prologueBits, int framing, int finish, int64_t firstBlock, uint8_t* d_out, size_t outCap,
-                       uint64_t* outBits, const knz_host_stages* hs = nullptr, u32 streamBlockSize = 0)
+                       uint64_t* outBits, const knz_host_stages* hs = nullptr, u32 streamBlockSize = 0, EncTab* tab = nullptr)
 {
     ProfInstall pi_(c);
     HIPCHK(c, hipSetDevice(c->device));
@@ -825,7 +863,9 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
     const int nTok = ch.n;
     hipStream_t s = c->stream;
 
-    const int nBlocks = (n == 0) ? 0 : (int)((n + bs - 1) / bs);
+    const int nBlocks = tab ? tab->nBlocks : (n == 0) ? 0 : (int)((n + bs - 1) / bs);
+    const u64* inOff = tab ? tab->d_inOff : nullptr;
+    const u32* lenTab = tab ? tab->d_len : nullptr;
     if (hs) {
         // one block, in the length the host stages left it (never longer than the block it came from)
         if (nBlocks != 1 || hs->orig_len > bs || n > hs->orig_len + 8192u) return fail(c, KNZ_ERR_INVALID_PARAM, "a hosted call takes exactly one block");
@@ -840,6 +880,18 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
     u64* d_total;
     if (int r = ws_get(c, "total", 64, (void**)&d_total, s)) return r;
 
+    FrameParams fp;
+    fp.framing = framing; fp.nTransforms = nTok; fp.checksumBits = p->checksum_bits; fp.finish = finish; fp.prologueBits = prologueBits;
+    u64* h_total = reinterpret_cast<u64*>(c->pinned);
+    if (nBlocks == 0 && tab) {
+        // empty streams only: each is its prologue and the end marker
+        launch_stream_frame(s, nullptr, nullptr, nullptr, nullptr, 0, tab->d_st, tab->nItems, fp, tab->d_excl, tab->d_res, d_total);
+        HIPCHK(c, hipMemcpyAsync(h_total, d_total, sizeof(u64), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        if (int r = streams_place(c, s, tab, d_out, outCap, *h_total)) return r;
+        if (outBits) *outBits = 8 * *h_total;
+        return streams_results(c, s, tab);
+    }
     if (nBlocks == 0) {
         HIPCHK(c, hipMemsetAsync(d_out, 0, needOut, s));
         if (prologueBits) {
@@ -857,16 +909,17 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
     u32 *d_origLen; BlockInfo* d_info;
     if (int r = ws_get(c, "origLen", sizeof(u32) * nBlocks, (void**)&d_origLen, s)) return r;
     if (int r = ws_get(c, "info", sizeof(BlockInfo) * nBlocks, (void**)&d_info, s)) return r;
-    const int maxIn = (int)((n < bs) ? n : bs);
+    const int maxIn = tab ? (int)tab->maxLen : (int)((n < bs) ? n : bs);
     const int required = seq_stride(ch, maxIn);
     const u64 S = ((u64)required + 255) & ~255ull;
     bool realStages = false, wantType = false;              // (wantType: a device stage reads the per-block data type)
     for (int i = 0; i < nTok; i++) { realStages |= ch.tok[i] != KNZ_T_NONE; wantType |= ch.xf[i] && ch.xf[i]->setsType; }
     SeqWs w;
+    if (tab && (u64)nBlocks * S > STREAMS_MAX_WORK) return fail(c, KNZ_ERR_INVALID_PARAM, "%d blocks with a longest block of %d bytes exceed the workspace limit of a call (blocks x longest block <= 2 GiB): split the call", nBlocks, maxIn);
     if (int r = seq_alloc(c, nBlocks, S, realStages, chain_scratch_u32(ch, true, nBlocks, (u32)S), &w, -1, s)) return r;
     w.a.origLen = d_origLen;
     const bool direct = !realStages && !p->checksum_bits;      // NullTransforms only: one bookkeeping launch
-    if (!direct) launch_init_blocks(s, n, bs, nBlocks, d_origLen, w.a.len);
+    if (!direct) launch_init_blocks(s, n, bs, nBlocks, d_origLen, w.a.len, lenTab);
     // block checksums of the ORIGINAL bytes (io/CompressedOutputStream.cpp:675-682)
     u64* d_sums = nullptr;
     if (p->checksum_bits) {
@@ -877,7 +930,7 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
             *hsum = hs->checksum;
             HIPCHK(c, hipMemcpyAsync(d_sums, hsum, sizeof(u64), hipMemcpyHostToDevice, s));
         } else {
-            launch_block_ptrs(s, d_in, bs, nBlocks, w.d_viewPtr);
+            launch_block_ptrs(s, d_in, bs, nBlocks, w.d_viewPtr, inOff);
             launch_xxhash(s, w.d_viewPtr, d_origLen, nBlocks, p->checksum_bits, d_sums);
         }
     }
@@ -891,10 +944,16 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
         u32* h = reinterpret_cast<u32*>(c->pinned);
         u32* hEven = h; u32* hOdd = h + nBlocks;
         std::vector<u32> slotBuf((size_t)jobs, 0);
-        for (int64_t b = 0; b < nBlocks; b++) {
-            const int64_t gid = firstBlock + b;
+        // (a batch of many streams: every stream starts with fresh buffers and counts its blocks from 0)
+        for (int64_t b = 0, it = 0; b < nBlocks; b++) {
+            if (tab) {
+                const int64_t was = it;
+                while ((int64_t)tab->first[(size_t)it + 1] <= b) it++;
+                if (it != was) std::fill(slotBuf.begin(), slotBuf.end(), 0u);
+            }
+            const int64_t gid = tab ? b - (int64_t)tab->first[(size_t)it] : firstBlock + b;
             const int slot = (int)(gid % jobs);
-            const u32 len = hs ? hs->orig_len : (u32)(((size_t)(b + 1) * bs <= n) ? bs : n - (size_t)b * bs);      // (the reference sizes its buffers by the block as read)
+            const u32 len = tab ? tab->len[(size_t)b] : hs ? hs->orig_len : (u32)(((size_t)(b + 1) * bs <= n) ? bs : n - (size_t)b * bs);      // (the reference sizes its buffers by the block as read)
             const u32 req = (u32)seq_required(ch, (int)len);
             // a slot's buffer is at least what a full block needed earlier on that slot
             u32 bufc = slotBuf[slot];
@@ -914,13 +973,13 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
     // ---- per-block data type: preset from the block's magic, or what the host stages left
     if (wantType) {
         if (hs) HIPCHK(c, hipMemsetAsync(w.a.dtype, hs->reserved <= 9 ? (int)hs->reserved : 0, (size_t)nBlocks, s));
-        else launch_seq_fwd_dtype(s, w.a, nBlocks, d_in, bs);
+        else launch_seq_fwd_dtype(s, w.a, nBlocks, d_in, bs, inOff);
     }
 
     // ---- transform stages
-    if (direct) launch_seq_fwd_direct(s, w.a, d_origLen, n, bs, nBlocks, nTok, d_in, w.d_viewPtr);
+    if (direct) launch_seq_fwd_direct(s, w.a, d_origLen, n, bs, nBlocks, nTok, d_in, w.d_viewPtr, inOff, lenTab);
     for (int i = 0; i < nTok && !direct; i++) {
-        launch_seq_fwd_prepare(s, w.a, nBlocks, i, d_in, bs, w.A, w.B, S);
+        launch_seq_fwd_prepare(s, w.a, nBlocks, i, d_in, bs, w.A, w.B, S, inOff);
         if (i < nHosted) {
             launch_seq_fwd_hosted(s, w.a, nBlocks, i, (hs->applied_mask >> i) & 1u);
             continue;
@@ -935,7 +994,7 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
         if (int r = run_stage(c, s, *ch.xf[i], true, st)) return r;
         launch_seq_fwd_commit(s, w.a, nBlocks, i);
     }
-    if (!direct) launch_seq_fwd_finish(s, w.a, nBlocks, d_in, bs, w.A, w.B, S, w.d_viewPtr);
+    if (!direct) launch_seq_fwd_finish(s, w.a, nBlocks, d_in, bs, w.A, w.B, S, w.d_viewPtr, inOff);
     BlockView view;
     view.ptr = w.d_viewPtr; view.len = w.a.len;
     u32* d_blockLen = w.a.len;
@@ -1009,13 +1068,15 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
     }
 
     // ---- framing + assembly
-    FrameParams fp;
-    fp.framing = framing; fp.nTransforms = nTok; fp.checksumBits = p->checksum_bits; fp.finish = finish; fp.prologueBits = prologueBits;
+    // (many streams: the blocks' places restart at every stream, and d_total holds the BYTES of output in use)
+    auto block_scan = [&] {
+        if (tab) launch_stream_frame(s, d_info, d_blockLen, d_origLen, tab->d_itemOf, nBlocks, tab->d_st, tab->nItems, fp, tab->d_excl, tab->d_res, d_total);
+        else launch_block_scan(s, d_info, d_blockLen, d_origLen, nBlocks, fp, d_total);
+    };
     launch_block_sum(s, d_desc, d_info, d_blockLen, nBlocks, maxChunks, entChunk, slotMul);
-    launch_block_scan(s, d_info, d_blockLen, d_origLen, nBlocks, fp, d_total);
+    block_scan();
     // The output must be zero before the OR-assembly; its size is only known on the device, so the
     // total is read back first (8 bytes) and only the used part is cleared.
-    u64* h_total = reinterpret_cast<u64*>(c->pinned);
     u32* h_marked = reinterpret_cast<u32*>(h_total + 1);
     *h_marked = 0;
     HIPCHK(c, hipMemcpyAsync(h_total, d_total, sizeof(u64), hipMemcpyDeviceToHost, s));
@@ -1037,9 +1098,16 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
         if (r == -2) return big.rc;                               // (ws_get has said why)
         if (r < 0) return fail(c, -1, "binary coder: encode failed: %s", hipGetErrorString(hipGetLastError()));
         launch_block_sum(s, d_desc, d_info, d_blockLen, nBlocks, maxChunks, entChunk, slotMul);
-        launch_block_scan(s, d_info, d_blockLen, d_origLen, nBlocks, fp, d_total);
+        block_scan();
         HIPCHK(c, hipMemcpyAsync(h_total, d_total, sizeof(u64), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
+    }
+    if (tab) {
+        if (int r = streams_place(c, s, tab, d_out, outCap, *h_total)) return r;
+        launch_assemble(s, d_desc, d_info, d_blockLen, d_origLen, d_skip, d_sums, d_tmp, nBlocks, maxChunks, entChunk, slotMul, hdrStride, fp,
+                        reinterpret_cast<u32*>(d_out));
+        if (outBits) *outBits = 8 * *h_total;
+        return streams_results(c, s, tab);
     }
     const u64 totalBits = *h_total;
     const size_t outBytes = (size_t)((totalBits + 7) >> 3);
@@ -1087,9 +1155,21 @@ int knz_hip_encode_block_hosted(knz_ctx* ctx, const knz_params* p, const knz_hos
 // ------------------------------------------------------------------------------------------------
 struct WalkResultHost { u64 endBit; int64_t nBlocks; int32_t ended; int32_t error; };
 
+// A batch of many streams as decode_impl takes it (knz_hip_decode_streams builds it): d_sd is the upload of the items, d_walk room for
+// one StreamWalk per stream and one more. The per-stream verdicts go back into `items`.
+struct DecTab {
+    int nItems = 0;
+    u32 maxUnit = 0;                           // the longest block any item has room for: min(block size, out_cap), at most
+    knz_item* items = nullptr;
+    const StreamDec* d_sd = nullptr; StreamWalk* d_walk = nullptr;
+};
+
+// tab: the batch holds many streams (inBits = the bits of d_in that any stream reaches; startBit, maxBlocks and the OUT arguments are
+// unused: every stream has its own start and gets its own verdict, and a stream's failure is no failure of the call)
 static int decode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, uint64_t inBits, uint64_t startBit, int64_t maxBlocks,
                        int framing, u32 rawLen, uint8_t* d_out, size_t outCap, uint64_t* outBytes, uint64_t* endBit,
-                       int64_t* blocksDone, int32_t* rawDecoded, uint64_t* usedBits, int nHosted = 0, uint32_t* skipOut = nullptr, uint64_t* sumOut = nullptr, u32 streamBlockSize = 0)
+                       int64_t* blocksDone, int32_t* rawDecoded, uint64_t* usedBits, int nHosted = 0, uint32_t* skipOut = nullptr, uint64_t* sumOut = nullptr, u32 streamBlockSize = 0,
+                       DecTab* tab = nullptr)
 {
     ProfInstall pi_(c);
     HIPCHK(c, hipSetDevice(c->device));
@@ -1113,28 +1193,63 @@ static int decode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, uint64_
     src.nWords = src.nBytes >> 2;
     src.limitBits = inBits;
 
-    int64_t bound = framing ? (int64_t)(outCap / bs) + 2 : 1;
-    if (maxBlocks > 0 && maxBlocks < bound) bound = maxBlocks;
-    DecBlock* d_blocks; void* d_walk;
-    if (int r = ws_get(c, "decBlocks", sizeof(DecBlock) * (size_t)bound, (void**)&d_blocks, s)) return r;
-    if (int r = ws_get(c, "walk", 64, &d_walk, s)) return r;
-    launch_walk_blocks(s, src, startBit, bound, framing, rawLen, p->checksum_bits, bs, d_blocks, d_walk);
-    WalkResultHost* h_walk = reinterpret_cast<WalkResultHost*>(c->pinned);
-    HIPCHK(c, hipMemcpyAsync(h_walk, d_walk, sizeof(WalkResultHost), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    const WalkResultHost walk = *h_walk;
-    if (walk.error) return fail(c, walk.error, "invalid block framing");
-    const int nBlocks = (int)walk.nBlocks;
-    if (endBit) *endBit = walk.endBit;
-    if (blocksDone) *blocksDone = nBlocks;
-    if (nBlocks == 0) { if (outBytes) *outBytes = 0; return 0; }
-    if (framing && (size_t)nBlocks * bs > outCap + bs) return fail(c, KNZ_ERR_WRITE_FILE, "output buffer too small");
-    if (framing && (size_t)nBlocks * bs > (size_t)0x7FFFFFFF) return fail(c, KNZ_ERR_INVALID_PARAM, "batch of %d blocks exceeds the 2 GiB per-call limit (pass max_blocks)", nBlocks);
+    DecBlock* d_blocks;
+    int nBlocks = 0;
+    std::vector<StreamWalk> sw;                              // many streams: every stream's first slot, block count and verdict of the walk
+    u64 *d_outOff = nullptr, *d_room = nullptr;              // many streams: every block's place in d_out and the room behind it
+    if (tab) {
+        // the walk in two passes (streams.hip): count, scan the counts -- the total sizes the block table --, then fill
+        sw.resize((size_t)tab->nItems + 1);
+        launch_walk_streams_count(s, d_in, tab->d_sd, tab->nItems, p->checksum_bits, bs, tab->d_walk);
+        HIPCHK(c, hipMemcpyAsync(sw.data(), tab->d_walk, sizeof(StreamWalk) * sw.size(), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        HIPCHK(c, hipGetLastError());
+        const u64 all = sw.back().first;
+        if (all > (u64)KNZ_STREAMS_MAX_BLOCKS) return fail(c, KNZ_ERR_INVALID_PARAM, "too many blocks in one batch (%llu)", (unsigned long long)all);
+        nBlocks = (int)all;
+        for (int i = 0; i < tab->nItems; i++) {
+            knz_item& it = tab->items[i];
+            it.error = sw[(size_t)i].error; it.blocks = (int32_t)sw[(size_t)i].count; it.out_len = 0;
+        }
+        if (nBlocks == 0) return 0;
+        if (int r = ws_get(c, "decBlocks", sizeof(DecBlock) * (size_t)nBlocks, (void**)&d_blocks, s)) return r;
+        if (int r = ws_get(c, "decOutOff", sizeof(u64) * (size_t)nBlocks, (void**)&d_outOff, s)) return r;
+        if (int r = ws_get(c, "decRoom", sizeof(u64) * (size_t)nBlocks, (void**)&d_room, s)) return r;
+        launch_walk_streams_fill(s, d_in, tab->d_sd, tab->nItems, p->checksum_bits, bs, tab->d_walk, d_blocks, d_outOff, d_room);
+    } else {
+        int64_t bound = framing ? (int64_t)(outCap / bs) + 2 : 1;
+        if (maxBlocks > 0 && maxBlocks < bound) bound = maxBlocks;
+        void* d_walk;
+        if (int r = ws_get(c, "decBlocks", sizeof(DecBlock) * (size_t)bound, (void**)&d_blocks, s)) return r;
+        if (int r = ws_get(c, "walk", 64, &d_walk, s)) return r;
+        launch_walk_blocks(s, src, startBit, bound, framing, rawLen, p->checksum_bits, bs, d_blocks, d_walk);
+        WalkResultHost* h_walk = reinterpret_cast<WalkResultHost*>(c->pinned);
+        HIPCHK(c, hipMemcpyAsync(h_walk, d_walk, sizeof(WalkResultHost), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        const WalkResultHost walk = *h_walk;
+        if (walk.error) return fail(c, walk.error, "invalid block framing");
+        nBlocks = (int)walk.nBlocks;
+        if (endBit) *endBit = walk.endBit;
+        if (blocksDone) *blocksDone = nBlocks;
+        if (nBlocks == 0) { if (outBytes) *outBytes = 0; return 0; }
+        if (framing && (size_t)nBlocks * bs > outCap + bs) return fail(c, KNZ_ERR_WRITE_FILE, "output buffer too small");
+    }
+    if (!tab && framing && (size_t)nBlocks * bs > (size_t)0x7FFFFFFF) return fail(c, KNZ_ERR_INVALID_PARAM, "batch of %d blocks exceeds the 2 GiB per-call limit (pass max_blocks)", nBlocks);
+    if (tab) {
+        // the same limit by what the items can hold: a stream of k blocks decodes to at most min(out_cap, k block sizes) bytes
+        u64 most = 0;
+        for (int i = 0; i < tab->nItems; i++) most += std::min<u64>(tab->items[i].out_cap, (u64)sw[(size_t)i].count * bs);
+        if (most > (u64)0x7FFFFFFF) return fail(c, KNZ_ERR_INVALID_PARAM, "the streams of this call decode to up to %llu bytes, more than the 2 GiB per-call limit: split the call", (unsigned long long)most);
+    }
 
     // workspace stride: large enough for every valid preTransformLength of this chain
-    const u32 unit = framing ? bs : rawLen;
+    // (many streams: no block can be longer than the largest room, so the workspaces are sized by that and not by the block size -- a
+    // thousand files of 1 KiB in a stream format of 4 MiB blocks take megabytes, not gigabytes; a longer block fails either way, with
+    // the code it gets below where its room is too small)
+    const u32 unit = tab ? std::max(tab->maxUnit, 1u) : framing ? bs : rawLen;
     const int required = seq_stride(ch, (int)unit);       // (the whole chain sizes the buffers, as in the encoder: a UTF stage adds 8 KiB of room)
     const u64 S = ((u64)required + 255) & ~255ull;
+    if (tab && (u64)nBlocks * S > STREAMS_MAX_WORK) return fail(c, KNZ_ERR_INVALID_PARAM, "%d blocks with a longest block of %u bytes exceed the workspace limit of a call (blocks x longest block <= 2 GiB): split the call", nBlocks, unit);
     const u32 maxPre = (u32)S;
     const int maxChunks = (int)((S + ENT_CHUNK - 1) / ENT_CHUNK);
     const u64 outStride = framing ? bs : 0;
@@ -1167,16 +1282,19 @@ static int decode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, uint64_
         int b0, nb;
         cut(nBlocks, lanes, k, &b0, &nb);
         DecBlock* blk = d_blocks + b0;
-        uint8_t* out = d_out + (size_t)b0 * outStride;
-        const u64 room = (u64)outCap - (u64)b0 * outStride;
+        // (many streams: the blocks' places and rooms come from the tables, `room` only has to differ from ~0)
+        uint8_t* out = tab ? d_out : d_out + (size_t)b0 * outStride;
+        const u64 room = tab ? 0 : (u64)outCap - (u64)b0 * outStride;
+        const u64* offT = tab ? d_outOff + b0 : nullptr;
+        const u64* roomT = tab ? d_room + b0 : nullptr;
         SeqWs w;
         if (int r = seq_alloc(c, nb, S, realStages, chain_scratch_u32(ch, false, nb, (u32)S), &w, lane, sp)) return r;
         const size_t nSlots = (size_t)nb * maxChunks;
         // entropy stage decodes into workspace A (or straight into the output when no transform applies)
         // with inverse stages the entropy decoder writes into the workspace (any valid preTransformLength fits);
         // the room in the caller's buffer is enforced where the last inverse stage gets its capacity
-        launch_check_prelen(sp, blk, nb, realStages ? maxPre : unit, realStages ? ~0ull : room, outStride);
-        launch_seq_inv_entropy_dst(sp, w.a, blk, nb, out, outStride, w.A, S, w.d_entDst, realMask, unit, room);
+        launch_check_prelen(sp, blk, nb, realStages ? maxPre : unit, realStages ? ~0ull : room, outStride, roomT);
+        launch_seq_inv_entropy_dst(sp, w.a, blk, nb, out, outStride, w.A, S, w.d_entDst, realMask, unit, room, offT, roomT);
         if (p->entropy_type == KNZ_E_ANS0) {
             void* d_meta;
             if (int r = ws_get(c, lane_ws("ansDecChunks", lane), ans0_dec_chunk_bytes() * nSlots, &d_meta, sp)) return r;
@@ -1211,16 +1329,18 @@ static int decode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, uint64_
         }
         // inverse transforms, last stage first (TransformSequence.hpp:197-224)
         if (realStages) {
-            const u32 capFinal = framing ? bs : (u32)p->jobs;           // per-stage API passes its capacity in p->jobs
+            const u32 capFinal = framing ? std::min(bs, unit) : (u32)p->jobs;           // per-stage API passes its capacity in p->jobs
             const u32 blkLenModel = std::max(bs + 512u, bs + (bs >> 4));
             const u32 capMid = framing ? (u32)std::min<u64>(S, blkLenModel) : (u32)p->jobs;
+            // (the reference's buffer, which the stages that judge by capacity go by, is sized by the stream's block size whatever the workspaces here are)
+            const u32 capModel = framing ? (u32)std::min<u64>(((u64)seq_stride(ch, (int)bs) + 255) & ~255ull, blkLenModel) : 0u;
             for (int i = nTok - 1; i >= 0; i--) {
                 if (ch.xf[i] == nullptr) continue;
-                launch_seq_inv_prepare(sp, w.a, blk, nb, i, out, outStride, w.A, w.B, S, capMid, capFinal, realMask, framing ? room : ~0ull);
+                launch_seq_inv_prepare(sp, w.a, blk, nb, i, out, outStride, w.A, w.B, S, capMid, capFinal, realMask, framing ? room : ~0ull, offT, roomT);
                 XfStage st = xf_stage(w, nb, (u32)S, p->entropy_type);
                 st.bsVersion = bsVersion;
                 st.maxCap = std::max(capMid, capFinal);
-                st.capModel = framing ? capMid : 0;
+                st.capModel = capModel;
                 st.blockSize = streamBlockSize ? streamBlockSize : (framing ? bs : 0u);
                 if (int r = run_stage(c, sp, *ch.xf[i], false, st, lane)) return r;
                 launch_seq_inv_commit(sp, w.a, blk, nb, i, ch.tok[i]);
@@ -1229,7 +1349,7 @@ static int decode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, uint64_
         if (p->checksum_bits && framing && nHosted == 0) {
             u64* d_sums;
             if (int r = ws_get(c, lane_ws("sums", lane), sizeof(u64) * nb, (void**)&d_sums, sp)) return r;
-            launch_verify_checksums(sp, blk, nb, p->checksum_bits, out, outStride, w.d_viewPtr, w.a.alen, d_sums);
+            launch_verify_checksums(sp, blk, nb, p->checksum_bits, out, outStride, w.d_viewPtr, w.a.alen, d_sums, offT);
         }
         return 0;
     };
@@ -1240,6 +1360,22 @@ static int decode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, uint64_
     std::vector<DecBlock> hb((size_t)nBlocks);
     HIPCHK(c, hipMemcpyAsync(hb.data(), d_blocks, sizeof(DecBlock) * (size_t)nBlocks, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
+    if (tab) {
+        // every stream by itself, by the rules below: the first failing block's code, the refusal of a short block that is not the last
+        for (int i = 0; i < tab->nItems; i++) {
+            knz_item& it = tab->items[i];
+            if (it.error) continue;
+            const size_t b0 = (size_t)sw[(size_t)i].first, b1 = b0 + sw[(size_t)i].count;
+            u64 bytes = 0;
+            for (size_t b = b0; b < b1 && !it.error; b++) {
+                if (hb[b].error) it.error = hb[b].error;
+                else if (b + 1 < b1 && hb[b].preLen != bs) it.error = KNZ_ERR_PROCESS_BLOCK;
+                bytes += hb[b].preLen;
+            }
+            it.out_len = it.error ? 0 : bytes;
+        }
+        return 0;
+    }
     u64 total = 0;
     for (int b = 0; b < nBlocks; b++) {
         if (hb[b].error) {
@@ -1279,6 +1415,136 @@ int knz_hip_decode_block_hosted(knz_ctx* ctx, const knz_params* p, int32_t host_
     if (checksum) *checksum = 0;
     const int r = decode_impl(c, p, d_in, in_bits, start_bit, 1, 1, 0, d_out, out_cap, out_bytes, end_bit, &nb, nullptr, nullptr, host_stages, skip_flags, checksum);
     if (done) *done = (int32_t)nb;
+    return r;
+}
+
+// ------------------------------------------------------------------------------------------------
+// many streams in one call
+// ------------------------------------------------------------------------------------------------
+static size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+size_t knz_hip_encode_streams_bound(const knz_params* p, const knz_item* items, size_t n_items)
+{
+    size_t bound = 16;
+    for (size_t i = 0; i < n_items; i++) bound += round16(knz_hip_encode_bound(p, (size_t)items[i].in_len) + ((size_t)items[i].prologue_bits + 7) / 8);
+    return bound;
+}
+
+static int streams_block_size(Ctx* c, const knz_params* p, size_t nItems)
+{
+    const u32 bs = (u32)p->block_size;
+    if (bs < 1024 || bs > (1u << 30) || (bs & 15)) return fail(c, KNZ_ERR_INVALID_PARAM, "invalid block size %u", bs);
+    if (nItems > (size_t)KNZ_STREAMS_MAX_ITEMS) return fail(c, KNZ_ERR_INVALID_PARAM, "too many streams in one batch (%zu, at most %d)", nItems, KNZ_STREAMS_MAX_ITEMS);
+    return 0;
+}
+
+int knz_hip_encode_streams(knz_ctx* ctx, const knz_params* p, const uint8_t* d_in, knz_item* items, size_t n_items, const uint8_t* prologues,
+                           int finish, uint8_t* d_out, size_t out_cap, uint64_t* out_bytes)
+{
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    CTX_LOCK(c);
+    if (out_bytes) *out_bytes = 0;
+    if (items == nullptr && n_items) return fail(c, KNZ_ERR_INVALID_PARAM, "no items");
+    if (int r = streams_block_size(c, p, n_items)) return r;
+    Chain ch;
+    if (int r = parse_chain(c, p, 0, true, &ch)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    const u32 bs = (u32)p->block_size;
+    EncTab tab;
+    tab.nItems = (int)n_items;
+    tab.first.resize(n_items + 1);
+    size_t total = 0, nBlocks = 0, proBytes = 0;
+    for (size_t i = 0; i < n_items; i++) {
+        const knz_item& it = items[i];
+        if (it.in_off & 15) return fail(c, KNZ_ERR_INVALID_PARAM, "stream %zu: in_off %llu is no multiple of 16", i, (unsigned long long)it.in_off);
+        if (((size_t)it.prologue_bits + 7) / 8 > 200) return fail(c, KNZ_ERR_INVALID_PARAM, "prologue too long");
+        if (it.prologue_bits && prologues == nullptr) return fail(c, KNZ_ERR_INVALID_PARAM, "stream %zu: no prologue bytes", i);
+        if (it.in_len > (u64)0x7FFFFFFF) return fail(c, KNZ_ERR_INVALID_PARAM, "batch of %llu bytes exceeds the 2 GiB per-call limit", (unsigned long long)it.in_len);
+        tab.first[i] = (u32)nBlocks;
+        total += (size_t)it.in_len;
+        nBlocks += ((size_t)it.in_len + bs - 1) / bs;
+        proBytes = std::max(proBytes, (size_t)it.prologue_off + ((size_t)it.prologue_bits + 7) / 8);
+        if (total > (size_t)0x7FFFFFFF) return fail(c, KNZ_ERR_INVALID_PARAM, "batch of %zu bytes exceeds the 2 GiB per-call limit", total);
+        if (nBlocks > (size_t)KNZ_STREAMS_MAX_BLOCKS) return fail(c, KNZ_ERR_INVALID_PARAM, "too many blocks in one batch (more than %d)", KNZ_STREAMS_MAX_BLOCKS);
+    }
+    tab.first[n_items] = (u32)nBlocks;
+    tab.nBlocks = (int)nBlocks;
+    const size_t need = knz_hip_encode_streams_bound(p, items, n_items);
+    if (out_cap < need) return fail(c, KNZ_ERR_WRITE_FILE, "output buffer too small: need %zu have %zu", need, out_cap);
+
+    // one upload: block offsets | streams | block lengths | the blocks' streams | prologue bytes; behind it the results and the scan's scratch
+    const size_t oOff = 0, oSt = oOff + round16(8 * nBlocks), oLen = oSt + sizeof(StreamEnc) * (n_items + 1), oItem = oLen + round16(4 * nBlocks),
+                 oPro = oItem + round16(4 * nBlocks), up = oPro + round16(proBytes + 8), oRes = up, oExcl = oRes + sizeof(StreamOut) * n_items;
+    std::vector<u8> host(up, 0);
+    u64* hOff = reinterpret_cast<u64*>(host.data() + oOff);
+    StreamEnc* hSt = reinterpret_cast<StreamEnc*>(host.data() + oSt);
+    u32* hLen = reinterpret_cast<u32*>(host.data() + oLen);
+    u32* hItem = reinterpret_cast<u32*>(host.data() + oItem);
+    for (size_t i = 0; i <= n_items; i++) {
+        hSt[i].first = tab.first[i];
+        if (i == n_items) break;
+        const knz_item& it = items[i];
+        hSt[i].prologueBits = it.prologue_bits; hSt[i].prologueOff = it.prologue_off;
+        for (size_t k = 0, b = tab.first[i]; b < tab.first[i + 1]; k++, b++) {
+            hOff[b] = it.in_off + (u64)k * bs;
+            hLen[b] = (u32)std::min<u64>(bs, it.in_len - (u64)k * bs);
+            hItem[b] = (u32)i;
+            tab.maxLen = std::max(tab.maxLen, hLen[b]);
+        }
+    }
+    if (proBytes) memcpy(host.data() + oPro, prologues, proBytes);
+    tab.len.assign(hLen, hLen + nBlocks);
+    u8* d_tab;
+    hipStream_t s = c->stream;
+    if (int r = ws_get(c, "streamTab", oExcl + 8 * (nBlocks + 1), (void**)&d_tab, s)) return r;
+    HIPCHK(c, hipMemcpyAsync(d_tab, host.data(), up, hipMemcpyHostToDevice, s));
+    tab.d_inOff = reinterpret_cast<const u64*>(d_tab + oOff); tab.d_st = reinterpret_cast<const StreamEnc*>(d_tab + oSt);
+    tab.d_len = reinterpret_cast<const u32*>(d_tab + oLen); tab.d_itemOf = reinterpret_cast<const u32*>(d_tab + oItem);
+    tab.d_pro = d_tab + oPro; tab.d_res = reinterpret_cast<StreamOut*>(d_tab + oRes); tab.d_excl = reinterpret_cast<u64*>(d_tab + oExcl);
+    u64 bits = 0;
+    const int r = encode_impl(c, p, d_in, total, nullptr, 0, 1, finish, 0, d_out, out_cap, &bits, nullptr, 0, &tab);
+    if (r) { hipStreamSynchronize(s); return r; }          // (`host` may still be on its way)
+    for (size_t i = 0; i < n_items; i++) {
+        items[i].out_off = tab.res[i].base;
+        items[i].out_len = tab.res[i].bits;
+        items[i].blocks = (int32_t)(tab.first[i + 1] - tab.first[i]);
+        items[i].error = 0;
+    }
+    if (out_bytes) *out_bytes = bits / 8;
+    return 0;
+}
+
+int knz_hip_decode_streams(knz_ctx* ctx, const knz_params* p, const uint8_t* d_in, knz_item* items, size_t n_items, uint8_t* d_out, size_t out_cap)
+{
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    CTX_LOCK(c);
+    if (items == nullptr && n_items) return fail(c, KNZ_ERR_INVALID_PARAM, "no items");
+    if (int r = streams_block_size(c, p, n_items)) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<StreamDec> sd(n_items);
+    u64 reach = 0;
+    u32 maxUnit = 0;
+    for (size_t i = 0; i < n_items; i++) {
+        knz_item& it = items[i];
+        if ((it.in_off & 15) || (it.out_off & 15)) return fail(c, KNZ_ERR_INVALID_PARAM, "stream %zu: in_off and out_off must be multiples of 16", i);
+        if (it.out_off > out_cap || it.out_cap > out_cap - it.out_off) return fail(c, KNZ_ERR_INVALID_PARAM, "stream %zu: its output range leaves the buffer", i);
+        if (it.start_bit > it.in_len) return fail(c, KNZ_ERR_INVALID_PARAM, "stream %zu: start_bit behind the stream", i);
+        sd[i].inOff = it.in_off; sd[i].inBits = it.in_len; sd[i].startBit = it.start_bit; sd[i].outOff = it.out_off; sd[i].outCap = it.out_cap;
+        maxUnit = (u32)std::max<u64>(maxUnit, std::min<u64>(it.out_cap, (u64)p->block_size));
+        reach = std::max(reach, 8 * it.in_off + it.in_len);
+        it.out_len = 0; it.blocks = 0; it.error = 0;
+    }
+    if (n_items == 0) return 0;
+    hipStream_t s = c->stream;
+    u8* d_tab;
+    const size_t oWalk = round16(sizeof(StreamDec) * n_items);
+    if (int r = ws_get(c, "streamTab", oWalk + sizeof(StreamWalk) * (n_items + 1), (void**)&d_tab, s)) return r;
+    HIPCHK(c, hipMemcpyAsync(d_tab, sd.data(), sizeof(StreamDec) * n_items, hipMemcpyHostToDevice, s));
+    DecTab tab;
+    tab.nItems = (int)n_items; tab.items = items; tab.maxUnit = maxUnit;
+    tab.d_sd = reinterpret_cast<const StreamDec*>(d_tab); tab.d_walk = reinterpret_cast<StreamWalk*>(d_tab + oWalk);
+    const int r = decode_impl(c, p, d_in, reach, 0, 0, 1, 0, d_out, out_cap, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, &tab);
+    if (r) hipStreamSynchronize(s);
     return r;
 }
 

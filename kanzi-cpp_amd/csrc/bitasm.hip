@@ -10,49 +10,10 @@
 //                      into the zero-initialised output.
 #include "common.hpp"
 #include "stages.hpp"
+#include "bitcopy.hpp"
 #include <algorithm>
 
 namespace knz {
-
-// ---------------------------------------------------------------- wave-cooperative bit copy
-// Copies nbits (MSB-first from src[0]) to bit position dstBit of the big-endian word stream dst.
-__device__ void wave_copy_bits(u32* __restrict__ dst, u64 dstBit, const u8* __restrict__ src, u64 nbits)
-{
-    if (nbits == 0) return;
-    const int lane = lane_id();
-    const u64 w0 = dstBit >> 5;
-    const u64 w1 = (dstBit + nbits - 1) >> 5;
-    const u64 srcBytes = (nbits + 7) >> 3;
-    for (u64 w = w0 + lane; w <= w1; w += 64) {
-        const u64 wb = w << 5;
-        const u64 lo = wb > dstBit ? wb : dstBit;
-        const u64 hiEnd = dstBit + nbits;
-        const u64 hi = (wb + 32) < hiEnd ? (wb + 32) : hiEnd;
-        const u32 nb = (u32)(hi - lo);
-        const u64 s = lo - dstBit;
-        const u64 b0 = s >> 3;
-        const u32 sh = (u32)(s & 7);
-        // 40 source bits starting at byte b0 (big-endian): one (unaligned) dword + one byte when they are inside
-        // the piece, single bytes only at its tail
-        u64 win = 0;
-        if (b0 + 5 <= srcBytes) {
-            u32 x;
-            __builtin_memcpy(&x, src + b0, 4);
-            win = ((u64)bswap32(x) << 8) | (u64)src[b0 + 4];
-        } else {
-#pragma unroll
-            for (int i = 0; i < 5; i++) {
-                const u64 idx = b0 + i;
-                const u64 v = idx < srcBytes ? (u64)src[idx] : 0ull;
-                win |= v << (32 - 8 * i);
-            }
-        }
-        const u32 val = (u32)((win >> (40 - sh - nb)) & (nb == 32 ? 0xFFFFFFFFull : ((1ull << nb) - 1)));
-        const u32 word = val << (u32)((wb + 32) - hi);
-        if (nb == 32) dst[w] = bswap32(word);
-        else if (word) atomicOr(&dst[w], bswap32(word));
-    }
-}
 
 // Inline bytes (held in registers/struct) appended by one lane.
 __device__ void lane_put_bytes(u32* dst, u64 dstBit, const u32* words, u32 nbytes)
@@ -62,15 +23,6 @@ __device__ void lane_put_bytes(u32* dst, u64 dstBit, const u32* words, u32 nbyte
         or_bits_mem(dst, dstBit + 8ull * i, b, 8);
     }
 }
-
-// ---------------------------------------------------------------- framing helpers
-// Block header bits: mode byte (+ skip byte when > 4 transforms) + length + checksum
-// (io/CompressedOutputStream.cpp:757-807)
-__device__ __forceinline__ u32 block_data_size(u32 postLen)
-{
-    return (postLen < 256) ? 1u : (u32)(ilog2_u32(postLen) >> 3) + 1u;
-}
-
 
 __global__ __launch_bounds__(256) void k_block_sum(ChunkDesc* __restrict__ desc, BlockInfo* __restrict__ info,
                                                     const u32* __restrict__ blockLen, int maxChunks, u32 chunkSize, u32 slotMul)
@@ -214,7 +166,6 @@ __global__ void k_walk_blocks(BitSrc src, u64 startBit, int64_t maxBlocks, int f
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     u64 pos = startBit;
     int64_t nb = 0;
-    int err = 0;
     int ended = 0;
     int error = 0;
     if (!framing) {
@@ -227,39 +178,11 @@ __global__ void k_walk_blocks(BitSrc src, u64 startBit, int64_t maxBlocks, int f
         return;
     }
     while (nb < maxBlocks) {
-        const u32 lr = 3 + take_bits(src, pos, 5, err);
-        if (err) { error = KNZ_ERR_READ_FILE; break; }
-        u64 len = 0;
-        if (lr > 32) { len = (u64)take_bits(src, pos, lr - 32, err) << 32; len |= take_bits(src, pos, 32, err); }
-        else len = take_bits(src, pos, lr, err);
-        if (err) { error = KNZ_ERR_READ_FILE; break; }
-        if (len == 0) { ended = 1; break; }
-        if (len > (1ull << 34)) { error = KNZ_ERR_BLOCK_SIZE; break; }
-        if (pos + len > src.limitBits) { error = KNZ_ERR_READ_FILE; break; }
         DecBlock db;
-        db.payloadBit = pos; db.bits = len; db.error = 0; db.usedBits = 0; db.checksum = 0;
-        u64 p = pos;
-        BitSrc bs = src;
-        bs.limitBits = pos + len;
-        int e2 = 0;
-        const u32 mode = take_bits(bs, p, 8, e2);
-        db.copyBlock = (mode & 0x80) ? 1u : 0u;
-        if (db.copyBlock) db.skipFlags = 0xFF;
-        else if (mode & 0x10) db.skipFlags = take_bits(bs, p, 8, e2);
-        else db.skipFlags = ((mode << 4) | 0x0F) & 0xFF;
-        const u32 ds = 1 + ((mode >> 5) & 3);
-        db.preLen = take_bits(bs, p, 8 * ds, e2);
-        const u32 blkLen = (blockSize + 512 > blockSize + (blockSize >> 4)) ? blockSize + 512 : blockSize + (blockSize >> 4);
-        u32 mts = blkLen + blkLen / 2;
-        if (mts < 2048) mts = 2048;
-        if (mts > (1u << 30)) mts = 1u << 30;
-        if (e2 || db.preLen == 0 || db.preLen > mts) db.error = KNZ_ERR_READ_FILE;
-        if (checksumBits == 32) db.checksum = take_bits(bs, p, 32, e2);
-        else if (checksumBits == 64) { db.checksum = (u64)take_bits(bs, p, 32, e2) << 32; db.checksum |= take_bits(bs, p, 32, e2); }
-        if (e2 && !db.error) db.error = KNZ_ERR_PROCESS_BLOCK;
-        db.entropyBit = p;
+        const int r = walk_step(src, pos, checksumBits, blockSize, db, error);
+        if (r == WALK_END) { ended = 1; break; }
+        if (r == WALK_ERROR) break;
         blocks[nb] = db;
-        pos += len;
         nb++;
     }
     res->endBit = pos;
@@ -293,34 +216,38 @@ void launch_assemble(hipStream_t s, const ChunkDesc* desc, const BlockInfo* info
                        hdrBase, maxChunks, chunkSize, slotMul, hdrStride, fp, out); }
 }
 
-__global__ void k_init_blocks(u64 n, u32 blockSize, int nBlocks, u32* origLen, u32* blockLen)
+// (lenTab: the blocks' lengths where the batch is no single stream cut into equal blocks; nullptr = that arithmetic)
+__global__ void k_init_blocks(u64 n, u32 blockSize, int nBlocks, u32* origLen, u32* blockLen, const u32* __restrict__ lenTab)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nBlocks) return;
     const u64 off = (u64)b * blockSize;
-    const u32 len = (n - off < blockSize) ? (u32)(n - off) : blockSize;
+    const u32 len = lenTab ? lenTab[b] : (n - off < blockSize) ? (u32)(n - off) : blockSize;
     origLen[b] = len;
     blockLen[b] = len;
 }
 
-void launch_init_blocks(hipStream_t s, u64 n, u32 blockSize, int nBlocks, u32* origLen, u32* blockLen)
+void launch_init_blocks(hipStream_t s, u64 n, u32 blockSize, int nBlocks, u32* origLen, u32* blockLen, const u32* lenTab)
 {
-    { KScope ks_("k_init_blocks"); hipLaunchKernelGGL(k_init_blocks, dim3((nBlocks + 255) / 256), dim3(256), 0, s, n, blockSize, nBlocks, origLen, blockLen); }
+    { KScope ks_("k_init_blocks"); hipLaunchKernelGGL(k_init_blocks, dim3((nBlocks + 255) / 256), dim3(256), 0, s, n, blockSize, nBlocks, origLen, blockLen, lenTab); }
 }
 
 // Reject blocks whose declared length cannot be written (guards every later kernel).
-__global__ void k_check_prelen(DecBlock* blocks, int nBlocks, u32 maxPre, u64 outCap, u64 outStride)
+// (roomTab: the room behind each block's place where the blocks lie at places of their own; with it, outCap only says whether the room
+// counts at all -- ~0 = the blocks go to a workspace first)
+__global__ void k_check_prelen(DecBlock* blocks, int nBlocks, u32 maxPre, u64 outCap, u64 outStride, const u64* __restrict__ roomTab)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nBlocks) return;
     DecBlock& db = blocks[b];
     if (db.error) return;
-    if (db.preLen > maxPre || (u64)b * outStride + db.preLen > outCap) db.error = KNZ_ERR_PROCESS_BLOCK;
+    const bool over = roomTab ? (outCap != ~0ull && db.preLen > roomTab[b]) : ((u64)b * outStride + db.preLen > outCap);
+    if (db.preLen > maxPre || over) db.error = KNZ_ERR_PROCESS_BLOCK;
 }
 
-void launch_check_prelen(hipStream_t s, DecBlock* blocks, int nBlocks, u32 maxPre, u64 outCap, u64 outStride)
+void launch_check_prelen(hipStream_t s, DecBlock* blocks, int nBlocks, u32 maxPre, u64 outCap, u64 outStride, const u64* roomTab)
 {
-    { KScope ks_("k_check_prelen"); hipLaunchKernelGGL(k_check_prelen, dim3((nBlocks + 255) / 256), dim3(256), 0, s, blocks, nBlocks, maxPre, outCap, outStride); }
+    { KScope ks_("k_check_prelen"); hipLaunchKernelGGL(k_check_prelen, dim3((nBlocks + 255) / 256), dim3(256), 0, s, blocks, nBlocks, maxPre, outCap, outStride, roomTab); }
 }
 
 // out = r zero bits (0 < r < 8) followed by the nbits bits of in, both MSB-first byte streams; out gets (r + nbits + 7) / 8 bytes

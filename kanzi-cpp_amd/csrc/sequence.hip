@@ -9,13 +9,17 @@
 
 namespace knz {
 
-__device__ __forceinline__ const u8* fwd_ptr(u8 where, int b, const u8* in, u64 inStride, u8* A, u8* B, u64 S)
+// Where block b lies in the caller's buffer: b * stride in a single stream cut into equal blocks, tab[b] in a batch of many streams
+// (knz_hip_encode_streams / knz_hip_decode_streams). Every kernel below takes such a table; nullptr = the arithmetic.
+__device__ __forceinline__ u64 blk_off(int b, u64 stride, const u64* __restrict__ tab) { return tab ? tab[b] : (u64)b * stride; }
+
+__device__ __forceinline__ const u8* fwd_ptr(u8 where, int b, const u8* in, u64 inStride, const u64* inOff, u8* A, u8* B, u64 S)
 {
-    return where == 0 ? in + (size_t)b * inStride : (where == 1 ? A + (size_t)b * S : B + (size_t)b * S);
+    return where == 0 ? in + (size_t)blk_off(b, inStride, inOff) : (where == 1 ? A + (size_t)b * S : B + (size_t)b * S);
 }
 
 // stage 0 additionally initialises the per-block state
-__global__ void k_seq_fwd_prepare(SeqArrays a, int nBlocks, int stage, const u8* in, u64 inStride, u8* A, u8* B, u64 S)
+__global__ void k_seq_fwd_prepare(SeqArrays a, int nBlocks, int stage, const u8* in, u64 inStride, u8* A, u8* B, u64 S, const u64* inOff)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nBlocks) return;
@@ -30,7 +34,7 @@ __global__ void k_seq_fwd_prepare(SeqArrays a, int nBlocks, int stage, const u8*
         a.active[b] = copy ? 0 : 1;
     }
     const u8 w = a.where[b];
-    a.src[b] = fwd_ptr(w, b, in, inStride, A, B, S);
+    a.src[b] = fwd_ptr(w, b, in, inStride, inOff, A, B, S);
     a.dst[b] = (w == 1) ? B + (size_t)b * S : A + (size_t)b * S;
     a.alen[b] = a.active[b] ? a.len[b] : 0;
     // TransformSequence.hpp:104-115: out is the task's "buffer" after an even number of swaps, its "data"
@@ -75,21 +79,23 @@ __global__ void k_seq_fwd_hosted(SeqArrays a, int nBlocks, int stage, int applie
     a.skip[b] &= (u8)~(1u << (7 - stage));
 }
 
-__global__ void k_seq_fwd_finish(SeqArrays a, int nBlocks, const u8* in, u64 inStride, u8* A, u8* B, u64 S, const u8** viewPtr)
+__global__ void k_seq_fwd_finish(SeqArrays a, int nBlocks, const u8* in, u64 inStride, u8* A, u8* B, u64 S, const u8** viewPtr, const u64* inOff)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nBlocks) return;
-    viewPtr[b] = fwd_ptr(a.where[b], b, in, inStride, A, B, S);
+    viewPtr[b] = fwd_ptr(a.where[b], b, in, inStride, inOff, A, B, S);
 }
 
 // Chains made of NullTransforms only (e.g. "-t NONE"): everything k_init_blocks + prepare + null + finish would
 // compute, in one launch.  Every stage "succeeds", the data never leaves the caller's buffer.
-__global__ void k_seq_fwd_direct(SeqArrays a, u32* origLen, u64 n, u32 blockSize, int nBlocks, int nStages, const u8* in, const u8** viewPtr)
+// (inOff, lenTab: the blocks' places and lengths in a batch of many streams, both or neither)
+__global__ void k_seq_fwd_direct(SeqArrays a, u32* origLen, u64 n, u32 blockSize, int nBlocks, int nStages, const u8* in, const u8** viewPtr,
+                                 const u64* inOff, const u32* lenTab)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nBlocks) return;
-    const u64 off = (u64)b * blockSize;
-    const u32 len = (n - off < blockSize) ? (u32)(n - off) : blockSize;
+    const u64 off = blk_off(b, blockSize, inOff);
+    const u32 len = lenTab ? lenTab[b] : (n - off < blockSize) ? (u32)(n - off) : blockSize;
     origLen[b] = len;
     a.len[b] = len;
     a.where[b] = 0;
@@ -101,8 +107,9 @@ __global__ void k_seq_fwd_direct(SeqArrays a, u32* origLen, u64 n, u32 blockSize
 }
 
 // ---- inverse
+// (outOff, roomTab: the blocks' places in the caller's buffer and the room behind each, in a batch of many streams; both or neither)
 __global__ void k_seq_inv_entropy_dst(SeqArrays a, DecBlock* blocks, int nBlocks, u8* out, u64 outStride, u8* A, u64 S, u8** entDst, u32 realMask,
-                                      u32 unit, u64 outCap)
+                                      u32 unit, u64 outCap, const u64* outOff, const u64* roomTab)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nBlocks) return;
@@ -113,17 +120,17 @@ __global__ void k_seq_inv_entropy_dst(SeqArrays a, DecBlock* blocks, int nBlocks
     // own slot there (TransformSequence::inverse refuses count > output room, TransformSequence.hpp:165-247).
     if (!any && !db.error) {
         const u64 at = (u64)b * outStride;
-        const u64 room = at < outCap ? outCap - at : 0;
+        const u64 room = roomTab ? roomTab[b] : (at < outCap ? outCap - at : 0);
         if (db.preLen > unit || (u64)db.preLen > room) db.error = KNZ_ERR_PROCESS_BLOCK;
     }
     a.skip[b] = db.copyBlock ? 0xFF : (u8)db.skipFlags;
     a.where[b] = any ? 1 : 0;
     a.len[b] = db.preLen;
-    entDst[b] = any ? A + (size_t)b * S : out + (size_t)b * outStride;
+    entDst[b] = any ? A + (size_t)b * S : out + (size_t)blk_off(b, outStride, outOff);
 }
 
 __global__ void k_seq_inv_prepare(SeqArrays a, DecBlock* blocks, int nBlocks, int stage, u8* out, u64 outStride, u8* A, u8* B, u64 S,
-                                  u32 capMid, u32 capFinal, u32 realMask, u64 outCap)
+                                  u32 capMid, u32 capFinal, u32 realMask, u64 outCap, const u64* outOff, const u64* roomTab)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nBlocks) return;
@@ -139,8 +146,8 @@ __global__ void k_seq_inv_prepare(SeqArrays a, DecBlock* blocks, int nBlocks, in
     else {
         // the last inverse to run writes into the caller's buffer, never past its end (a short last block may
         // leave less than a block of room)
-        const u64 off = (u64)b * outStride;
-        const u64 room = (outCap > off) ? outCap - off : 0;
+        const u64 off = blk_off(b, outStride, outOff);
+        const u64 room = roomTab ? (outCap == ~0ull ? ~0ull : roomTab[b]) : ((outCap > off) ? outCap - off : 0);
         a.dst[b] = out + off;
         a.cap[b] = (room < capFinal) ? (u32)room : capFinal;
     }
@@ -160,34 +167,36 @@ __global__ void k_seq_inv_commit(SeqArrays a, DecBlock* blocks, int nBlocks, int
     a.where[b] = a.swaps[b] ? ((a.where[b] == 1) ? 2 : 1) : 0;
 }
 
-__global__ void k_seq_fwd_dtype(SeqArrays a, int nBlocks, const u8* in, u64 inStride)
+__global__ void k_seq_fwd_dtype(SeqArrays a, int nBlocks, const u8* in, u64 inStride, const u64* inOff)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nBlocks) return;
-    a.dtype[b] = (u8)knz_magic::data_type_preset(in + (size_t)b * inStride, a.origLen[b]);   // io/CompressedOutputStream.cpp:722-731
+    a.dtype[b] = (u8)knz_magic::data_type_preset(in + (size_t)blk_off(b, inStride, inOff), a.origLen[b]);   // io/CompressedOutputStream.cpp:722-731
 }
 
 #define L1D(k, ...) hipLaunchKernelGGL(k, dim3((nBlocks + 255) / 256), dim3(256), 0, s, __VA_ARGS__)
 
-void launch_seq_fwd_direct(hipStream_t s, const SeqArrays& a, u32* origLen, u64 n, u32 blockSize, int nBlocks, int nStages, const u8* in, const u8** viewPtr)
-{ KScope ks_("k_seq_fwd_direct"); L1D(k_seq_fwd_direct, a, origLen, n, blockSize, nBlocks, nStages, in, viewPtr); }
-void launch_seq_fwd_prepare(hipStream_t s, const SeqArrays& a, int nBlocks, int stage, const u8* in, u64 inStride, u8* A, u8* B, u64 S)
-{ KScope ks_("k_seq_fwd_prepare"); L1D(k_seq_fwd_prepare, a, nBlocks, stage, in, inStride, A, B, S); }
+void launch_seq_fwd_direct(hipStream_t s, const SeqArrays& a, u32* origLen, u64 n, u32 blockSize, int nBlocks, int nStages, const u8* in, const u8** viewPtr,
+                           const u64* inOff, const u32* lenTab)
+{ KScope ks_("k_seq_fwd_direct"); L1D(k_seq_fwd_direct, a, origLen, n, blockSize, nBlocks, nStages, in, viewPtr, inOff, lenTab); }
+void launch_seq_fwd_prepare(hipStream_t s, const SeqArrays& a, int nBlocks, int stage, const u8* in, u64 inStride, u8* A, u8* B, u64 S, const u64* inOff)
+{ KScope ks_("k_seq_fwd_prepare"); L1D(k_seq_fwd_prepare, a, nBlocks, stage, in, inStride, A, B, S, inOff); }
 void launch_seq_fwd_commit(hipStream_t s, const SeqArrays& a, int nBlocks, int stage)
 { KScope ks_("k_seq_fwd_commit"); L1D(k_seq_fwd_commit, a, nBlocks, stage); }
 void launch_seq_fwd_null(hipStream_t s, const SeqArrays& a, int nBlocks, int stage)
 { KScope ks_("k_seq_fwd_null"); L1D(k_seq_fwd_null, a, nBlocks, stage); }
 void launch_seq_fwd_hosted(hipStream_t s, const SeqArrays& a, int nBlocks, int stage, int applied)
 { KScope ks_("k_seq_fwd_hosted"); L1D(k_seq_fwd_hosted, a, nBlocks, stage, applied); }
-void launch_seq_fwd_dtype(hipStream_t s, const SeqArrays& a, int nBlocks, const u8* in, u64 inStride)
-{ KScope ks_("k_seq_fwd_dtype"); L1D(k_seq_fwd_dtype, a, nBlocks, in, inStride); }
-void launch_seq_fwd_finish(hipStream_t s, const SeqArrays& a, int nBlocks, const u8* in, u64 inStride, u8* A, u8* B, u64 S, const u8** viewPtr)
-{ KScope ks_("k_seq_fwd_finish"); L1D(k_seq_fwd_finish, a, nBlocks, in, inStride, A, B, S, viewPtr); }
+void launch_seq_fwd_dtype(hipStream_t s, const SeqArrays& a, int nBlocks, const u8* in, u64 inStride, const u64* inOff)
+{ KScope ks_("k_seq_fwd_dtype"); L1D(k_seq_fwd_dtype, a, nBlocks, in, inStride, inOff); }
+void launch_seq_fwd_finish(hipStream_t s, const SeqArrays& a, int nBlocks, const u8* in, u64 inStride, u8* A, u8* B, u64 S, const u8** viewPtr, const u64* inOff)
+{ KScope ks_("k_seq_fwd_finish"); L1D(k_seq_fwd_finish, a, nBlocks, in, inStride, A, B, S, viewPtr, inOff); }
 void launch_seq_inv_entropy_dst(hipStream_t s, const SeqArrays& a, DecBlock* blocks, int nBlocks, u8* out, u64 outStride, u8* A, u64 S, u8** entDst, u32 realMask,
-                                u32 unit, u64 outCap)
-{ KScope ks_("k_seq_inv_entropy_dst"); L1D(k_seq_inv_entropy_dst, a, blocks, nBlocks, out, outStride, A, S, entDst, realMask, unit, outCap); }
-void launch_seq_inv_prepare(hipStream_t s, const SeqArrays& a, DecBlock* blocks, int nBlocks, int stage, u8* out, u64 outStride, u8* A, u8* B, u64 S, u32 capMid, u32 capFinal, u32 realMask, u64 outCap)
-{ KScope ks_("k_seq_inv_prepare"); L1D(k_seq_inv_prepare, a, blocks, nBlocks, stage, out, outStride, A, B, S, capMid, capFinal, realMask, outCap); }
+                                u32 unit, u64 outCap, const u64* outOff, const u64* roomTab)
+{ KScope ks_("k_seq_inv_entropy_dst"); L1D(k_seq_inv_entropy_dst, a, blocks, nBlocks, out, outStride, A, S, entDst, realMask, unit, outCap, outOff, roomTab); }
+void launch_seq_inv_prepare(hipStream_t s, const SeqArrays& a, DecBlock* blocks, int nBlocks, int stage, u8* out, u64 outStride, u8* A, u8* B, u64 S, u32 capMid, u32 capFinal, u32 realMask, u64 outCap,
+                            const u64* outOff, const u64* roomTab)
+{ KScope ks_("k_seq_inv_prepare"); L1D(k_seq_inv_prepare, a, blocks, nBlocks, stage, out, outStride, A, B, S, capMid, capFinal, realMask, outCap, outOff, roomTab); }
 void launch_seq_inv_commit(hipStream_t s, const SeqArrays& a, DecBlock* blocks, int nBlocks, int stage, int ttype)
 { KScope ks_("k_seq_inv_commit"); L1D(k_seq_inv_commit, a, blocks, nBlocks, stage, ttype); }
 

@@ -13,7 +13,10 @@ struct FrameParams {
 };
 
 // bitasm.hip
-void launch_init_blocks(hipStream_t s, u64 n, u32 blockSize, int nBlocks, u32* origLen, u32* blockLen);
+// Per-block tables (the trailing arguments of the bookkeeping launchers here, in sequence.hip and in xxhash.hip): a batch of many
+// streams (streams.hip) places block b at a byte offset of its own, with a length and, on the way back, a room of its own. nullptr =
+// one stream cut into equal blocks, b * stride.
+void launch_init_blocks(hipStream_t s, u64 n, u32 blockSize, int nBlocks, u32* origLen, u32* blockLen, const u32* lenTab = nullptr);
 // A block owns ceil(len / chunkSize) * slotMul consecutive ChunkDesc slots (slotMul > 1: ANS1, one slot per context table).
 void launch_block_sum(hipStream_t s, ChunkDesc* desc, BlockInfo* info, const u32* blockLen, int nBlocks, int maxChunks, u32 chunkSize, u32 slotMul);
 void launch_block_scan(hipStream_t s, BlockInfo* info, const u32* blockLen, const u32* origLen, int nBlocks, FrameParams fp, u64* totalBits);
@@ -24,7 +27,24 @@ void launch_put_prologue(hipStream_t s, u32* out, const u8* d_prologue, u32 bits
 void launch_shift_bits(hipStream_t s, const u8* in, u64 nbits, u32 r, u8* out);
 void launch_walk_blocks(hipStream_t s, BitSrc src, u64 startBit, int64_t maxBlocks, int framing, u32 rawLen, int checksumBits,
                         u32 blockSize, DecBlock* blocks, void* res);
-void launch_check_prelen(hipStream_t s, DecBlock* blocks, int nBlocks, u32 maxPre, u64 outCap, u64 outStride);
+void launch_check_prelen(hipStream_t s, DecBlock* blocks, int nBlocks, u32 maxPre, u64 outCap, u64 outStride, const u64* roomTab = nullptr);
+
+// streams.hip: the framing of a batch of many independent streams. Stream i owns the blocks [st[i].first, st[i + 1].first) of the batch
+// (st has one entry more than there are streams); itemOf[b] is the stream of block b.
+struct StreamEnc { u32 first; u32 prologueBits; u32 prologueOff; u32 pad; };      // prologueOff: into the call's prologue bytes
+struct StreamOut { u64 base; u64 bits; };                                         // where the stream lies in the output (bytes), its length
+struct StreamDec { u64 inOff; u64 inBits; u64 startBit; u64 outOff; u64 outCap; };
+struct StreamWalk { u64 first; u32 count; int32_t error; int32_t ended; u32 pad; };   // first block's slot, blocks, the walk's verdict
+// hdrBits / written / lw / bitOff of every block (payloadBits set by launch_block_sum), res[i] and *totalBytes: what launch_block_scan
+// leaves for one stream, for all of them; the streams lie back to back from byte 0, each at a multiple of 16. excl: nBlocks + 1 words.
+void launch_stream_frame(hipStream_t s, BlockInfo* info, const u32* blockLen, const u32* origLen, const u32* itemOf, int nBlocks, const StreamEnc* st, int nItems,
+                         FrameParams fp, u64* excl, StreamOut* res, u64* totalBytes);
+void launch_stream_prologues(hipStream_t s, u32* out, const StreamEnc* st, const StreamOut* res, int nItems, const u8* prologues);
+// res: nItems + 1 entries; res[nItems].first = blocks of all streams. Then, with room for that many: the DecBlock entries (bit positions
+// counted from `in`) and every block's place and room in the output.
+void launch_walk_streams_count(hipStream_t s, const u8* in, const StreamDec* sd, int nItems, int checksumBits, u32 blockSize, StreamWalk* res);
+void launch_walk_streams_fill(hipStream_t s, const u8* in, const StreamDec* sd, int nItems, int checksumBits, u32 blockSize, const StreamWalk* res,
+                              DecBlock* blocks, u64* outOff, u64* room);
 
 // none.hip
 void launch_none_encode(hipStream_t s, BlockView view, int nBlocks, int maxChunks, ChunkDesc* desc);
@@ -214,9 +234,9 @@ size_t lz_forward_scratch_bytes(int ttype, int nBlocks, u32 maxLen);
 
 // xxhash.hip
 void launch_xxhash(hipStream_t s, const u8* const* ptr, const u32* lens, int nBlocks, int bits, u64* out);
-void launch_block_ptrs(hipStream_t s, const u8* base, u64 stride, int nBlocks, const u8** ptr);
+void launch_block_ptrs(hipStream_t s, const u8* base, u64 stride, int nBlocks, const u8** ptr, const u64* offTab = nullptr);
 void launch_verify_checksums(hipStream_t s, DecBlock* blocks, int nBlocks, int bits, const u8* out, u64 outStride, const u8** ptrScratch,
-                             u32* lenScratch, u64* sumScratch);
+                             u32* lenScratch, u64* sumScratch, const u64* offTab = nullptr);
 
 // sequence.hip : TransformSequence bookkeeping on the device
 struct SeqArrays {
@@ -236,15 +256,18 @@ struct SeqArrays {
     const u32* bufCap;
     u8* dtype;               // per-block data type (forward: preset from the block's magic, io/CompressedOutputStream.cpp:722-731)
 };
-void launch_seq_fwd_direct(hipStream_t s, const SeqArrays& a, u32* origLen, u64 n, u32 blockSize, int nBlocks, int nStages, const u8* in, const u8** viewPtr);
-void launch_seq_fwd_prepare(hipStream_t s, const SeqArrays& a, int nBlocks, int stage, const u8* in, u64 inStride, u8* A, u8* B, u64 S);
+void launch_seq_fwd_direct(hipStream_t s, const SeqArrays& a, u32* origLen, u64 n, u32 blockSize, int nBlocks, int nStages, const u8* in, const u8** viewPtr,
+                           const u64* inOff = nullptr, const u32* lenTab = nullptr);
+void launch_seq_fwd_prepare(hipStream_t s, const SeqArrays& a, int nBlocks, int stage, const u8* in, u64 inStride, u8* A, u8* B, u64 S, const u64* inOff = nullptr);
 void launch_seq_fwd_null(hipStream_t s, const SeqArrays& a, int nBlocks, int stage);
 void launch_seq_fwd_hosted(hipStream_t s, const SeqArrays& a, int nBlocks, int stage, int applied);
 void launch_seq_fwd_commit(hipStream_t s, const SeqArrays& a, int nBlocks, int stage);
-void launch_seq_fwd_dtype(hipStream_t s, const SeqArrays& a, int nBlocks, const u8* in, u64 inStride);
-void launch_seq_fwd_finish(hipStream_t s, const SeqArrays& a, int nBlocks, const u8* in, u64 inStride, u8* A, u8* B, u64 S, const u8** viewPtr);
-void launch_seq_inv_entropy_dst(hipStream_t s, const SeqArrays& a, DecBlock* blocks, int nBlocks, u8* out, u64 outStride, u8* A, u64 S, u8** entDst, u32 realMask, u32 unit, u64 outCap);
-void launch_seq_inv_prepare(hipStream_t s, const SeqArrays& a, DecBlock* blocks, int nBlocks, int stage, u8* out, u64 outStride, u8* A, u8* B, u64 S, u32 capMid, u32 capFinal, u32 realMask, u64 outCap);
+void launch_seq_fwd_dtype(hipStream_t s, const SeqArrays& a, int nBlocks, const u8* in, u64 inStride, const u64* inOff = nullptr);
+void launch_seq_fwd_finish(hipStream_t s, const SeqArrays& a, int nBlocks, const u8* in, u64 inStride, u8* A, u8* B, u64 S, const u8** viewPtr, const u64* inOff = nullptr);
+void launch_seq_inv_entropy_dst(hipStream_t s, const SeqArrays& a, DecBlock* blocks, int nBlocks, u8* out, u64 outStride, u8* A, u64 S, u8** entDst, u32 realMask, u32 unit, u64 outCap,
+                                const u64* outOff = nullptr, const u64* roomTab = nullptr);
+void launch_seq_inv_prepare(hipStream_t s, const SeqArrays& a, DecBlock* blocks, int nBlocks, int stage, u8* out, u64 outStride, u8* A, u8* B, u64 S, u32 capMid, u32 capFinal, u32 realMask, u64 outCap,
+                            const u64* outOff = nullptr, const u64* roomTab = nullptr);
 void launch_seq_inv_commit(hipStream_t s, const SeqArrays& a, DecBlock* blocks, int nBlocks, int stage, int ttype);
 
 // huffman.hip

@@ -89,10 +89,11 @@ __global__ __launch_bounds__(64) void k_xxhash(const u8* const* __restrict__ ptr
     }
 }
 
-__global__ void k_block_ptrs(const u8* base, u64 stride, int nBlocks, const u8** ptr)
+// (offTab: the blocks' byte offsets where they do not lie b * stride apart; nullptr = that arithmetic)
+__global__ void k_block_ptrs(const u8* base, u64 stride, int nBlocks, const u8** ptr, const u64* __restrict__ offTab)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < nBlocks) ptr[b] = base + (size_t)b * stride;
+    if (b < nBlocks) ptr[b] = base + (offTab ? (size_t)offTab[b] : (size_t)b * stride);
 }
 
 // decode side: compare with the checksum stored in the stream (io/CompressedInputStream.cpp:1003-1022)
@@ -118,15 +119,15 @@ void launch_xxhash(hipStream_t s, const u8* const* ptr, const u32* lens, int nBl
     { KScope ks_("k_xxhash"); hipLaunchKernelGGL(k_xxhash, dim3((nBlocks + 15) / 16), dim3(64), 0, s, ptr, lens, nBlocks, bits, out); }
 }
 
-void launch_block_ptrs(hipStream_t s, const u8* base, u64 stride, int nBlocks, const u8** ptr)
+void launch_block_ptrs(hipStream_t s, const u8* base, u64 stride, int nBlocks, const u8** ptr, const u64* offTab)
 {
-    { KScope ks_("k_block_ptrs"); hipLaunchKernelGGL(k_block_ptrs, dim3((nBlocks + 255) / 256), dim3(256), 0, s, base, stride, nBlocks, ptr); }
+    { KScope ks_("k_block_ptrs"); hipLaunchKernelGGL(k_block_ptrs, dim3((nBlocks + 255) / 256), dim3(256), 0, s, base, stride, nBlocks, ptr, offTab); }
 }
 
 void launch_verify_checksums(hipStream_t s, DecBlock* blocks, int nBlocks, int bits, const u8* out, u64 outStride, const u8** ptrScratch,
-                             u32* lenScratch, u64* sumScratch)
+                             u32* lenScratch, u64* sumScratch, const u64* offTab)
 {
-    launch_block_ptrs(s, out, outStride, nBlocks, ptrScratch);
+    launch_block_ptrs(s, out, outStride, nBlocks, ptrScratch, offTab);
     { KScope ks_("k_declen"); hipLaunchKernelGGL(k_declen, dim3((nBlocks + 255) / 256), dim3(256), 0, s, blocks, nBlocks, lenScratch); }
     launch_xxhash(s, ptrScratch, lenScratch, nBlocks, bits, sumScratch);
     { KScope ks_("k_verify_checksums"); hipLaunchKernelGGL(k_verify_checksums, dim3((nBlocks + 255) / 256), dim3(256), 0, s, blocks, nBlocks, bits, sumScratch); }

@@ -25,12 +25,22 @@ SYMBOLS = [
     "knz_hip_entropy_encode_bs", "knz_hip_entropy_decode_bs", "knz_hip_tpaq_params",
     "knz_hip_transform_forward_bs", "knz_hip_transform_inverse_bs",
     "knz_hip_prims_info", "knz_hip_prims_scan", "knz_hip_prims_sort",
+    "knz_hip_encode_streams_bound", "knz_hip_encode_streams", "knz_hip_decode_streams",
 ]
+STREAMS_MAX_ITEMS = STREAMS_MAX_BLOCKS = 65536      # KNZ_STREAMS_MAX_ITEMS / _BLOCKS of include/knz_hip.h
+BATCH_MAX_BYTES = 0x7FFFFFFF                        # input of one encode call, decoded bytes of one decode call
 
 
 class Params(C.Structure):
     _fields_ = [("transform_type", C.c_uint64), ("entropy_type", C.c_int32), ("block_size", C.c_int32),
                 ("checksum_bits", C.c_int32), ("jobs", C.c_int32), ("bs_version", C.c_int32)]
+
+
+class Item(C.Structure):
+    """knz_item: one stream of a knz_hip_encode_streams / knz_hip_decode_streams call."""
+    _fields_ = [("in_off", C.c_uint64), ("in_len", C.c_uint64), ("start_bit", C.c_uint64), ("prologue_off", C.c_uint32),
+                ("prologue_bits", C.c_uint32), ("out_off", C.c_uint64), ("out_cap", C.c_uint64), ("out_len", C.c_uint64),
+                ("blocks", C.c_int32), ("error", C.c_int32)]
 
 
 class KernelTime(C.Structure):
@@ -112,6 +122,9 @@ def lib():
         L.knz_hip_prims_info.argtypes = [C.POINTER(C.c_uint32)]
         L.knz_hip_prims_scan.argtypes = [vp, C.c_int, vp, vp, sz, vp, vp]
         L.knz_hip_prims_sort.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, sz, C.c_int, C.c_int, vp, vp]
+        L.knz_hip_encode_streams_bound.argtypes = [C.POINTER(Params), C.POINTER(Item), sz]; L.knz_hip_encode_streams_bound.restype = sz
+        L.knz_hip_encode_streams.argtypes = [vp, C.POINTER(Params), u8p, C.POINTER(Item), sz, C.c_char_p, C.c_int, u8p, sz, C.POINTER(C.c_uint64)]
+        L.knz_hip_decode_streams.argtypes = [vp, C.POINTER(Params), u8p, C.POINTER(Item), sz, u8p, sz]
         _lib = L
     return _lib
 
@@ -188,6 +201,23 @@ class Context:
         self._chk(self.L.knz_hip_decode_blocks(self.h, C.byref(p), C.c_void_p(d_in), in_bits, start_bit, max_blocks,
                                                C.c_void_p(d_out), out_cap, C.byref(ob), C.byref(eb), C.byref(nb)))
         return ob.value, eb.value, nb.value
+
+    # ---- many streams in one call, on device pointers
+    def encode_streams_bound(self, p, items):
+        return self.L.knz_hip_encode_streams_bound(C.byref(p), items, len(items))
+
+    def encode_streams(self, p, d_in, items, d_out, out_cap, prologues=b"", finish=1):
+        """items: an array of Item (in_off, in_len, prologue_off, prologue_bits set); the call fills out_off, out_len (bits) and blocks.
+        Returns the bytes of d_out in use."""
+        used = C.c_uint64(0)
+        self._chk(self.L.knz_hip_encode_streams(self.h, C.byref(p), C.c_void_p(d_in), items, len(items), prologues, finish,
+                                                C.c_void_p(d_out), out_cap, C.byref(used)))
+        return used.value
+
+    def decode_streams(self, p, d_in, items, d_out, out_cap):
+        """items: an array of Item (in_off, in_len in bits, start_bit, out_off, out_cap set); the call fills out_len (bytes), blocks and
+        error per item. Raises only for a failure of the call itself."""
+        self._chk(self.L.knz_hip_decode_streams(self.h, C.byref(p), C.c_void_p(d_in), items, len(items), C.c_void_p(d_out), out_cap))
 
     # ---- per-stage API on host buffers
     def entropy_encode(self, entropy, data, stream_block_size=0):

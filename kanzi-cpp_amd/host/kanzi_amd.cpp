@@ -14,6 +14,7 @@
 #include <memory>
 #include <mutex>
 #include <sstream>
+#include <tuple>
 #include <sys/stat.h>
 #include <chrono>
 #include <deque>
@@ -2461,6 +2462,296 @@ void CompressedInputStream::close()
         fprintf(stderr, "[knz in] lanes %zu: reader source-read %.2f ms, stage-copy %.2f | decoders upload-wait %.2f, kernels %.2f | caller wait-batch %.2f, download-wait %.2f, copy-out %.2f\n",
                 _ps.size(), _tns[0] / 1e6, _tns[1] / 1e6, _tns[2] / 1e6, _tns[3] / 1e6, _tns[4] / 1e6, _tns[5] / 1e6, _tns[6] / 1e6);
     setstate(std::ios::eofbit);
+}
+
+// ------------------------------------------------------------------------------------------------
+// many small buffers, many per device call (include/kanzi_amd.hpp: compressMany / decompressMany)
+// ------------------------------------------------------------------------------------------------
+// The device entry points are bound weakly: a device library from before they existed (such as the CPU stand-in the host layer is
+// tested against) lacks them, and every item then goes through a stream class of its own.
+#pragma weak knz_hip_encode_streams_bound
+#pragma weak knz_hip_encode_streams
+#pragma weak knz_hip_decode_streams
+
+bool deviceBatchesStreams()
+{
+    static const bool off = getenv("KNZ_STREAMS_BATCH") != nullptr && atoi(getenv("KNZ_STREAMS_BATCH")) == 0;
+    return !off && knz_hip_encode_streams_bound != nullptr && knz_hip_encode_streams != nullptr && knz_hip_decode_streams != nullptr;
+}
+
+namespace {
+constexpr size_t MANY_BATCH_BYTES = size_t(24) << 20;      // bytes of one device call: the stream classes' batch size
+constexpr size_t MANY_CALL_MAX = size_t(0x7FFFFFFF);       // what a call takes at all (include/knz_hip.h)
+
+size_t up16(size_t v) { return (v + 15) & ~size_t(15); }
+
+void noteFailure(std::vector<std::string>* messages, size_t item, const std::string& what)
+{
+    if (messages != nullptr && item < messages->size() && (*messages)[item].empty()) (*messages)[item] = what;
+}
+
+// one item through a stream class of its own (the path of a device library without the batch entry points)
+int compressOne(const ByteSpan& in, const std::string& entropy, const std::string& transform, int blockSize, int checksum, int jobs, std::vector<byte>& out,
+                std::vector<std::string>* message, size_t item)
+{
+    try {
+        std::ostringstream os(std::ios::binary);
+        CompressedOutputStream cos(os, jobs, entropy, transform, blockSize, checksum, uint64(in.size), false);
+        if (in.size) cos.write(reinterpret_cast<const char*>(in.data), std::streamsize(in.size));
+        cos.close();
+        const std::string str = os.str();
+        out.assign(str.begin(), str.end());
+        return 0;
+    } catch (const IOException& e) { noteFailure(message, item, e.what()); return e.error();
+    } catch (const std::exception& e) { noteFailure(message, item, e.what()); return Error::ERR_UNKNOWN; }
+}
+
+int decompressOne(const ByteSpan& in, int jobs, std::vector<byte>& out, std::vector<std::string>* message, size_t item)
+{
+    try {
+        std::istringstream is(std::string(reinterpret_cast<const char*>(in.data), in.size), std::ios::binary);
+        Context ctx;
+        ctx.putInt("jobs", jobs);
+        CompressedInputStream cis(is, ctx);
+        std::vector<char> buf(size_t(1) << 20);
+        out.clear();
+        for (;;) {
+            cis.read(buf.data(), std::streamsize(buf.size()));
+            const std::streamsize got = cis.gcount();
+            if (got <= 0) break;
+            out.insert(out.end(), buf.begin(), buf.begin() + got);
+        }
+        cis.close();
+        return 0;
+    } catch (const IOException& e) { out.clear(); noteFailure(message, item, e.what()); return e.error();
+    } catch (const std::exception& e) { out.clear(); noteFailure(message, item, e.what()); return Error::ERR_UNKNOWN; }
+}
+
+// staging of one call: a page-locked buffer and a device buffer each way, back to their pools when the call is done
+struct ManyBufs {
+    knz_ctx* c;
+    byte *hIn = nullptr, *hOut = nullptr; size_t hInCap = 0, hOutCap = 0;
+    void *dIn = nullptr, *dOut = nullptr; size_t dInCap = 0, dOutCap = 0;
+    explicit ManyBufs(knz_ctx* ctx) : c(ctx) {}
+    ~ManyBufs() { g_pinned.put(hIn, hInCap); g_pinned.put(hOut, hOutCap); g_devPool.put(c, dIn, dInCap); g_devPool.put(c, dOut, dOutCap); }
+    void in(size_t bytes) { hIn = g_pinned.get(bytes, &hInCap); dIn = g_devPool.get(c, bytes, &dInCap); }
+    void out(size_t bytes) { g_devPool.put(c, dOut, dOutCap); dOut = nullptr; dOut = g_devPool.get(c, bytes, &dOutCap); }
+    void upload(size_t bytes)
+    {
+        uint64_t t = 0;
+        devCheck(c, knz_hip_memcpy_h2d_async(c, dIn, hIn, bytes, &t), "h2d");
+        devCheck(c, knz_hip_copy_wait(c, t), "h2d");
+    }
+    void download(size_t bytes)
+    {
+        g_pinned.put(hOut, hOutCap); hOut = nullptr;
+        hOut = g_pinned.get(bytes + 16, &hOutCap);
+        uint64_t t = 0;
+        devCheck(c, knz_hip_memcpy_d2h_async(c, hOut, dOut, bytes, &t), "d2h");
+        devCheck(c, knz_hip_copy_wait(c, t), "d2h");
+    }
+};
+
+// What the workspaces of a call cost: blocks x longest block must stay below 2 GiB (include/knz_hip.h). The device sizes them by the
+// longest block's stride, which a chain makes somewhat longer than the block: twice the block and 64 KiB hold any chain.
+bool workFits(size_t blocks, size_t longest) { return blocks * (2 * longest + 65536) <= MANY_CALL_MAX; }
+
+// runs of item numbers that one call takes: a batch of bytes, never more items, blocks or workspace than the device layer allows
+// (sizes: the items' plain bytes -- on the way back the stored sizes, which are the rooms the call is given)
+std::vector<std::vector<size_t>> manyCalls(const std::vector<size_t>& which, const std::vector<size_t>& sizes, size_t blockSize)
+{
+    std::vector<std::vector<size_t>> runs;
+    std::vector<size_t> cur;
+    size_t bytes = 0, blocks = 0, longest = 0;
+    for (size_t i : which) {
+        const size_t nb = (sizes[i] + blockSize - 1) / blockSize, len = std::min(sizes[i], blockSize);
+        if (!cur.empty() && (bytes + up16(sizes[i]) > MANY_BATCH_BYTES || cur.size() >= size_t(KNZ_STREAMS_MAX_ITEMS) || blocks + nb > size_t(KNZ_STREAMS_MAX_BLOCKS) ||
+                             !workFits(blocks + nb, std::max(longest, len)))) {
+            runs.push_back(cur); cur.clear(); bytes = 0; blocks = 0; longest = 0;
+        }
+        cur.push_back(i); bytes += up16(sizes[i]); blocks += nb; longest = std::max(longest, len);
+    }
+    if (!cur.empty()) runs.push_back(cur);
+    return runs;
+}
+
+bool fitsOneCall(size_t bytes, size_t blockSize)
+{
+    const size_t nb = (bytes + blockSize - 1) / blockSize;
+    return nb <= size_t(KNZ_STREAMS_MAX_BLOCKS) && bytes + 8448 * (nb + 1) <= MANY_CALL_MAX &&      // (the 2 GiB of a call include slack per block, csrc/api.hip)
+           workFits(nb, std::min(bytes, blockSize));
+}
+
+void putHeader(BitPacker& pro, int checksum, int entropyType, uint64 transformType, int blockSize, uint64 inputSize)
+{
+    const uint32_t ckSize = checksum == 32 ? 1 : (checksum == 64 ? 2 : 0);
+    pro.put(0x4B414E5Au, 32); pro.put(6, 4); pro.put(ckSize, 2); pro.put(uint64(entropyType), 5); pro.put(transformType, 48);
+    pro.put(uint64(blockSize >> 4), 28);
+    int szMask = 0;
+    if (inputSize != 0 && inputSize < (uint64(1) << 48)) { int lg = 63; while (!((inputSize >> lg) & 1)) lg--; szMask = (lg >> 4) + 1; }
+    pro.put(uint64(szMask), 2);
+    if (szMask) pro.put(inputSize, uint(16 * szMask));
+    pro.put(0, 15);
+    pro.put(headerChecksum(ckSize, uint32_t(entropyType), transformType, uint32_t(blockSize), szMask, inputSize), 24);
+}
+
+// a current header with a stored size, as compressMany writes it; anything else is left to CompressedInputStream
+struct ManyHdr { int etype; uint64 ttype; int blockSize; int checksum; uint64 size; uint64 bits; };
+bool parseManyHeader(const ByteSpan& s, ManyHdr& h)
+{
+    if (s.size < 22) return false;
+    std::vector<byte> d(s.data, s.data + std::min<size_t>(s.size, 40));
+    d.resize(48, 0);
+    uint64 pos = 0;
+    auto get = [&](uint n) { const uint64 v = getBitsAt(d, pos, n); pos += n; return v; };
+    if (uint32_t(get(32)) != 0x4B414E5Au || get(4) != 6) return false;
+    const uint64 ckSize = get(2);
+    if (ckSize == 3) return false;
+    h.checksum = int(32 * ckSize);
+    h.etype = int(get(5));
+    h.ttype = get(48);
+    h.blockSize = int(get(28) << 4);
+    if (h.blockSize < 1024 || h.blockSize > (1 << 30)) return false;
+    const int szMask = int(get(2));
+    if (szMask == 0 || s.size < size_t(20 + 2 * szMask)) return false;
+    h.size = get(uint(16 * szMask));
+    get(15);
+    if (uint32_t(get(24)) != headerChecksum(uint32_t(ckSize), uint32_t(h.etype), h.ttype, uint32_t(h.blockSize), szMask, h.size)) return false;
+    h.bits = pos;
+    return h.size != 0;
+}
+}  // namespace
+
+void compressMany(const std::vector<ByteSpan>& inputs, const std::string& entropy, const std::string& transform, int blockSize, int checksum, int jobs,
+                  std::vector<std::vector<byte>>& streams, std::vector<int>& errors, std::vector<std::string>* message)
+{
+    if ((jobs <= 0) || (jobs > 64)) throw std::invalid_argument("The number of jobs must be in [1..64], got " + std::to_string(jobs));
+    if (blockSize > 1024 * 1024 * 1024) throw std::invalid_argument("The block size must be at most 1024 MB");
+    if (blockSize < 1024) throw std::invalid_argument("The block size must be at least 1024");
+    if ((blockSize & -16) != blockSize) throw std::invalid_argument("The block size must be a multiple of 16");
+    if ((checksum != 0) && (checksum != 32) && (checksum != 64)) throw std::invalid_argument("The block checksum size must be 0, 32 or 64");
+    const int etype = EntropyEncoderFactory::getType(entropy.c_str());
+    const uint64 ttype = TransformFactory<byte>::getType(transform.c_str());
+    streams.assign(inputs.size(), std::vector<byte>());
+    errors.assign(inputs.size(), 0);
+    if (message) message->assign(inputs.size(), std::string());
+    int hostIds[8];
+    const bool batched = deviceBatchesStreams() && hostedStagesOf(ttype, hostIds, false) == 0;
+    std::vector<size_t> sizes(inputs.size()), which;
+    for (size_t i = 0; i < inputs.size(); i++) {
+        sizes[i] = inputs[i].size;
+        if (batched && fitsOneCall(sizes[i], size_t(blockSize))) which.push_back(i);
+        else errors[i] = compressOne(inputs[i], entropy, transform, blockSize, checksum, jobs, streams[i], message, i);
+    }
+    if (which.empty()) return;
+    knz_ctx* c = deviceContext(-1);
+    knz_params p;
+    memset(&p, 0, sizeof(p));
+    p.transform_type = ttype; p.entropy_type = etype; p.block_size = blockSize; p.checksum_bits = checksum; p.jobs = jobs;
+    for (const std::vector<size_t>& run : manyCalls(which, sizes, size_t(blockSize))) {
+        try {
+            std::vector<knz_item> items(run.size());
+            BitPacker pro;
+            size_t bytes = 0;
+            for (size_t k = 0; k < run.size(); k++) {
+                knz_item& it = items[k];
+                memset(&it, 0, sizeof(it));
+                it.in_off = bytes; it.in_len = sizes[run[k]];
+                bytes += up16(sizes[run[k]]);
+                pro.nbits = 8 * uint64(pro.bytes.size());                  // every header starts at a byte of its own
+                it.prologue_off = uint32_t(pro.bytes.size());
+                putHeader(pro, checksum, etype, ttype, blockSize, uint64(sizes[run[k]]));
+                it.prologue_bits = uint32_t(pro.nbits - 8 * uint64(it.prologue_off));
+            }
+            ManyBufs b(c);
+            b.in(bytes + 64);
+            for (size_t k = 0; k < run.size(); k++) {
+                if (sizes[run[k]]) memcpy(b.hIn + items[k].in_off, inputs[run[k]].data, sizes[run[k]]);
+                memset(b.hIn + items[k].in_off + sizes[run[k]], 0, up16(sizes[run[k]]) - sizes[run[k]]);
+            }
+            b.upload(bytes);
+            size_t cap = knz_hip_encode_streams_bound(&p, items.data(), items.size());
+            uint64_t used = 0;
+            b.out(cap);
+            int rc = knz_hip_encode_streams(c, &p, static_cast<const uint8_t*>(b.dIn), items.data(), items.size(), pro.bytes.data(), 1, static_cast<uint8_t*>(b.dOut), cap, &used);
+            if (rc == KNZ_ERR_WRITE_FILE && isBinaryCoder(etype)) {
+                // the bound of the binary coders is their first tier (include/knz_hip.h): the second holds whatever the format can write
+                cap += 32 * bytes;
+                b.out(cap);
+                rc = knz_hip_encode_streams(c, &p, static_cast<const uint8_t*>(b.dIn), items.data(), items.size(), pro.bytes.data(), 1, static_cast<uint8_t*>(b.dOut), cap, &used);
+            }
+            devCheck(c, rc, "encode_streams");
+            b.download(size_t(used));
+            for (size_t k = 0; k < run.size(); k++)
+                streams[run[k]].assign(b.hOut + items[k].out_off, b.hOut + items[k].out_off + (items[k].out_len + 7) / 8);
+        } catch (const IOException&) {
+            // the call as a whole was refused or failed: every item of it by itself, so that each gets its own verdict
+            for (size_t i : run) errors[i] = compressOne(inputs[i], entropy, transform, blockSize, checksum, jobs, streams[i], message, i);
+        }
+    }
+}
+
+void decompressMany(const std::vector<ByteSpan>& streams, int jobs, std::vector<std::vector<byte>>& outputs, std::vector<int>& errors, std::vector<std::string>* message)
+{
+    if ((jobs <= 0) || (jobs > 64)) throw std::invalid_argument("The number of jobs must be in [1..64], got " + std::to_string(jobs));
+    outputs.assign(streams.size(), std::vector<byte>());
+    errors.assign(streams.size(), 0);
+    if (message) message->assign(streams.size(), std::string());
+    struct Key { int etype; uint64 ttype; int blockSize; int checksum; bool operator<(const Key& o) const { return std::tie(etype, ttype, blockSize, checksum) < std::tie(o.etype, o.ttype, o.blockSize, o.checksum); } };
+    std::map<Key, std::vector<size_t>> groups;
+    std::vector<ManyHdr> hdr(streams.size());
+    std::vector<size_t> sizes(streams.size(), 0);
+    const bool batched = deviceBatchesStreams();
+    for (size_t i = 0; i < streams.size(); i++) {
+        int hostIds[8];
+        if (batched && parseManyHeader(streams[i], hdr[i]) && hostedStagesOf(hdr[i].ttype, hostIds, true) == 0 && fitsOneCall(size_t(hdr[i].size), size_t(hdr[i].blockSize)) &&
+            fitsOneCall(streams[i].size, 1024)) {
+            sizes[i] = size_t(hdr[i].size);
+            groups[Key{ hdr[i].etype, hdr[i].ttype, hdr[i].blockSize, hdr[i].checksum }].push_back(i);
+        } else {
+            errors[i] = decompressOne(streams[i], jobs, outputs[i], message, i);
+        }
+    }
+    if (groups.empty()) return;
+    knz_ctx* c = deviceContext(-1);
+    for (const auto& g : groups) {
+        knz_params p;
+        memset(&p, 0, sizeof(p));
+        p.transform_type = g.first.ttype; p.entropy_type = g.first.etype; p.block_size = g.first.blockSize; p.checksum_bits = g.first.checksum; p.jobs = jobs; p.bs_version = 6;
+        for (const std::vector<size_t>& run : manyCalls(g.second, sizes, size_t(g.first.blockSize))) {
+            try {
+                std::vector<knz_item> items(run.size());
+                size_t inBytes = 0, outBytes = 0;
+                for (size_t k = 0; k < run.size(); k++) {
+                    knz_item& it = items[k];
+                    memset(&it, 0, sizeof(it));
+                    it.in_off = inBytes; it.in_len = 8 * uint64(streams[run[k]].size); it.start_bit = hdr[run[k]].bits;
+                    it.out_off = outBytes; it.out_cap = sizes[run[k]];
+                    inBytes += up16(streams[run[k]].size);
+                    outBytes += up16(sizes[run[k]]);
+                }
+                if (inBytes + 64 > MANY_CALL_MAX) throw IOException("the streams of one batch exceed what a device call reads", Error::ERR_INVALID_PARAM);
+                ManyBufs b(c);
+                b.in(inBytes + 64);
+                memset(b.hIn, 0, inBytes + 64);
+                for (size_t k = 0; k < run.size(); k++) memcpy(b.hIn + items[k].in_off, streams[run[k]].data, streams[run[k]].size);
+                b.upload(inBytes + 64);
+                b.out(outBytes + 64);
+                devCheck(c, knz_hip_decode_streams(c, &p, static_cast<const uint8_t*>(b.dIn), items.data(), items.size(), static_cast<uint8_t*>(b.dOut), outBytes + 64), "decode_streams");
+                b.download(outBytes);
+                for (size_t k = 0; k < run.size(); k++) {
+                    const size_t i = run[k];
+                    if (items[k].error == 0 && items[k].out_len != sizes[i]) items[k].error = Error::ERR_PROCESS_BLOCK;      // (fewer bytes than the header promises)
+                    errors[i] = items[k].error;
+                    if (items[k].error) noteFailure(message, i, "decoding failed (code " + std::to_string(items[k].error) + ")");
+                    else outputs[i].assign(b.hOut + items[k].out_off, b.hOut + items[k].out_off + items[k].out_len);
+                }
+            } catch (const IOException&) {
+                // the call as a whole was refused or failed: every stream of it by itself, so that each gets its own verdict
+                for (size_t i : run) errors[i] = decompressOne(streams[i], jobs, outputs[i], message, i);
+            }
+        }
+    }
 }
 
 }  // namespace kanzi_amd

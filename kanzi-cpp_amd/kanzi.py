@@ -3,8 +3,12 @@
 Mirrors the reference's ctypes shim (src/api/kanzi_c_api.py:88-137 for the bindings,
 src/api/kanzi.py for the two classes): same struct layouts, same call sequence
 (init -> compress()/decompress() per block -> dispose). Only marshals data.
+
+compress_many / decompress_many (at the end) are the batch form for many small independent buffers: they go over the device
+C ABI directly (hipapi.Context.encode_streams / decode_streams) and framing.py, many buffers per device call.
 """
 import ctypes as C
+import importlib
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -188,3 +192,142 @@ class Decompressor:
             self._f = None
             if rc != 0:
                 raise KanziError(rc, "disposeDecompressor")
+
+
+# ---- many small buffers, many per device call (include/knz_hip.h: knz_hip_encode_streams / knz_hip_decode_streams)
+def _mods():
+    return (importlib.import_module("kanzi_amd.hipapi"), importlib.import_module("kanzi_amd.framing"),
+            importlib.import_module("kanzi_amd.sharded"))
+
+
+def _work_fits(blocks, longest, hipapi):
+    """blocks x longest block of a call stay below 2 GiB (include/knz_hip.h): the device sizes its workspaces by the longest block's
+    stride, which a chain makes somewhat longer than the block -- twice the block and 64 KiB hold any chain."""
+    return blocks * (2 * longest + 65536) <= hipapi.BATCH_MAX_BYTES
+
+
+def _fits_one_call(n, block_size, hipapi):
+    blocks = (n + block_size - 1) // block_size
+    return (n + 8448 * (blocks + 1) <= hipapi.BATCH_MAX_BYTES and blocks <= hipapi.STREAMS_MAX_BLOCKS and
+            _work_fits(blocks, min(n, block_size), hipapi))
+
+
+def _calls(sizes, block_size, hipapi):
+    """Cuts the item numbers into runs that one device call takes: its item and block counts, its bytes (every item at a multiple
+    of 16; the 2 GiB limit of a call leaves room for the blocks' slack, csrc/api.hip encode_impl) and its workspaces (blocks x longest
+    block). On the way back the sizes are the stored ones, which are the rooms the call is given. An item that is too large for any
+    call is a ValueError: such a buffer belongs to the stream classes."""
+    runs, cur, nbytes, nblocks, longest = [], [], 0, 0, 0
+    for i, n in enumerate(sizes):
+        blocks = (n + block_size - 1) // block_size
+        if not _fits_one_call(n, block_size, hipapi):
+            raise ValueError("buffer %d (%d bytes) exceeds what one device call takes; use Compressor / Decompressor" % (i, n))
+        pad = (n + 15) & ~15
+        if cur and (len(cur) == hipapi.STREAMS_MAX_ITEMS or nblocks + blocks > hipapi.STREAMS_MAX_BLOCKS or
+                    nbytes + pad + 8448 * (nblocks + blocks + 1) > hipapi.BATCH_MAX_BYTES or
+                    not _work_fits(nblocks + blocks, max(longest, min(n, block_size)), hipapi)):
+            runs.append(cur)
+            cur, nbytes, nblocks, longest = [], 0, 0, 0
+        cur.append(i)
+        nbytes += pad
+        nblocks += blocks
+        longest = max(longest, min(n, block_size))
+    if cur:
+        runs.append(cur)
+    return runs
+
+
+def _pack(buffers):
+    blob, offs = bytearray(), []
+    for b in buffers:
+        blob += bytes(-len(blob) % 16)
+        offs.append(len(blob))
+        blob += b
+    blob += bytes(64)
+    return bytes(blob), offs
+
+
+def compress_many(buffers, transform, entropy, block_size, checksum=0, jobs=1, device=0):
+    """Every buffer as a stream of its own: the file the reference CLI writes for those bytes (the header stores the buffer's length
+    as the original size), many buffers per device call. Returns the streams in the buffers' order."""
+    hipapi, framing, sharded = _mods()
+    buffers = [bytes(b) for b in buffers]
+    ctx = hipapi.Context(device)
+    try:
+        p = ctx.params(transform, entropy, block_size, checksum, jobs)
+        bufs = sharded._DeviceBuffers(ctx)
+        out = [None] * len(buffers)
+        for run in _calls([len(b) for b in buffers], block_size, hipapi):
+            blob, offs = _pack([buffers[i] for i in run])
+            items = (hipapi.Item * len(run))()
+            pro = bytearray()
+            for k, i in enumerate(run):
+                h, hb = framing.make_header(p.entropy_type, p.transform_type, block_size, checksum, len(buffers[i]))
+                items[k].in_off, items[k].in_len, items[k].prologue_off, items[k].prologue_bits = offs[k], len(buffers[i]), len(pro), hb
+                pro += h
+            cap = ctx.encode_streams_bound(p, items)
+            d_in = bufs.get("in", len(blob))
+            ctx.h2d(d_in, blob)
+            try:
+                used = ctx.encode_streams(p, d_in, items, bufs.get("out", cap), cap, prologues=bytes(pro))
+            except hipapi.KnzError as e:
+                # CM, TPAQ, TPAQX: the bound is a first tier (include/knz_hip.h); the second holds whatever the format can write
+                if e.code != 12 or p.entropy_type not in hipapi.BINARY_CODERS:
+                    raise
+                cap += 32 * len(blob)
+                used = ctx.encode_streams(p, d_in, items, bufs.get("out", cap), cap, prologues=bytes(pro))
+            raw = ctx.d2h(bufs.get("out", cap), used)
+            for k, i in enumerate(run):
+                out[i] = raw[items[k].out_off:items[k].out_off + (items[k].out_len + 7) // 8]
+        return out
+    finally:
+        ctx.close()
+
+
+def decompress_many(streams, jobs=1, device=0):
+    """The way back: the headers are parsed here, streams of equal parameters share device calls, each stream's room is its stored
+    original size. A stream without a stored size is decoded by itself (sharded.decompress_sharded). Raises KanziError with the code
+    of the first stream that fails."""
+    hipapi, framing, sharded = _mods()
+    streams = [bytes(s) for s in streams]
+    out = [None] * len(streams)
+    groups = {}
+    ctx = hipapi.Context(device)
+    try:
+        for i, s in enumerate(streams):
+            try:
+                h = framing.parse_header(s)
+            except framing.HeaderError as e:
+                raise KanziError(e.code, "stream %d: %s" % (i, e))
+            if h["orig_size"] == 0 or not _fits_one_call(h["orig_size"], h["block_size"], hipapi) or not _fits_one_call(len(s), 1024, hipapi):
+                # no stored size (it may still hold data), or more than one call decodes
+                out[i] = sharded.decompress_sharded(s, 0, 1, sharded.DeviceRunDecoder(device, jobs), lambda part: [part])
+                continue
+            key = (h["etype"], h["ttype"], h["block_size"], h["checksum_bits"], h["bs_version"])
+            groups.setdefault(key, []).append((i, h))
+        bufs = sharded._DeviceBuffers(ctx)
+        for (etype, ttype, bs, ck, ver), members in groups.items():
+            p = ctx.params(ttype, etype, bs, ck, jobs, ver or 1)       # a parsed version 0 is an old layout (the C ABI keeps 0 for "unset = current")
+            for run in _calls([h["orig_size"] for _, h in members], bs, hipapi):
+                blob, offs = _pack([streams[members[k][0]] for k in run])
+                items = (hipapi.Item * len(run))()
+                at = 0
+                for n, k in enumerate(run):
+                    i, h = members[k]
+                    items[n].in_off, items[n].in_len, items[n].start_bit = offs[n], 8 * len(streams[i]), h["bits"]
+                    items[n].out_off, items[n].out_cap = at, h["orig_size"]
+                    at += (h["orig_size"] + 15) & ~15
+                d_in, d_out = bufs.get("in", len(blob)), bufs.get("out", at + 64)
+                ctx.h2d(d_in, blob)
+                ctx.decode_streams(p, d_in, items, d_out, at + 64)
+                raw = ctx.d2h(d_out, at)
+                for n, k in enumerate(run):
+                    i, h = members[k]
+                    if items[n].error:
+                        raise KanziError(items[n].error, "stream %d: decoding" % i)
+                    if items[n].out_len != h["orig_size"]:      # (the stream ends before the size its header promises)
+                        raise KanziError(13, "stream %d: %d bytes where the header stores %d" % (i, items[n].out_len, h["orig_size"]))
+                    out[i] = raw[items[n].out_off:items[n].out_off + items[n].out_len]
+        return out
+    finally:
+        ctx.close()
