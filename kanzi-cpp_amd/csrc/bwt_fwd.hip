@@ -13,6 +13,9 @@
 //   the text. Then:
 //     * the small groups once on the next seven text bytes, in the kernel that places round 0 (k_bwt_f_r0_place_text),
 //     * run groups (4 equal symbols) in one round by run length: the runs are sorted, the members follow their runs (k_bwt_f_run_*),
+//       and because that round rebuilds every member from the text, the members stay out of round 0's sort: the run groups are found in
+//       the text before the sort (FwdSort::run_scan), the first pass drops their members, the last pass leaves a gap per group where they
+//       belong, one key fills it (TextSrcKept, LastPassSrc, k_bwt_f_r0_fill; knob bwt_run_in_sort: through the sort as before),
 //   and the doubling rounds, h = 4, 8, 16, ..., refine what is left on the key ISA[p + h] (0 past the block end: "shorter sorts first"):
 //     * small groups (2..256 members) need no list at all: a kernel sweeps the bit map in windows of 2048 slots, finds the groups that
 //       start in its window and ranks every member by counting inside LDS (less / equal / equal-before),
@@ -115,6 +118,8 @@ enum FwdCounter : u32 {
     CNT_STAT_ASLEEP_MEMBERS = 22,
     CNT_RUN_TILES = 23,          // tiles of the run round's direct placement (device side only: k_bwt_f_run_tile_starts' scan)
     CNT_ROUND_SLOTS = 24,
+    CNT_GAP_CLASSES = 25,        // run groups found before round 0's sort (k_bwt_f_run_scan_classes; behind the rounds' slots: round 0 zeroes those)
+    CNT_GAP_MEMBERS = 26,        // their members: what stays out of the sort
     CNT_PROBE_SLOTS = 2,         // slots 0-1 (CNT_SMALL_LEFT, CNT_MED): what the probe zeroes, recounts and reads back
     CNT_LONGEST_BLOCK = 32,      // longest block the transform applies to (k_bwt_bases)
     CNT_NSYM = 33,               // round-0 key length the entropy asks for (k_bwt_f_choose_nsym)
@@ -242,9 +247,13 @@ __global__ void k_bwt_bases(BwtView v, u32* __restrict__ base, u8* __restrict__ 
 // sort is stable -- so among equal padded keys they come first, shortest first, which is their place ("a proper prefix sorts
 // first"); the flag kernel makes each of them a group of its own.
 struct TextSrc {
-    static constexpr bool STAGED = true;
+    static constexpr bool STAGED = true, FILTER = false, SHIFTS = false;
     const u8* const* src;
     int P, pbits, shift;
+    __device__ __forceinline__ u32 tab(int, u32) const { return 0u; }
+    __device__ __forceinline__ bool keep(int, u32, u64, const u32*) const { return true; }
+    __device__ __forceinline__ u32 out_shift(u64, u32, u32 at, const u32*) const { return at; }
+    __device__ __forceinline__ void note_tile(int, u32, const u64*, u32, u32, const u32*) const {}
     __device__ __forceinline__ u32 pos_of(u32 n, u32 i) const
     {
         const u32 nShort = (u32)(P - 1) < n ? (u32)(P - 1) : n;
@@ -302,6 +311,56 @@ struct TextSrc {
     {
         const u32 q = pos_of(n, i) + (u32)(P - 1);
         return q < n ? (u32)ldg<u8>(src[sgm] + q) : 0u;
+    }
+};
+
+// ---- round 0 without the run members ---------------------------------------------------------------------------------------------------
+// A suffix that starts with P copies of a byte c, full length, is a RUN MEMBER when its block holds more than SM_G of them: round 0 makes
+// one group of them (a run group) and the run round then rebuilds every one of them -- position, label and all -- from the text alone.
+// So they stay out of the sort (FwdSort::run_scan decides, before the sort, from the runs of the text):
+//   * the first pass drops them (TextSrcKept) and writes every block's other keys as a compact segment, which the middle passes sort;
+//   * the last pass (LastPassSrc) writes to the slots the full sort would have used: the first output position of a first byte comes from
+//     the full byte histogram, and a key with first byte c that is larger than c c .. c moves up by the members of c. What is in front of
+//     the gap -- the smaller keys and the short suffixes, whose zero padding makes them at most equal -- is where stability puts it;
+//   * the gap is filled with the class's key and the position of its first member (k_bwt_f_r0_fill), so that the flag and placing kernels
+//     find one group per gap exactly where the run group was; the placing kernel writes SA and label for the gap's first slot only.
+// Knob bwt_run_in_sort: the members go through the sort as before.
+__host__ __device__ __forceinline__ u64 rep_key(u32 c, int P) { return (u64)c * (0x0101010101010101ull >> (64 - 8 * P)); }     // P copies of c
+
+struct TextSrcKept : TextSrc {
+    static constexpr bool FILTER = true;
+    const u32* members;      // [block][256]: members of the byte's run group (0: it has none)
+    __device__ __forceinline__ u32 tab(int sgm, u32 c) const { return members[(u32)sgm * 256u + c]; }
+    __device__ __forceinline__ bool keep(int, u32 n, u64 k, const u32* tab) const
+    {
+        const u64 bytes = k >> pbits;
+        const u32 c = (u32)bytes & 255u;
+        if (bytes != rep_key(c, P)) return true;
+        if ((u32)(k & ((1ull << pbits) - 1ull)) + (u32)P > n) return true;         // (a short suffix of zeros)
+        return tab[c] == 0u;
+    }
+};
+
+struct LastPassSrc : prims::DigitOfKey<u64> {
+    static constexpr bool SHIFTS = true;
+    const u32* members;      // as above
+    u32* gapStart;           // [block][256]: first slot of the gap, preset to the end of the byte's slots less the members; the least unshifted
+                             // position of a key that moves is where the gap starts
+    int P, pbits;
+    __device__ __forceinline__ bool above(u64 k) const { const u64 bytes = k >> pbits; return bytes > rep_key((u32)(bytes >> (8 * (P - 1))), P); }
+    __device__ __forceinline__ u32 tab(int sgm, u32 d) const { return members[(u32)sgm * 256u + d]; }
+    __device__ __forceinline__ u32 out_shift(u64 k, u32 d, u32 at, const u32* tab) const { return above(k) ? at + tab[d] : at; }
+    // The tile's cnt keys of first byte d, whose first goes to at0: they come in the order of their other bytes, so the ones that move are
+    // behind the ones that stay, and the first of them (found by bisection) is this tile's bid for the gap's start. Most tiles bid
+    // nothing: no key that moves, or a bid that is not below what is known (read first: an atomic per tile and byte on the classes' few
+    // words would queue up)
+    __device__ __forceinline__ void note_tile(int sgm, u32 d, const u64* ks, u32 cnt, u32 at0, const u32* tab) const
+    {
+        if (tab[d] == 0u || cnt == 0u || !above(ks[cnt - 1u])) return;
+        u32 lo = 0, hi = cnt - 1u;
+        while (lo < hi) { const u32 mid = (lo + hi) >> 1; if (above(ks[mid])) hi = mid; else lo = mid + 1u; }
+        u32* g = &gapStart[(u32)sgm * 256u + d];
+        if (at0 + lo < prims::rs_ld_dev(g)) atomicMin(g, at0 + lo);
     }
 };
 
@@ -390,18 +449,57 @@ __global__ __launch_bounds__(256) void k_bwt_f_choose_nsym(const u32* __restrict
 
 // digit counts of the P round-0 passes of a block: the digit of pass k of the suffix at pos is the text byte at pos + o, o = P - 1 - k,
 // or 0 behind the block's end, so its histogram is the block's byte histogram minus the block's first o bytes, plus o zeros
-__global__ __launch_bounds__(256) void k_bwt_f_r0_counts(BwtView bv, const u32* __restrict__ base, const u32* __restrict__ byteHist, int P, prims::RsLayout L)
+// (members: the run members that stay out of the sort, per block and byte, or null. Every digit of a member is its byte; the last pass keeps
+// the full counts, which leaves the members' slots free)
+__global__ __launch_bounds__(256) void k_bwt_f_r0_counts(BwtView bv, const u32* __restrict__ base, const u32* __restrict__ byteHist, int P, prims::RsLayout L,
+                                                         const u32* __restrict__ members)
 {
     const int sgm = blockIdx.x, tid = (int)threadIdx.x;
     const u32 n = base[sgm + 1] - base[sgm];
     const u32 c = n ? byteHist[(size_t)sgm * 256 + tid] : 0u;
+    const u32 out = (members != nullptr && n) ? members[(size_t)sgm * 256 + tid] : 0u;
     const u8* t = bv.src[sgm];
     for (int k = 0; k < P; k++) {
         const u32 o = (u32)(P - 1 - k);
         const u32 oo = o < n ? o : n;
         u32 cut = 0;
         for (u32 j = 0; j < oo; j++) cut += ((u32)ldg<u8>(t + j) == (u32)tid) ? 1u : 0u;
-        L.histAll[((size_t)k * L.nSeg + sgm) * 256 + tid] = c - cut + ((tid == 0) ? oo : 0u);
+        L.histAll[((size_t)k * L.nSeg + sgm) * 256 + tid] = c - cut + ((tid == 0) ? oo : 0u) - ((k + 1 < P) ? out : 0u);
+    }
+}
+
+// prims::k_rs_digit_bases for the sort without the run members: the passes in front of the last one write compact segments (cbase), the
+// last one the blocks' slots (base); the gap of every run group is preset to the end of its byte's slots (LastPassSrc::gapStart)
+__global__ __launch_bounds__(256) void k_bwt_f_r0_bases(prims::RsLayout L, const u32* __restrict__ base, const u32* __restrict__ cbase, int P,
+                                                        const u32* __restrict__ members, u32* __restrict__ gapStart)
+{
+    __shared__ u32 wsum[4];
+    __shared__ u32 inclAll[256];
+    const int sgm = blockIdx.x, ps = blockIdx.y;
+    const int tid = (int)threadIdx.x;
+    u32* h = L.histAll + ((size_t)ps * L.nSeg + sgm) * 256;
+    const u32 c = h[tid];
+    u32 tot;
+    const u32 incl = prims::sc_block_incl<prims::SCAN_SUM_EXCL>(c, wsum, &tot);
+    inclAll[tid] = incl;
+    __syncthreads();
+    const bool last = ps + 1 == P;
+    const u32 b0 = last ? base[sgm] : cbase[sgm];
+    h[tid] = b0 + (tid ? inclAll[tid - 1] : 0u);
+    if (last) gapStart[(size_t)sgm * 256 + tid] = b0 + incl - members[(size_t)sgm * 256 + tid];
+}
+
+// the gaps filled: the class's key with the position of its first member in every slot
+__global__ __launch_bounds__(256) void k_bwt_f_r0_fill(u64* __restrict__ keys, const u32* __restrict__ members, const u32* __restrict__ gapStart,
+                                                       const u32* __restrict__ firstPos, int P, int pbits)
+{
+    const u32 sgm = blockIdx.y;
+    for (u32 c = 0; c < 256u; c++) {
+        const u32 m = members[sgm * 256u + c];
+        if (m == 0u) continue;
+        const u32 g0 = gapStart[sgm * 256u + c];
+        const u64 key = (rep_key(c, P) << pbits) | (u64)firstPos[sgm * 256u + c];
+        for (u32 i = blockIdx.x * 256u + threadIdx.x; i < m; i += gridDim.x * 256u) keys[g0 + i] = key;
     }
 }
 
@@ -536,8 +634,11 @@ __device__ __forceinline__ bool sm_group_of(const SmWindow& W, u32 i, u32& s, u3
 // random read for seven symbols of depth where a doubling round at h = 4 buys four (a separate text round read SA back, and wrote SA
 // and the labels of every member that moved a second time).
 __global__ __launch_bounds__(256) void k_bwt_f_r0_place_text(BwtView bv, FwdView v, const u32* __restrict__ winLastIncl, const u32* __restrict__ winFirstInclRev, u32 nWin,
-                                                             uint2* __restrict__ largeNext, const u64* __restrict__ keys, int nsym, int pbits, uint2* __restrict__ runList)
+                                                             uint2* __restrict__ largeNext, const u64* __restrict__ keys, int nsym, int pbits, uint2* __restrict__ runList,
+                                                             const u32* __restrict__ gapTab)
 {
+    // gapTab (null: the run members went through the sort): [block][256], != 0xFFFFFFFF where the byte's run group is a gap that
+    // k_bwt_f_r0_fill filled. Only its first slot is placed -- the run round writes position and label of every member
     __shared__ SmWindow W;
     __shared__ int sBlk;
     __shared__ ClassAgg A;
@@ -653,6 +754,13 @@ __global__ __launch_bounds__(256) void k_bwt_f_r0_place_text(BwtView bv, FwdView
             const u32 ei = m2 ? (w * 32 + (u32)__ffs((int)m2) - 1) : W.nextSet[w];
             const u32 endSlot = (ei != NO_BIT) ? slot0 + ei : after;
             if (endSlot - hd <= SM_G) continue;
+        }
+        if (gapTab != nullptr && hd != a) {
+            // (the key bytes in registers decide for nearly every slot; the table is read for equal symbols only)
+            const u64 bytes = kk[k] >> pbits;
+            const u32 c = (u32)bytes & 255u;
+            const int blk = blkOf[k];
+            if (bytes == rep_key(c, nsym) && (u32)(kk[k] & pmask) + (u32)nsym <= v.base[blk + 1] - v.base[blk] && gapTab[(u32)blk * 256u + c] != 0xFFFFFFFFu) continue;
         }
         v.SA[a] = gp[k];
         lab_set(v, gp[k], v.base[blkOf[k]], hd, hd);
@@ -2228,15 +2336,22 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_ends(BwtView bv, FwdView v, u
 }
 
 // R[gp] = distance to the end of the run that holds gp (1 = the run ends here); one workgroup per window of 2048 positions
+// SCAN (FwdSort::run_scan, before round 0's sort, when nobody knows yet which bytes have run groups): every run of at least nsym bytes is
+// a candidate start, and its members are counted for its (block, byte): L - nsym + 1 into members[], its position into firstPos[] (the
+// least one stays). Per workgroup through LDS where the window lies in one block: a zero-filled stretch is thousands of windows that
+// would otherwise all add to one word.
+template <bool SCAN>
 __global__ __launch_bounds__(256) void k_bwt_f_run_len(BwtView bv, FwdView v, const u32* __restrict__ ebits, const u32* __restrict__ winFirstInclRev, u32 nWin,
                                                        u32* __restrict__ R, const u32* __restrict__ classTab, u32 nsym, unsigned long long* __restrict__ startBits64,
-                                                       u32* __restrict__ startCount)
+                                                       u32* __restrict__ startCount, u32* __restrict__ members, u32* __restrict__ firstPos)
 {
     __shared__ u32 bw[64];
     __shared__ u32 nextSet[64];
     __shared__ int sBlk;
+    __shared__ u32 sMem[SCAN ? 256 : 1], sFirst[SCAN ? 256 : 1];
     const int tid = (int)threadIdx.x;
     const u32 win = blockIdx.x, pos0 = win * SM_WIN;
+    if (SCAN) { sMem[tid] = 0u; sFirst[tid] = 0xFFFFFFFFu; }
     if (tid == 64) sBlk = find_block(v.base, v.nBlocks, pos0 < v.total ? pos0 : v.total - 1);
     if (tid < 64) {
         const u32 w = ebits[(pos0 >> 5) + (u32)tid];
@@ -2253,6 +2368,7 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_len(BwtView bv, FwdView v, co
     __syncthreads();
     const u32 after = (win + 1 < nWin) ? winFirstInclRev[nWin - 2 - win] : v.total - 1;
     const u32 prevWord = pos0 ? ebits[(pos0 >> 5) - 1] : 0xFFFFFFFFu;      // (the run-end bit of the position in front of the window)
+    const bool oneBlock = SCAN && pos0 + SM_WIN <= v.base[sBlk + 1];       // (uniform)
     u32 rmax = 0;
 #pragma unroll
     for (int k = 0; k < (int)(SM_WIN / 256); k++) {
@@ -2273,19 +2389,75 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_len(BwtView bv, FwdView v, co
             if (endBefore && r >= nsym) {
                 int b = sBlk;
                 while (gp >= v.base[b + 1]) b++;
-                start = classTab[(u32)b * 256u + (u32)bv.src[b][gp - v.base[b]]] != 0xFFFFFFFFu;
+                const u32 c = (u32)bv.src[b][gp - v.base[b]];
+                if (SCAN) {
+                    start = true;
+                    if (oneBlock) { atomicAdd(&sMem[c], r - nsym + 1u); atomicMin(&sFirst[c], gp - v.base[b]); }
+                    else { atomicAdd(&members[(u32)b * 256u + c], r - nsym + 1u); atomicMin(&firstPos[(u32)b * 256u + c], gp - v.base[b]); }
+                } else start = classTab[(u32)b * 256u + c] != 0xFFFFFFFFu;
             }
         }
         const unsigned long long m64 = __ballot(start);
         if ((tid & 63) == 0) {
             startBits64[(pos0 + 256u * (u32)k + (u32)(tid & ~63)) >> 6] = m64;
-            startCount[((pos0 + 256u * (u32)k + (u32)(tid & ~63)) >> 5)] = (u32)__popc((u32)m64);
-            startCount[((pos0 + 256u * (u32)k + (u32)(tid & ~63)) >> 5) + 1] = (u32)__popc((u32)(m64 >> 32));
+            if (!SCAN) {                                             // (k_bwt_f_run_starts counts what it leaves of the candidates)
+                startCount[((pos0 + 256u * (u32)k + (u32)(tid & ~63)) >> 5)] = (u32)__popc((u32)m64);
+                startCount[((pos0 + 256u * (u32)k + (u32)(tid & ~63)) >> 5) + 1] = (u32)__popc((u32)(m64 >> 32));
+            }
         }
+    }
+    if (SCAN) {
+        __syncthreads();
+        if (oneBlock && sMem[tid]) { atomicAdd(&members[(u32)sBlk * 256u + (u32)tid], sMem[tid]); atomicMin(&firstPos[(u32)sBlk * 256u + (u32)tid], sFirst[tid]); }
     }
     rmax = wave_max(rmax);
     // longest run: sizes the key of the run-length sort (read first: one atomic per wave on one address would serialise the launch)
     if ((tid & 63) == 0 && rmax > __atomic_load_n(&v.counters[CNT_RUN_LONGEST], __ATOMIC_RELAXED)) atomicMax(&v.counters[CNT_RUN_LONGEST], rmax);
+}
+
+// The run groups known before the sort (FwdSort::run_scan): a (block, byte) with more than SM_G members is a run group -- the group
+// round 0 would make of them. classTab marks them (any value but 0xFFFFFFFF; k_bwt_f_run_classes puts the descriptor indexes there once
+// round 0 has listed the groups), members[] keeps their counts and drops the others, cbase[] = the blocks' bases without the members in
+// front of them: the compact segments of the sort. One workgroup.
+__global__ __launch_bounds__(256) void k_bwt_f_run_scan_classes(u32* __restrict__ members, u32* __restrict__ classTab, const u32* __restrict__ base, u32* __restrict__ cbase,
+                                                                int nBlocks, u32* __restrict__ counters)
+{
+    __shared__ u32 sSum;
+    const int tid = (int)threadIdx.x;
+    u32 out = 0, mine = 0;                                           // (thread 0: members in the blocks so far)
+    for (int b = 0; b < nBlocks; b++) {
+        const u32 m = members[(u32)b * 256u + (u32)tid];
+        const bool q = m > SM_G;
+        classTab[(u32)b * 256u + (u32)tid] = q ? 0u : 0xFFFFFFFFu;
+        if (!q) members[(u32)b * 256u + (u32)tid] = 0u;
+        if (tid == 0) sSum = 0;
+        __syncthreads();
+        if (q) { atomicAdd(&sSum, m); mine++; }
+        __syncthreads();
+        if (tid == 0) { cbase[b] = base[b] - out; out += sSum; }
+        __syncthreads();
+    }
+    if (tid == 0) { cbase[nBlocks] = base[nBlocks] - out; counters[CNT_GAP_MEMBERS] = out; }
+    if (mine) atomicAdd(&counters[CNT_GAP_CLASSES], mine);
+}
+
+// the candidate run starts of k_bwt_f_run_len<true> cut down to the runs of run-group bytes, and counted per word
+__global__ __launch_bounds__(256) void k_bwt_f_run_starts(BwtView bv, FwdView v, u32* __restrict__ bits, u32 nWords, const u32* __restrict__ classTab, u32* __restrict__ startCount)
+{
+    const u32 w = blockIdx.x * 256 + threadIdx.x;
+    if (w >= nWords) return;
+    u32 x = bits[w], out = 0;
+    if (x) {
+        int b = find_block(v.base, v.nBlocks, 32u * w);               // (a candidate is a position: 32 w < total)
+        while (x) {
+            const u32 k = (u32)__ffs((int)x) - 1u, gp = 32u * w + k;
+            while (gp >= v.base[b + 1]) b++;
+            if (classTab[(u32)b * 256u + (u32)bv.src[b][gp - v.base[b]]] != 0xFFFFFFFFu) out |= 1u << k;
+            x &= x - 1u;
+        }
+        bits[w] = out;
+    }
+    startCount[w] = (u32)__popc(out);
 }
 
 // the run groups as ordinary groups (when the run-length round cannot take them)
@@ -2333,7 +2505,7 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_compact(const u32* __restrict
 // run k: end, length, and the sort key [class | above? | T | k]
 __global__ __launch_bounds__(256) void k_bwt_f_run_table(BwtView bv, FwdView v, const u32* __restrict__ runPos, u32 nRuns, const u32* __restrict__ R,
                                                          const u32* __restrict__ classTab, int kbits, int idxBits, u64* __restrict__ runKeys,
-                                                         u32* __restrict__ runE, u32* __restrict__ runL)
+                                                         u32* __restrict__ runE, u32* __restrict__ runL, const uint2* __restrict__ gapList, u32 nsym)
 {
     const u32 k = blockIdx.x * 256 + threadIdx.x;
     if (k >= nRuns) return;
@@ -2343,7 +2515,14 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_table(BwtView bv, FwdView v, 
     const u8* t = bv.src[b];
     const u32 c = t[p - bb], L = R[p], e = p + L;
     const bool below = (e >= be) || (t[e - bb] < c);                 // the block end sorts in front of every byte
-    const u64 T = (e < be) ? (u64)(lab_cur(v, e, bb) - bb + 1u) : 0ull;
+    u64 T = 0ull;
+    if (e < be) {
+        // gapList (the run list, when the members stayed out of round 0's sort): a member of a run group has no label yet. Behind a run
+        // that can only be the first position of another run, and its label is its group's first slot
+        u32 d = 0xFFFFFFFFu;
+        if (gapList != nullptr && R[e] >= nsym) d = classTab[(u32)b * 256u + (u32)t[e - bb]];
+        T = (u64)((d != 0xFFFFFFFFu ? gapList[d].x : lab_cur(v, e, bb)) - bb + 1u);
+    }
     const u64 cls = classTab[(u32)b * 256u + c];
     runKeys[k] = ((((cls << 1) | (below ? 0ull : 1ull)) << kbits | T) << idxBits) | (u64)k;
     runE[k] = e;
@@ -2663,7 +2842,7 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_flags(const u64* __restrict__
 __global__ __launch_bounds__(256) void k_bwt_f_run_place(FwdView v, const uint2* __restrict__ desc, const u32* __restrict__ loff, u32 M, int kbits, const u64* __restrict__ keys,
                                                          const u32* __restrict__ vals, const u32* __restrict__ bits, const u32* __restrict__ winLastIncl,
                                                          const u32* __restrict__ winFirstInclRev, u32 nWin, uint2* __restrict__ largeNext, const u32* __restrict__ memberR,
-                                                         u32* __restrict__ ovr, u32* __restrict__ rtbits, const u32* __restrict__ lbase)
+                                                         u32* __restrict__ ovr, u32* __restrict__ rtbits, const u32* __restrict__ lbase, int allLabels)
 {
     // one member per thread (the kernel is a scatter of labels: occupancy is what hides its latency); the 64 words of the member's window of
     // 2048 are looked at by every one of the window's eight workgroups
@@ -2709,7 +2888,8 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_place(FwdView v, const uint2*
         const u32 gp = vals[j];
         mySlot = gs + (j - off);
         v.SA[mySlot] = gp;
-        if (nh != off) lab_set(v, gp, lbase[di], gs + (nh - off), gs);      // (the first tie of a group keeps the group's label)
+        // (the first tie of a group keeps the group's label, which round 0 wrote -- unless the members stayed out of its sort: allLabels)
+        if (nh != off || allLabels) lab_set(v, gp, lbase[di], gs + (nh - off), gs);
         ovr[mySlot] = memberR[j];                                            // what the doubling rounds need to look behind the run
         if (nh == j) {
             const u32 m2 = word & ~lowmask;
@@ -2845,11 +3025,11 @@ __global__ __launch_bounds__(256) void k_bwt_f_med_compact(uint2* __restrict__ s
 // knobs (tests, diagnostics): read from the environment once per process, or set through knz_hip_tune(). Each one forces, at test
 // sizes, a path that some inputs take by themselves (round-0 key length, no run round, the run groups' fall-back, the plain labels of
 // blocks above 256 MiB, the plain keys of blocks above 8 MiB, where the link step starts), or reports (stats).
-struct FwdTuning { int nsym; int noRunRound; int runFallback; int stats; int link; int plainLabels; int noPack; int noUnsplitSkip; int noGroupSleep; int noMediumFuse; int runSort; int chainList; };
+struct FwdTuning { int nsym; int noRunRound; int runFallback; int stats; int link; int plainLabels; int noPack; int noUnsplitSkip; int noGroupSleep; int noMediumFuse; int runSort; int chainList; int runInSort; };
 static FwdTuning& fwd_tuning()
 {
     static FwdTuning t = [] {
-        FwdTuning x; x.nsym = 0; x.noRunRound = 0; x.runFallback = 0; x.stats = 0; x.link = 1; x.plainLabels = 0; x.noPack = 0; x.noUnsplitSkip = 0; x.noGroupSleep = 0; x.noMediumFuse = 0; x.runSort = 0; x.chainList = 0;     // link: 0 off, 1 on (from h = 32), n > 1: from h = n
+        FwdTuning x; x.nsym = 0; x.noRunRound = 0; x.runFallback = 0; x.stats = 0; x.link = 1; x.plainLabels = 0; x.noPack = 0; x.noUnsplitSkip = 0; x.noGroupSleep = 0; x.noMediumFuse = 0; x.runSort = 0; x.chainList = 0; x.runInSort = 0;     // link: 0 off, 1 on (from h = 32), n > 1: from h = n
         if (getenv("KNZ_BWT_PLAIN_LABELS")) x.plainLabels = 1;
         if (getenv("KNZ_BWT_NO_PACK")) x.noPack = 1;
         if (getenv("KNZ_BWT_NO_UNSPLIT_SKIP")) x.noUnsplitSkip = 1;
@@ -2857,6 +3037,7 @@ static FwdTuning& fwd_tuning()
         if (getenv("KNZ_BWT_NO_MEDIUM_FUSE")) x.noMediumFuse = 1;
         if (const char* e = getenv("KNZ_BWT_RUN_SORT")) x.runSort = atoi(e);
         if (const char* e = getenv("KNZ_BWT_CHAIN_LIST")) x.chainList = atoi(e);
+        if (const char* e = getenv("KNZ_BWT_RUN_IN_SORT")) x.runInSort = atoi(e);
         if (const char* e = getenv("KNZ_BWT_LINK")) x.link = atoi(e);
         if (getenv("KNZ_BWT_STATS")) x.stats = 1;
         if (const char* e = getenv("KNZ_BWT_NSYM")) x.nsym = atoi(e);
@@ -2882,6 +3063,7 @@ int bwt_forward_tune(const char* key, int value)
     else if (!strcmp(key, "bwt_no_medium_fuse")) t.noMediumFuse = value;        // medium groups through k_bwt_f_gather_desc and k_bwt_f_sort_medium on versioned labels too
     else if (!strcmp(key, "bwt_run_sort")) t.runSort = value;                   // 1: the run round's members generated and sorted (k_bwt_f_run_members, _expand), not placed directly
     else if (!strcmp(key, "bwt_chain_list")) t.chainList = value;               // 1: k_bwt_f_medium_fused lists the chain round's groups for k_bwt_f_super (keys through K), not in place
+    else if (!strcmp(key, "bwt_run_in_sort")) t.runInSort = value;              // 1: the run members go through round 0's sort (no FwdSort::run_scan, no gaps)
     else return -1;
     return 0;
 }
@@ -2907,6 +3089,7 @@ struct FwdScratch {
     u32* runPos; u32* runE; u32* runL; u32* sE; u32* rcnt; u32* moff;
     u64* runKeysA; u64* runKeysB; u64* sKey;
     u32* runTileStart; u32* runColTab;      // direct placement of the members: first runs of the tiles, column tables of the segments of several tiles
+    u32* gapMembers; u32* gapFirst; u32* gapStart; u32* cbase;      // run members kept out of round 0's sort: [nBlocks][256] each, and the compact segments' bases
     size_t maxRuns;
 };
 
@@ -2959,6 +3142,8 @@ static size_t fwd_carve(u8* p, int nBlocks, size_t total, FwdScratch* w, u32 VS)
     // tiles of segments of several tiles -- 8 * RUN_COLS / RUN_TILE = 8 bytes per run, 2 per byte of input, whatever the input holds
     w->runTileStart = (u32*)take(4 * w->maxRuns + 64);
     w->runColTab = (u32*)take(4ull * RUN_COLS * run_tile_slots(w->maxRuns));
+    w->gapMembers = (u32*)take(1024ull * (size_t)nBlocks); w->gapFirst = (u32*)take(1024ull * (size_t)nBlocks); w->gapStart = (u32*)take(1024ull * (size_t)nBlocks);
+    w->cbase = (u32*)take(4ull * (nBlocks + 2));
     return (size_t)(q - p);
 }
 
@@ -3012,6 +3197,8 @@ struct FwdSort {
     u64 *keysFree, *keysFree2;                             // key buffers of the rounds (keysFree2: round 0's sorted keys until they are placed)
     bool medFuse = false;                                  // medium groups through k_bwt_f_medium_fused (versioned labels; knob bwt_no_medium_fuse)
     bool runDirect = false;                                // the run round placed its members directly (k_bwt_f_run_emit; knob bwt_run_sort)
+    bool gaps = false;                                     // the run members stay out of round 0's sort (run_scan; knob bwt_run_in_sort)
+    u32 gapClasses = 0, keptOut = 0, scanRuns = 0, scanLongest = 0;     // what run_scan found: run groups, their members, runs of their bytes, longest run
     u32 nMedLo = 0;                                        // descriptors of the lower size class among the nMed of the list
     u32 nRun, runElems, surv, nMed, nLarge, largeElems, survMembers;   // run groups of round 0 and their members; left: small groups (!= 0),
                                                                        // medium and large groups, large members, small members still tied
@@ -3086,6 +3273,63 @@ struct FwdSort {
         while (2 * h <= (u32)nsym) h <<= 1;
         return 0;
     }
+    // 30-bit counts in the look-back words (a 1 GiB block: count + scatter)
+    bool one_read() const { return prims::rs_onesweep_knob().load() != 0 && nsym <= prims::RS_MAXPASS && (size_t)bv.VS < (size_t)prims::RS_VAL_MASK; }
+    // The run groups found in the text before round 0 sorts anything, so that their members can stay out of the sort (see TextSrcKept): the
+    // run round's own first steps -- run ends, run lengths (R stays in w.K until the run round has read it), the runs of run-group bytes
+    // compacted -- with the members counted per (block, byte) on the way. Everything the run round could fall back on is known after the
+    // one read-back, which is the run round's, moved here: `gaps` is set only when it will take every run group.
+    int run_scan()
+    {
+        gaps = false; keptOut = 0;
+        kbits = bits_for((u64)bv.VS + 2, 1);
+        if (tune.noRunRound || tune.runFallback || tune.runInSort || (2 * kbits + 1) >= 64 || !one_read() || nsym < 2) return 0;
+        const u32 nWin = (total + SM_WIN - 1) / SM_WIN, nRW = nWin * (SM_WIN / 32);
+        hipMemsetAsync(w.counters, 0, 4 * (CNT_GAP_MEMBERS + 1), s);
+        hipMemsetAsync(w.gapMembers, 0, 1024ull * (size_t)st.nBlocks, s); hipMemsetAsync(w.gapFirst, 0xFF, 1024ull * (size_t)st.nBlocks, s);
+        { KScope ks_("k_bwt_f_run_ends"); hipLaunchKernelGGL(k_bwt_f_run_ends, dim3(nWin), dim3(256), 0, s, bv, v, reinterpret_cast<u8*>(w.ebits)); }
+        bounds(nWin, false, w.ebits, total, SM_WIN / 32);
+        { KScope ks_("k_bwt_f_run_len"); hipLaunchKernelGGL(k_bwt_f_run_len<true>, dim3(nWin), dim3(256), 0, s, bv, v, w.ebits, w.t3, nWin, w.K, (const u32*)nullptr, (u32)nsym,
+                                                            reinterpret_cast<unsigned long long*>(w.rbits), w.rcount, w.gapMembers, w.gapFirst); }
+        { KScope ks_("k_bwt_f_run_scan_classes");
+          hipLaunchKernelGGL(k_bwt_f_run_scan_classes, dim3(1), dim3(256), 0, s, w.gapMembers, w.classTab, w.base, w.cbase, st.nBlocks, w.counters);
+          hipLaunchKernelGGL(k_bwt_f_run_starts, GRID1(nRW), bv, v, w.rbits, nRW, w.classTab, w.rcount); }
+        { KScope ks_("k_bwt_f_scan_sum"); prims::launch_scan<prims::SCAN_SUM_EXCL>(s, w.rcount, w.rprefix, nRW, nullptr, w.scanTmp, w.counters + CNT_RUNS); }
+        { KScope ks_("k_bwt_f_run_compact"); hipLaunchKernelGGL(k_bwt_f_run_compact, GRID1(nRW), w.rbits, w.rprefix, nRW, w.runPos); }
+        if (fetch(CNT_RUN_LONGEST, CNT_GAP_MEMBERS + 1 - CNT_RUN_LONGEST)) return -1;
+        gapClasses = hp[CNT_GAP_CLASSES]; scanRuns = hp[CNT_RUNS]; scanLongest = hp[CNT_RUN_LONGEST];
+        // (the conditions of run_round's fall-backs, with the groups round 0 is going to list)
+        const int hbits = bits_for((u64)scanLongest + 1, 1) + 1, rbits = bits_for(gapClasses, 0), idxBits = bits_for(scanRuns, 1);
+        if (gapClasses == 0 || (u64)gapClasses > (1ull << (64 - (2 * kbits + 1)))) return 0;
+        if (scanRuns == 0 || scanRuns > w.maxRuns || rbits + hbits > 32 || idxBits + kbits + 1 + rbits > 64) return 0;
+        gaps = true; keptOut = hp[CNT_GAP_MEMBERS];
+        return 0;
+    }
+    // round 0's sort without the run members: compact segments up to the last pass, which leaves the gaps; the gaps filled
+    void round0_sort_gaps(const prims::RsWs& rs)
+    {
+        const prims::RsWs rsC = prims::rs_carve(w.rsMem, maxTotal, st.nBlocks + 1, w.cbase, st.nBlocks);      // (the same memory: one layout at a time)
+        u64* kin = w.keysA; u64* kout = w.keysB;
+        KScope ks_("k_bwt_f_r0_sort");
+        hipLaunchKernelGGL(k_bwt_f_r0_counts, dim3((unsigned)rs.L.nSeg), dim3(256), 0, s, bv, w.base, w.byteHist, nsym, rs.L, w.gapMembers);
+        hipLaunchKernelGGL(k_bwt_f_r0_bases, dim3((unsigned)rs.L.nSeg, (unsigned)nsym), dim3(256), 0, s, rs.L, w.base, w.cbase, nsym, w.gapMembers, w.gapStart);
+        for (int pass = 0; pass < nsym; pass++) {
+            if (pass == 0) {                                          // reads every position of the blocks (layout: base), keeps the others
+                TextSrcKept src; src.src = bv.src; src.P = nsym; src.pbits = pbits; src.shift = pbits; src.members = w.gapMembers;
+                prims::rs_launch_pass_os<u64, false>(s, rs, src, nullptr, kout, nullptr, (size_t)bv.VS, pass);
+                prims::rs_launch_layout(s, rsC);
+            } else if (pass + 1 < nsym) {
+                prims::DigitOfKey<u64> src; src.keys = kin; src.shift = pbits + 8 * pass; src.mask = 255u;
+                prims::rs_launch_pass_os<u64, false>(s, rsC, src, nullptr, kout, nullptr, (size_t)bv.VS, pass);
+            } else {
+                LastPassSrc src; src.keys = kin; src.shift = pbits + 8 * pass; src.mask = 255u; src.members = w.gapMembers; src.gapStart = w.gapStart; src.P = nsym; src.pbits = pbits;
+                prims::rs_launch_pass_os<u64, false>(s, rsC, src, nullptr, kout, nullptr, (size_t)bv.VS, pass);
+            }
+            std::swap(kin, kout);
+        }
+        hipLaunchKernelGGL(k_bwt_f_r0_fill, dim3(128, (unsigned)st.nBlocks), dim3(256), 0, s, kin, w.gapMembers, w.gapStart, w.gapFirst, nsym, pbits);
+        keysFree = kout; keysFree2 = kin;
+    }
     // Round 0: the suffixes of every block sorted by their first nsym symbols. Keys = [nsym bytes | position in the block]; one stable LSD
     // pass per symbol, the first one reads the text, the blocks are the segments of the sort.
     void round0_sort()
@@ -3094,11 +3338,11 @@ struct FwdSort {
         rs1 = prims::rs_carve(w.rsMem, maxTotal, st.nBlocks + 1, w.seg2, 1);
         { KScope ks_("k_bwt_f_r0_layout"); prims::rs_launch_layout(s, rs); }
         u64* kin = w.keysA; u64* kout = w.keysB;
-        const bool oneRead = prims::rs_onesweep_knob().load() != 0 && nsym <= prims::RS_MAXPASS
-                             && (size_t)bv.VS < (size_t)prims::RS_VAL_MASK;   // 30-bit counts in the look-back words (a 1 GiB block: count + scatter)
+        const bool oneRead = one_read();
+        if (gaps) { round0_sort_gaps(rs); return; }
         if (oneRead) {                                                // the digits of all passes counted from the text, once
             KScope ks_("k_bwt_f_r0_sort");
-            hipLaunchKernelGGL(k_bwt_f_r0_counts, dim3((unsigned)rs.L.nSeg), dim3(256), 0, s, bv, w.base, w.byteHist, nsym, rs.L);
+            hipLaunchKernelGGL(k_bwt_f_r0_counts, dim3((unsigned)rs.L.nSeg), dim3(256), 0, s, bv, w.base, w.byteHist, nsym, rs.L, (const u32*)nullptr);
             hipLaunchKernelGGL(prims::k_rs_digit_bases, dim3((unsigned)rs.L.nSeg, (unsigned)nsym), dim3(256), 0, s, rs.L);
         }
         auto sortPass = [&](const auto& src, int pass) {
@@ -3129,7 +3373,8 @@ struct FwdSort {
         // that close to 2 GiB)
         const bool runRound = (2 * kbits + 1) < 64 && !tune.noRunRound;
         { KScope ks_("k_bwt_f_r0_place");
-          hipLaunchKernelGGL(k_bwt_f_r0_place_text, dim3(nTiles), dim3(256), 0, s, bv, v, w.t1, w.t3, nTiles, w.large[cur], keysFree2, nsym, pbits, runRound ? w.runList : (uint2*)nullptr);
+          hipLaunchKernelGGL(k_bwt_f_r0_place_text, dim3(nTiles), dim3(256), 0, s, bv, v, w.t1, w.t3, nTiles, w.large[cur], keysFree2, nsym, pbits, runRound ? w.runList : (uint2*)nullptr,
+                             gaps ? w.classTab : (const u32*)nullptr);
           merge_bits(); }
         if (fetch(0, CNT_ROUND_SLOTS)) return -1;
         nRun = hp[CNT_RUN]; runElems = hp[CNT_RUN_MEMBERS];
@@ -3147,6 +3392,13 @@ struct FwdSort {
     {
         // more run groups than the key has index bits left for (thousands of blocks in one batch; the knob: tests force this path)
         if (nRun && ((u64)nRun > (1ull << (64 - (2 * kbits + 1))) || tune.runFallback) && run_fallback()) return -1;
+        if (gaps) {
+            // run_scan has done the steps up to the read-back, and knows that none of the fall-backs applies; round 0 must have listed the
+            // groups it counted. The class table gets the descriptor indexes.
+            if (nRun != gapClasses || runElems != keptOut) return -1;
+            { KScope ks_("k_bwt_f_run_classes"); hipLaunchKernelGGL(k_bwt_f_run_classes, GRID1(nRun), bv, v, w.runList, nRun, w.classTab); }
+            return run_round_sorted(scanRuns, scanLongest);
+        }
         if (!nRun) return 0;
         const u32 nWin = (total + SM_WIN - 1) / SM_WIN;          // (windows of 2048 positions)
         { KScope ks_("k_bwt_f_run_ends"); hipLaunchKernelGGL(k_bwt_f_run_ends, dim3(nWin), dim3(256), 0, s, bv, v, reinterpret_cast<u8*>(w.ebits)); }
@@ -3154,27 +3406,32 @@ struct FwdSort {
         // run lengths of every position, and the starts of the runs of run-group bytes as a bit map
         hipMemsetAsync(w.classTab, 0xFF, 1024ull * (size_t)st.nBlocks, s);
         { KScope ks_("k_bwt_f_run_classes"); hipLaunchKernelGGL(k_bwt_f_run_classes, GRID1(nRun), bv, v, w.runList, nRun, w.classTab); }
-        { KScope ks_("k_bwt_f_run_len"); hipLaunchKernelGGL(k_bwt_f_run_len, dim3(nWin), dim3(256), 0, s, bv, v, w.ebits, w.t3, nWin, w.K, w.classTab, (u32)nsym,
-                                                            reinterpret_cast<unsigned long long*>(w.rbits), w.rcount); }
+        { KScope ks_("k_bwt_f_run_len"); hipLaunchKernelGGL(k_bwt_f_run_len<false>, dim3(nWin), dim3(256), 0, s, bv, v, w.ebits, w.t3, nWin, w.K, w.classTab, (u32)nsym,
+                                                            reinterpret_cast<unsigned long long*>(w.rbits), w.rcount, (u32*)nullptr, (u32*)nullptr); }
         // the runs themselves, compacted in position order (the windows of k_bwt_f_run_len cover whole words up to nWin * 2048)
         const u32 nRW = nWin * (SM_WIN / 32);
         { KScope ks_("k_bwt_f_scan_sum"); prims::launch_scan<prims::SCAN_SUM_EXCL>(s, w.rcount, w.rprefix, nRW, nullptr, w.scanTmp, w.counters + CNT_RUNS); }
         { KScope ks_("k_bwt_f_run_compact"); hipLaunchKernelGGL(k_bwt_f_run_compact, GRID1(nRW), w.rbits, w.rprefix, nRW, w.runPos); }
         if (fetch(CNT_RUN_LONGEST, 3)) return -1;
-        const u32 nRuns = hp[CNT_RUNS];
-        const int hbits = bits_for((u64)hp[CNT_RUN_LONGEST] + 1, 1) + 1;     // (+ 1: both halves of the order: R and 2^hbits - 1 - R)
+        return run_round_sorted(hp[CNT_RUNS], hp[CNT_RUN_LONGEST]);
+    }
+    // the rest of the run round: nRuns runs of run-group bytes in w.runPos, R in w.K, the class table filled
+    int run_round_sorted(const u32 nRuns, const u32 longest)
+    {
+        const int hbits = bits_for((u64)longest + 1, 1) + 1;     // (+ 1: both halves of the order: R and 2^hbits - 1 - R)
         const int rbits = bits_for(nRun, 0), idxBits = bits_for(nRuns, 1);
         // more runs than the tables hold (a round-0 key shorter than 4 symbols) or fields that do not fit their words: the ordinary way
-        if (nRuns == 0 || nRuns > w.maxRuns || rbits + hbits > 32 || idxBits + kbits + 1 + rbits > 64) return run_fallback();
+        if (nRuns == 0 || nRuns > w.maxRuns || rbits + hbits > 32 || idxBits + kbits + 1 + rbits > 64) return gaps ? -1 : run_fallback();
         { KScope ks_("k_bwt_f_large_prefix"); hipLaunchKernelGGL(k_bwt_f_large_prefix, dim3(1), dim3(1024), 0, s, w.runList, nRun, w.loff, w.base, st.nBlocks, w.lbase); }
-        { KScope ks_("k_bwt_f_run_table"); hipLaunchKernelGGL(k_bwt_f_run_table, GRID1(nRuns), bv, v, w.runPos, nRuns, w.K, w.classTab, kbits, idxBits, w.runKeysA, w.runE, w.runL); }
+        { KScope ks_("k_bwt_f_run_table"); hipLaunchKernelGGL(k_bwt_f_run_table, GRID1(nRuns), bv, v, w.runPos, nRuns, w.K, w.classTab, kbits, idxBits, w.runKeysA, w.runE, w.runL,
+                                                              gaps ? w.runList : (const uint2*)nullptr, (u32)nsym); }
         const u64* rkSorted;
         { KScope ks_("k_bwt_f_sort_runs");
           rkSorted = sort_one_segment<u64, false>(nRuns, w.runKeysA, w.runKeysB, nullptr, nullptr, idxBits, idxBits + kbits + 1 + rbits) ? w.runKeysB : w.runKeysA; }
         { KScope ks_("k_bwt_f_run_sorted"); hipLaunchKernelGGL(k_bwt_f_run_sorted, GRID1(nRuns), rkSorted, nRuns, idxBits, w.runE, w.runL, (u32)nsym, w.sE, w.sKey, w.rcnt); }
         { KScope ks_("k_bwt_f_scan_sum"); prims::launch_scan<prims::SCAN_SUM_EXCL>(s, w.rcnt, w.moff, nRuns, nullptr, w.scanTmp); }
         u64* rk; u32* rv = w.valsA;
-        runDirect = !tune.runSort && hp[CNT_RUN_LONGEST] <= RUN_DIRECT_LMAX;
+        runDirect = !tune.runSort && longest <= RUN_DIRECT_LMAX;
         if (runDirect) {
             // the members placed without a sort (k_bwt_f_run_emit): segments and tiles of the sorted runs, the column tables of the segments
             // of several tiles, the records. The tables of the unsorted runs are free by now: runPos holds the segments' first runs, runE
@@ -3210,7 +3467,7 @@ struct FwdSort {
         { KScope ks_("k_bwt_f_large_place");
           hipMemsetAsync(w.rtbits, 0, 4 * w.gbitsWords, s);
           hipLaunchKernelGGL(k_bwt_f_run_place, dim3((runElems + 255) / 256), dim3(256), 0, s, v, w.runList, w.loff, runElems, hbits + kbits, rk, rv, mbits, w.t1, w.t3, nWinM, w.large[cur],
-                             w.valsB, w.ovr, w.rtbits, w.lbase);
+                             w.valsB, w.ovr, w.rtbits, w.lbase, gaps ? 1 : 0);
           v.ovr = w.ovr; v.rtbits = w.rtbits; }
         { KScope ks_("k_bwt_f_merge_bits"); merge_bits(); }
         return 0;
@@ -3235,8 +3492,8 @@ struct FwdSort {
             if (fetch(0, CNT_MED_LO + 1)) return -1;                    // (the probe's two slots, and the class count that goes with CNT_MED)
             surv |= hp[CNT_SMALL_LEFT]; nMed += hp[CNT_MED]; nMedLo += hp[CNT_MED_LO];
         }
-        if (tune.stats) fprintf(stderr, "after round 0 (nsym %d, total %u): run groups %u (%u members); small left %u, medium %u, large %u (%u members); run members placed directly %u, sorted %u\n",
-                                nsym, total, nRun, runElems, surv, nMed, nLarge, largeElems, (nRun && runDirect) ? runElems : 0u, (nRun && !runDirect) ? runElems : 0u);
+        if (tune.stats) fprintf(stderr, "after round 0 (nsym %d, total %u): run groups %u (%u members); small left %u, medium %u, large %u (%u members); run members placed directly %u, sorted %u, kept out of the round-0 sort %u\n",
+                                nsym, total, nRun, runElems, surv, nMed, nLarge, largeElems, (nRun && runDirect) ? runElems : 0u, (nRun && !runDirect) ? runElems : 0u, gaps ? keptOut : 0u);
         statT = std::chrono::steady_clock::now();
         return 0;
     }
@@ -3379,6 +3636,7 @@ static int bwt_forward_run(hipStream_t s, const XfStage& st, void* scratch, size
     FwdSort f{ s, st, h_pinned };
     if (int r = f.setup(scratch, scratchBytes, sa)) return r;
     if (f.total == 0) return 0;
+    if (f.run_scan()) return -1;
     f.round0_sort();
     if (f.round0_place() || f.run_round() || f.probe()) return -1;
     while (f.surv || f.nMed || f.nLarge) if (int r = f.round()) return r;

@@ -257,9 +257,20 @@ static __global__ void k_rs_layout(RsLayout L)
 // digit of element i alone (what the counting kernel needs). The functor may read anything: a key array, or the text for the
 // first pass of the suffix sort.
 // STAGED: the source wants the tile's input staged in LDS first (stage() by the whole workgroup, then load_staged() per element).
+// Two more hooks, for k_rs_onesweep alone (compile-time: a source without them gets the kernel it always got):
+// Both read a table of 256 words per segment, tab(sgm, index), which the kernel holds in LDS.
+// FILTER: keep(sgm, len, key, tab) says which elements take part; the others are read and dropped, so the pass reads `len` elements of a
+//   segment and writes fewer. Where they go is the caller's business: the digits' first output positions (RsLayout::histAll) must
+//   count the kept elements only.
+// SHIFTS: out_shift(key, digit, at, tab) moves an element's output position, or not: a gap inside a digit's output range. note_tile()
+//   is called once per tile and digit with the tile's keys of that digit, in order, and the output position of the first of them.
 template <class KEY> struct DigitOfKey {
-    static constexpr bool STAGED = false;
+    static constexpr bool STAGED = false, FILTER = false, SHIFTS = false;
     const KEY* keys; int shift; u32 mask;
+    __device__ __forceinline__ u32 tab(int, u32) const { return 0u; }
+    __device__ __forceinline__ bool keep(int, u32, KEY, const u32*) const { return true; }
+    __device__ __forceinline__ u32 out_shift(KEY, u32, u32 at, const u32*) const { return at; }
+    __device__ __forceinline__ void note_tile(int, u32, const KEY*, u32, u32, const u32*) const {}
     __device__ __forceinline__ bool stage(int, u32, u32, u32*, int) const { return false; }
     __device__ __forceinline__ KEY load_staged(int, u32, u32, u32, const u32*, u32) const { return (KEY)0; }
     __device__ __forceinline__ KEY load(int, u32 b0, u32, u32 i) const { return keys[b0 + i]; }
@@ -488,6 +499,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_onesweep(SRC src, const u32* 
     __shared__ KEY sK[RS_TILE];
     __shared__ u32 sV[HAS_VAL ? RS_TILE : 1];
     __shared__ u32 sTicket;
+    __shared__ u32 sTab[(SRC::SHIFTS || SRC::FILTER) ? 256 : 1];
     const int sgm = blockIdx.y;
     const u32 b0 = L.base[sgm], len = L.base[sgm + 1] - b0;
     const u32 nT = (len + RS_TILE - 1) / RS_TILE;
@@ -496,6 +508,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_onesweep(SRC src, const u32* 
     // started before its own -- they are running or done -- whatever order the dispatcher, several queues or several XCDs start
     // workgroups in.
     if (tid == 0) sTicket = atomicAdd(&L.grpSum[sgm], 1u);
+    if ((SRC::SHIFTS || SRC::FILTER) && tid < 256) sTab[tid] = src.tab(sgm, (u32)tid);
     __syncthreads();
     const u32 t = sTicket;
     if (t >= nT) return;
@@ -509,6 +522,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_onesweep(SRC src, const u32* 
         valid[r] = i < len;
         if (SRC::STAGED && staged) key[r] = valid[r] ? src.load_staged(sgm, b0, len, i, reinterpret_cast<const u32*>(sK), t * RS_TILE) : (KEY)0;
         else key[r] = valid[r] ? src.load(sgm, b0, len, i) : (KEY)0;
+        if (SRC::FILTER) valid[r] = valid[r] && src.keep(sgm, len, key[r], sTab);
         if (HAS_VAL) val[r] = valid[r] ? vin[b0 + i] : 0u;
         dg[r] = valid[r] ? src.digit(key[r]) : 0u;
     }
@@ -537,7 +551,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_onesweep(SRC src, const u32* 
     __syncthreads();
 #pragma unroll
     for (int r = 0; r < 16; r++) if (valid[r]) { pos[r] += cnt[wave][dg[r]]; sK[pos[r]] = key[r]; if (HAS_VAL) sV[pos[r]] = val[r]; }
-    const u32 cntTile = (len - t * RS_TILE < RS_TILE) ? len - t * RS_TILE : RS_TILE;
+    // (a filtering source: the elements it kept, which is what the tile ranked)
+    const u32 cntTile = SRC::FILTER ? tot : ((len - t * RS_TILE < RS_TILE) ? len - t * RS_TILE : RS_TILE);
     if (tid < 256) {
         u32 excl = 0;
         if (t != 0) {
@@ -552,11 +567,13 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_onesweep(SRC src, const u32* 
         gBase[tid] = L.histAll[((size_t)pass * L.nSeg + sgm) * 256 + tid] + excl;
     }
     __syncthreads();
+    if (SRC::SHIFTS && tid < 256) src.note_tile(sgm, (u32)tid, sK + dStart[tid], mine, gBase[tid], sTab);
 #pragma unroll 4
     for (u32 j = (u32)tid; j < cntTile; j += RS_THREADS) {
         const KEY k = sK[j];
         const u32 d = src.digit(k);
-        const u32 at = gBase[d] + (j - dStart[d]);
+        u32 at = gBase[d] + (j - dStart[d]);
+        if (SRC::SHIFTS) at = src.out_shift(k, d, at, sTab);
         kout[at] = k;
         if (HAS_VAL) vout[at] = sV[j];
     }
