@@ -194,6 +194,22 @@ KNZ_API int knz_hip_encode_streams(knz_ctx* ctx, const knz_params* p, const uint
 KNZ_API int knz_hip_decode_streams(knz_ctx* ctx, const knz_params* p, const uint8_t* d_in, knz_item* items, size_t n_items,
                                    uint8_t* d_out, size_t out_cap);
 
+/*
+ * n independent device-to-device copies in ONE kernel launch: what moves scattered device buffers into the packed, 16-aligned d_in of
+ * knz_hip_encode_streams, its 16-aligned output streams into one tight blob, and streams at arbitrary byte offsets back to 16-aligned
+ * ones for knz_hip_decode_streams. src and dst are absolute device addresses of any alignment, in any relation to each other; len
+ * may be 0. Nothing outside [src, src + len) is read and nothing outside [dst, dst + len) is written. No destination range of a call
+ * may overlap another range of the same call, source or destination (sources may coincide); this is not checked.
+ *
+ * The launch is enqueued on the context's stream and the call does not wait for it; the table is staged, so `copies` may be reused
+ * as soon as the call returns. n == 0 is a successful no-op. Limits of a call: at most KNZ_COPY_MAX_COPIES copies, every len below
+ * 2^32, fewer than 2^31 tiles of 16 KiB in all (a copy of len bytes has at most len / 16384 + 2); a call over a limit fails as a whole
+ * with KNZ_ERR_INVALID_PARAM, says which, and launches nothing.
+ */
+#define KNZ_COPY_MAX_COPIES 1048576
+typedef struct { uint64_t src; uint64_t dst; uint64_t len; } knz_copy;   /* device addresses, bytes */
+KNZ_API int knz_hip_copy_many(knz_ctx* ctx, const knz_copy* copies /* host */, size_t n);
+
 /* ---- per-stage entry points (host buffers in/out; used by the host mirror classes and tests) ---- */
 
 /* EntropyEncoder::encode for one buffer (entropy/EntropyEncoder.hpp:30-37). out receives the bits

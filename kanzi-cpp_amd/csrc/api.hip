@@ -84,6 +84,11 @@ struct Ctx {
     std::vector<hipEvent_t> copyIdle;
     std::map<uint64_t, hipEvent_t> copyPending;
     uint64_t copyNext = 1;
+    // knz_hip_copy_many's table on its way to the device: pinned, grown on demand, reused by the next call once tabStageEv (recorded
+    // behind the upload) has passed
+    void* tabStage = nullptr;
+    size_t tabStageCap = 0;
+    hipEvent_t tabStageEv = nullptr;
 };
 #define CTX_LOCK(c) std::lock_guard<std::recursive_mutex> ctx_lock_((c)->mu)
 
@@ -209,6 +214,8 @@ void knz_hip_destroy(knz_ctx* ctx)
     for (auto& kv : c->ws) if (kv.second.p) hipFree(kv.second.p);
     for (auto& e : c->prof) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
     if (c->pinned) hipHostFree(c->pinned);
+    if (c->tabStage) hipHostFree(c->tabStage);
+    if (c->tabStageEv) hipEventDestroy(c->tabStageEv);
     for (auto& kv : c->copyPending) { hipEventSynchronize(kv.second); hipEventDestroy(kv.second); }
     for (auto& e : c->copyIdle) hipEventDestroy(e);
     for (int k = 0; k < 3; k++) { if (c->stream2[k]) hipStreamDestroy(c->stream2[k]); if (c->evJoin[k]) hipEventDestroy(c->evJoin[k]); }
@@ -1546,6 +1553,52 @@ int knz_hip_decode_streams(knz_ctx* ctx, const knz_params* p, const uint8_t* d_i
     const int r = decode_impl(c, p, d_in, reach, 0, 0, 1, 0, d_out, out_cap, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, &tab);
     if (r) hipStreamSynchronize(s);
     return r;
+}
+
+// ------------------------------------------------------------------------------------------------
+// many device-to-device copies in one launch (copy_many.hip)
+// ------------------------------------------------------------------------------------------------
+int knz_hip_copy_many(knz_ctx* ctx, const knz_copy* copies, size_t n)
+{
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    CTX_LOCK(c);
+    ProfInstall pi_(c);
+    if (n == 0) return 0;
+    if (copies == nullptr) return fail(c, KNZ_ERR_INVALID_PARAM, "no copies");
+    if (n > (size_t)KNZ_COPY_MAX_COPIES) return fail(c, KNZ_ERR_INVALID_PARAM, "too many copies in one call (%zu, at most %d)", n, KNZ_COPY_MAX_COPIES);
+    u64 tiles = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (copies[i].len >> 32) return fail(c, KNZ_ERR_INVALID_PARAM, "copy %zu: %llu bytes, a copy takes fewer than 2^32", i, (unsigned long long)copies[i].len);
+        tiles += copy_many_tiles(copies[i].dst, copies[i].len);
+    }
+    if (tiles >= (1ull << 31)) return fail(c, KNZ_ERR_INVALID_PARAM, "%llu tiles of %u bytes in one call, fewer than 2^31 are taken", (unsigned long long)tiles, copy_many_tile_bytes());
+    if (tiles == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    // one upload: the copies | the exclusive prefix of their tile counts
+    const size_t oFirst = sizeof(knz_copy) * n, bytes = oFirst + 4 * (n + 1);
+    if (c->tabStageEv == nullptr) HIPCHK(c, hipEventCreateWithFlags(&c->tabStageEv, hipEventDisableTiming));
+    HIPCHK(c, hipEventSynchronize(c->tabStageEv));          // the upload of the call before has left the staging (its kernel may still run)
+    if (c->tabStageCap < bytes) {
+        if (c->tabStage) HIPCHK(c, hipHostFree(c->tabStage));
+        c->tabStage = nullptr; c->tabStageCap = 0;
+        const size_t want = bytes + (bytes >> 3) + 4096;
+        HIPCHK(c, hipHostMalloc(&c->tabStage, want, hipHostMallocDefault));
+        c->tabStageCap = want;
+    }
+    u8* h = reinterpret_cast<u8*>(c->tabStage);
+    memcpy(h, copies, oFirst);
+    u32* first = reinterpret_cast<u32*>(h + oFirst);
+    u32 at = 0;
+    for (size_t i = 0; i < n; i++) { first[i] = at; at += (u32)copy_many_tiles(copies[i].dst, copies[i].len); }
+    first[n] = at;
+    u8* d_tab;
+    if (int r = ws_get(c, "copyTab", bytes, (void**)&d_tab, s)) return r;
+    HIPCHK(c, hipMemcpyAsync(d_tab, h, bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipEventRecord(c->tabStageEv, s));
+    launch_copy_many(s, reinterpret_cast<const knz_copy*>(d_tab), reinterpret_cast<const u32*>(d_tab + oFirst), (u32)n, at);
+    HIPCHK(c, hipGetLastError());
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------

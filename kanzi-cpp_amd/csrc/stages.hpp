@@ -270,6 +270,11 @@ void launch_seq_inv_prepare(hipStream_t s, const SeqArrays& a, DecBlock* blocks,
                             const u64* outOff = nullptr, const u64* roomTab = nullptr);
 void launch_seq_inv_commit(hipStream_t s, const SeqArrays& a, DecBlock* blocks, int nBlocks, int stage, int ttype);
 
+// copy_many.hip : n device-to-device copies in one launch; tileFirst = the exclusive prefix of copy_many_tiles over the copies (n + 1 words)
+u64 copy_many_tiles(u64 dst, u64 len);
+u32 copy_many_tile_bytes();
+void launch_copy_many(hipStream_t s, const knz_copy* copies, const u32* tileFirst, u32 n, u32 nTiles);
+
 // huffman.hip
 void launch_huffman_encode(hipStream_t s, BlockView view, int nBlocks, int maxChunks, ChunkDesc* desc, u8* tmp);
 void launch_huffman_decode(hipStream_t s, BitSrc src, DecBlock* blocks, int nBlocks, int maxChunks, void* chunkMeta, u8* const* outPtr, int bsVersion = 6);

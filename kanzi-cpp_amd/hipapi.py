@@ -25,10 +25,11 @@ SYMBOLS = [
     "knz_hip_entropy_encode_bs", "knz_hip_entropy_decode_bs", "knz_hip_tpaq_params",
     "knz_hip_transform_forward_bs", "knz_hip_transform_inverse_bs",
     "knz_hip_prims_info", "knz_hip_prims_scan", "knz_hip_prims_sort",
-    "knz_hip_encode_streams_bound", "knz_hip_encode_streams", "knz_hip_decode_streams",
+    "knz_hip_encode_streams_bound", "knz_hip_encode_streams", "knz_hip_decode_streams", "knz_hip_copy_many",
 ]
 STREAMS_MAX_ITEMS = STREAMS_MAX_BLOCKS = 65536      # KNZ_STREAMS_MAX_ITEMS / _BLOCKS of include/knz_hip.h
 BATCH_MAX_BYTES = 0x7FFFFFFF                        # input of one encode call, decoded bytes of one decode call
+COPY_MAX_COPIES = 1 << 20                           # KNZ_COPY_MAX_COPIES
 
 
 class Params(C.Structure):
@@ -41,6 +42,11 @@ class Item(C.Structure):
     _fields_ = [("in_off", C.c_uint64), ("in_len", C.c_uint64), ("start_bit", C.c_uint64), ("prologue_off", C.c_uint32),
                 ("prologue_bits", C.c_uint32), ("out_off", C.c_uint64), ("out_cap", C.c_uint64), ("out_len", C.c_uint64),
                 ("blocks", C.c_int32), ("error", C.c_int32)]
+
+
+class Copy(C.Structure):
+    """knz_copy: one copy of a knz_hip_copy_many call (device addresses, bytes)."""
+    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("len", C.c_uint64)]
 
 
 class KernelTime(C.Structure):
@@ -125,6 +131,7 @@ def lib():
         L.knz_hip_encode_streams_bound.argtypes = [C.POINTER(Params), C.POINTER(Item), sz]; L.knz_hip_encode_streams_bound.restype = sz
         L.knz_hip_encode_streams.argtypes = [vp, C.POINTER(Params), u8p, C.POINTER(Item), sz, C.c_char_p, C.c_int, u8p, sz, C.POINTER(C.c_uint64)]
         L.knz_hip_decode_streams.argtypes = [vp, C.POINTER(Params), u8p, C.POINTER(Item), sz, u8p, sz]
+        L.knz_hip_copy_many.argtypes = [vp, C.POINTER(Copy), sz]
         _lib = L
     return _lib
 
@@ -218,6 +225,14 @@ class Context:
         """items: an array of Item (in_off, in_len in bits, start_bit, out_off, out_cap set); the call fills out_len (bytes), blocks and
         error per item. Raises only for a failure of the call itself."""
         self._chk(self.L.knz_hip_decode_streams(self.h, C.byref(p), C.c_void_p(d_in), items, len(items), C.c_void_p(d_out), out_cap))
+
+    def copy_many(self, copies):
+        """copies: an array of Copy, or a sequence of (src, dst, len) device addresses and byte counts: all of them in one kernel launch
+        on the context's stream. Returns without waiting for it; the sequence may be reused at once."""
+        if not isinstance(copies, C.Array):
+            flat = [v for c in copies for v in c]
+            copies = (Copy * (len(flat) // 3)).from_buffer_copy((C.c_uint64 * len(flat))(*flat)) if flat else (Copy * 0)()
+        self._chk(self.L.knz_hip_copy_many(self.h, copies, len(copies)))
 
     # ---- per-stage API on host buffers
     def entropy_encode(self, entropy, data, stream_block_size=0):

@@ -4,9 +4,11 @@ Mirrors the reference's ctypes shim (src/api/kanzi_c_api.py:88-137 for the bindi
 src/api/kanzi.py for the two classes): same struct layouts, same call sequence
 (init -> compress()/decompress() per block -> dispose). Only marshals data.
 
-compress_many / decompress_many (at the end) are the batch form for many small independent buffers: they go over the device
-C ABI directly (hipapi.Context.encode_streams / decode_streams) and framing.py, many buffers per device call.
+compress_many / decompress_many (near the end) are the batch form for many small independent buffers: they go over the device
+C ABI directly (hipapi.Context.encode_streams / decode_streams) and framing.py, many buffers per device call. TensorCodec (at the end) is
+the same for torch tensors that live on the GPU: the payload never leaves the device. torch is imported only there, on first use.
 """
+import contextlib
 import ctypes as C
 import importlib
 import os
@@ -247,6 +249,22 @@ def _pack(buffers):
     return bytes(blob), offs
 
 
+def _encode_two_tier(ctx, hipapi, p, d_in, in_bytes, items, prologues, room):
+    """One encode_streams call over the packed input at d_in (in_bytes with its pads and slack) into room(cap), a device address with cap
+    bytes behind it. For CM, TPAQ and TPAQX the bound is a first tier (include/knz_hip.h): a call that it does not hold is made again with
+    the second, which holds whatever the format can write. Returns (the output's address, its bytes in use)."""
+    cap = ctx.encode_streams_bound(p, items)
+    try:
+        d_out = room(cap)
+        return d_out, ctx.encode_streams(p, d_in, items, d_out, cap, prologues=prologues)
+    except hipapi.KnzError as e:
+        if e.code != 12 or p.entropy_type not in hipapi.BINARY_CODERS:
+            raise
+    cap += 32 * in_bytes
+    d_out = room(cap)
+    return d_out, ctx.encode_streams(p, d_in, items, d_out, cap, prologues=prologues)
+
+
 def compress_many(buffers, transform, entropy, block_size, checksum=0, jobs=1, device=0):
     """Every buffer as a stream of its own: the file the reference CLI writes for those bytes (the header stores the buffer's length
     as the original size), many buffers per device call. Returns the streams in the buffers' order."""
@@ -265,18 +283,10 @@ def compress_many(buffers, transform, entropy, block_size, checksum=0, jobs=1, d
                 h, hb = framing.make_header(p.entropy_type, p.transform_type, block_size, checksum, len(buffers[i]))
                 items[k].in_off, items[k].in_len, items[k].prologue_off, items[k].prologue_bits = offs[k], len(buffers[i]), len(pro), hb
                 pro += h
-            cap = ctx.encode_streams_bound(p, items)
             d_in = bufs.get("in", len(blob))
             ctx.h2d(d_in, blob)
-            try:
-                used = ctx.encode_streams(p, d_in, items, bufs.get("out", cap), cap, prologues=bytes(pro))
-            except hipapi.KnzError as e:
-                # CM, TPAQ, TPAQX: the bound is a first tier (include/knz_hip.h); the second holds whatever the format can write
-                if e.code != 12 or p.entropy_type not in hipapi.BINARY_CODERS:
-                    raise
-                cap += 32 * len(blob)
-                used = ctx.encode_streams(p, d_in, items, bufs.get("out", cap), cap, prologues=bytes(pro))
-            raw = ctx.d2h(bufs.get("out", cap), used)
+            d_out, used = _encode_two_tier(ctx, hipapi, p, d_in, len(blob), items, bytes(pro), lambda cap: bufs.get("out", cap))
+            raw = ctx.d2h(d_out, used)
             for k, i in enumerate(run):
                 out[i] = raw[items[k].out_off:items[k].out_off + (items[k].out_len + 7) // 8]
         return out
@@ -331,3 +341,240 @@ def decompress_many(streams, jobs=1, device=0):
         return out
     finally:
         ctx.close()
+
+
+# ---- the same for tensors that are on the device already: nothing payload-sized crosses the bus
+HEADER_PEEK = 32                # bytes of every stream that decompress reads on the host: the longest header framing.make_header writes
+                                # is 208 bits (32 + 4 + 2 + 5 + 48 + 28 + 2 + 48 + 15 + 24), and an empty stream's end marker follows a
+                                # header without size (160 bits) inside them
+
+
+def _check_tensors(tensors, device):
+    """The ValueErrors of TensorCodec.compress, by index, before any device work: what is no tensor first, then what is not contiguous,
+    then what is in the wrong place. device None leaves out the comparison of devices."""
+    import torch
+    for i, t in enumerate(tensors):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("tensor %d is no torch.Tensor but %s" % (i, type(t).__name__))
+    for i, t in enumerate(tensors):
+        if not t.is_contiguous():
+            raise ValueError("tensor %d is not contiguous (its bytes in memory order are asked for; call .contiguous() first)" % i)
+    for i, t in enumerate(tensors):
+        if t.device.type != "cuda":
+            raise ValueError("tensor %d is on %s, not on the GPU (compress_many takes host bytes)" % (i, t.device))
+        if device is not None and t.device != device:
+            raise ValueError("tensor %d is on %s, the codec on %s" % (i, t.device, device))
+
+
+def _only_end_marker(head, bits, length):
+    """A stream without a stored size has no bytes when the end marker (eight zero bits) is all that follows its header: what compress
+    writes for an empty tensor. Told from the stream's first bytes when the header ends at a byte boundary (it does since version 6)."""
+    return bits % 8 == 0 and length == bits // 8 + 1 and head[bits // 8:bits // 8 + 1] == b"\0"
+
+
+class TensorCodec:
+    """compress_many / decompress_many for tensors that are on the GPU, with one device context, its workspaces and torch's caching
+    allocator kept across calls. Every stream is byte for byte what compress_many returns for the tensor's bytes, so the file the reference
+    CLI writes for them; the payload stays on the device in both directions (scattered tensors are gathered, and the streams compacted,
+    by knz_hip_copy_many), and only the stream headers (HEADER_PEEK bytes each) and the per-item results are read on the host.
+
+    All work is ordered on `stream` (a torch.cuda.Stream; default: the stream current on `device` when the codec is made), and every buffer
+    is allocated from torch's allocator while the stream that the kernels run on is current. The calls wait for that stream where the C
+    ABI does (the read-back of the items, the header table); they synchronise nothing else. Tensors produced on the same stream need no
+    synchronisation by the caller; tensors produced on another stream are the caller's to order (stream.wait_stream / events), and
+    results used on another stream likewise: torch's own rule.
+
+    A torch build that ships its own HIP runtime has to be imported before the device library is first loaded (hipapi.lib(), any
+    hipapi.Context), as bench.py does: the library then shares torch's runtime. The other way round torch finds no GPU."""
+
+    def __init__(self, device=None, stream=None):
+        import torch
+        hipapi, self._framing, self._sharded = _mods()
+        self._hipapi = hipapi
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError("TensorCodec needs a GPU device, not %s" % dev)
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        self.stream = torch.cuda.current_stream(dev) if stream is None else stream
+        # torch's default stream has the handle 0, which knz_hip_create takes as "a stream of the context's own": the codec then works on a
+        # torch stream of its own that every call puts behind what `stream` holds and that `stream` is put behind again afterwards, both on
+        # the device (events, no host synchronisation), so that the caller sees the order of one stream
+        self._work = self.stream if self.stream.cuda_stream else torch.cuda.Stream(dev)
+        self.ctx = hipapi.Context(dev.index, stream=self._work.cuda_stream)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        self.close()
+
+    def close(self):
+        if self.ctx is not None:
+            self.ctx.close()
+            self.ctx = None
+
+    def _open(self):
+        if self.ctx is None:
+            raise RuntimeError("TensorCodec is closed")
+
+    @contextlib.contextmanager
+    def _enqueue(self):
+        """The codec's device and working stream current; the working stream behind the caller's stream before, in front of it after."""
+        import torch
+        with torch.cuda.device(self.device), torch.cuda.stream(self._work):
+            if self._work is not self.stream:
+                self._work.wait_stream(self.stream)
+            try:
+                yield
+            finally:
+                if self._work is not self.stream:
+                    self.stream.wait_stream(self._work)
+
+    def _hand_over(self, t):
+        """A result allocated on the working stream is the caller's from here on: torch's allocator is told the stream that uses it."""
+        if self._work is not self.stream and t.numel():
+            t.record_stream(self.stream)
+        return t
+
+    def _empty(self, n):
+        import torch
+        return torch.empty(n, dtype=torch.uint8, device=self.device)
+
+    def _copy(self, copies):
+        most = self._hipapi.COPY_MAX_COPIES
+        for k in range(0, len(copies), most):
+            self.ctx.copy_many(copies[k:k + most])
+
+    def _gather(self, parts):
+        """parts: (device address, bytes) each. One copy_many moves them into a new buffer, every part at a multiple of 16, the pads
+        between them and 64 bytes behind the last zero, as _pack leaves them. Returns (the buffer, the parts' offsets)."""
+        import torch
+        offs, at = [], 0
+        for _, n in parts:
+            offs.append(at)
+            at += (n + 15) & ~15
+        buf = self._empty(at + 64)
+        zeros = torch.zeros(64, dtype=torch.uint8, device=self.device)
+        base, z = buf.data_ptr(), zeros.data_ptr()
+        copies = [(a, base + o, n) for (a, n), o in zip(parts, offs)]
+        copies += [(z, base + o + n, -n % 16) for (_, n), o in zip(parts, offs) if n % 16]
+        copies.append((z, base + at, 64))
+        self._copy(copies)
+        return buf, offs
+
+    def compress(self, tensors, transform, entropy, block_size, checksum=0, jobs=1):
+        """tensors: torch tensors of any dtype on the codec's device, contiguous; tensor i stands for its numel() * element_size() bytes in
+        memory order. Returns (blob, offsets): blob a 1-D uint8 tensor on the device, offsets a list of len(tensors) + 1 ints, stream k =
+        blob[offsets[k]:offsets[k + 1]]. ValueError, with the index, for a tensor that is not contiguous, on the CPU or on another
+        device (nothing is moved or made contiguous behind the caller's back), and for one too large for a device call."""
+        import torch
+        self._open()
+        tensors = list(tensors)
+        _check_tensors(tensors, self.device)
+        hipapi, framing, ctx = self._hipapi, self._framing, self.ctx
+        sizes = [t.numel() * t.element_size() for t in tensors]
+        runs = _calls(sizes, block_size, hipapi)
+        with self._enqueue():
+            p = ctx.params(transform, entropy, block_size, checksum, jobs)
+            where, keep = [None] * len(tensors), []                  # (address, bytes) of every stream in its call's output, which `keep` holds
+            for run in runs:
+                packed, offs = self._gather([(tensors[i].data_ptr(), sizes[i]) for i in run])
+                items = (hipapi.Item * len(run))()
+                pro = bytearray()
+                for k, i in enumerate(run):
+                    h, hb = framing.make_header(p.entropy_type, p.transform_type, block_size, checksum, sizes[i])
+                    items[k].in_off, items[k].in_len, items[k].prologue_off, items[k].prologue_bits = offs[k], sizes[i], len(pro), hb
+                    pro += h
+
+                def room(cap):
+                    keep.append(self._empty(cap))
+                    return keep[-1].data_ptr()
+                d_out, _ = _encode_two_tier(ctx, hipapi, p, packed.data_ptr(), packed.numel(), items, bytes(pro), room)
+                for k, i in enumerate(run):
+                    where[i] = (d_out + items[k].out_off, (items[k].out_len + 7) // 8)
+            offsets = [0]
+            for _, n in where:
+                offsets.append(offsets[-1] + n)
+            blob = self._empty(offsets[-1])
+            self._copy([(a, blob.data_ptr() + o, n) for (a, n), o in zip(where, offsets)])
+        return self._hand_over(blob), offsets
+
+    def decompress(self, blob, offsets):
+        """The way back: blob a 1-D uint8 tensor on the codec's device, stream k = blob[offsets[k]:offsets[k + 1]], written by this class,
+        by compress_many or by the reference. Returns a list of uint8 tensors on the device, each starting at a multiple of 16 bytes (so
+        .view(dtype) gives any dtype back); the tensors of one device call are views of one allocation. The first HEADER_PEEK bytes of
+        every stream are read on the host, the headers parsed there, streams of equal parameters share device calls. Raises KanziError
+        with the stream's index as decompress_many does. A stream without a stored size that holds data, or one that needs more than one
+        device call, goes decompress_many's way through the host and is uploaded again; streams that compress wrote never do."""
+        import torch
+        self._open()
+        hipapi, framing, sharded, ctx = self._hipapi, self._framing, self._sharded, self.ctx
+        offsets = [int(o) for o in offsets]
+        n = len(offsets) - 1
+        if not isinstance(blob, torch.Tensor) or blob.device != self.device or blob.dtype != torch.uint8 or blob.dim() != 1 or not blob.is_contiguous():
+            raise ValueError("blob must be a contiguous 1-D uint8 tensor on %s" % self.device)
+        if n < 0 or offsets[0] < 0 or offsets[-1] > blob.numel() or any(a > b for a, b in zip(offsets, offsets[1:])):
+            raise ValueError("offsets must rise from 0 to at most the blob's length")
+        if n == 0:
+            return []
+        out = [None] * n
+        lens = [offsets[k + 1] - offsets[k] for k in range(n)]
+        base = blob.data_ptr()
+        with self._enqueue():
+            table = self._empty(HEADER_PEEK * n)
+            self._copy([(base + offsets[k], table.data_ptr() + HEADER_PEEK * k, min(HEADER_PEEK, lens[k])) for k in range(n)])
+            heads = ctx.d2h(table.data_ptr(), HEADER_PEEK * n)
+            groups = {}
+            for i in range(n):
+                head = heads[HEADER_PEEK * i:HEADER_PEEK * i + min(HEADER_PEEK, lens[i])]
+                try:
+                    h = framing.parse_header(head)
+                except framing.HeaderError as e:
+                    raise KanziError(e.code, "stream %d: %s" % (i, e))
+                if h["orig_size"] == 0 and _only_end_marker(head, h["bits"], lens[i]):
+                    out[i] = self._empty(0)
+                    continue
+                if h["orig_size"] == 0 or not _fits_one_call(h["orig_size"], h["block_size"], hipapi) or not _fits_one_call(lens[i], 1024, hipapi):
+                    s = bytes(blob[offsets[i]:offsets[i + 1]].cpu().numpy())
+                    back = sharded.decompress_sharded(s, 0, 1, sharded.DeviceRunDecoder(self.device.index, 1), lambda part: [part])
+                    out[i] = self._hand_over(torch.frombuffer(bytearray(back), dtype=torch.uint8).to(self.device)) if back else self._empty(0)
+                    continue
+                key = (h["etype"], h["ttype"], h["block_size"], h["checksum_bits"], h["bs_version"])
+                groups.setdefault(key, []).append((i, h))
+            for (etype, ttype, bs, ck, ver), members in groups.items():
+                p = ctx.params(ttype, etype, bs, ck, 1, ver or 1)
+                for run in _calls([h["orig_size"] for _, h in members], bs, hipapi):
+                    packed, offs = self._gather([(base + offsets[members[k][0]], lens[members[k][0]]) for k in run])
+                    items = (hipapi.Item * len(run))()
+                    at = 0
+                    for m, k in enumerate(run):
+                        i, h = members[k]
+                        items[m].in_off, items[m].in_len, items[m].start_bit = offs[m], 8 * lens[i], h["bits"]
+                        items[m].out_off, items[m].out_cap = at, h["orig_size"]
+                        at += (h["orig_size"] + 15) & ~15
+                    d_out = self._hand_over(self._empty(at + 64))
+                    ctx.decode_streams(p, packed.data_ptr(), items, d_out.data_ptr(), at + 64)
+                    for m, k in enumerate(run):
+                        i, h = members[k]
+                        if items[m].error:
+                            raise KanziError(items[m].error, "stream %d: decoding" % i)
+                        if items[m].out_len != h["orig_size"]:
+                            raise KanziError(13, "stream %d: %d bytes where the header stores %d" % (i, items[m].out_len, h["orig_size"]))
+                        out[i] = d_out[items[m].out_off:items[m].out_off + items[m].out_len]
+        return out
+
+
+def compress_tensors(tensors, transform, entropy, block_size, checksum=0, jobs=1):
+    """TensorCodec.compress on torch's current device and stream, with a codec made for this one call."""
+    tensors = list(tensors)
+    _check_tensors(tensors, None)
+    with TensorCodec() as codec:
+        return codec.compress(tensors, transform, entropy, block_size, checksum, jobs)
+
+
+def decompress_tensors(blob, offsets):
+    """TensorCodec.decompress on the blob's device and torch's current stream there, with a codec made for this one call."""
+    with TensorCodec(blob.device) as codec:
+        return codec.decompress(blob, offsets)
