@@ -608,7 +608,7 @@ static const XfInfo XF[] = {
       .setsType = true },
     // (DNA, id 19: AliasCodec with the Context entry packOnlyDNA, TransformFactory.hpp:293-294. PACK's launchers; the forward refuses a
     // preset type other than UNDEFINED or DNA and a block whose detection does not say DNA, after it wrote what detection found. The
-    // inverse is PACK's)
+    // inverse is PACK's. The Context entry outlives the stage: a PACK behind DNA in one chain is built with it too, encode_impl)
     { .id = KNZ_T_DNA, .ws = "packScratch",
       .fwd = { .wsBytes = pack_scratch_bytes, .launch = [](const StageCall& k) { XfStage st = k.st; st.onlyDNA = 1; launch_pack_forward(k.s, st, k.ws); return 0; } },
       .inv = { .wsBytes = pack_scratch_bytes, .launch = [](const StageCall& k) { launch_pack_inverse(k.s, k.st, k.ws); return 0; } },
@@ -998,6 +998,9 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
         XfStage st = xf_stage(w, nBlocks, (u32)S, p->entropy_type);
         st.dtype = wantType ? w.a.dtype : nullptr;
         st.blockSize = streamBlockSize ? streamBlockSize : (framing ? bs : 0u);
+        // (TransformFactory.hpp:290-295: the DNA transform leaves packOnlyDNA in the Context that the chain's later stages are built
+        // from, so a PACK anywhere behind it in the same chain refuses what is not DNA as well)
+        for (int j = 0; j < i; j++) if (ch.tok[j] == KNZ_T_DNA) st.onlyDNA = 1;
         if (int r = run_stage(c, s, *ch.xf[i], true, st)) return r;
         launch_seq_fwd_commit(s, w.a, nBlocks, i);
     }

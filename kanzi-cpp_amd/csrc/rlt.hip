@@ -14,6 +14,7 @@
 //   * only the token itself (<= 5 bytes) is written by one lane.
 // The inverse scans 64 bytes per step for the next escape, copies literals and fills runs with the whole wave.
 #include "common.hpp"
+#include "datatype.hpp"
 #include "stages.hpp"
 
 namespace knz {
@@ -38,24 +39,6 @@ __device__ int rlt_emit_run(u8* dst, int run, u8 escape, u8 val)
     }
     dst[dstIdx] = (u8)run;
     return dstIdx + 1;
-}
-
-// Global.cpp:354-397 (only the classes RLT cares about: DNA / BASE64 refuse the transform)
-__device__ int rlt_refuses(int count, const u32* f)
-{
-    const char DNA[] = "acgntuACGNTU";
-    const char NUM[] = "0123456789+-*/=,.:; ";
-    const char B64[] = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/";
-    int sum = 0;
-    for (int i = 0; i < 12; i++) sum += (int)f[(u8)DNA[i]];
-    if (sum > (count - count / 12)) return 1;                 // DNA
-    sum = 0;
-    for (int i = 0; i < 20; i++) sum += (int)f[(u8)NUM[i]];
-    if (sum == count) return 0;                               // NUMERIC
-    sum = (f[0x3D] == 1) ? 1 : 0;
-    for (int i = 0; i < 64; i++) sum += (int)f[(u8)B64[i]];
-    if (sum == count) return 1;                               // BASE64
-    return 0;
 }
 
 // LDS window over a byte array: bytes [base, base + RLT_WIN) (zero past `count`)
@@ -95,8 +78,9 @@ __global__ __launch_bounds__(64) void k_rlt_forward(XfStage st)
     if (lane == 0) { st.ok[b] = 0; st.newLen[b] = 0; }
     if (count == 0) { if (lane == 0) st.ok[b] = 1; return; }
     if (count < 16) return;
-    // RLT.cpp:60-65: DNA (6), BASE64 (5) and UTF8 (8) blocks are refused (st.dtype is set only in chains behind PACK)
-    if (st.dtype) { const int dt = st.dtype[b]; if (dt == 6 || dt == 5 || dt == 8) return; }
+    // RLT.cpp:60-65: DNA, BASE64 and UTF8 blocks are refused (st.dtype is set only in chains with a stage that sets the data type)
+    const int dt = st.dtype ? (int)st.dtype[b] : (int)DT_UNDEFINED;
+    if (dt == DT_DNA || dt == DT_BASE64 || dt == DT_UTF8) return;
     const int maxEnc = (count <= 512) ? count + 32 : count;
     if ((int)st.cap[b] < maxEnc) return;
     const u8* src = st.src[b];
@@ -113,8 +97,14 @@ __global__ __launch_bounds__(64) void k_rlt_forward(XfStage st)
         for (int i = lane; i < count; i += 64) atomicAdd(&freqs[src[i]], 1u);
         __syncthreads();
         if (lane == 0) {
-            int e = -1;
-            if (!rlt_refuses(count, freqs)) {
+            // RLT.cpp:82-90: only a block that comes without a type is looked at (behind TEXT a block of four symbols arrives as TEXT
+            // and is transformed), and what detection finds stays on the block for the stages behind
+            int e = -1, found = DT_UNDEFINED;
+            if (dt == DT_UNDEFINED) {
+                found = pk_simple_type((u32)count, freqs);
+                if (st.dtype && found != DT_UNDEFINED) st.dtype[b] = (u8)found;
+            }
+            if (found != DT_DNA && found != DT_BASE64 && found != DT_UTF8) {
                 int minIdx = 0;
                 if (freqs[minIdx] > 0) {
                     for (int i = 1; i < 256; i++) {

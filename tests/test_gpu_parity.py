@@ -822,8 +822,8 @@ def test_randomised_soak(hip):
 
 
 def test_randomised_soak_newer_stages(hip):
-    """The same soak drawn over the first-generation tables plus BWTS, PACK, MM, LZP, ROLZX and UTF chains (alone, mixed with older
-    stages, two of them in one chain), the coders RANGE, CM, TPAQ and TPAQX and five input kinds these stages accept (tools/gpu_soak.py, mode `newer`):
+    """The same soak drawn over the first-generation tables plus BWTS, PACK, MM, LZP, ROLZX, UTF, EXE, TEXT and DNA chains (alone, mixed with older
+    stages, two of them in one chain), the coders RANGE, CM, TPAQ and TPAQX and six input kinds these stages accept (tools/gpu_soak.py, mode `newer`):
     every job count, checksum width and block size from 1 KiB to 1 MiB against the reference build's stream (oracle/_ref, which
     build() makes and which travels with the tree), which the device must write and read. A process and a budget of its own.
     The floor of 10 newer-stage cases keeps the test from passing on nothing, a missing reference build included; streams the
@@ -839,7 +839,7 @@ def test_randomised_soak_newer_stages(hip):
     import os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "tools", "gpu_soak.py"), "6", "15", "newer"], capture_output=True, text=True, timeout=300)
-    print(r.stdout[-600:])
+    print(r.stdout[-1500:])          # with the tool's count of cases per newer chain
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     m = re.search(r"newer stages (\d+); of which undecodable by the reference too: (\d+); skipped for want of the reference build: (\d+)", r.stdout)
     assert m, r.stdout[-500:]

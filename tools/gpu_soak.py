@@ -4,25 +4,30 @@ device decode of the expected stream (developer tool).   usage: gpu_soak.py SEED
 first (the default; tests/test_gpu_parity.py::test_randomised_soak): the 16 chains and 5 coders of the first generation, expected
 streams from the C oracle.
 
-newer (test_randomised_soak_newer_stages): the same draw over those tables plus the chains of NEWER_CHAINS (BWTS, PACK, MM, LZP, ROLZX and
-UTF alone, in front of and behind first-generation stages, and two of them in one chain) and the coders RANGE, CM, TPAQ and TPAQX. A case whose chain
+newer (test_randomised_soak_newer_stages): the same draw over those tables plus the chains of NEWER_CHAINS (BWTS, PACK, MM, LZP, ROLZX,
+UTF, EXE, TEXT and DNA alone, in front of and behind first-generation stages, and two of them in one chain) and the coders RANGE, CM, TPAQ and TPAQX. A case whose chain
 and coder the oracle knows stays on the oracle; any other takes its expected stream from the reference build (knzlib.Ref,
 oracle/_ref/libkanzi_ref.so) with the same jobs and checksum, and where that build is absent the case is skipped and counted. The
-input kinds grow by five that the newer stages accept: four at every block size from 4,096 up (checked with Ref.forward at 4,096, 65,536,
+input kinds grow by six that the newer stages accept: four at every block size from 4,096 up (checked with Ref.forward at 4,096, 65,536,
 262,144 and 1 MiB): `walk` (a bounded random walk: MM, and PACK in its digram mode), `alpha12` and `acgt` (12 skewed symbols and
 ACGT: PACK's digram and 2-bit modes) and `repeats` (corpus.repeats, text with copied spans of 1 KiB and more: LZP, and PACK), and
-`utf8` (utf_cases.utf8, code points of one byte and more, cut wherever a block ends: UTF). Of the
+`utf8` (utf_cases.utf8, code points of one byte and more, cut wherever a block ends: UTF), and `x86` (exe_cases.x86, instruction-like
+bytes with relative jumps: EXE from 4,096 up). EXE, TEXT and DNA are device stages; the pair matrix holds them at 16 KiB only, and TEXT's
+scratch and EXE's scan tiles depend on the block size, which this draw varies. Their 13 chains (EXE, EXE+ROLZX, EXE+PACK+ZRLT,
+EXE+BWT+RANK+ZRLT, MM+EXE, TEXT, TEXT+UTF+BWT+RANK+ZRLT, TEXT+PACK, TEXT+ROLZX, LZP+TEXT, EXE+TEXT, DNA, DNA+RLT) were run through
+knzlib.Ref alone over all twelve input kinds at the five block sizes, with NONE, HUFFMAN, ANS0 and TPAQ, 1 to 8 jobs and every checksum
+width: the reference read back every stream it wrote, so none of them was dropped. Of the
 older kinds MM also takes `runs`, LZP `mixed`, `runs` and `sparse`, PACK `text` and `small_alpha` at all four sizes.
 CM, TPAQ, TPAQX and FPAQ code one block per wave (CM at 2.85 us per byte): n is capped at 65,536 for CM, TPAQ and TPAQX
 and at 300,000 for FPAQ. The three binary coders get the output buffer of their second tier (knz_hip_encode_bound is their first).
 
 Left out in both: BWT+ZRLT and BWT+RLT+ZRLT, and chains that start with ZRLT / RLT / SRT on `rand`; LZ and LZX
 behind PACK, MM, UTF or ROLZX (the device refuses to write those chains by design; tests/test_gpu_pairs.py has it read the
-reference's); EXE, TEXT and the other host-side stages; block sizes above 1 MiB (the per-stage tests and tests/test_emu_pack.py hold
+reference's) and behind EXE, TEXT or DNA (the same refusal); TIMESTAMP, which has no name at the stream level; block sizes above 1 MiB (the per-stage tests and tests/test_emu_pack.py hold
 the larger blocks). Every ordered pair of the device transforms, which this draw only samples, is in tests/test_gpu_pairs.py."""
 import sys, os, time, importlib
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
-import knzlib, vectors, utf_cases
+import knzlib, vectors, utf_cases, exe_cases
 import numpy as np
 
 # chains whose even-indexed stages cannot expand into the caller's buffer (see DESIGN.md section 4)
@@ -34,9 +39,11 @@ KINDS = ["text", "mixed", "rand", "runs", "sparse", "small_alpha"]
 NEWER_CHAINS = ["BWTS", "BWTS+MTFT+ZRLT", "BWTS+SRT+ZRLT", "PACK", "PACK+BWT+MTFT+ZRLT", "PACK+RLT", "PACK+MM", "MM", "MM+PACK", "MM+RLT",
                 "MM+BWT+MTFT+ZRLT", "LZP", "LZP+BWT+RANK+ZRLT", "BWT+LZP", "LZP+LZX", "LZP+BWTS+MTFT+ZRLT", "PACK+LZP", "LZP+BWT+LZP",
                 "ROLZX", "PACK+ROLZX", "ROLZX+RLT", "MM+ROLZX", "ROLZX+BWT+RANK+ZRLT",
-                "UTF", "UTF+BWT+RANK+ZRLT", "LZP+UTF+BWT+LZP", "UTF+PACK+RLT", "UTF+ROLZX"]
+                "UTF", "UTF+BWT+RANK+ZRLT", "LZP+UTF+BWT+LZP", "UTF+PACK+RLT", "UTF+ROLZX",
+                "EXE", "EXE+ROLZX", "EXE+PACK+ZRLT", "EXE+BWT+RANK+ZRLT", "MM+EXE", "TEXT", "TEXT+UTF+BWT+RANK+ZRLT", "TEXT+PACK",
+                "TEXT+ROLZX", "LZP+TEXT", "EXE+TEXT", "DNA", "DNA+RLT"]
 NEWER_ENTS = ["RANGE", "CM", "TPAQ", "TPAQX"]
-NEWER_KINDS = ["walk", "alpha12", "acgt", "repeats", "utf8"]
+NEWER_KINDS = ["walk", "alpha12", "acgt", "repeats", "utf8", "x86"]
 BINARY_ENTS = ("CM", "TPAQ", "TPAQX")
 CM_MAX = 65536
 FPAQ_MAX = 300000
@@ -69,6 +76,8 @@ def gen(kind, n, rng):
         return knzlib.corpus().repeats(n, int(rng.integers(1, 1000)))
     if kind == "utf8":
         return utf_cases.utf8(n, int(rng.integers(1, 1000)))
+    if kind == "x86":
+        return bytes(exe_cases.x86(n, int(rng.integers(1, 1000))))
     return bytes((rng.integers(0, 3, n, dtype=np.uint8) * 37 + 65).astype(np.uint8))
 
 
@@ -120,7 +129,7 @@ def main():
     ctx = hipapi.Context(0)
     rng = np.random.default_rng(seed)
     chains, ents, kinds = (CHAINS, ENTS, KINDS) if mode == "first" else (CHAINS + NEWER_CHAINS, ENTS + NEWER_ENTS, KINDS + NEWER_KINDS)
-    t0 = time.time(); n_ok = [0, 0]; bad = 0; n_refbug = 0; n_skipped = 0
+    t0 = time.time(); n_ok = [0, 0]; bad = 0; n_refbug = 0; n_skipped = 0; per_chain = {}
     while time.time() - t0 < budget:
         chain, ent, bs, n, kind, jobs, ck = draw(rng, chains, ents, kinds)
         d = gen(kind, n, rng) if n else b""
@@ -160,10 +169,13 @@ def main():
         if ok and dok:
             n_ok[int(newer)] += 1
             n_refbug += int(refbug)
+            if chain in NEWER_CHAINS: per_chain[chain] = per_chain.get(chain, 0) + 1
         else:
             bad += 1
             print("MISMATCH chain=%s ent=%s bs=%d n=%d kind=%s jobs=%d ck=%d enc=%s dec=%s" % (chain, ent, bs, n, kind, jobs, ck, ok, dok), flush=True)
             open("/tmp/soak_fail_%d.bin" % bad, "wb").write(d)
+    if mode == "newer":
+        print("cases ok per newer chain:", ", ".join("%s %d" % (c, per_chain[c]) for c in NEWER_CHAINS if c in per_chain))
     print("soak seed", seed, "cases ok", sum(n_ok), "(first generation %d, newer stages %d; of which undecodable by the reference too: %d; skipped for want of the reference build: %d)"
           % (n_ok[0], n_ok[1], n_refbug, n_skipped), "bad", bad, "%.0f s" % (time.time() - t0))
     sys.exit(1 if bad else 0)
