@@ -170,10 +170,6 @@ static int count_transforms(uint64_t t, int* tok)
 }
 
 static bool host_stage_id(int t) { return t == KNZ_T_TEXT || t == KNZ_T_UTF; }
-static bool entropy_supported(int e) { return e == KNZ_E_NONE || e == KNZ_E_ANS0 || e == KNZ_E_ANS1 || e == KNZ_E_HUFFMAN || e == KNZ_E_FPAQ || e == KNZ_E_RANGE || e == KNZ_E_CM || e == KNZ_E_TPAQ || e == KNZ_E_TPAQX; }
-// the coders behind BinaryEntropyEncoder: two-tier staging, one chunk rule (binary_coder.hpp)
-static bool binary_coder(int e) { return e == KNZ_E_CM || e == KNZ_E_TPAQ || e == KNZ_E_TPAQX; }
-static bool tpaq_coder(int e) { return e == KNZ_E_TPAQ || e == KNZ_E_TPAQX; }
 
 }  // namespace knz
 
@@ -272,24 +268,6 @@ const char* knz_hip_last_error(knz_ctx* ctx)
     memcpy(copy, c->err, sizeof(copy));
     copy[sizeof(copy) - 1] = 0;
     return copy;
-}
-
-size_t knz_hip_encode_bound(const knz_params* p, size_t n)
-{
-    const size_t bs = (size_t)p->block_size;
-    const size_t nb = (n + bs - 1) / bs + 1;
-    // worst case: every symbol emits 16 bits (ANS) or 12 bits (Huffman) plus per-chunk headers
-    size_t bound = 2 * n + nb * 64 + ((n / ENT_CHUNK) + nb) * (HDR_BYTES + 32) + 4096;
-    // order-1 rANS writes 256 frequency tables per 4 MiB chunk (<= 3498 bits each), however small the block
-    if (p->entropy_type == KNZ_E_ANS1) bound += (n / ANS1_CHUNK + nb) * 256 * (size_t)HDR_BYTES;
-    // RANGE: a chunk of c bytes leaves at most c + c / 64 + 2 units of 28 bits and 60 bits of low (range.hip), behind its header
-    if (p->entropy_type == KNZ_E_RANGE) bound = 4 * (n + n / 64) + nb * 64 + (n / RANGE_CHUNK + nb) * (HDR_BYTES + 64) + 4096;
-    // CM: no bound is proved below the format's 32 bytes per byte, so this is the FIRST tier, what the encoder stages a block at
-    // (n + n / 8, cm.hip) plus var-ints and tails. An encode whose stream is longer fails with KNZ_ERR_WRITE_FILE and names the size;
-    // 32 * n on top of this value always holds it (include/knz_hip.h).
-    // (TPAQ and TPAQX: the same coder behind another predictor, the same two tiers)
-    if (binary_coder(p->entropy_type)) bound = (cm_tier1_div() ? n / cm_tier1_div() : n + n / 8) + nb * 64 + nb * (size_t)CM_MAX_CHUNKS * 16 + 4096;
-    return bound;
 }
 
 int knz_hip_set_profiling(knz_ctx* ctx, int enabled)
@@ -665,9 +643,196 @@ static int unsupported(Ctx* c, int t) { return fail(c, KNZ_ERR_INVALID_CODEC, "t
 
 static size_t scratch_u32(const XfDir& d, int nBlocks, u32 maxLen) { return d.scratchU32 ? d.scratchU32(nBlocks, maxLen) : 0; }
 
+// ------------------------------------------------------------------------------------------------
+// the device entropy coders
+// ------------------------------------------------------------------------------------------------
+// One batch for an encoder: the blocks behind the transforms (view), their ChunkDesc slots (block b owns maxChunks = chunksPerBlock *
+// slots per chunk of the nSlots at desc), and what the coders that write copy blocks themselves go by (origLen, copyThreshold).
+// rbsz is the "blockSize" of the stream's Context (per-stage calls pass it) and extra the row's, both TPAQ's.
+struct EcEnc {
+    Ctx* c; hipStream_t s; BlockView view; const u32* origLen; u32 copyThreshold; int nBlocks; u64 S;
+    int chunksPerBlock, maxChunks; size_t nSlots; ChunkDesc* desc; u32 rbsz; int extra;
+};
+
+// What an encoder leaves for the framing and for a second tier: the header base and stride launch_assemble reads, the device word that
+// counts the blocks which did not fit their staging (two-tier coders), TPAQ's tables
+struct EcStaged { u8* hdr = nullptr; u32 hdrStride = TMP_STRIDE; u32* marked = nullptr; void* tables = nullptr; };
+
+// One range of blocks for a decoder, on stream s with the workspaces of `lane` (lane_ws). maxChunks and nSlots count ENT_CHUNK chunks.
+struct EcDec {
+    Ctx* c; hipStream_t s; int lane; BitSrc src; DecBlock* blk; int nb; u64 S; int maxChunks; size_t nSlots;
+    int framing, bsVersion; u32 rbsz; int extra; u8* const* dst;
+};
+
+// What the drivers know of one entropy coder. Everything else about it lives in its launchers.
+struct EcInfo {
+    int id;
+    u32 entChunk;                // chunk length of the framing's arithmetic (launch_block_sum, launch_assemble)
+    u32 slots = 1;               // ChunkDesc slots per chunk, or
+    int (*slotsOf)(u64 S) = nullptr;                       // the same where it depends on the longest block
+    bool twoTier = false;        // bound() is a first tier: the coders behind BinaryEntropyEncoder (binary_coder.hpp)
+    int extra = 0;               // TPAQ / TPAQX
+    size_t (*bound)(size_t n, size_t nb) = nullptr;        // the row's term of knz_hip_encode_bound; nullptr: default_bound
+    int (*encode)(const EcEnc&, EcStaged*);                // takes the coder's workspaces and launches
+    int (*again)(const EcEnc&, const EcStaged&, CmBigAlloc, void* user) = nullptr;      // launch_cm_encode_again's contract (stages.hpp)
+    int (*decode)(const EcDec&);
+};
+
+// worst case: every symbol emits 16 bits (ANS) or 12 bits (Huffman) plus per-chunk headers
+static size_t default_bound(size_t n, size_t nb) { return 2 * n + nb * 64 + ((n / ENT_CHUNK) + nb) * (HDR_BYTES + 32) + 4096; }
+
+// CM: no bound is proved below the format's 32 bytes per byte, so this is the FIRST tier, what the encoder stages a block at
+// (n + n / 8, cm.hip) plus var-ints and tails. An encode whose stream is longer fails with KNZ_ERR_WRITE_FILE and names the size;
+// 32 * n on top of this value always holds it (include/knz_hip.h).
+// (TPAQ and TPAQX: the same coder behind another predictor, the same two tiers)
+static size_t binary_bound(size_t n, size_t nb) { return (cm_tier1_div() ? n / cm_tier1_div() : n + n / 8) + nb * 64 + nb * (size_t)CM_MAX_CHUNKS * 16 + 4096; }
+
+static int ans1_encode(const EcEnc& k, EcStaged* o)
+{
+    const size_t nCh = (size_t)k.nBlocks * k.chunksPerBlock;
+    Ans1EncWs aw;
+    aw.payStride = (2ull * std::min<u64>(k.S, ANS1_CHUNK) + 511) & ~255ull;
+    if (int r = ws_get(k.c, "ans1Hist", ans1_hist_bytes(nCh), (void**)&aw.hist, k.s)) return r;
+    if (int r = ws_get(k.c, "ans1EncTab", ans1_enctab_bytes(nCh), (void**)&aw.encTab, k.s)) return r;
+    if (int r = ws_get(k.c, "chunkTmp", (size_t)HDR_BYTES * k.nSlots, (void**)&aw.hdr, k.s)) return r;
+    if (int r = ws_get(k.c, "ans1Pay", (size_t)aw.payStride * nCh, (void**)&aw.pay, k.s)) return r;
+    o->hdr = aw.hdr;
+    o->hdrStride = HDR_BYTES;
+    launch_ans1_encode(k.s, k.view, k.nBlocks, k.chunksPerBlock, k.desc, aw);
+    return 0;
+}
+
+// (its metadata by its own 4 MiB chunks, not by the ENT_CHUNK slots)
+static int ans1_decode(const EcDec& k)
+{
+    const int chunksPerBlock = (int)((k.S + ANS1_CHUNK - 1) / ANS1_CHUNK);
+    const size_t nCh = (size_t)k.nb * chunksPerBlock;
+    Ans1DecWs aw;
+    if (int r = ws_get(k.c, lane_ws("ans1Meta", k.lane), ans1_meta_bytes(nCh), &aw.meta, k.s)) return r;
+    if (int r = ws_get(k.c, lane_ws("ans1SlotTab", k.lane), ans1_slottab_bytes(nCh), (void**)&aw.slotTab, k.s)) return r;
+    launch_ans1_decode(k.s, k.src, k.blk, k.nb, chunksPerBlock, aw, k.dst);
+    return 0;
+}
+
+static int fpaq_encode(const EcEnc& k, EcStaged* o)
+{
+    const u64 fStride = (4u << 20) + (4u << 17) + 256;      // FPAQEncoder.cpp:65-68 buffer size (+ slack)
+    u16* d_fprobs;
+    if (int r = ws_get(k.c, "chunkTmp", (size_t)fStride * k.nSlots, (void**)&o->hdr, k.s)) return r;
+    if (int r = ws_get(k.c, "fpaqProbs", fpaq_probs_bytes(k.nBlocks, k.S), (void**)&d_fprobs, k.s)) return r;
+    launch_fpaq_encode(k.s, k.view, k.origLen, k.copyThreshold, k.nBlocks, k.maxChunks, k.desc, o->hdr, fStride, d_fprobs, k.S);
+    return 0;
+}
+
+// The staging the binary coders share: block b at hdr + b * cm_stage_stride(S), and the control words, of which the first counts the
+// blocks that did not fit (read back with the total; they are coded again into 32 n + 16 bytes each, workspace taken only then)
+static int binary_staging(const EcEnc& k, EcStaged* o)
+{
+    if (int r = ws_get(k.c, "chunkTmp", (size_t)cm_stage_stride(k.S) * k.nBlocks, (void**)&o->hdr, k.s)) return r;
+    return ws_get(k.c, "cmCtrl", cm_ctrl_bytes(k.nBlocks), (void**)&o->marked, k.s);
+}
+
+static int cm_encode(const EcEnc& k, EcStaged* o)
+{
+    if (int r = binary_staging(k, o)) return r;
+    launch_cm_encode(k.s, k.view, k.origLen, k.copyThreshold, k.nBlocks, k.maxChunks, k.desc, o->hdr, cm_stage_stride(k.S), o->marked);
+    return 0;
+}
+
+// (the predictor's tables, for as many blocks as the budget lets run at once, tpaq.hip)
+static int tpaq_encode(const EcEnc& k, EcStaged* o)
+{
+    if (int r = binary_staging(k, o)) return r;
+    const size_t tb = tpaq_table_bytes(k.rbsz, (u32)k.S, k.extra);
+    if (int r = ws_get(k.c, "tpaqTables", tb * (size_t)tpaq_slice_blocks(tb, k.nBlocks), &o->tables, k.s)) return r;
+    launch_tpaq_encode(k.s, k.extra, k.view, k.origLen, k.copyThreshold, k.nBlocks, k.maxChunks, k.desc, o->hdr, cm_stage_stride(k.S), o->marked, o->tables, k.rbsz, (u32)k.S);
+    return 0;
+}
+
+static int tpaq_again(const EcEnc& k, const EcStaged& o, CmBigAlloc bigAlloc, void* user)
+{
+    return launch_tpaq_encode_again(k.s, k.extra, k.view, k.origLen, k.copyThreshold, k.nBlocks, k.maxChunks, k.desc, o.hdr, cm_stage_stride(k.S), o.marked, bigAlloc, user,
+                                    o.tables, k.rbsz, (u32)k.S);
+}
+
+// (tables per lane; a valid block is at most S bytes)
+static int tpaq_decode(const EcDec& k)
+{
+    const size_t tb = tpaq_table_bytes(k.rbsz, (u32)k.S, k.extra);
+    void* d_tables;
+    if (int r = ws_get(k.c, lane_ws("tpaqTables", k.lane), tb * (size_t)tpaq_slice_blocks(tb, k.nb), &d_tables, k.s)) return r;
+    launch_tpaq_decode(k.s, k.extra, k.src, k.blk, k.nb, k.dst, d_tables, k.rbsz, (u32)k.S);
+    return 0;
+}
+
+static const EcInfo EC[] = {
+    // (nothing is staged: the 64 bytes keep the one buffer under its name)
+    { .id = KNZ_E_NONE, .entChunk = ENT_CHUNK,
+      .encode = [](const EcEnc& k, EcStaged* o) {
+          if (int r = ws_get(k.c, "chunkTmp", 64, (void**)&o->hdr, k.s)) return r;
+          launch_none_encode(k.s, k.view, k.nBlocks, k.maxChunks, k.desc); return 0; },
+      .decode = [](const EcDec& k) { launch_none_decode(k.s, k.src, k.blk, k.nb, k.dst); return 0; } },
+    { .id = KNZ_E_ANS0, .entChunk = ENT_CHUNK,
+      .encode = [](const EcEnc& k, EcStaged* o) {
+          uint2* d_encTab;
+          if (int r = ws_get(k.c, "chunkTmp", (size_t)TMP_STRIDE * k.nSlots, (void**)&o->hdr, k.s)) return r;
+          if (int r = ws_get(k.c, "encTab", sizeof(uint2) * 256 * k.nSlots, (void**)&d_encTab, k.s)) return r;
+          launch_ans0_encode(k.s, k.view, k.nBlocks, k.maxChunks, k.desc, d_encTab, o->hdr); return 0; },
+      .decode = [](const EcDec& k) {
+          void* d_meta;
+          if (int r = ws_get(k.c, lane_ws("ansDecChunks", k.lane), ans0_dec_chunk_bytes() * k.nSlots, &d_meta, k.s)) return r;
+          launch_ans0_decode(k.s, k.src, k.blk, k.nb, k.maxChunks, d_meta, k.dst); return 0; } },
+    // order-1 rANS writes 256 frequency tables per 4 MiB chunk (<= 3498 bits each), however small the block
+    { .id = KNZ_E_ANS1, .entChunk = ANS1_CHUNK, .slots = ANS1_SLOTS,
+      .bound = [](size_t n, size_t nb) { return default_bound(n, nb) + (n / ANS1_CHUNK + nb) * 256 * (size_t)HDR_BYTES; },
+      .encode = ans1_encode, .decode = ans1_decode },
+    { .id = KNZ_E_HUFFMAN, .entChunk = ENT_CHUNK,
+      .encode = [](const EcEnc& k, EcStaged* o) {
+          if (int r = ws_get(k.c, "chunkTmp", (size_t)TMP_STRIDE * k.nSlots, (void**)&o->hdr, k.s)) return r;
+          launch_huffman_encode(k.s, k.view, k.nBlocks, k.maxChunks, k.desc, o->hdr); return 0; },
+      .decode = [](const EcDec& k) {
+          void* d_meta;
+          if (int r = ws_get(k.c, lane_ws("hufDecChunks", k.lane), huffman_dec_chunk_bytes() * k.nSlots, &d_meta, k.s)) return r;
+          launch_huffman_decode(k.s, k.src, k.blk, k.nb, k.maxChunks, d_meta, k.dst, k.bsVersion); return 0; } },
+    { .id = KNZ_E_FPAQ, .entChunk = 4u << 20,
+      .encode = fpaq_encode,
+      .decode = [](const EcDec& k) { launch_fpaq_decode(k.s, k.src, k.blk, k.nb, k.dst); return 0; } },
+    // RANGE: a chunk of c bytes leaves at most c + c / 64 + 2 units of 28 bits and 60 bits of low (range.hip), behind its header
+    { .id = KNZ_E_RANGE, .entChunk = RANGE_CHUNK,
+      .bound = [](size_t n, size_t nb) { return 4 * (n + n / 64) + nb * 64 + (n / RANGE_CHUNK + nb) * (HDR_BYTES + 64) + 4096; },
+      .encode = [](const EcEnc& k, EcStaged* o) {
+          u32* d_cumFreq;
+          if (int r = ws_get(k.c, "chunkTmp", (size_t)RANGE_STRIDE * k.nSlots, (void**)&o->hdr, k.s)) return r;
+          if (int r = ws_get(k.c, "rangeCumFreq", sizeof(u32) * 256 * k.nSlots, (void**)&d_cumFreq, k.s)) return r;
+          o->hdrStride = RANGE_STRIDE;
+          launch_range_encode(k.s, k.view, k.origLen, k.copyThreshold, k.nBlocks, k.maxChunks, k.desc, d_cumFreq, o->hdr); return 0; },
+      .decode = [](const EcDec& k) { launch_range_decode(k.s, k.src, k.blk, k.nb, k.dst, k.framing); return 0; } },
+    // (the binary coders: the chunk length depends on the block's own length, so a block is ONE chunk of the framing's arithmetic that
+    // owns cm_max_chunks(S) slots; the slots a block does not use stay zero and add nothing)
+    { .id = KNZ_E_CM, .entChunk = 0x80000000u, .slotsOf = cm_max_chunks, .twoTier = true, .bound = binary_bound,
+      .encode = cm_encode,
+      .again = [](const EcEnc& k, const EcStaged& o, CmBigAlloc bigAlloc, void* user) {
+          return launch_cm_encode_again(k.s, k.view, k.origLen, k.copyThreshold, k.nBlocks, k.maxChunks, k.desc, o.hdr, cm_stage_stride(k.S), o.marked, bigAlloc, user); },
+      .decode = [](const EcDec& k) { launch_cm_decode(k.s, k.src, k.blk, k.nb, k.dst); return 0; } },
+    { .id = KNZ_E_TPAQ, .entChunk = 0x80000000u, .slotsOf = cm_max_chunks, .twoTier = true, .extra = 0, .bound = binary_bound,
+      .encode = tpaq_encode, .again = tpaq_again, .decode = tpaq_decode },
+    { .id = KNZ_E_TPAQX, .entChunk = 0x80000000u, .slotsOf = cm_max_chunks, .twoTier = true, .extra = 1, .bound = binary_bound,
+      .encode = tpaq_encode, .again = tpaq_again, .decode = tpaq_decode },
+};
+
+static const EcInfo* ec_info(int id) { for (const EcInfo& e : EC) if (e.id == id) return &e; return nullptr; }
+
+size_t knz_hip_encode_bound(const knz_params* p, size_t n)
+{
+    const size_t bs = (size_t)p->block_size;
+    const size_t nb = (n + bs - 1) / bs + 1;
+    const EcInfo* ec = ec_info(p->entropy_type);
+    return ec && ec->bound ? ec->bound(n, nb) : default_bound(n, nb);
+}
+
 // A chain as a batch entry point takes it: the ids in stream order, and the table row of every stage the device runs (nullptr: NONE, or
-// one of the leading stages the host runs)
-struct Chain { int n = 0; int tok[8]; const XfInfo* xf[8]; };
+// one of the leading stages the host runs), and the entropy coder's row
+struct Chain { int n = 0; int tok[8]; const XfInfo* xf[8]; const EcInfo* ec = nullptr; };
 
 // The checks every batch entry point makes: the chain's ids (host stages first, device stages behind them), LZ / LZX behind PACK (encoding
 // only), the entropy id, the checksum width
@@ -686,7 +851,7 @@ static int parse_chain(Ctx* c, const knz_params* p, int nHosted, bool encoding, 
         if (typed && ch->xf[i]->ignoresType) return fail(c, KNZ_ERR_INVALID_CODEC, "LZ / LZX behind PACK is not implemented on device");
         typed |= ch->xf[i]->setsType;
     }
-    if (!entropy_supported(p->entropy_type)) return fail(c, KNZ_ERR_INVALID_CODEC, "entropy id %d not implemented on device", p->entropy_type);
+    if ((ch->ec = ec_info(p->entropy_type)) == nullptr) return fail(c, KNZ_ERR_INVALID_CODEC, "entropy id %d not implemented on device", p->entropy_type);
     if (p->checksum_bits != 0 && p->checksum_bits != 32 && p->checksum_bits != 64) return fail(c, KNZ_ERR_INVALID_PARAM, "checksum must be 0, 32 or 64");
     return 0;
 }
@@ -1011,71 +1176,18 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
     u8* d_skip = w.a.skip;
 
     // ---- entropy stage
-    const bool ans1 = (p->entropy_type == KNZ_E_ANS1);
-    const bool rangeCoder = (p->entropy_type == KNZ_E_RANGE);
-    const bool cm = binary_coder(p->entropy_type);
-    const bool tpaq = tpaq_coder(p->entropy_type);
-    const int tpaqExtra = p->entropy_type == KNZ_E_TPAQX ? 1 : 0;
-    const u32 tpaqRbsz = streamBlockSize ? streamBlockSize : bs;      // the "blockSize" of the stream's Context (per-stage calls pass it)
-    void* d_tpaqTables = nullptr;
-    // (CM: the chunk length depends on the block's own length, so a block is ONE chunk of the framing's arithmetic that owns
-    // cm_max_chunks(S) slots; the slots a block does not use stay zero and add nothing)
-    const u32 entChunk = (p->entropy_type == KNZ_E_FPAQ || ans1) ? (4u << 20) : rangeCoder ? RANGE_CHUNK : cm ? 0x80000000u : ENT_CHUNK;
-    const u32 slotMul = ans1 ? ANS1_SLOTS : cm ? (u32)cm_max_chunks(S) : 1u;
-    u32 hdrStride = rangeCoder ? RANGE_STRIDE : TMP_STRIDE;
+    const EcInfo* ec = ch.ec;
+    const u32 entChunk = ec->entChunk;
+    const u32 slotMul = ec->slotsOf ? (u32)ec->slotsOf(S) : ec->slots;
     const int chunksPerBlock = (int)((S + entChunk - 1) / entChunk);
     const int maxChunks = chunksPerBlock * (int)slotMul;
     const size_t nSlots = (size_t)nBlocks * maxChunks;
-    ChunkDesc* d_desc; u8* d_tmp; uint2* d_encTab;
-    u32* d_cmMarked = nullptr;
+    ChunkDesc* d_desc;
     if (int r = ws_get(c, "desc", sizeof(ChunkDesc) * nSlots, (void**)&d_desc, s)) return r;
-    if (p->entropy_type == KNZ_E_ANS0) {
-        if (int r = ws_get(c, "chunkTmp", (size_t)TMP_STRIDE * nSlots, (void**)&d_tmp, s)) return r;
-        if (int r = ws_get(c, "encTab", sizeof(uint2) * 256 * nSlots, (void**)&d_encTab, s)) return r;
-        launch_ans0_encode(s, view, nBlocks, maxChunks, d_desc, d_encTab, d_tmp);
-    } else if (ans1) {
-        const size_t nCh = (size_t)nBlocks * chunksPerBlock;
-        Ans1EncWs aw;
-        aw.payStride = (2ull * std::min<u64>(S, ANS1_CHUNK) + 511) & ~255ull;
-        if (int r = ws_get(c, "ans1Hist", ans1_hist_bytes(nCh), (void**)&aw.hist, s)) return r;
-        if (int r = ws_get(c, "ans1EncTab", ans1_enctab_bytes(nCh), (void**)&aw.encTab, s)) return r;
-        if (int r = ws_get(c, "chunkTmp", (size_t)HDR_BYTES * nSlots, (void**)&d_tmp, s)) return r;
-        if (int r = ws_get(c, "ans1Pay", (size_t)aw.payStride * nCh, (void**)&aw.pay, s)) return r;
-        aw.hdr = d_tmp;
-        hdrStride = HDR_BYTES;
-        launch_ans1_encode(s, view, nBlocks, chunksPerBlock, d_desc, aw);
-    } else if (p->entropy_type == KNZ_E_HUFFMAN) {
-        if (int r = ws_get(c, "chunkTmp", (size_t)TMP_STRIDE * nSlots, (void**)&d_tmp, s)) return r;
-        launch_huffman_encode(s, view, nBlocks, maxChunks, d_desc, d_tmp);
-    } else if (p->entropy_type == KNZ_E_FPAQ) {
-        const u64 fStride = (4u << 20) + (4u << 17) + 256;      // FPAQEncoder.cpp:65-68 buffer size (+ slack)
-        if (int r = ws_get(c, "chunkTmp", (size_t)fStride * nSlots, (void**)&d_tmp, s)) return r;
-        u16* d_fprobs;
-        if (int r = ws_get(c, "fpaqProbs", fpaq_probs_bytes(nBlocks, S), (void**)&d_fprobs, s)) return r;
-        launch_fpaq_encode(s, view, d_origLen, framing ? 15u : 0u, nBlocks, maxChunks, d_desc, d_tmp, fStride, d_fprobs, S);
-    } else if (rangeCoder) {
-        u32* d_cumFreq;
-        if (int r = ws_get(c, "chunkTmp", (size_t)RANGE_STRIDE * nSlots, (void**)&d_tmp, s)) return r;
-        if (int r = ws_get(c, "rangeCumFreq", sizeof(u32) * 256 * nSlots, (void**)&d_cumFreq, s)) return r;
-        launch_range_encode(s, view, d_origLen, framing ? 15u : 0u, nBlocks, maxChunks, d_desc, d_cumFreq, d_tmp);
-    } else if (cm) {
-        const u64 cStride = cm_stage_stride(S);
-        void* d_cmCtrl;
-        if (int r = ws_get(c, "chunkTmp", (size_t)cStride * nBlocks, (void**)&d_tmp, s)) return r;
-        if (int r = ws_get(c, "cmCtrl", cm_ctrl_bytes(nBlocks), &d_cmCtrl, s)) return r;
-        // blocks that did not fit their staging are coded again into 32 n + 16 bytes each: workspace taken only then
-        if (tpaq) {
-            // the predictor's tables, for as many blocks as the budget lets run at once (tpaq.hip)
-            const size_t tb = tpaq_table_bytes(tpaqRbsz, (u32)S, tpaqExtra);
-            if (int r = ws_get(c, "tpaqTables", tb * (size_t)tpaq_slice_blocks(tb, nBlocks), &d_tpaqTables, s)) return r;
-            launch_tpaq_encode(s, tpaqExtra, view, d_origLen, framing ? 15u : 0u, nBlocks, maxChunks, d_desc, d_tmp, cStride, d_cmCtrl, d_tpaqTables, tpaqRbsz, (u32)S);
-        } else
-        launch_cm_encode(s, view, d_origLen, framing ? 15u : 0u, nBlocks, maxChunks, d_desc, d_tmp, cStride, d_cmCtrl);
-        d_cmMarked = static_cast<u32*>(d_cmCtrl);                 // how many blocks did not fit: read back with the total below
-    } else {
-        if (int r = ws_get(c, "chunkTmp", 64, (void**)&d_tmp, s)) return r;
-        launch_none_encode(s, view, nBlocks, maxChunks, d_desc);
-    }
+    const EcEnc enc = { c, s, view, d_origLen, framing ? 15u : 0u, nBlocks, S, chunksPerBlock, maxChunks, nSlots, d_desc,
+                        streamBlockSize ? streamBlockSize : bs, ec->extra };
+    EcStaged staged;
+    if (int r = ec->encode(enc, &staged)) return r;
 
     // ---- framing + assembly
     // (many streams: the blocks' places restart at every stream, and d_total holds the BYTES of output in use)
@@ -1090,11 +1202,11 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
     u32* h_marked = reinterpret_cast<u32*>(h_total + 1);
     *h_marked = 0;
     HIPCHK(c, hipMemcpyAsync(h_total, d_total, sizeof(u64), hipMemcpyDeviceToHost, s));
-    if (d_cmMarked) HIPCHK(c, hipMemcpyAsync(h_marked, d_cmMarked, sizeof(u32), hipMemcpyDeviceToHost, s));
+    if (staged.marked) HIPCHK(c, hipMemcpyAsync(h_marked, staged.marked, sizeof(u32), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     if (*h_marked) {
-        // CM, the rare path: blocks that did not fit their staging are coded again into 32 n + 16 bytes each (workspace taken only now),
-        // then the lengths are summed again
+        // the two-tier coders, the rare path: blocks that did not fit their staging are coded again into 32 n + 16 bytes each (workspace
+        // taken only now), then the lengths are summed again
         struct Big { Ctx* c; hipStream_t s; int rc; } big = { c, s, 0 };
         auto bigAlloc = [](void* user, size_t bytes) -> void* {
             Big* g = static_cast<Big*>(user);
@@ -1102,9 +1214,7 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
             g->rc = ws_get(g->c, "cmBig", bytes, &m, g->s);
             return g->rc ? nullptr : m;
         };
-        const int r = tpaq ? launch_tpaq_encode_again(s, tpaqExtra, view, d_origLen, framing ? 15u : 0u, nBlocks, maxChunks, d_desc, d_tmp, cm_stage_stride(S), d_cmMarked, bigAlloc, &big,
-                                                      d_tpaqTables, tpaqRbsz, (u32)S)
-                           : launch_cm_encode_again(s, view, d_origLen, framing ? 15u : 0u, nBlocks, maxChunks, d_desc, d_tmp, cm_stage_stride(S), d_cmMarked, bigAlloc, &big);
+        const int r = ec->again(enc, staged, bigAlloc, &big);
         if (r == -2) return big.rc;                               // (ws_get has said why)
         if (r < 0) return fail(c, -1, "binary coder: encode failed: %s", hipGetErrorString(hipGetLastError()));
         launch_block_sum(s, d_desc, d_info, d_blockLen, nBlocks, maxChunks, entChunk, slotMul);
@@ -1114,7 +1224,7 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
     }
     if (tab) {
         if (int r = streams_place(c, s, tab, d_out, outCap, *h_total)) return r;
-        launch_assemble(s, d_desc, d_info, d_blockLen, d_origLen, d_skip, d_sums, d_tmp, nBlocks, maxChunks, entChunk, slotMul, hdrStride, fp,
+        launch_assemble(s, d_desc, d_info, d_blockLen, d_origLen, d_skip, d_sums, staged.hdr, nBlocks, maxChunks, entChunk, slotMul, staged.hdrStride, fp,
                         reinterpret_cast<u32*>(d_out));
         if (outBits) *outBits = 8 * *h_total;
         return streams_results(c, s, tab);
@@ -1132,7 +1242,7 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
         HIPCHK(c, hipMemcpyAsync(d_pro, prologue, (prologueBits + 7) / 8, hipMemcpyHostToDevice, s));
         launch_put_prologue(s, reinterpret_cast<u32*>(d_out), d_pro, prologueBits);
     }
-    launch_assemble(s, d_desc, d_info, d_blockLen, d_origLen, d_skip, d_sums, d_tmp, nBlocks, maxChunks, entChunk, slotMul, hdrStride, fp,
+    launch_assemble(s, d_desc, d_info, d_blockLen, d_origLen, d_skip, d_sums, staged.hdr, nBlocks, maxChunks, entChunk, slotMul, staged.hdrStride, fp,
                     reinterpret_cast<u32*>(d_out));
     HIPCHK(c, hipGetLastError());
     if (outBits) {
@@ -1305,38 +1415,8 @@ static int decode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, uint64_
         // the room in the caller's buffer is enforced where the last inverse stage gets its capacity
         launch_check_prelen(sp, blk, nb, realStages ? maxPre : unit, realStages ? ~0ull : room, outStride, roomT);
         launch_seq_inv_entropy_dst(sp, w.a, blk, nb, out, outStride, w.A, S, w.d_entDst, realMask, unit, room, offT, roomT);
-        if (p->entropy_type == KNZ_E_ANS0) {
-            void* d_meta;
-            if (int r = ws_get(c, lane_ws("ansDecChunks", lane), ans0_dec_chunk_bytes() * nSlots, &d_meta, sp)) return r;
-            launch_ans0_decode(sp, src, blk, nb, maxChunks, d_meta, w.d_entDst);
-        } else if (p->entropy_type == KNZ_E_ANS1) {
-            const int chunksPerBlock = (int)((S + ANS1_CHUNK - 1) / ANS1_CHUNK);
-            const size_t nCh = (size_t)nb * chunksPerBlock;
-            Ans1DecWs aw;
-            if (int r = ws_get(c, lane_ws("ans1Meta", lane), ans1_meta_bytes(nCh), &aw.meta, sp)) return r;
-            if (int r = ws_get(c, lane_ws("ans1SlotTab", lane), ans1_slottab_bytes(nCh), (void**)&aw.slotTab, sp)) return r;
-            launch_ans1_decode(sp, src, blk, nb, chunksPerBlock, aw, w.d_entDst);
-        } else if (p->entropy_type == KNZ_E_HUFFMAN) {
-            void* d_meta;
-            if (int r = ws_get(c, lane_ws("hufDecChunks", lane), huffman_dec_chunk_bytes() * nSlots, &d_meta, sp)) return r;
-            launch_huffman_decode(sp, src, blk, nb, maxChunks, d_meta, w.d_entDst, bsVersion);
-        } else if (p->entropy_type == KNZ_E_FPAQ) {
-            launch_fpaq_decode(sp, src, blk, nb, w.d_entDst);
-        } else if (p->entropy_type == KNZ_E_RANGE) {
-            launch_range_decode(sp, src, blk, nb, w.d_entDst, framing);
-        } else if (p->entropy_type == KNZ_E_CM) {
-            launch_cm_decode(sp, src, blk, nb, w.d_entDst);
-        } else if (tpaq_coder(p->entropy_type)) {
-            // the predictor's tables, per lane, for as many blocks as the budget lets run at once; a valid block is at most S bytes
-            const int extra = p->entropy_type == KNZ_E_TPAQX ? 1 : 0;
-            const u32 rbsz = streamBlockSize ? streamBlockSize : bs;
-            const size_t tb = tpaq_table_bytes(rbsz, (u32)S, extra);
-            void* d_tables;
-            if (int r = ws_get(c, lane_ws("tpaqTables", lane), tb * (size_t)tpaq_slice_blocks(tb, nb), &d_tables, sp)) return r;
-            launch_tpaq_decode(sp, extra, src, blk, nb, w.d_entDst, d_tables, rbsz, (u32)S);
-        } else {
-            launch_none_decode(sp, src, blk, nb, w.d_entDst);
-        }
+        if (int r = ch.ec->decode({ c, sp, lane, src, blk, nb, S, maxChunks, nSlots, framing, bsVersion, streamBlockSize ? streamBlockSize : bs,
+                                    ch.ec->extra, w.d_entDst })) return r;
         // inverse transforms, last stage first (TransformSequence.hpp:197-224)
         if (realStages) {
             const u32 capFinal = framing ? std::min(bs, unit) : (u32)p->jobs;           // per-stage API passes its capacity in p->jobs
@@ -1629,7 +1709,7 @@ int knz_hip_entropy_encode_bs(knz_ctx* ctx, int entropy_type, uint32_t stream_bl
     HIPCHK(c, hipMemcpyAsync(d_in, in, n, hipMemcpyHostToDevice, c->stream));
     u64 bits = 0;
     int r = encode_impl(c, &p, d_in, n, nullptr, 0, 0, 0, 0, d_out, cap, &bits, nullptr, stream_block_size);
-    if (r == KNZ_ERR_WRITE_FILE && binary_coder(entropy_type)) {
+    if (r == KNZ_ERR_WRITE_FILE && ec_info(entropy_type)->twoTier) {         // (an id without a row has failed in parse_chain, with another code)
         // the bound of the binary coders is their first tier (knz_hip_encode_bound): the second holds whatever the format can write
         const size_t cap2 = cap + 32 * (size_t)n;
         if (int r2 = ws_get(c, "stageOut", cap2, (void**)&d_out, c->stream)) return r2;

@@ -183,6 +183,8 @@ CHAINS = [
     ("PACK", "RANGE", 0, "typed"),                            # the data type per block
     ("LZP", "CM", 0, "small"),
     ("RLT", "TPAQ", 0, "few"),
+    ("RLT", "ANS1", 32, "small"),                             # metadata per decode lane
+    ("RLT", "TPAQX", 0, "few"),                               # tables per decode lane
 ]
 
 
