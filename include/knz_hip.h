@@ -210,6 +210,26 @@ KNZ_API int knz_hip_decode_streams(knz_ctx* ctx, const knz_params* p, const uint
 typedef struct { uint64_t src; uint64_t dst; uint64_t len; } knz_copy;   /* device addresses, bytes */
 KNZ_API int knz_hip_copy_many(knz_ctx* ctx, const knz_copy* copies /* host */, size_t n);
 
+/*
+ * n device buffers split into byte planes, or joined from them, in ONE kernel launch. An entry of len bytes holds m = len / elem
+ * elements of elem bytes; split writes dst[k * m + i] = src[i * elem + k] (byte k of every element to plane k), join writes
+ * dst[i * elem + k] = src[k * m + i]; with elem == 1 both are a plain copy, so one call can carry ordinary copies beside its planes.
+ * What gathers tensors of 2-, 4- and 8-byte elements for knz_hip_encode_streams with their compressible bytes side by side, at the
+ * price of the copy that knz_hip_copy_many would make anyway. The element width is not stored anywhere: the caller keeps it.
+ *
+ * src and dst are absolute device addresses of any alignment; len may be 0. Nothing outside [src, src + len) is read and nothing
+ * outside [dst, dst + len) is written. The result is undefined where an entry's dst range overlaps its own src range or any other
+ * range of the same call (sources may coincide); this is not checked.
+ *
+ * Staging, ordering and limits are knz_hip_copy_many's: enqueued on the context's stream without waiting, `entries` reusable as soon
+ * as the call returns, n == 0 a successful no-op; at most KNZ_COPY_MAX_COPIES entries, every len below 2^32, fewer than 2^31 tiles
+ * of 16 KiB in all (an entry has len / 16384 rounded up). elem has to be 1, 2, 4 or 8 and to divide len, reserved has to be 0. A call
+ * that breaks one of these fails as a whole with KNZ_ERR_INVALID_PARAM, names the entry, and launches nothing.
+ */
+typedef struct { uint64_t src; uint64_t dst; uint64_t len; uint32_t elem; uint32_t reserved; } knz_plane_copy;
+KNZ_API int knz_hip_split_many(knz_ctx* ctx, const knz_plane_copy* entries /* host */, size_t n);
+KNZ_API int knz_hip_join_many(knz_ctx* ctx, const knz_plane_copy* entries /* host */, size_t n);
+
 /* ---- per-stage entry points (host buffers in/out; used by the host mirror classes and tests) ---- */
 
 /* EntropyEncoder::encode for one buffer (entropy/EntropyEncoder.hpp:30-37). out receives the bits

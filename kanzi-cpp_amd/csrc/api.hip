@@ -1641,6 +1641,31 @@ int knz_hip_decode_streams(knz_ctx* ctx, const knz_params* p, const uint8_t* d_i
 // ------------------------------------------------------------------------------------------------
 // many device-to-device copies in one launch (copy_many.hip)
 // ------------------------------------------------------------------------------------------------
+// the pinned staging of a call's table with room for `bytes`, free of the upload of the call before (whose kernel may still run)
+static int tab_stage(Ctx* c, size_t bytes, u8** h)
+{
+    if (c->tabStageEv == nullptr) HIPCHK(c, hipEventCreateWithFlags(&c->tabStageEv, hipEventDisableTiming));
+    HIPCHK(c, hipEventSynchronize(c->tabStageEv));
+    if (c->tabStageCap < bytes) {
+        if (c->tabStage) HIPCHK(c, hipHostFree(c->tabStage));
+        c->tabStage = nullptr; c->tabStageCap = 0;
+        const size_t want = bytes + (bytes >> 3) + 4096;
+        HIPCHK(c, hipHostMalloc(&c->tabStage, want, hipHostMallocDefault));
+        c->tabStageCap = want;
+    }
+    *h = reinterpret_cast<u8*>(c->tabStage);
+    return 0;
+}
+
+// the staged table to the workspace `name` on the stream; the staging is free again once tabStageEv has passed
+static int tab_upload(Ctx* c, const char* name, const u8* h, size_t bytes, hipStream_t s, u8** d_tab)
+{
+    if (int r = ws_get(c, name, bytes, (void**)d_tab, s)) return r;
+    HIPCHK(c, hipMemcpyAsync(*d_tab, h, bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipEventRecord(c->tabStageEv, s));
+    return 0;
+}
+
 int knz_hip_copy_many(knz_ctx* ctx, const knz_copy* copies, size_t n)
 {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
@@ -1660,29 +1685,62 @@ int knz_hip_copy_many(knz_ctx* ctx, const knz_copy* copies, size_t n)
     hipStream_t s = c->stream;
     // one upload: the copies | the exclusive prefix of their tile counts
     const size_t oFirst = sizeof(knz_copy) * n, bytes = oFirst + 4 * (n + 1);
-    if (c->tabStageEv == nullptr) HIPCHK(c, hipEventCreateWithFlags(&c->tabStageEv, hipEventDisableTiming));
-    HIPCHK(c, hipEventSynchronize(c->tabStageEv));          // the upload of the call before has left the staging (its kernel may still run)
-    if (c->tabStageCap < bytes) {
-        if (c->tabStage) HIPCHK(c, hipHostFree(c->tabStage));
-        c->tabStage = nullptr; c->tabStageCap = 0;
-        const size_t want = bytes + (bytes >> 3) + 4096;
-        HIPCHK(c, hipHostMalloc(&c->tabStage, want, hipHostMallocDefault));
-        c->tabStageCap = want;
-    }
-    u8* h = reinterpret_cast<u8*>(c->tabStage);
+    u8* h;
+    if (int r = tab_stage(c, bytes, &h)) return r;
     memcpy(h, copies, oFirst);
     u32* first = reinterpret_cast<u32*>(h + oFirst);
     u32 at = 0;
     for (size_t i = 0; i < n; i++) { first[i] = at; at += (u32)copy_many_tiles(copies[i].dst, copies[i].len); }
     first[n] = at;
     u8* d_tab;
-    if (int r = ws_get(c, "copyTab", bytes, (void**)&d_tab, s)) return r;
-    HIPCHK(c, hipMemcpyAsync(d_tab, h, bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipEventRecord(c->tabStageEv, s));
+    if (int r = tab_upload(c, "copyTab", h, bytes, s, &d_tab)) return r;
     launch_copy_many(s, reinterpret_cast<const knz_copy*>(d_tab), reinterpret_cast<const u32*>(d_tab + oFirst), (u32)n, at);
     HIPCHK(c, hipGetLastError());
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------
+// many buffers split into byte planes, or joined from them, in one launch (planes.hip)
+// ------------------------------------------------------------------------------------------------
+static int planes_many(knz_ctx* ctx, const knz_plane_copy* entries, size_t n, bool split)
+{
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    CTX_LOCK(c);
+    ProfInstall pi_(c);
+    if (n == 0) return 0;
+    if (entries == nullptr) return fail(c, KNZ_ERR_INVALID_PARAM, "no entries");
+    if (n > (size_t)KNZ_COPY_MAX_COPIES) return fail(c, KNZ_ERR_INVALID_PARAM, "too many entries in one call (%zu, at most %d)", n, KNZ_COPY_MAX_COPIES);
+    u64 tiles = 0;
+    for (size_t i = 0; i < n; i++) {
+        const knz_plane_copy& e = entries[i];
+        if (e.elem != 1 && e.elem != 2 && e.elem != 4 && e.elem != 8) return fail(c, KNZ_ERR_INVALID_PARAM, "entry %zu: elements of %u bytes, 1, 2, 4 and 8 are taken", i, e.elem);
+        if (e.reserved != 0) return fail(c, KNZ_ERR_INVALID_PARAM, "entry %zu: reserved is %u, not 0", i, e.reserved);
+        if (e.len >> 32) return fail(c, KNZ_ERR_INVALID_PARAM, "entry %zu: %llu bytes, an entry takes fewer than 2^32", i, (unsigned long long)e.len);
+        if (e.len % e.elem) return fail(c, KNZ_ERR_INVALID_PARAM, "entry %zu: %llu bytes are no multiple of its %u-byte elements", i, (unsigned long long)e.len, e.elem);
+        tiles += planes_tiles(e.len);
+    }
+    if (tiles >= (1ull << 31)) return fail(c, KNZ_ERR_INVALID_PARAM, "%llu tiles of %u bytes in one call, fewer than 2^31 are taken", (unsigned long long)tiles, planes_tile_bytes());
+    if (tiles == 0) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    // one upload: the entries | the exclusive prefix of their tile counts
+    const size_t oFirst = sizeof(knz_plane_copy) * n, bytes = oFirst + 4 * (n + 1);
+    u8* h;
+    if (int r = tab_stage(c, bytes, &h)) return r;
+    memcpy(h, entries, oFirst);
+    u32* first = reinterpret_cast<u32*>(h + oFirst);
+    u32 at = 0;
+    for (size_t i = 0; i < n; i++) { first[i] = at; at += (u32)planes_tiles(entries[i].len); }
+    first[n] = at;
+    u8* d_tab;
+    if (int r = tab_upload(c, "copyTab", h, bytes, s, &d_tab)) return r;
+    (split ? launch_split_many : launch_join_many)(s, reinterpret_cast<const knz_plane_copy*>(d_tab), reinterpret_cast<const u32*>(d_tab + oFirst), (u32)n, at);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+int knz_hip_split_many(knz_ctx* ctx, const knz_plane_copy* entries, size_t n) { return planes_many(ctx, entries, n, true); }
+int knz_hip_join_many(knz_ctx* ctx, const knz_plane_copy* entries, size_t n) { return planes_many(ctx, entries, n, false); }
 
 // ------------------------------------------------------------------------------------------------
 // per-stage (host buffers)

@@ -275,6 +275,13 @@ u64 copy_many_tiles(u64 dst, u64 len);
 u32 copy_many_tile_bytes();
 void launch_copy_many(hipStream_t s, const knz_copy* copies, const u32* tileFirst, u32 n, u32 nTiles);
 
+// planes.hip : n buffers split into byte planes, or joined from them, in one launch; tileFirst = the exclusive prefix of planes_tiles
+// over the entries (n + 1 words)
+u64 planes_tiles(u64 len);
+u32 planes_tile_bytes();
+void launch_split_many(hipStream_t s, const knz_plane_copy* entries, const u32* tileFirst, u32 n, u32 nTiles);
+void launch_join_many(hipStream_t s, const knz_plane_copy* entries, const u32* tileFirst, u32 n, u32 nTiles);
+
 // huffman.hip
 void launch_huffman_encode(hipStream_t s, BlockView view, int nBlocks, int maxChunks, ChunkDesc* desc, u8* tmp);
 void launch_huffman_decode(hipStream_t s, BitSrc src, DecBlock* blocks, int nBlocks, int maxChunks, void* chunkMeta, u8* const* outPtr, int bsVersion = 6);

@@ -26,6 +26,7 @@ SYMBOLS = [
     "knz_hip_transform_forward_bs", "knz_hip_transform_inverse_bs",
     "knz_hip_prims_info", "knz_hip_prims_scan", "knz_hip_prims_sort",
     "knz_hip_encode_streams_bound", "knz_hip_encode_streams", "knz_hip_decode_streams", "knz_hip_copy_many",
+    "knz_hip_split_many", "knz_hip_join_many",
 ]
 STREAMS_MAX_ITEMS = STREAMS_MAX_BLOCKS = 65536      # KNZ_STREAMS_MAX_ITEMS / _BLOCKS of include/knz_hip.h
 BATCH_MAX_BYTES = 0x7FFFFFFF                        # input of one encode call, decoded bytes of one decode call
@@ -47,6 +48,11 @@ class Item(C.Structure):
 class Copy(C.Structure):
     """knz_copy: one copy of a knz_hip_copy_many call (device addresses, bytes)."""
     _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("len", C.c_uint64)]
+
+
+class PlaneCopy(C.Structure):
+    """knz_plane_copy: one entry of a knz_hip_split_many / knz_hip_join_many call (device addresses, bytes, bytes per element)."""
+    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("len", C.c_uint64), ("elem", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class KernelTime(C.Structure):
@@ -132,6 +138,8 @@ def lib():
         L.knz_hip_encode_streams.argtypes = [vp, C.POINTER(Params), u8p, C.POINTER(Item), sz, C.c_char_p, C.c_int, u8p, sz, C.POINTER(C.c_uint64)]
         L.knz_hip_decode_streams.argtypes = [vp, C.POINTER(Params), u8p, C.POINTER(Item), sz, u8p, sz]
         L.knz_hip_copy_many.argtypes = [vp, C.POINTER(Copy), sz]
+        L.knz_hip_split_many.argtypes = [vp, C.POINTER(PlaneCopy), sz]
+        L.knz_hip_join_many.argtypes = [vp, C.POINTER(PlaneCopy), sz]
         _lib = L
     return _lib
 
@@ -233,6 +241,27 @@ class Context:
             flat = [v for c in copies for v in c]
             copies = (Copy * (len(flat) // 3)).from_buffer_copy((C.c_uint64 * len(flat))(*flat)) if flat else (Copy * 0)()
         self._chk(self.L.knz_hip_copy_many(self.h, copies, len(copies)))
+
+    @staticmethod
+    def _plane_entries(entries):
+        if isinstance(entries, C.Array):
+            return entries
+        arr = (PlaneCopy * len(entries))()
+        for e, (src, dst, n, elem) in zip(arr, entries):
+            e.src, e.dst, e.len, e.elem = src, dst, n, elem
+        return arr
+
+    def split_many(self, entries):
+        """entries: an array of PlaneCopy, or a sequence of (src, dst, len, elem): every entry's len / elem elements of elem bytes split into
+        elem byte planes, dst[k * (len / elem) + i] = src[i * elem + k], all entries in one kernel launch on the context's stream (elem 1:
+        a plain copy). Returns without waiting for it."""
+        entries = self._plane_entries(entries)
+        self._chk(self.L.knz_hip_split_many(self.h, entries, len(entries)))
+
+    def join_many(self, entries):
+        """The way back of split_many: dst[i * elem + k] = src[k * (len / elem) + i]."""
+        entries = self._plane_entries(entries)
+        self._chk(self.L.knz_hip_join_many(self.h, entries, len(entries)))
 
     # ---- per-stage API on host buffers
     def entropy_encode(self, entropy, data, stream_block_size=0):

@@ -343,15 +343,64 @@ def decompress_many(streams, jobs=1, device=0):
         ctx.close()
 
 
+# ---- byte planes: byte k of every element next to byte k of the others, so that an order-0 coder sees the compressible bytes of
+# floating-point data (sign and exponent) apart from the incompressible ones (mantissa). No transform of the format: the stream codes the
+# split bytes and does not store the width, which the caller keeps with the dtype and shape.
+PLANE_WIDTHS = (1, 2, 4, 8)
+
+
+def _as_elements(data, width):
+    import numpy as np
+    if width not in PLANE_WIDTHS:
+        raise ValueError("width %r: elements of 1, 2, 4 and 8 bytes are taken" % (width,))
+    a = np.frombuffer(data, dtype=np.uint8)
+    if a.size % width:
+        raise ValueError("%d bytes are no multiple of the width %d" % (a.size, width))
+    return a
+
+
+def split_bytes(data, width):
+    """data as len(data) / width elements of width bytes: plane 0 (byte 0 of every element), then plane 1, ... as bytes. What
+    TensorCodec.compress(planes=...) codes, done on the host with numpy: for compress_many, and the specification of the device kernel."""
+    return _as_elements(data, width).reshape(-1, width).T.tobytes()
+
+
+def join_bytes(data, width):
+    """The way back of split_bytes: what turns the output of the reference tool for a stream of planes into the tensor's bytes."""
+    return _as_elements(data, width).reshape(width, -1).T.tobytes()
+
+
 # ---- the same for tensors that are on the device already: nothing payload-sized crosses the bus
-HEADER_PEEK = 32                # bytes of every stream that decompress reads on the host: the longest header framing.make_header writes
+HEADER_PEEK = 32               # bytes of every stream that decompress reads on the host: the longest header framing.make_header writes
                                 # is 208 bits (32 + 4 + 2 + 5 + 48 + 28 + 2 + 48 + 15 + 24), and an empty stream's end marker follows a
                                 # header without size (160 bits) inside them
 
 
-def _check_tensors(tensors, device):
+def _plane_widths(tensors, planes):
+    """The `planes` argument of TensorCodec.compress as one width per tensor (None: no planes), with its ValueErrors, by index."""
+    if planes is None or planes is False:
+        return None
+    if planes is True:
+        widths = [t.element_size() // 2 if t.is_complex() else t.element_size() for t in tensors]
+        for i, w in enumerate(widths):
+            if w > 8:
+                raise ValueError("tensor %d: %s has numbers of %d bytes, planes of at most 8 are taken" % (i, tensors[i].dtype, w))
+        return widths
+    widths = list(planes)
+    if len(widths) != len(tensors):
+        raise ValueError("planes holds %d widths for %d tensors" % (len(widths), len(tensors)))
+    for i, (t, w) in enumerate(zip(tensors, widths)):
+        if isinstance(w, bool) or w not in PLANE_WIDTHS:
+            raise ValueError("tensor %d: width %r, planes of 1, 2, 4 and 8 bytes are taken" % (i, w))
+        if t.numel() * t.element_size() % w:
+            raise ValueError("tensor %d: %d bytes are no multiple of the width %d" % (i, t.numel() * t.element_size(), w))
+    return [int(w) for w in widths]
+
+
+def _check_tensors(tensors, device, planes=False):
     """The ValueErrors of TensorCodec.compress, by index, before any device work: what is no tensor first, then what is not contiguous,
-    then what is in the wrong place. device None leaves out the comparison of devices."""
+    then what `planes` cannot mean for these tensors, then what is in the wrong place. device None leaves out the comparison of devices.
+    Returns the plane widths (_plane_widths)."""
     import torch
     for i, t in enumerate(tensors):
         if not isinstance(t, torch.Tensor):
@@ -359,11 +408,13 @@ def _check_tensors(tensors, device):
     for i, t in enumerate(tensors):
         if not t.is_contiguous():
             raise ValueError("tensor %d is not contiguous (its bytes in memory order are asked for; call .contiguous() first)" % i)
+    widths = _plane_widths(tensors, planes)
     for i, t in enumerate(tensors):
         if t.device.type != "cuda":
             raise ValueError("tensor %d is on %s, not on the GPU (compress_many takes host bytes)" % (i, t.device))
         if device is not None and t.device != device:
             raise ValueError("tensor %d is on %s, the codec on %s" % (i, t.device, device))
+    return widths
 
 
 def _only_end_marker(head, bits, length):
@@ -376,7 +427,8 @@ class TensorCodec:
     """compress_many / decompress_many for tensors that are on the GPU, with one device context, its workspaces and torch's caching
     allocator kept across calls. Every stream is byte for byte what compress_many returns for the tensor's bytes, so the file the reference
     CLI writes for them; the payload stays on the device in both directions (scattered tensors are gathered, and the streams compacted,
-    by knz_hip_copy_many), and only the stream headers (HEADER_PEEK bytes each) and the per-item results are read on the host.
+    by knz_hip_copy_many), and only the stream headers (HEADER_PEEK bytes each) and the per-item results are read on the host. With
+    `planes` the tensors are coded as the byte planes of their elements (split_bytes above), split and joined by the gathering kernels.
 
     All work is ordered on `stream` (a torch.cuda.Stream; default: the stream current on `device` when the codec is made), and every buffer
     is allocated from torch's allocator while the stream that the kernels run on is current. The calls wait for that stream where the C
@@ -447,9 +499,15 @@ class TensorCodec:
         for k in range(0, len(copies), most):
             self.ctx.copy_many(copies[k:k + most])
 
-    def _gather(self, parts):
+    def _planes(self, entries, split):
+        most = self._hipapi.COPY_MAX_COPIES
+        for k in range(0, len(entries), most):
+            (self.ctx.split_many if split else self.ctx.join_many)(entries[k:k + most])
+
+    def _gather(self, parts, widths=None):
         """parts: (device address, bytes) each. One copy_many moves them into a new buffer, every part at a multiple of 16, the pads
-        between them and 64 bytes behind the last zero, as _pack leaves them. Returns (the buffer, the parts' offsets)."""
+        between them and 64 bytes behind the last zero, as _pack leaves them. With widths (one per part) it is one split_many, which
+        leaves part k as its byte planes and copies the zeros as elements of one byte. Returns (the buffer, the parts' offsets)."""
         import torch
         offs, at = [], 0
         for _, n in parts:
@@ -461,18 +519,28 @@ class TensorCodec:
         copies = [(a, base + o, n) for (a, n), o in zip(parts, offs)]
         copies += [(z, base + o + n, -n % 16) for (_, n), o in zip(parts, offs) if n % 16]
         copies.append((z, base + at, 64))
-        self._copy(copies)
+        if widths is None:
+            self._copy(copies)
+        else:
+            self._planes([c + (w,) for c, w in zip(copies, list(widths) + [1] * (len(copies) - len(parts)))], True)
         return buf, offs
 
-    def compress(self, tensors, transform, entropy, block_size, checksum=0, jobs=1):
+    def compress(self, tensors, transform, entropy, block_size, checksum=0, jobs=1, planes=False):
         """tensors: torch tensors of any dtype on the codec's device, contiguous; tensor i stands for its numel() * element_size() bytes in
         memory order. Returns (blob, offsets): blob a 1-D uint8 tensor on the device, offsets a list of len(tensors) + 1 ints, stream k =
         blob[offsets[k]:offsets[k + 1]]. ValueError, with the index, for a tensor that is not contiguous, on the CPU or on another
-        device (nothing is moved or made contiguous behind the caller's back), and for one too large for a device call."""
+        device (nothing is moved or made contiguous behind the caller's back), and for one too large for a device call.
+
+        planes: True codes every tensor as the byte planes of its elements (split_bytes of its bytes; the width is element_size(), half of
+        it for a complex dtype), which is what makes an order-0 coder worth its while on floating-point data; a sequence gives one width
+        of 1, 2, 4 or 8 per tensor, for uint8 tensors that hold the bytes of another type. Stream k is then compress_many's for
+        split_bytes(bytes of tensor k, width k), and the kernel that gathers the call's input does the split, so the payload is still
+        moved once. The width is NOT stored in the stream: decompress has to be given it again. ValueError, with the index, for a width
+        that is not taken or does not divide the tensor's bytes."""
         import torch
         self._open()
         tensors = list(tensors)
-        _check_tensors(tensors, self.device)
+        widths = _check_tensors(tensors, self.device, planes)
         hipapi, framing, ctx = self._hipapi, self._framing, self.ctx
         sizes = [t.numel() * t.element_size() for t in tensors]
         runs = _calls(sizes, block_size, hipapi)
@@ -480,7 +548,7 @@ class TensorCodec:
             p = ctx.params(transform, entropy, block_size, checksum, jobs)
             where, keep = [None] * len(tensors), []                  # (address, bytes) of every stream in its call's output, which `keep` holds
             for run in runs:
-                packed, offs = self._gather([(tensors[i].data_ptr(), sizes[i]) for i in run])
+                packed, offs = self._gather([(tensors[i].data_ptr(), sizes[i]) for i in run], None if widths is None else [widths[i] for i in run])
                 items = (hipapi.Item * len(run))()
                 pro = bytearray()
                 for k, i in enumerate(run):
@@ -501,13 +569,18 @@ class TensorCodec:
             self._copy([(a, blob.data_ptr() + o, n) for (a, n), o in zip(where, offsets)])
         return self._hand_over(blob), offsets
 
-    def decompress(self, blob, offsets):
+    def decompress(self, blob, offsets, planes=None):
         """The way back: blob a 1-D uint8 tensor on the codec's device, stream k = blob[offsets[k]:offsets[k + 1]], written by this class,
         by compress_many or by the reference. Returns a list of uint8 tensors on the device, each starting at a multiple of 16 bytes (so
         .view(dtype) gives any dtype back); the tensors of one device call are views of one allocation. The first HEADER_PEEK bytes of
         every stream are read on the host, the headers parsed there, streams of equal parameters share device calls. Raises KanziError
         with the stream's index as decompress_many does. A stream without a stored size that holds data, or one that needs more than one
-        device call, goes decompress_many's way through the host and is uploaded again; streams that compress wrote never do."""
+        device call, goes decompress_many's way through the host and is uploaded again; streams that compress wrote never do.
+
+        planes: one width of 1, 2, 4 or 8 per stream, the widths that compress(planes=...) split the tensors with (the streams do not
+        store them). Every device call then decodes into a buffer of its own, and one join_many writes the results from there (join_bytes
+        of what the stream decodes to). ValueError, with the stream's index, for a width that is not taken or does not divide the
+        decoded length."""
         import torch
         self._open()
         hipapi, framing, sharded, ctx = self._hipapi, self._framing, self._sharded, self.ctx
@@ -517,6 +590,17 @@ class TensorCodec:
             raise ValueError("blob must be a contiguous 1-D uint8 tensor on %s" % self.device)
         if n < 0 or offsets[0] < 0 or offsets[-1] > blob.numel() or any(a > b for a, b in zip(offsets, offsets[1:])):
             raise ValueError("offsets must rise from 0 to at most the blob's length")
+        widths = None if planes is None else list(planes)
+        if widths is not None:
+            if len(widths) != n:
+                raise ValueError("planes holds %d widths for %d streams" % (len(widths), n))
+            for i, w in enumerate(widths):
+                if isinstance(w, bool) or w not in PLANE_WIDTHS:
+                    raise ValueError("stream %d: width %r, planes of 1, 2, 4 and 8 bytes are taken" % (i, w))
+
+        def whole_elements(i, decoded):
+            if widths is not None and decoded % widths[i]:
+                raise ValueError("stream %d: %d decoded bytes are no multiple of the width %d" % (i, decoded, widths[i]))
         if n == 0:
             return []
         out = [None] * n
@@ -539,8 +623,12 @@ class TensorCodec:
                 if h["orig_size"] == 0 or not _fits_one_call(h["orig_size"], h["block_size"], hipapi) or not _fits_one_call(lens[i], 1024, hipapi):
                     s = bytes(blob[offsets[i]:offsets[i + 1]].cpu().numpy())
                     back = sharded.decompress_sharded(s, 0, 1, sharded.DeviceRunDecoder(self.device.index, 1), lambda part: [part])
+                    whole_elements(i, len(back))
+                    if widths is not None:
+                        back = join_bytes(back, widths[i])
                     out[i] = self._hand_over(torch.frombuffer(bytearray(back), dtype=torch.uint8).to(self.device)) if back else self._empty(0)
                     continue
+                whole_elements(i, h["orig_size"])
                 key = (h["etype"], h["ttype"], h["block_size"], h["checksum_bits"], h["bs_version"])
                 groups.setdefault(key, []).append((i, h))
             for (etype, ttype, bs, ck, ver), members in groups.items():
@@ -555,7 +643,8 @@ class TensorCodec:
                         items[m].out_off, items[m].out_cap = at, h["orig_size"]
                         at += (h["orig_size"] + 15) & ~15
                     d_out = self._hand_over(self._empty(at + 64))
-                    ctx.decode_streams(p, packed.data_ptr(), items, d_out.data_ptr(), at + 64)
+                    d_dec = d_out if widths is None else self._empty(at + 64)       # planes: decoded here, joined into d_out
+                    ctx.decode_streams(p, packed.data_ptr(), items, d_dec.data_ptr(), at + 64)
                     for m, k in enumerate(run):
                         i, h = members[k]
                         if items[m].error:
@@ -563,18 +652,22 @@ class TensorCodec:
                         if items[m].out_len != h["orig_size"]:
                             raise KanziError(13, "stream %d: %d bytes where the header stores %d" % (i, items[m].out_len, h["orig_size"]))
                         out[i] = d_out[items[m].out_off:items[m].out_off + items[m].out_len]
+                    if widths is not None:
+                        self._planes([(d_dec.data_ptr() + items[m].out_off, d_out.data_ptr() + items[m].out_off, items[m].out_len, widths[members[k][0]])
+                                      for m, k in enumerate(run)], False)
         return out
 
 
-def compress_tensors(tensors, transform, entropy, block_size, checksum=0, jobs=1):
+def compress_tensors(tensors, transform, entropy, block_size, checksum=0, jobs=1, planes=False):
     """TensorCodec.compress on torch's current device and stream, with a codec made for this one call."""
     tensors = list(tensors)
-    _check_tensors(tensors, None)
+    planes = planes if planes is None or isinstance(planes, bool) else list(planes)
+    _check_tensors(tensors, None, planes)
     with TensorCodec() as codec:
-        return codec.compress(tensors, transform, entropy, block_size, checksum, jobs)
+        return codec.compress(tensors, transform, entropy, block_size, checksum, jobs, planes)
 
 
-def decompress_tensors(blob, offsets):
+def decompress_tensors(blob, offsets, planes=None):
     """TensorCodec.decompress on the blob's device and torch's current stream there, with a codec made for this one call."""
     with TensorCodec(blob.device) as codec:
-        return codec.decompress(blob, offsets)
+        return codec.decompress(blob, offsets, planes)
