@@ -91,12 +91,6 @@ __global__ __launch_bounds__(64) void k_ans0_stats(BlockView view, int maxChunks
 // ------------------------------------------------------------------------------------------------
 // encode: 16 chunks per wave, 4 lanes (= 4 rANS states) per chunk
 // ------------------------------------------------------------------------------------------------
-template <int K>
-__device__ __forceinline__ u32 quad_bcast(u32 v)
-{
-    return (u32)__builtin_amdgcn_update_dpp(0, (int)v, K * 0x55, 0xF, 0xF, false);
-}
-
 __global__ __launch_bounds__(64) void k_ans0_encode(BlockView view, int maxChunks, int nSlots, ChunkDesc* __restrict__ desc,
                                                     const uint2* __restrict__ encTab, u8* __restrict__ tmp)
 {

@@ -49,13 +49,6 @@ struct AnsDecChunk {
 constexpr u32 SCAN_WIN_BITS = 8192;
 constexpr u32 SCAN_NEED_BITS = 3498 + 40 + 128 + 64;   // longest header + var-int + 4 states + one spare dword pair
 
-#ifdef KNZ_EMU
-struct u32x4 { u32 x, y, z, w; };                     // (the CPU emulation of tests/emu is built with g++)
-#else
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-#endif
-
-__device__ __forceinline__ u32 rl(u32 v, u32 l) { return (u32)__builtin_amdgcn_readlane((int)v, (int)l); }
 // values the compiler must have in registers at this point (it would otherwise move an LDS read it thinks is optional behind the
 // condition that picks it, i.e. behind the memory load the read is meant to overlap)
 #ifdef KNZ_EMU
@@ -63,8 +56,6 @@ __device__ __forceinline__ u32 rl(u32 v, u32 l) { return (u32)__builtin_amdgcn_r
 #else
 #define KNZ_KEEP3(a, b, c) asm volatile("" : "+v"(a), "+v"(b), "+v"(c))
 #endif
-__device__ __forceinline__ u32 uni(u32 v) { return (u32)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ u64 uni64(u64 v) { return ((u64)uni((u32)(v >> 32)) << 32) | uni((u32)v); }
 
 // n in [1, 32]; rel = bit offset from the window start
 __device__ __forceinline__ u32 lds_bits(const u32* win, u32 rel, u32 n)
@@ -320,33 +311,6 @@ constexpr u32 CHECK_STEPS = 8;       // <= 8 bytes consumed per step -> <= RQ pe
 constexpr u32 SYM_STRIDE = 260;
 constexpr u32 OST = 32;              // steps of output staged in LDS per chunk (dwords)
 
-// a store that is a global store whatever the compiler knows about the pointer (a flat store also counts as an LDS operation)
-__device__ __forceinline__ void st_global_u32(u8* p, u32 v)
-{
-#ifdef KNZ_EMU
-    *reinterpret_cast<u32*>(p) = v;
-#else
-    *reinterpret_cast<__attribute__((address_space(1))) u32*>(reinterpret_cast<uintptr_t>(p)) = v;
-#endif
-}
-
-__device__ __forceinline__ void st_global_u32x4(u8* p, u32x4 v)
-{
-#ifdef KNZ_EMU
-    *reinterpret_cast<u32x4*>(p) = v;
-#else
-    *reinterpret_cast<__attribute__((address_space(1))) u32x4*>(reinterpret_cast<uintptr_t>(p)) = v;
-#endif
-}
-// every load issued so far has arrived (before a burst of stores: one counter for loads and stores, counted in issue order)
-// (KNZ_LOADS_DONE: common.hpp)
-
-template <int K>
-__device__ __forceinline__ u32 quad_bcast(u32 v)
-{
-    return (u32)__builtin_amdgcn_update_dpp(0, (int)v, K * 0x55, 0xF, 0xF, false);
-}
-
 __device__ __forceinline__ u32 quad_transpose_word(u32 acc, int j)
 {
     // lanes of a quad hold acc = symbols of steps 0..3 (byte k = step k); lane j returns the dword
@@ -590,7 +554,7 @@ __global__ __launch_bounds__(64) void k_ans0_decode(BitSrc src, DecBlock* __rest
     auto put_word = [&](u32 word, u32 stepIdx) {
         if (stepIdx < steps) {
             u8* o = dst + 4 * (size_t)stepIdx;
-            if (aligned4) st_global_u32(o, word);
+            if (aligned4) stg<u32>(o, word);
             else { stg<u8>(o, (u8)word); stg<u8>(o + 1, (u8)(word >> 8)); stg<u8>(o + 2, (u8)(word >> 16)); stg<u8>(o + 3, (u8)(word >> 24)); }
         }
     };
@@ -609,7 +573,7 @@ __global__ __launch_bounds__(64) void k_ans0_decode(BitSrc src, DecBlock* __rest
                 const u32 d0 = base + (OST / 4) * (u32)j + 4u * k;     // lane j of the chunk writes a quarter of the staged dwords
                 if (d0 >= lim) continue;
                 const u32x4 v = *reinterpret_cast<const u32x4*>(&stgw[(OST / 4) * (u32)j + 4u * k]);
-                if (aligned16 && d0 + 4 <= lim) st_global_u32x4(dst + 4 * (size_t)d0, v);
+                if (aligned16 && d0 + 4 <= lim) stg<u32x4>(dst + 4 * (size_t)d0, v);
                 else {
                     const u32 w[4] = { v.x, v.y, v.z, v.w };
                     for (u32 i = 0; i < 4; i++) put_word(w[i], d0 + i);
@@ -881,7 +845,7 @@ __global__ __launch_bounds__(64) void k_ans1_decode(BitSrc src, DecBlock* __rest
             if (dw < full) {
                 const u32 v = stage[jj * (A1_INTERVAL / 4) + dw];
                 u8* o = q0 + (size_t)jj * quarter + s0 + 4 * dw;
-                if (alignedAll) st_global_u32(o, v);
+                if (alignedAll) stg<u32>(o, v);
                 else { o[0] = (u8)v; o[1] = (u8)(v >> 8); o[2] = (u8)(v >> 16); o[3] = (u8)(v >> 24); }
             }
             // the last bytes of a quarter that is not a multiple of four

@@ -40,9 +40,6 @@ __host__ __device__ __forceinline__ u64 cm_stage1(u64 n, u32 div)
     return div ? n / div + 64 : n + n / 8 + 64;
 }
 
-__device__ __forceinline__ u32 cm_rl(u32 v, u32 l) { return (u32)__builtin_amdgcn_readlane((int)v, (int)l); }
-__device__ __forceinline__ u32 cm_uni(u32 v) { return (u32)__builtin_amdgcn_readfirstlane((int)v); }
-
 // A copy block: entropy type forced to NONE (io/CompressedOutputStream.cpp:691-695)
 __device__ __forceinline__ void binary_copy_desc(ChunkDesc& cd, const u8* blk, u32 count)
 {
@@ -74,7 +71,7 @@ __device__ __forceinline__ bool binary_encode_block(P& pr, const u8* __restrict_
             const u32 nb = (endChunk - i0 < 64) ? endChunk - i0 : 64;
             u32 cnt = 0;
             for (u32 l = 0; l < nb && !full; l++) {
-                const u32 bv = cm_rl(byte, l);
+                const u32 bv = rl(byte, l);
 #pragma unroll
                 for (int k = 0; k < 8; k++) {
                     const u64 pred = pr.get();
@@ -166,7 +163,7 @@ __device__ __forceinline__ bool binary_decode_block(P& pr, const BitSrc& src, co
                         } else {
                             const u32 u = index >> 2;
                             if (u - winBase >= 64) { winCur = winNext; winBase += 64; winNext = loadWin(winBase + 64); }
-                            const u64 val = cm_rl(winCur, (u - winBase) & 63);
+                            const u64 val = rl(winCur, (u - winBase) & 63);
                             current = ((current << 32) | val) & CM_MASK56;
                             index += 4;
                         }

@@ -180,7 +180,7 @@ __global__ __launch_bounds__(256) void k_bwt_i_hist(BwtView v, const BwtHdr* __r
 #pragma unroll
     for (int r = 0; r < 16; r++) {
         const bool valid = sy[r] != 0xFFFFFFFFu;
-        const u32 s0 = (u32)__builtin_amdgcn_readfirstlane((int)sy[r]);
+        const u32 s0 = uni(sy[r]);
         const unsigned long long va = __ballot(valid);
         if (__ballot(valid && sy[r] != s0) == 0) { if (lane == 0 && va) atomicAdd(&cnt[s0], (u32)__popcll(va)); }
         else if (valid) atomicAdd(&cnt[sy[r]], 1u);

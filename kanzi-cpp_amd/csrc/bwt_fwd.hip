@@ -360,7 +360,7 @@ struct LastPassSrc : prims::DigitOfKey<u64> {
         u32 lo = 0, hi = cnt - 1u;
         while (lo < hi) { const u32 mid = (lo + hi) >> 1; if (above(ks[mid])) hi = mid; else lo = mid + 1u; }
         u32* g = &gapStart[(u32)sgm * 256u + d];
-        if (at0 + lo < prims::rs_ld_dev(g)) atomicMin(g, at0 + lo);
+        if (at0 + lo < ld_agent(g)) atomicMin(g, at0 + lo);
     }
 };
 
@@ -394,7 +394,7 @@ __global__ __launch_bounds__(256) void k_bwt_f_bytehist(BwtView bv, const u32* _
         for (u32 j = 0; j < 16; j++) {
             const bool valid = j < m;
             const u32 dg = (wds[j >> 2] >> (8 * (j & 3))) & 255u;
-            const u32 d0 = (u32)__builtin_amdgcn_readfirstlane((int)dg);
+            const u32 d0 = uni(dg);
             const unsigned long long va = __ballot(valid);
             if (__ballot(valid && dg != d0) == 0) { if (lane == 0 && va) mine[d0] += (u32)__popcll(va); }
             else if (valid) atomicAdd(&mine[dg], 1u);

@@ -86,14 +86,14 @@ struct CmCells { u32 a, b, d, e, idx, row; };
 __device__ __forceinline__ u32 cm_get(const CmTables& t, const CmCtx& s, CmCells& k)
 {
     const u16* r1 = t.c1 + s.ctx * 257;
-    k.a = cm_uni(r1[256]);
-    k.b = cm_uni(r1[s.c1]);
-    const u32 c = cm_uni(r1[s.c2]);
+    k.a = uni(r1[256]);
+    k.b = uni(r1[s.c1]);
+    const u32 c = uni(r1[s.c2]);
     const u32 p = (13 * (k.a + k.b) + 6 * c) >> 5;
     k.idx = p >> 12;
     k.row = s.ctx | s.runMask;
-    k.d = cm_uni(t.c2[k.row * 16 + k.idx]);
-    k.e = cm_uni(k.idx == 15 ? t.c2top[k.row] : (u32)t.c2[k.row * 16 + ((k.idx + 1) & 15)]);
+    k.d = uni(t.c2[k.row * 16 + k.idx]);
+    k.e = uni(k.idx == 15 ? t.c2top[k.row] : (u32)t.c2[k.row * 16 + ((k.idx + 1) & 15)]);
     return (p + p + 3 * (k.d + k.e) + 64) >> 7;
 }
 

@@ -87,6 +87,60 @@ __device__ __forceinline__ void stg(void* p, T v)
     *(__attribute__((address_space(1))) T*)(uintptr_t)p = v;
 #endif
 }
+// four words moved as one 16-byte access
+#ifdef KNZ_EMU
+struct u32x4 { u32 x, y, z, w; };                     // (the CPU emulation of tests/emu is built with g++)
+#else
+typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+#endif
+// ldg / stg at any address: block text read at a match position, a byte plane that starts at an arbitrary offset
+template <typename T>
+__device__ __forceinline__ T ldg_u(const void* p)
+{
+#ifdef KNZ_EMU
+    T v; __builtin_memcpy(&v, p, sizeof(T)); return v;
+#else
+    typedef T __attribute__((aligned(1))) TU;
+    return *(const __attribute__((address_space(1))) TU*)(uintptr_t)p;
+#endif
+}
+template <typename T>
+__device__ __forceinline__ void stg_u(void* p, T v)
+{
+#ifdef KNZ_EMU
+    __builtin_memcpy(p, &v, sizeof(T));
+#else
+    typedef T __attribute__((aligned(1))) TU;
+    *(__attribute__((address_space(1))) TU*)(uintptr_t)p = v;
+#endif
+}
+// a store to any address that leaves the address space to the compiler (the LZ family's literal and match copies)
+template <typename T>
+__device__ __forceinline__ void st_u(void* p, T v) { __builtin_memcpy(p, &v, sizeof(T)); }
+
+// Relaxed atomic accesses at agent scope: flags and counters that another workgroup, possibly on another XCD, polls or publishes
+// (look-back of the radix sort, progress of the FPAQ families). Ordering comes from the fences around them.
+template <typename T>
+__device__ __forceinline__ T ld_agent(const T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+template <typename T>
+__device__ __forceinline__ void st_agent(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// Wave-level values. uni: the value of the first active lane, which tells the compiler that a value it cannot prove uniform lives
+// in a scalar register; rl: the value of a given (uniform) lane; quad_bcast<K>: the value of lane K of the caller's group of four.
+// (Six places that compare such a value with the lane's own -- hj == h in lz.hip and lzp.hip, dg != d0 in prims.hpp -- spell the builtin
+// out: through the wrapper the compiler swaps the operands of the s_and that follows the compare.)
+__device__ __forceinline__ u32 uni(u32 v) { return (u32)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ u64 uni64(u64 v) { return ((u64)uni((u32)(v >> 32)) << 32) | uni((u32)v); }
+__device__ __forceinline__ u32 rl(u32 v, u32 lane) { return (u32)__builtin_amdgcn_readlane((int)v, (int)lane); }
+template <int K>
+__device__ __forceinline__ u32 quad_bcast(u32 v)
+{
+    return (u32)__builtin_amdgcn_update_dpp(0, (int)v, K * 0x55, 0xF, 0xF, false);
+}
+// what the wave's lanes stored before this point is what its lanes load behind it (tables that belong to one wave)
+__device__ __forceinline__ void wave_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
+
 // eight bytes of a block's text from position q (little endian; bytes at or behind n read as zero), from three aligned dwords
 __device__ __forceinline__ u64 text8(const u8* t, u32 q, u32 n)
 {

@@ -24,18 +24,9 @@ constexpr int CM_THREADS = 256;
 constexpr u32 CM_PASS = 16 * CM_THREADS;          // body bytes the workgroup moves per load
 static_assert(CM_TILE % 16 == 0 && CM_TILE >= 16, "tiles end at 16-byte boundaries");
 
-// 16 bytes from any address (the source is aligned only when src = dst mod 16), 16 bytes to a 16-byte boundary; through the global
-// address space (see ldg in common.hpp)
-#ifdef KNZ_EMU
-struct cm_v4 { u32 w[4]; };
-__device__ __forceinline__ cm_v4 cm_ld16(u64 p) { cm_v4 v; __builtin_memcpy(&v, reinterpret_cast<const void*>((uintptr_t)p), 16); return v; }
-__device__ __forceinline__ void cm_st16(u64 p, cm_v4 v) { __builtin_memcpy(reinterpret_cast<void*>((uintptr_t)p), &v, 16); }
-#else
-typedef u32 cm_v4 __attribute__((ext_vector_type(4)));
-typedef cm_v4 __attribute__((aligned(1))) cm_v4_u;
-__device__ __forceinline__ cm_v4 cm_ld16(u64 p) { return *(const __attribute__((address_space(1))) cm_v4_u*)(uintptr_t)p; }
-__device__ __forceinline__ void cm_st16(u64 p, cm_v4 v) { *(__attribute__((address_space(1))) cm_v4*)(uintptr_t)p = v; }
-#endif
+// 16 bytes from any address (the source is aligned only when src = dst mod 16), 16 bytes to a 16-byte boundary
+__device__ __forceinline__ u32x4 cm_load(u64 p) { return ldg_u<u32x4>(reinterpret_cast<const void*>((uintptr_t)p)); }
+__device__ __forceinline__ void cm_store(u64 p, u32x4 v) { stg<u32x4>(reinterpret_cast<void*>((uintptr_t)p), v); }
 __device__ __forceinline__ void cm_byte(u64 dst, u64 delta) { stg<u8>(reinterpret_cast<void*>((uintptr_t)dst), ldg<u8>(reinterpret_cast<const void*>((uintptr_t)(dst + delta)))); }
 
 u64 copy_many_tiles(u64 dst, u64 len) { return len ? ((dst & 15) + len + CM_TILE - 1) / CM_TILE : 0; }
@@ -62,10 +53,10 @@ __global__ __launch_bounds__(CM_THREADS) void k_copy_many(const knz_copy* __rest
     if (bodyHi + tid < b) cm_byte(bodyHi + tid, delta);
     u64 p = bodyLo + 16u * tid;
     for (; p + 3 * CM_PASS < bodyHi; p += 4 * CM_PASS) {
-        const cm_v4 v0 = cm_ld16(p + delta), v1 = cm_ld16(p + CM_PASS + delta), v2 = cm_ld16(p + 2 * CM_PASS + delta), v3 = cm_ld16(p + 3 * CM_PASS + delta);
-        cm_st16(p, v0); cm_st16(p + CM_PASS, v1); cm_st16(p + 2 * CM_PASS, v2); cm_st16(p + 3 * CM_PASS, v3);
+        const u32x4 v0 = cm_load(p + delta), v1 = cm_load(p + CM_PASS + delta), v2 = cm_load(p + 2 * CM_PASS + delta), v3 = cm_load(p + 3 * CM_PASS + delta);
+        cm_store(p, v0); cm_store(p + CM_PASS, v1); cm_store(p + 2 * CM_PASS, v2); cm_store(p + 3 * CM_PASS, v3);
     }
-    for (; p < bodyHi; p += CM_PASS) cm_st16(p, cm_ld16(p + delta));
+    for (; p < bodyHi; p += CM_PASS) cm_store(p, cm_load(p + delta));
 }
 
 void launch_copy_many(hipStream_t s, const knz_copy* copies, const u32* tileFirst, u32 n, u32 nTiles)

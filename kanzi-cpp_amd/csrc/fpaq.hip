@@ -39,9 +39,6 @@ constexpr u64 FPAQ_MASK24 = 0x0000000000FFFFFFull;
 constexpr u64 FPAQ_MASK32 = 0x00000000FFFFFFFFull;
 constexpr u64 FPAQ_MASK56 = 0x00FFFFFFFFFFFFFFull;
 
-__device__ __forceinline__ u32 fpaq_rl(u32 v, u32 l) { return (u32)__builtin_amdgcn_readlane((int)v, (int)l); }
-__device__ __forceinline__ u32 fpaq_uni(u32 v) { return (u32)__builtin_amdgcn_readfirstlane((int)v); }
-
 // FPAQEncoder.hpp:75-84: towards 0 after a 0 bit, towards 65536 after a 1 bit, by 1/64 of the distance
 __device__ __forceinline__ u32 fpaq_update(u32 p, u32 bit)
 {
@@ -52,12 +49,8 @@ __device__ __forceinline__ u32 fpaq_update(u32 p, u32 bit)
 constexpr u32 FPAQ_PUBLISH = 1024;       // tiles between two publications (64 KiB of the block: a release fence writes the L2 back)
 constexpr u32 FPAQ_CTRL_PROG = 64;       // ctrl[0] = ticket counter of the launch
 #ifdef KNZ_EMU
-__device__ __forceinline__ u32 fpaq_ld_dev(const u32* p) { return *p; }
-__device__ __forceinline__ void fpaq_st_dev(u32* p, u32 v) { *p = v; }
 #define FPAQ_SPIN() do { fprintf(stderr, "k_fpaq_encode: the families of this block have not run\n"); abort(); } while (0)
 #else
-__device__ __forceinline__ u32 fpaq_ld_dev(const u32* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void fpaq_st_dev(u32* p, u32 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 #define FPAQ_SPIN() __builtin_amdgcn_s_sleep(8)
 #endif
 
@@ -65,7 +58,7 @@ __device__ __forceinline__ void fpaq_st_dev(u32* p, u32 v) { __hip_atomic_store(
 __device__ __forceinline__ void fpaq_publish(u32* prog, u32 tilesDone)
 {
     __threadfence();
-    if (lane_id() == 0) fpaq_st_dev(prog, tilesDone);
+    if (lane_id() == 0) st_agent(prog, tilesDone);
 }
 
 // the coding wave: wait until all 32 families of the block have published `need` tiles; returns what they have published
@@ -74,9 +67,9 @@ __device__ __forceinline__ u32 fpaq_await(const u32* progBlock, u32 need)
     const int lane = lane_id();
     u32 have;
     for (;;) {
-        u32 v = (lane < 32) ? fpaq_ld_dev(progBlock + lane) : 0xFFFFFFFFu;
+        u32 v = (lane < 32) ? ld_agent(progBlock + lane) : 0xFFFFFFFFu;
         for (int o = 32; o > 0; o >>= 1) { const u32 t = (u32)__shfl_xor((int)v, o, 64); v = t < v ? t : v; }
-        have = fpaq_uni(v);
+        have = uni(v);
         if (have >= need) break;
         FPAQ_SPIN();
     }
@@ -193,8 +186,8 @@ __device__ __forceinline__ void fpaq_code_block(BlockView view, int b, const u32
             const u32 nb = (endChunk - i0 < 64) ? endChunk - i0 : 64;
             u32 cnt = 0;
             for (u32 l = 0; l < nb; l++) {
-                const u32 bv = fpaq_rl(byte, l);
-                const u32 q[4] = { fpaq_rl(pw.x, l), fpaq_rl(pw.y, l), fpaq_rl(pw.z, l), fpaq_rl(pw.w, l) };
+                const u32 bv = rl(byte, l);
+                const u32 q[4] = { rl(pw.x, l), rl(pw.y, l), rl(pw.z, l), rl(pw.w, l) };
 #pragma unroll
                 for (int k = 0; k < 8; k++) {
                     const u64 p = (k & 1) ? (q[k >> 1] >> 16) : (q[k >> 1] & 0xFFFFu);
@@ -300,7 +293,7 @@ __global__ __launch_bounds__(64) void k_fpaq_decode(BitSrc src, DecBlock* __rest
         const u32 chunkSize = (FPAQ_CHUNK < count - startChunk) ? FPAQ_CHUNK : count - startChunk;
         const u32 endChunk = startChunk + chunkSize;
         u32 c2 = 0;
-        u32 pRoot = fpaq_uni(pr32[0]) >> 16;                      // node 1 of class 0
+        u32 pRoot = uni(pr32[0]) >> 16;                      // node 1 of class 0
         for (u32 i0 = startChunk; i0 < endChunk && !fail; i0 += 64) {
             const u32 nb = (endChunk - i0 < 64) ? endChunk - i0 : 64;
             u32 myByte = 0;
@@ -320,7 +313,7 @@ __global__ __launch_bounds__(64) void k_fpaq_decode(BitSrc src, DecBlock* __rest
                     high = one ? split : high;
                     low = one ? low : split + 1;
                     ctx = 2 * ctx + (one ? 1u : 0u);
-                    if (k < 7) { pair = fpaq_uni(pair); p = one ? (pair >> 16) : (pair & 0xFFFFu); }
+                    if (k < 7) { pair = uni(pair); p = one ? (pair >> 16) : (pair & 0xFFFFu); }
                     if (k == 1) nextRoot = pr32[(ctx & 3) * 128];          // the class of the next byte is known after two bits
                     const u64 x = low ^ high;
                     if ((((u32)(x >> 32)) | ((u32)x >> 24)) == 0) {
@@ -332,7 +325,7 @@ __global__ __launch_bounds__(64) void k_fpaq_decode(BitSrc src, DecBlock* __rest
                         } else {
                             const u32 u = index >> 2;
                             if (u - winBase >= 64) { winCur = winNext; winBase += 64; winNext = loadWin(winBase + 64); }
-                            const u64 val = fpaq_rl(winCur, (u - winBase) & 63);
+                            const u64 val = rl(winCur, (u - winBase) & 63);
                             current = ((current << 32) | val) & FPAQ_MASK56;
                             index += 4;
                         }
@@ -343,7 +336,7 @@ __global__ __launch_bounds__(64) void k_fpaq_decode(BitSrc src, DecBlock* __rest
                 // next byte: class = top two bits of this one; its root probability was read after bit 1, but the root of the
                 // same class may have been this byte's own root (updated at bit 0, before that read) -- LDS keeps program order
                 c2 = (ctx & 0xFF) >> 6;
-                pRoot = fpaq_uni(nextRoot) >> 16;
+                pRoot = uni(nextRoot) >> 16;
             }
             if ((u32)lane < nb && !fail) block[i0 + (u32)lane] = (u8)myByte;
             else if (fail) { /* partial tile: the block is rejected anyway */ }

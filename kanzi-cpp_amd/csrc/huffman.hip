@@ -485,11 +485,6 @@ struct HufDecChunk {
     u8 sizes[256];
 };
 
-#ifdef KNZ_EMU
-struct hu32x4 { u32 x, y, z, w; };                    // (the CPU emulation of tests/emu is built with g++)
-#else
-typedef u32 hu32x4 __attribute__((ext_vector_type(4)));
-#endif
 
 // n in [1, 32]; rel = bit offset from the start of the LDS window (words in bit order)
 __device__ __forceinline__ u32 hwin_bits(const u32* win, u32 rel, u32 n)
@@ -535,7 +530,7 @@ __global__ __launch_bounds__(64) void k_huff_scan(BitSrc src, DecBlock* __restri
         return;
     }
     const u64 lastWord = ((src.nBytes + 3) >> 2) - 1;
-    auto issue = [&](u64 bit0, hu32x4& dstv) {
+    auto issue = [&](u64 bit0, u32x4& dstv) {
         const u64 w = (bit0 >> 5) + 4ull * (u32)lane;
         const u64 w1 = w + 1, w2 = w + 2, w3 = w + 3;
         const u32* p = src.words;
@@ -544,7 +539,7 @@ __global__ __launch_bounds__(64) void k_huff_scan(BitSrc src, DecBlock* __restri
         dstv.z = p[w2 < lastWord ? w2 : lastWord];
         dstv.w = p[w3 < lastWord ? w3 : lastWord];
     };
-    hu32x4 wr = { 0, 0, 0, 0 }, guess = { 0, 0, 0, 0 };
+    u32x4 wr = { 0, 0, 0, 0 }, guess = { 0, 0, 0, 0 };
     u64 winBit0 = 0, guessBit0 = 0;
     bool winValid = false, guessValid = false;
     auto ensure = [&](u32 need) {
@@ -554,8 +549,8 @@ __global__ __launch_bounds__(64) void k_huff_scan(BitSrc src, DecBlock* __restri
         guessValid = false;
         __syncthreads();
         {
-            hu32x4 sw = { bswap32(wr.x), bswap32(wr.y), bswap32(wr.z), bswap32(wr.w) };
-            *reinterpret_cast<hu32x4*>(&win[4 * lane]) = sw;
+            u32x4 sw = { bswap32(wr.x), bswap32(wr.y), bswap32(wr.z), bswap32(wr.w) };
+            *reinterpret_cast<u32x4*>(&win[4 * lane]) = sw;
         }
         __syncthreads();
         winValid = true;
@@ -616,11 +611,11 @@ __global__ __launch_bounds__(64) void k_huff_scan(BitSrc src, DecBlock* __restri
             const u64 nz = __ballot(present != 0);
             if (nz) {
                 const int fl = __ffsll((long long)nz) - 1;
-                const u32 fp = (u32)__builtin_amdgcn_readlane((int)present, fl);
+                const u32 fp = rl(present, fl);
                 firstSym = 4u * (u32)fl + (u32)(__ffs((int)fp) - 1);
             }
         }
-        asz = (u32)__builtin_amdgcn_readfirstlane((int)asz);
+        asz = uni(asz);
         if (asz == 0) { err = 2; break; }
         // ---- code length deltas (ExpGolombDecoder.hpp:52-75)
         // A valid delta has |d| <= 11, i.e. a code of at most 8 bits (prefix of <= 3 zeros); a longer prefix can only decode to an
@@ -633,7 +628,7 @@ __global__ __launch_bounds__(64) void k_huff_scan(BitSrc src, DecBlock* __restri
         // code. Ranks (popcount of the mask below the lane), the running length (a wave scan over the deltas of the lanes that start a
         // code), the range check and the stores are parallel.
         u32 curSize = 2;
-        u32 q = (u32)__builtin_amdgcn_readfirstlane((int)p);
+        u32 q = uni(p);
         u32 bad = 0;
         const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
         u32 k = 0;
@@ -652,7 +647,7 @@ __global__ __launch_bounds__(64) void k_huff_scan(BitSrc src, DecBlock* __restri
 #pragma unroll
                 for (int u = 0; u < 8; u++) {
                     starts |= 1ull << pos;
-                    pos = (u32)__builtin_amdgcn_readlane((int)nxt, (int)pos);
+                    pos = rl(nxt, pos);
                 }
             } while (pos < 56);
             starts &= (1ull << 56) - 1ull;
@@ -674,7 +669,7 @@ __global__ __launch_bounds__(64) void k_huff_scan(BitSrc src, DecBlock* __restri
                 codeSize[k + rank] = (u8)cs;
             }
             if (__ballot(bad != 0) != 0) { bad = 1; break; }
-            curSize = (u32)__builtin_amdgcn_readlane((int)cs, 63);
+            curSize = rl(cs, 63);
             k += cnt;
             q += adv;
         }

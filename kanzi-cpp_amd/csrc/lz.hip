@@ -33,23 +33,8 @@ constexpr int LZ_MINBLOCK = 24;
 
 __host__ __device__ inline int lz_max_encoded(int n) { return ((n <= 1024) ? n + 16 : n + n / 64) + 2; }
 
-// unaligned loads of block text, through the GLOBAL address space: a block's pointer comes out of an array of pointers, so the compiler
-// would make every access a flat load, which counts as an LDS operation too -- and the walk waits for its LDS windows all the time
-#ifdef KNZ_EMU
-__device__ __forceinline__ u64 ld64u(const u8* p) { u64 v; __builtin_memcpy(&v, p, 8); return v; }
-__device__ __forceinline__ u32 ld32u(const u8* p) { u32 v; __builtin_memcpy(&v, p, 4); return v; }
-#else
-typedef u64 __attribute__((aligned(1))) lz_u64_u;
-typedef u32 __attribute__((aligned(1))) lz_u32_u;
-__device__ __forceinline__ u64 ld64u(const u8* p) { return *(const __attribute__((address_space(1))) lz_u64_u*)(uintptr_t)p; }
-__device__ __forceinline__ u32 ld32u(const u8* p) { return *(const __attribute__((address_space(1))) lz_u32_u*)(uintptr_t)p; }
-#endif
-__device__ __forceinline__ void st64u(u8* p, u64 v) { __builtin_memcpy(p, &v, 8); }
-__device__ __forceinline__ int sgpr(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ u64 sgpr64(u64 v)
-{
-    return ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)v);
-}
+// block text is read with ldg_u (common.hpp): a flat load would count as an LDS operation too, and the walk waits for its LDS
+// windows all the time
 
 template <int HASH_LOG>
 __device__ __forceinline__ u32 lz_hash(u64 w) { return (u32)(((w << 24) * 0x1E35A7BDull) >> (64 - HASH_LOG)); }
@@ -93,12 +78,12 @@ __device__ int lz_match(const u8* s, int a, int b, int limit, int lane, int n = 
         const int o = n + 8 * lane;
         const bool valid = o + 8 <= limit;
         u64 x = 0;
-        if (valid) x = ld64u(s + a + o) ^ ld64u(s + b + o);
+        if (valid) x = ldg_u<u64>(s + a + o) ^ ldg_u<u64>(s + b + o);
         const u64 stop = __ballot(!valid || x != 0);
         if (stop) {
             const int f = __ffsll((long long)stop) - 1;
-            const u32 xl = (u32)__builtin_amdgcn_readlane((int)(u32)x, f);
-            const u32 xh = (u32)__builtin_amdgcn_readlane((int)(u32)(x >> 32), f);
+            const u32 xl = rl((u32)x, f);
+            const u32 xh = rl((u32)(x >> 32), f);
             const int vf = __builtin_amdgcn_readlane(valid ? 1 : 0, f);
             if (!vf) return n + 8 * f;
             return n + 8 * f + (xl ? (__ffs((int)xl) - 1) >> 3 : 4 + ((__ffs((int)xh) - 1) >> 3));
@@ -112,7 +97,7 @@ __device__ int lz_match(const u8* s, int a, int b, int limit, int lane, int n = 
 __device__ __forceinline__ void wave_copy(u8* dst, const u8* src, int len, int lane)
 {
     const int bulk = len & ~7;
-    for (int i = 8 * lane; i < bulk; i += 512) st64u(dst + i, ld64u(src + i));
+    for (int i = 8 * lane; i < bulk; i += 512) st_u<u64>(dst + i, ldg_u<u64>(src + i));
     if (lane < len - bulk) dst[bulk + lane] = src[bulk + lane];
 }
 
@@ -161,7 +146,7 @@ __global__ __launch_bounds__(256) void k_lz_keys(XfStage st, u32 S, int nBlocks,
     const u32 q = (u32)(g - (size_t)b * S);
     const int n = (int)st.len[b];
     const bool live = n >= LZ_MINBLOCK && st.cap[b] >= (u32)lz_max_encoded(n) && (int)q < n - 18;
-    keys[g] = live ? (((u32)b << HL) | lz_hash<HL>(ld64u(st.src[b] + q))) : ((u32)nBlocks << HL);
+    keys[g] = live ? (((u32)b << HL) | lz_hash<HL>(ldg_u<u64>(st.src[b] + q))) : ((u32)nBlocks << HL);
     vals[g] = (u32)g;
 }
 
@@ -187,7 +172,7 @@ __global__ __launch_bounds__(256) void k_lz_prev(XfStage st, u32 S, int nBlocks,
         const int limit = min(srcEnd - (int)q, LZ_MAXMATCH);
         int l = 0;
         while (l + 8 <= limit && l < LZ_LCAP) {
-            const u64 x = ld64u(src + q + l) ^ ld64u(src + pv + l);
+            const u64 x = ldg_u<u64>(src + q + l) ^ ldg_u<u64>(src + pv + l);
             if (x) { l += (int)(__ffsll((long long)x) - 1) >> 3; inf = 0x8000u; break; }
             l += 8;
         }
@@ -198,7 +183,7 @@ __global__ __launch_bounds__(256) void k_lz_prev(XfStage st, u32 S, int nBlocks,
 
 __device__ __forceinline__ u64 readlane64(u64 v, int l)
 {
-    return ((u64)(u32)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) | (u32)__builtin_amdgcn_readlane((int)v, l);
+    return ((u64)rl(v >> 32, l) << 32) | rl(v, l);
 }
 
 // The walk.  Positions of a literal run do not depend on one another except through the table, so the next <= 64
@@ -260,7 +245,7 @@ __global__ __launch_bounds__(64) void k_lz_walk(XfStage st, LzWs ws)
             for (int k = lane; k < LZW / 4 + 4; k += 64) {
                 const int o = from + 4 * k;
                 u32 v = 0;
-                if (o + 4 <= n) v = ld32u(src + o);
+                if (o + 4 <= n) v = ldg_u<u32>(src + o);
                 else for (int j = 0; j < 4; j++) if (o + j < n) v |= (u32)src[o + j] << (8 * j);
                 wSrc[k] = v;
             }
@@ -273,7 +258,7 @@ __global__ __launch_bounds__(64) void k_lz_walk(XfStage st, LzWs ws)
         };
         auto hash_at = [&](int p) -> u32 {                    // uniform p
             const int o = p - wbase;
-            return (o >= 0 && o < LZW) ? (u32)sgpr((int)wHash[o]) : ((u32)sgpr((int)gKeys[p]) & HMASK);
+            return (o >= 0 && o < LZW) ? (u32)uni((int)wHash[o]) : ((u32)uni((int)gKeys[p]) & HMASK);
         };
         while (pos < srcEnd) {
             KNZ_WAVE_ORDER();
@@ -298,7 +283,7 @@ __global__ __launch_bounds__(64) void k_lz_walk(XfStage st, LzWs ws)
                 cd = (int)pv;
                 if (act && !fromPrev) cd = tab_get(table, bh);
             } else {
-                const u64 bw = act ? ld64u(src + bp) : 0ull;
+                const u64 bw = act ? ldg_u<u64>(src + bp) : 0ull;
                 bh = lz_hash<HASH_LOG>(bw);
                 w4 = (u32)bw;
                 n4 = (u32)(bw >> 8);
@@ -319,11 +304,11 @@ __global__ __launch_bounds__(64) void k_lz_walk(XfStage st, LzWs ws)
             if (act) {
                 const int blo = (bp - maxDist > 0) ? bp - maxDist : 0;
                 const int rx = bp + 1 - rep0, ry = bp + 1 - rep1;
-                x8 = ld64u(src + (rx > blo ? rx - 1 : 0));    // byte 0: the byte before the candidate, bytes 1-4: compared
-                y8 = ld64u(src + (ry > blo ? ry - 1 : 0));
+                x8 = ldg_u<u64>(src + (rx > blo ? rx - 1 : 0));    // byte 0: the byte before the candidate, bytes 1-4: compared
+                y8 = ldg_u<u64>(src + (ry > blo ? ry - 1 : 0));
                 bool hh;
                 if (fromPrev) hh = (inf & 0x7FFFu) >= 4;
-                else { cw = ld32u(src + (cd > blo ? cd : 0)); hh = cw == w4; }
+                else { cw = ldg_u<u32>(src + (cd > blo ? cd : 0)); hh = cw == w4; }
                 hit = (cd > blo && hh) || (rx > blo && (u32)(x8 >> 8) == n4) || (ry > blo && (u32)(y8 >> 8) == n4);
             }
             const u64 hitMask = __ballot(hit);
@@ -334,7 +319,7 @@ __global__ __launch_bounds__(64) void k_lz_walk(XfStage st, LzWs ws)
                 bool lose = false;
 #pragma unroll 9
                 for (int j = 1; j < 64; j++) {
-                    const u32 hj = (u32)__builtin_amdgcn_readlane((int)bh, j);
+                    const u32 hj = rl(bh, j);
                     if (j < f && j > lane && hj == bh) lose = true;
                 }
                 if (lane < f && !lose) tab_put(table, bh, bp);
@@ -346,13 +331,13 @@ __global__ __launch_bounds__(64) void k_lz_walk(XfStage st, LzWs ws)
             if (f == 64 || !((hitMask >> f) & 1)) continue;
 
             // ---- the serial step of the reference at `pos`
-            const u32 w4f = (u32)__builtin_amdgcn_readlane((int)w4, f);
-            const u32 nx4 = (u32)__builtin_amdgcn_readlane((int)n4, f);
-            const u32 h0 = (u32)__builtin_amdgcn_readlane((int)bh, f);
+            const u32 w4f = rl(w4, f);
+            const u32 nx4 = rl(n4, f);
+            const u32 h0 = rl(bh, f);
             const int cand = __builtin_amdgcn_readlane(cd, f);
             const bool candPrev = __builtin_amdgcn_readlane(fromPrev ? 1 : 0, f) != 0;
-            const u32 inf0 = (u32)__builtin_amdgcn_readlane((int)inf, f);
-            const u32 c4 = (u32)__builtin_amdgcn_readlane((int)cw, f);
+            const u32 inf0 = rl(inf, f);
+            const u32 c4 = rl(cw, f);
             const u64 x8f = readlane64(x8, f), y8f = readlane64(y8, f);
             if (lane == 0) tab_put(table, h0, pos);
             KNZ_WAVE_ORDER();
@@ -393,14 +378,14 @@ __global__ __launch_bounds__(64) void k_lz_walk(XfStage st, LzWs ws)
                         int ck;
                         bool fromk = false;
                         if (inWin) {
-                            const int pvk = sgpr((int)wPrev[ok_]);
-                            hk = (u32)sgpr((int)wHash[ok_]);
-                            infk = (u32)sgpr((int)wInfo[ok_]);
+                            const int pvk = uni((int)wPrev[ok_]);
+                            hk = (u32)uni((int)wHash[ok_]);
+                            infk = (u32)uni((int)wInfo[ok_]);
                             fromk = (pvk == 0) || (pvk > maxGap);
-                            ck = fromk ? pvk : sgpr(tab_get(table, hk));
+                            ck = fromk ? pvk : uni(tab_get(table, hk));
                         } else {
-                            hk = lz_hash<HASH_LOG>(sgpr64(ld64u(src + pk)));
-                            ck = sgpr(tab_get(table, hk));
+                            hk = lz_hash<HASH_LOG>(uni64(ldg_u<u64>(src + pk)));
+                            ck = uni(tab_get(table, hk));
                         }
                         if (lane == 0) tab_put(table, hk, pk);
                         KNZ_WAVE_ORDER();
@@ -411,7 +396,7 @@ __global__ __launch_bounds__(64) void k_lz_walk(XfStage st, LzWs ws)
                         int bk = -1;
                         if (fromk && (infk >> 15)) { if (lk >= best + 1) bk = lk; }
                         else if (fromk && lk >= best + 1) bk = capped ? lz_match(src, pk, ck, limk, lane, LZ_LCAP) : lk;
-                        else if (sgpr((int)ld32u(src + pk + best - 3)) == sgpr((int)ld32u(src + ck + best - 3)))
+                        else if (uni((int)ldg_u<u32>(src + pk + best - 3)) == uni((int)ldg_u<u32>(src + ck + best - 3)))
                             bk = lz_match(src, pk, ck, limk, lane);
                         if (bk >= best) { ref = ck; best = bk; pos = pk; }
                     }
@@ -512,7 +497,7 @@ struct LzByteWin {
     {
         base = from;
         const int o = from + 4 * lane;
-        if (o + 4 <= limit) reg = ld32u(s + o);
+        if (o + 4 <= limit) reg = ldg_u<u32>(s + o);
         else {
             u32 v = 0;
             for (int k = 0; k < 4; k++) if (o + k < limit) v |= (u32)s[o + k] << (8 * k);
@@ -523,7 +508,7 @@ struct LzByteWin {
     {
         if (x < base || x >= base + 256) refill(s, x, limit, lane);
         const int o = x - base;
-        const u32 wv = (u32)__builtin_amdgcn_readlane((int)reg, sgpr(o >> 2));
+        const u32 wv = rl(reg, uni(o >> 2));
         return (wv >> (8 * (o & 3))) & 0xFFu;
     }
 };
@@ -557,11 +542,11 @@ __global__ __launch_bounds__(64) void k_lz_inverse(XfStage st, const u32* __rest
     int ok = 0, d = 0;
     do {
         if (n < 13) break;
-        const int litEnd = sgpr((int)ld32u(src)), nTok = sgpr((int)ld32u(src + 4)), nDist = sgpr((int)ld32u(src + 8));
+        const int litEnd = uni((int)ldg_u<u32>(src)), nTok = uni((int)ldg_u<u32>(src + 4)), nDist = uni((int)ldg_u<u32>(src + 8));
         if (litEnd < 0 || nTok < 0 || nDist < 0) break;
         if (litEnd < 13 || litEnd > n || nTok > n - litEnd || nDist > n - litEnd - nTok) break;
         int t = litEnd, m = litEnd + nTok, l = m + nDist;
-        const int flags = sgpr((int)src[12]);
+        const int flags = uni((int)src[12]);
         const int maxDist = (flags & 1) ? LZ_MAXD2 : LZ_MAXD1;
         const int mm = V5 ? ((((flags >> 1) & 3) == 0) ? 4 : ((((flags >> 1) & 3) == 1) ? 9 : 6)) : ((flags >> 1) & 7) + 2;
         int s = 13, rep0 = V5 ? 0 : n, rep1 = V5 ? 0 : n;
@@ -672,11 +657,11 @@ __global__ __launch_bounds__(64) void k_lz_i_parse(XfStage st, LzInvWs w)
     u32 nr = 0;
     do {
         if (n < 13) break;
-        const int litEnd = sgpr((int)ld32u(src)), nTok = sgpr((int)ld32u(src + 4)), nDist = sgpr((int)ld32u(src + 8));
+        const int litEnd = uni((int)ldg_u<u32>(src)), nTok = uni((int)ldg_u<u32>(src + 4)), nDist = uni((int)ldg_u<u32>(src + 8));
         if (litEnd < 0 || nTok < 0 || nDist < 0) break;
         if (litEnd < 13 || litEnd > n || nTok > n - litEnd || nDist > n - litEnd - nTok) break;
         int t = litEnd, m = litEnd + nTok, l = m + nDist;
-        const int flags = sgpr((int)src[12]);
+        const int flags = uni((int)src[12]);
         const int maxDist = (flags & 1) ? LZ_MAXD2 : LZ_MAXD1;
         const int mm = V5 ? ((((flags >> 1) & 3) == 0) ? 4 : ((((flags >> 1) & 3) == 1) ? 9 : 6)) : ((flags >> 1) & 7) + 2;
         int s = 13, rep0 = V5 ? 0 : n, rep1 = V5 ? 0 : n;
@@ -865,7 +850,7 @@ __global__ __launch_bounds__(1024) void k_lz_i_pparse(XfStage st, LzInvWs w, LzP
     bool plain = !oldLayout && n >= 13 && n < (1 << 30) && (size_t)cap <= w.pStride && (size_t)cap / 2 + 4 <= w.recStride;
     int litEnd = 0, nTok = 0, nDist = 0, flags = 0;
     if (plain) {
-        litEnd = (int)ld32u(src); nTok = (int)ld32u(src + 4); nDist = (int)ld32u(src + 8); flags = (int)src[12];
+        litEnd = (int)ldg_u<u32>(src); nTok = (int)ldg_u<u32>(src + 4); nDist = (int)ldg_u<u32>(src + 8); flags = (int)src[12];
         if (litEnd < 13 || nTok < 1 || nDist < 0 || litEnd > n || nTok > n - litEnd || nDist > n - litEnd - nTok) plain = false;
         if (plain && (size_t)nTok + 2 > w.recStride) plain = false;      // (more tokens than the output has room for: nothing that decodes)
     }
@@ -961,11 +946,11 @@ __global__ __launch_bounds__(1024) void k_lz_i_pparse(XfStage st, LzInvWs w, LzP
             uint2 res = make_uint2(0u, 0u);
             u32 resX = 0;
             for (u32 j = 0; j < cnt; j++) {
-                const u32 S = (u32)__builtin_amdgcn_readlane((int)mine.y, (int)j);
+                const u32 S = rl(mine.y, j);
                 const u32 sp = 13u + S + X;
                 if (sp >= (u32)litEnd) { bad = true; break; }
                 u32 size;
-                const u32 lit = 7u + lzp_len_at(src, sgpr((int)sp), n, size);
+                const u32 lit = 7u + lzp_len_at(src, uni((int)sp), n, size);
                 const u32 sa = sp + size;
                 if (sa > (u32)litEnd || lit > (u32)litEnd - sa) { bad = true; break; }
                 if ((u32)lane == j) { res = make_uint2(sa, lit); resX = X; }

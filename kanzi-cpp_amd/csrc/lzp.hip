@@ -35,17 +35,6 @@ constexpr u32 LZP_FLAG = 0xFC;
 
 __host__ __device__ inline u32 lzp_max_encoded(u32 n) { return (n <= 1024) ? n + 16 : n + n / 64; }      // = knz_max_encoded_len(KNZ_T_LZP, n)
 
-// unaligned loads of block text through the global address space (see ldg in common.hpp)
-#ifdef KNZ_EMU
-__device__ __forceinline__ u64 lzp_ld64(const u8* p) { u64 v; __builtin_memcpy(&v, p, 8); return v; }
-#else
-typedef u64 __attribute__((aligned(1))) lzp_u64_u;
-__device__ __forceinline__ u64 lzp_ld64(const u8* p) { return *(const __attribute__((address_space(1))) lzp_u64_u*)(uintptr_t)p; }
-#endif
-__device__ __forceinline__ void lzp_st64(u8* p, u64 v) { __builtin_memcpy(p, &v, 8); }
-__device__ __forceinline__ int lzp_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ void lzp_wave_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
-
 __device__ __forceinline__ u32 lzp_hash(u32 ctx) { return (0x7FEB352Du * ctx) >> (32 - LZP_HASH_LOG); }
 
 // The context the reference holds when it visits position p (>= 4) with `run` literals behind the last reload (4 = four or more):
@@ -53,7 +42,7 @@ __device__ __forceinline__ u32 lzp_hash(u32 ctx) { return (0x7FEB352Du * ctx) >>
 __device__ __forceinline__ u32 lzp_ctx(const u8* t, u32 p, u32 run)
 {
     u64 w = 0;                                            // byte k = t[p - 1 - k]
-    if (p >= 8) w = __builtin_bswap64(lzp_ld64(t + p - 8));
+    if (p >= 8) w = __builtin_bswap64(ldg_u<u64>(t + p - 8));
     else for (u32 k = 0; k < p; k++) w |= (u64)ldg<u8>(t + p - 1 - k) << (8 * k);
     if (run >= 4) return (u32)w;
     const u32 word = __builtin_bswap32((u32)(w >> (8 * run)));
@@ -92,12 +81,12 @@ __device__ u32 lzp_match(const u8* s, u32 a, u32 b, u32 limit, int lane, u32 n)
         const u32 o = n + 8u * (u32)lane;
         const bool valid = o + 8 <= limit && o + 8 > o;
         u64 x = 0;
-        if (valid) x = lzp_ld64(s + a + o) ^ lzp_ld64(s + b + o);
+        if (valid) x = ldg_u<u64>(s + a + o) ^ ldg_u<u64>(s + b + o);
         const u64 stop = __ballot(!valid || x != 0);
         if (stop) {
             const int f = __ffsll((long long)stop) - 1;
-            const u32 xl = (u32)__builtin_amdgcn_readlane((int)(u32)x, f);
-            const u32 xh = (u32)__builtin_amdgcn_readlane((int)(u32)(x >> 32), f);
+            const u32 xl = rl((u32)x, f);
+            const u32 xh = rl((u32)(x >> 32), f);
             const int vf = __builtin_amdgcn_readlane(valid ? 1 : 0, f);
             if (!vf) return n + 8u * (u32)f;
             return n + 8u * (u32)f + (u32)(xl ? (__ffs((int)xl) - 1) >> 3 : 4 + ((__ffs((int)xh) - 1) >> 3));
@@ -143,10 +132,10 @@ __global__ __launch_bounds__(64) void k_lzp_forward(XfStage st, u32* __restrict_
                 }
             }
             bool hit = false;
-            if (act && ref != 0 && p + LZP_MIN_MATCH < count && lzp_ld64(src + ref + 56) == lzp_ld64(src + p + 56)) {
+            if (act && ref != 0 && p + LZP_MIN_MATCH < count && ldg_u<u64>(src + ref + 56) == ldg_u<u64>(src + p + 56)) {
                 hit = true;
 #pragma unroll
-                for (u32 k = 0; k < 56; k += 8) hit = hit && lzp_ld64(src + ref + k) == lzp_ld64(src + p + k);
+                for (u32 k = 0; k < 56; k += 8) hit = hit && ldg_u<u64>(src + ref + k) == ldg_u<u64>(src + p + k);
             }
             const u64 hitMask = __ballot(hit);
             const u32 nAct = count - s < 64u ? count - s : 64u;
@@ -168,7 +157,7 @@ __global__ __launch_bounds__(64) void k_lzp_forward(XfStage st, u32* __restrict_
             if (d >= dstEnd) { ok = 0; break; }
             if (m >= nAct) continue;
             // ---- the match at s
-            const u32 mref = (u32)__builtin_amdgcn_readlane((int)ref, (int)m);
+            const u32 mref = rl(ref, m);
             const u32 len = lzp_match(src, s, mref, count - s, lane, LZP_MIN_MATCH);
             const u32 rest = len - LZP_MIN_MATCH;
             const u32 nFE = rest / 254;
@@ -176,7 +165,7 @@ __global__ __launch_bounds__(64) void k_lzp_forward(XfStage st, u32* __restrict_
             if (lane == 0) { dst[d] = (u8)LZP_FLAG; dst[d + 1 + nFE] = (u8)(rest - 254 * nFE); }
             u8* fe = dst + d + 1;
             const u32 bulk = nFE & ~7u;
-            for (u32 i = 8u * (u32)lane; i < bulk; i += 512) lzp_st64(fe + i, 0xFEFEFEFEFEFEFEFEull);
+            for (u32 i = 8u * (u32)lane; i < bulk; i += 512) st_u<u64>(fe + i, 0xFEFEFEFEFEFEFEFEull);
             if ((u32)lane < nFE - bulk) fe[bulk + lane] = 0xFE;
             d += nFE + 2;
             s += len;
@@ -217,7 +206,7 @@ __global__ __launch_bounds__(64) void k_lzp_inverse(XfStage st, u32* __restrict_
             if (f > dstEnd - di) { ok = 0; break; }                               // a literal does not fit
             const bool lit = (u32)lane < f;
             if (lit) dst[di + lane] = (u8)v;
-            lzp_wave_fence();                                                     // contexts come from the bytes written (this batch, the match before it)
+            wave_fence();                                                     // contexts come from the bytes written (this batch, the match before it)
             // ---- their buckets, and the flag's context
             const u32 p = di + (u32)lane;
             const u32 r = run + (u32)lane;
@@ -229,16 +218,16 @@ __global__ __launch_bounds__(64) void k_lzp_inverse(XfStage st, u32* __restrict_
             run = run + f < 4 ? run + f : 4u;
             if (m >= nAct) continue;
             // ---- 0xFC at si: one lookup behind those stores
-            lzp_wave_fence();
-            const u32 hf = (u32)__builtin_amdgcn_readlane((int)h, (int)m);
-            const u32 ref = (u32)lzp_uni((int)table[hf]);
-            lzp_wave_fence();
+            wave_fence();
+            const u32 hf = rl(h, m);
+            const u32 ref = (u32)uni((int)table[hf]);
+            wave_fence();
             if (lane == 0) table[hf] = di;
             u32 literal = ref == 0 ? 1u : 0u;
             if (!literal) {
                 si++;
                 if (si >= count) { ok = 0; break; }
-                if ((u32)lzp_uni((int)ldg<u8>(src + si)) == 0xFFu) literal = 2;
+                if ((u32)uni((int)ldg<u8>(src + si)) == 0xFFu) literal = 2;
             }
             if (literal) {                                                        // 0xFC itself: its bucket was empty, or 0xFF follows
                 if (di >= dstEnd) { ok = 0; break; }
@@ -257,13 +246,13 @@ __global__ __launch_bounds__(64) void k_lzp_inverse(XfStage st, u32* __restrict_
                 if (other) break;
             }
             if (si >= count) { ok = 0; break; }
-            mLen += (u32)lzp_uni((int)ldg<u8>(src + si));
+            mLen += (u32)uni((int)ldg<u8>(src + si));
             si++;
             if (mLen > (u64)(dstEnd - di)) { ok = 0; break; }
             const u32 len = (u32)mLen, dist = di - ref;
             if (dist >= len) {
                 const u32 bulk = len & ~7u;
-                for (u32 i = 8u * (u32)lane; i < bulk; i += 512) lzp_st64(dst + di + i, lzp_ld64(dst + ref + i));
+                for (u32 i = 8u * (u32)lane; i < bulk; i += 512) st_u<u64>(dst + di + i, ldg_u<u64>(dst + ref + i));
                 if ((u32)lane < len - bulk) dst[di + bulk + lane] = dst[ref + bulk + lane];
             } else {
                 for (u32 i = (u32)lane; i < len; i += 64) dst[di + i] = dst[ref + i % dist];

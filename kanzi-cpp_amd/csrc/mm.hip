@@ -572,7 +572,7 @@ __global__ __launch_bounds__(MM_T) void k_mm_i_maps(XfStage st, u32* scratch, si
             const u32 A = C & 0x7F7F7F7Fu, B = (C & 0x80808080u) ^ ((sv >> 8) * 0x01010101u);
 #pragma unroll
             for (int k = 0; k < 64; k++) {
-                const u32 ak = (u32)__builtin_amdgcn_readlane((int)A, k), bk = (u32)__builtin_amdgcn_readlane((int)B, k);
+                const u32 ak = rl(A, k), bk = rl(B, k);
                 x = (((x & 0x7F7F7F7Fu) + ak) ^ (x & 0x80808080u)) ^ bk;
             }
         }
@@ -630,7 +630,7 @@ __global__ __launch_bounds__(MM_T) void k_mm_i_apply(XfStage st, u32* scratch, s
     const u8* inval = reinterpret_cast<const u8*>(ws + L.inval);
     for (u32 c = 0; c < dist && c < cntS; c++) {
         const u32 M = (cntS - c + dist - 1) / dist;
-        u32 v = (u32)__builtin_amdgcn_readfirstlane((int)inval[(size_t)sId * 16 + c]);
+        u32 v = uni((u32)inval[(size_t)sId * 16 + c]);
         for (u32 m0 = 0; m0 < M; m0 += 64) {
             const u32 m = m0 + lane;
             const u32 sv = (m < M) ? steps[k0 + c + m * dist] : 0u;
@@ -638,7 +638,7 @@ __global__ __launch_bounds__(MM_T) void k_mm_i_apply(XfStage st, u32* scratch, s
             u32 mine = 0;
 #pragma unroll
             for (int k = 0; k < 64; k++) {
-                const u32 ak = (u32)__builtin_amdgcn_readlane((int)A, k), bk = (u32)__builtin_amdgcn_readlane((int)B, k);
+                const u32 ak = rl(A, k), bk = rl(B, k);
                 v = ((v + ak) & 255u) ^ bk;
                 mine = (lane == (u32)k) ? v : mine;
             }

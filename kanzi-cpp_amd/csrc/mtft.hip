@@ -186,7 +186,7 @@ __global__ __launch_bounds__(64) void k_mtf_f_rank(XfView v, int perTiles, const
     }
     __syncthreads();
     u32 w = listw[lane];
-    u32 front = (u32)__builtin_amdgcn_readfirstlane((int)w) & 0xFF;   // symbol at list position 0 (uniform)
+    u32 front = uni(w) & 0xFF;   // symbol at list position 0 (uniform)
     const u32 cnt = (n - tbase < MT) ? (n - tbase) : MT;
     const u8* src = s + tbase;
     u8* dst = d + tbase;
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(64) void k_mtf_f_rank(XfView v, int perTiles, const
                 const u32 hz = (x - 0x01010101u) & ~x & 0x80808080u;
                 const u64 m = __ballot(hz != 0);                        // (never 0: the list holds every symbol)
                 const int lane0 = MTF_CTZ64(m);
-                const u32 hz0 = (u32)__builtin_amdgcn_readlane((int)hz, lane0);
+                const u32 hz0 = rl(hz, lane0);
                 const int byteIdx = MTF_CTZ32(hz0) >> 3;
                 out4 |= (u32)(4 * lane0 + byteIdx) << (8 * q);
                 w = mtf_rotate(w, lane, lane0, ((hz0 & (0u - hz0)) << 1) - 1u, front4);
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(64) void k_mtf_f_rank(XfView v, int perTiles, const
         for (int t = 0; t < (int)(MT / 256); t++) {
             u32 acc = 0;
             for (int l = 0; l < 64; l++) {
-                const u32 o = rank4((u32)__builtin_amdgcn_readlane((int)inr[t], l));
+                const u32 o = rank4(rl(inr[t], l));
                 acc = (lane == l) ? o : acc;
             }
             outr[t] = acc;
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(64) void k_mtf_f_rank(XfView v, int perTiles, const
         u32 in4;
         if (al) in4 = *reinterpret_cast<const u32*>(src + k);
         else in4 = (u32)src[k] | ((u32)src[k + 1] << 8) | ((u32)src[k + 2] << 16) | ((u32)src[k + 3] << 24);
-        in4 = (u32)__builtin_amdgcn_readfirstlane((int)in4);
+        in4 = uni(in4);
         const u32 out4 = rank4(in4);
         if (lane == 0) {
             if (al) *reinterpret_cast<u32*>(dst + k) = out4;
@@ -246,14 +246,14 @@ __global__ __launch_bounds__(64) void k_mtf_f_rank(XfView v, int perTiles, const
         }
     }
     for (; k < cnt; k++) {
-        const u32 c = (u32)__builtin_amdgcn_readfirstlane((int)src[k]);
+        const u32 c = uni((u32)src[k]);
         if (c == front) { if (lane == 0) dst[k] = 0; continue; }
         front = c;
         const u32 x = w ^ (c * 0x01010101u);
         const u32 hz = (x - 0x01010101u) & ~x & 0x80808080u;
         const u64 m = __ballot(hz != 0);
         const int lane0 = MTF_CTZ64(m);
-        const u32 hz0 = (u32)__builtin_amdgcn_readlane((int)hz, lane0);
+        const u32 hz0 = rl(hz, lane0);
         const int byteIdx = MTF_CTZ32(hz0) >> 3;
         if (lane == 0) dst[k] = (u8)(4 * lane0 + byteIdx);
         w = mtf_rotate(w, lane, lane0, ((hz0 & (0u - hz0)) << 1) - 1u, c << 24);
@@ -340,16 +340,16 @@ __global__ __launch_bounds__(64) void k_mtf_f_rank_par(XfView v, int perTiles, c
             if (lane == 0) pb = carry;
             const u64 m = __ballot(valid && bv != pb);
             if (lane == (int)c) headMask = m;
-            carry = (u32)__builtin_amdgcn_readlane((int)bv, 63);
+            carry = rl(bv, 63);
         }
         const u32 mine = mtf_popc64(headMask);
         const u32 incl = wave_incl_scan(mine);
         headBase = incl - mine;
-        const u32 nH = (u32)__builtin_amdgcn_readlane((int)incl, 63);
+        const u32 nH = rl(incl, 63);
         if (nH * 8u <= cnt * 7u) {
             for (u32 k = 0, c = 0; k < cnt; k += 64, c++) {
-                const u64 m = ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(headMask >> 32), (int)c) << 32) | (u64)(u32)__builtin_amdgcn_readlane((int)(u32)headMask, (int)c);
-                const u32 base = (u32)__builtin_amdgcn_readlane((int)headBase, (int)c);
+                const u64 m = ((u64)rl((u32)(headMask >> 32), c) << 32) | (u64)rl((u32)headMask, c);
+                const u32 base = rl(headBase, c);
                 const bool head = (m >> lane) & 1ull;
                 const u32 bv = head ? (u32)tileB[k + (u32)lane] : 0u;
                 KNZ_WAVE_ORDER();                        // (every lane has read its byte before one is overwritten)
@@ -395,7 +395,7 @@ __global__ __launch_bounds__(64) void k_mtf_f_rank_par(XfView v, int perTiles, c
             while (rem) {
                 const int kf = __builtin_ctzll((unsigned long long)rem);
                 rem &= rem - 1;
-                const u32 Lk = (u32)__builtin_amdgcn_readlane((int)Lc, kf);
+                const u32 Lk = rl(Lc, kf);
                 G += (Lk > Lc && lane > kf) ? 1u : 0u;
             }
             if (first) rank = Lc + G;
@@ -442,8 +442,8 @@ __global__ __launch_bounds__(64) void k_mtf_f_rank_par(XfView v, int perTiles, c
         // the ranks of the heads back to their places, last chunk first: chunk c reads tile bytes below 64 c + 64 and writes [64 c, 64 c + 64),
         // the chunks in front of it read below 64 c
         for (int c = (int)((cnt + 63u) / 64u) - 1; c >= 0; c--) {
-            const u64 m = ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(headMask >> 32), c) << 32) | (u64)(u32)__builtin_amdgcn_readlane((int)(u32)headMask, c);
-            const u32 base = (u32)__builtin_amdgcn_readlane((int)headBase, c);
+            const u64 m = ((u64)rl((u32)(headMask >> 32), c) << 32) | (u64)rl((u32)headMask, c);
+            const u32 base = rl(headBase, c);
             const bool head = (m >> lane) & 1ull;
             u32 r = 0;
             if (head) r = (u32)tileB[base + mtf_popc64(m & below)];
@@ -484,7 +484,7 @@ __global__ __launch_bounds__(64) void k_mtf_i_symbolic(XfView v, int perTiles, u
                 const int lane0 = (int)(r >> 2);
                 const int byteIdx = (int)(r & 3);
                 // (the byte is cut out on the vector unit, in every lane, before lane0's copy is read: two scalar instructions less)
-                const u32 c = (u32)__builtin_amdgcn_readlane((int)((w >> (8 * byteIdx)) & 0xFFu), lane0);
+                const u32 c = rl((w >> (8 * byteIdx)) & 0xFFu, lane0);
                 out4 |= c << (8 * q);
                 front = c;
                 w = mtf_rotate(w, lane, lane0, (u32)((1ull << (8 * (byteIdx + 1))) - 1ull), mtf_top(c));
@@ -509,7 +509,7 @@ __global__ __launch_bounds__(64) void k_mtf_i_symbolic(XfView v, int perTiles, u
             u32 acc = 0;
             for (u64 m = nz; m != 0; m &= m - 1) {
                 const int l = MTF_CTZ64(m);
-                const u32 o = ids4((u32)__builtin_amdgcn_readlane((int)x, l));
+                const u32 o = ids4(rl(x, l));
                 acc = (lane == l) ? o : acc;
             }
             const u64 bel = nz & belowL;
@@ -525,7 +525,7 @@ __global__ __launch_bounds__(64) void k_mtf_i_symbolic(XfView v, int perTiles, u
         u32 in4;
         if (al) in4 = *reinterpret_cast<const u32*>(src + k);
         else in4 = (u32)src[k] | ((u32)src[k + 1] << 8) | ((u32)src[k + 2] << 16) | ((u32)src[k + 3] << 24);
-        in4 = (u32)__builtin_amdgcn_readfirstlane((int)in4);
+        in4 = uni(in4);
         const u32 out4 = ids4(in4);
         if (lane == 0) {
             if (al) *reinterpret_cast<u32*>(dst + k) = out4;
@@ -533,11 +533,11 @@ __global__ __launch_bounds__(64) void k_mtf_i_symbolic(XfView v, int perTiles, u
         }
     }
     for (; k < cnt; k++) {
-        const u32 r = (u32)__builtin_amdgcn_readfirstlane((int)src[k]);
+        const u32 r = uni((u32)src[k]);
         if (r == 0) { if (lane == 0) dst[k] = (u8)front; continue; }
         const int lane0 = (int)(r >> 2);
         const int byteIdx = (int)(r & 3);
-        const u32 wl = (u32)__builtin_amdgcn_readlane((int)w, lane0);
+        const u32 wl = rl(w, lane0);
         const u32 c = (wl >> (8 * byteIdx)) & 0xFF;
         if (lane == 0) dst[k] = (u8)c;
         front = c;
@@ -598,10 +598,10 @@ __global__ __launch_bounds__(64) void k_mtf_i_symbolic_par(XfView v, int perTile
     const u32 evMine = mtf_popc64(evMask);
     const u32 evIncl = wave_incl_scan(evMine);
     const u32 evBase = evIncl - evMine;
-    const u32 nEv = (u32)__builtin_amdgcn_readlane((int)evIncl, 63);
+    const u32 nEv = rl(evIncl, 63);
     for (u32 k = 0, c = 0; k < cnt; k += 64, c++) {
-        const u64 m = ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(evMask >> 32), (int)c) << 32) | (u64)(u32)__builtin_amdgcn_readlane((int)(u32)evMask, (int)c);
-        const u32 base = (u32)__builtin_amdgcn_readlane((int)evBase, (int)c);
+        const u64 m = ((u64)rl((u32)(evMask >> 32), c) << 32) | (u64)rl((u32)evMask, c);
+        const u32 base = rl(evBase, c);
         const bool ev = (m >> lane) & 1ull;
         const u32 r = ev ? (u32)tileB[k + (u32)lane] : 0u;
         KNZ_WAVE_ORDER();                            // (every lane has read its byte before one is overwritten)
@@ -621,7 +621,7 @@ __global__ __launch_bounds__(64) void k_mtf_i_symbolic_par(XfView v, int perTile
         // find is read off at the end. Past its first event -- rank 0 from below -- a lane does nothing, except that a place 0 "finds"
         // an event in front of the chunk, which the step number tells. The trip count is uniform and rounded up: extra steps see rank 0)
         int q = (int)rho, rs = (int)rho;
-        const u32 steps = ((u32)__builtin_amdgcn_readfirstlane((int)nv) + 2u) & ~3u;      // >= nv - 1, a multiple of 4
+        const u32 steps = (uni(nv) + 2u) & ~3u;      // >= nv - 1, a multiple of 4
         for (u32 t = 0; t < steps; t += 4) {
 #pragma unroll
             for (int u = 0; u < 4; u++) {
@@ -682,8 +682,8 @@ __global__ __launch_bounds__(64) void k_mtf_i_symbolic_par(XfView v, int perTile
     }
     // ---- every byte of the tile: the id of the last event at or in front of it (none: the list's first id, 0)
     for (int c = (int)((cnt + 63u) / 64u) - 1; c >= 0; c--) {
-        const u64 m = ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(evMask >> 32), c) << 32) | (u64)(u32)__builtin_amdgcn_readlane((int)(u32)evMask, c);
-        const u32 base = (u32)__builtin_amdgcn_readlane((int)evBase, c);
+        const u64 m = ((u64)rl((u32)(evMask >> 32), c) << 32) | (u64)rl((u32)evMask, c);
+        const u32 base = rl(evBase, c);
         const u32 upto = base + mtf_popc64(m & (below | (1ull << lane)));       // events up to and including this byte
         const u32 id = upto ? (u32)tileB[upto - 1] : 0u;
         KNZ_WAVE_ORDER();

@@ -27,24 +27,17 @@ constexpr int PL_THREADS = 256;
 constexpr u32 PL_UNIT = 16;                       // elements of a lane's unit
 static_assert(PL_TILE % 8 == 0 && PL_TILE >= 8, "a tile holds whole elements of every width");
 
-// 16 bytes from and to any address, through the global address space (see ldg in common.hpp)
-#ifdef KNZ_EMU
-__device__ __forceinline__ void pl_ld16(u64 p, u32* w) { __builtin_memcpy(w, reinterpret_cast<const void*>((uintptr_t)p), 16); }
-__device__ __forceinline__ void pl_st16(u64 p, const u32* w) { __builtin_memcpy(reinterpret_cast<void*>((uintptr_t)p), w, 16); }
-#else
-typedef u32 pl_v4 __attribute__((ext_vector_type(4)));
-typedef pl_v4 __attribute__((aligned(1))) pl_v4_u;
-__device__ __forceinline__ void pl_ld16(u64 p, u32* w)
+// four words from and to any address
+__device__ __forceinline__ void pl_load(u64 p, u32* w)
 {
-    const pl_v4 v = *(const __attribute__((address_space(1))) pl_v4_u*)(uintptr_t)p;
+    const u32x4 v = ldg_u<u32x4>(reinterpret_cast<const void*>((uintptr_t)p));
     w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
 }
-__device__ __forceinline__ void pl_st16(u64 p, const u32* w)
+__device__ __forceinline__ void pl_store(u64 p, const u32* w)
 {
-    pl_v4 v; v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
-    *(__attribute__((address_space(1))) pl_v4_u*)(uintptr_t)p = v;
+    u32x4 v; v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+    stg_u<u32x4>(reinterpret_cast<void*>((uintptr_t)p), v);
 }
-#endif
 __device__ __forceinline__ void pl_byte(u64 dst, u64 src) { stg<u8>(reinterpret_cast<void*>((uintptr_t)dst), ldg<u8>(reinterpret_cast<const void*>((uintptr_t)src))); }
 
 // the 4 x 4 byte transpose: byte j of r_i = byte i of w_j (its own inverse)
@@ -106,8 +99,8 @@ __device__ __forceinline__ void pl_units(u64 inter, u64 plane, u64 m)
     for (int b = 0; b < B; b++) {
 #pragma unroll
         for (int j = 0; j < ELEM; j++) {
-            if (SPLIT) pl_ld16(inter + b * stepI + 16u * j, &w[b][4 * j]);
-            else pl_ld16(plane + b * stepP + j * m, &p[b][4 * j]);
+            if (SPLIT) pl_load(inter + b * stepI + 16u * j, &w[b][4 * j]);
+            else pl_load(plane + b * stepP + j * m, &p[b][4 * j]);
         }
     }
 #pragma unroll
@@ -115,8 +108,8 @@ __device__ __forceinline__ void pl_units(u64 inter, u64 plane, u64 m)
         if (SPLIT) pl_to_planes<ELEM>(w[b], p[b]); else pl_from_planes<ELEM>(p[b], w[b]);
 #pragma unroll
         for (int j = 0; j < ELEM; j++) {
-            if (SPLIT) pl_st16(plane + b * stepP + j * m, &p[b][4 * j]);
-            else pl_st16(inter + b * stepI + 16u * j, &w[b][4 * j]);
+            if (SPLIT) pl_store(plane + b * stepP + j * m, &p[b][4 * j]);
+            else pl_store(inter + b * stepI + 16u * j, &w[b][4 * j]);
         }
     }
 }

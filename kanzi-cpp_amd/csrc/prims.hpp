@@ -299,7 +299,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_count(SRC src, RsLayout L)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             const bool valid = dg[r] != 0xFFFFFFFFu;
-            const u32 d0 = (u32)__builtin_amdgcn_readfirstlane((int)dg[r]);        // (lane 0 is valid when any lane of the row is)
+            const u32 d0 = uni(dg[r]);        // (lane 0 is valid when any lane of the row is)
             const unsigned long long va = __ballot(valid);
             if (__ballot(valid && dg[r] != d0) == 0) { if (lane == 0 && va) cnt[wave][d0] += (u32)__popcll(va); }
             else if (valid) atomicAdd(&cnt[wave][dg[r]], 1u);
@@ -429,13 +429,9 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(SRC src, const u32* _
 // tiles in front of this one run on other XCDs).
 constexpr u32 RS_FLAG_AGG = 1u << 30, RS_FLAG_PRE = 2u << 30, RS_VAL_MASK = (1u << 30) - 1u;
 #ifdef KNZ_EMU
-__device__ __forceinline__ u32 rs_ld_dev(const u32* p) { return *p; }
-__device__ __forceinline__ void rs_st_dev(u32* p, u32 v) { *p = v; }
 #define RS_SPIN() do { fprintf(stderr, "k_rs_onesweep: a tile in front of this one has not run\n"); abort(); } while (0)
 #else
 #define RS_SPIN() __builtin_amdgcn_s_sleep(1)
-__device__ __forceinline__ u32 rs_ld_dev(const u32* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void rs_st_dev(u32* p, u32 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 #endif
 
 // digit counts of passes 0 .. nPass-1 (digit of pass p = (key >> (shift0 + 8 p)) & 255, the last pass masked with lastMask)
@@ -538,7 +534,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_onesweep(SRC src, const u32* 
     u32 mine = 0;
     if (tid < 256) { for (int w = 0; w < RS_WAVES; w++) { c[w] = cnt[w][tid]; mine += c[w]; } }
     u32* stat = L.tileHist + ((size_t)L.tileOff[sgm] + t) * 256 + (tid & 255);     // this tile's status word for digit tid
-    if (tid < 256) rs_st_dev(stat, (t == 0 ? RS_FLAG_PRE : RS_FLAG_AGG) | mine);
+    if (tid < 256) st_agent(stat, (t == 0 ? RS_FLAG_PRE : RS_FLAG_AGG) | mine);
     u32 tot;
     const u32 incl = sc_block_incl<SCAN_SUM_EXCL, RS_WAVES>(mine, wsum, &tot);
     if (tid < 256) inclAll[tid] = incl;
@@ -558,11 +554,11 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_onesweep(SRC src, const u32* 
         if (t != 0) {
             for (u32 q = 1; q <= t; q++) {
                 u32 v;
-                while (((v = rs_ld_dev(stat - (size_t)q * 256)) >> 30) == 0) RS_SPIN();
+                while (((v = ld_agent(stat - (size_t)q * 256)) >> 30) == 0) RS_SPIN();
                 excl += v & RS_VAL_MASK;
                 if (v & RS_FLAG_PRE) break;
             }
-            rs_st_dev(stat, RS_FLAG_PRE | (excl + mine));
+            st_agent(stat, RS_FLAG_PRE | (excl + mine));
         }
         gBase[tid] = L.histAll[((size_t)pass * L.nSeg + sgm) * 256 + tid] + excl;
     }

@@ -35,7 +35,6 @@ constexpr u64 RANGE_BOTTOM = 0xFFFFull;
 constexpr u64 RANGE_MASK = 0x0FFFFFFF00000000ull;
 constexpr int RCH = 16;                  // chunks per encoder wave
 
-__device__ __forceinline__ u32 range_rl(u32 v, u32 l) { return (u32)__builtin_amdgcn_readlane((int)v, (int)l); }
 
 // ------------------------------------------------------------------------------------------------
 // statistics + header
@@ -402,7 +401,7 @@ __global__ __launch_bounds__(64) void k_range_decode(BitSrc src, DecBlock* __res
         if (asz == 1) {
             const u64 any = __ballot(present != 0);
             const int fl = __ffsll((long long)any) - 1;
-            const u32 sym = 4u * (u32)fl + (u32)(__ffs((int)range_rl(present, (u32)fl)) - 1);
+            const u32 sym = 4u * (u32)fl + (u32)(__ffs((int)rl(present, (u32)fl)) - 1);
             for (u32 i = (u32)lane; i < n; i += 64) block[start + i] = (u8)sym;
             start += n;
             continue;
@@ -507,8 +506,8 @@ __global__ __launch_bounds__(64) void k_range_decode(BitSrc src, DecBlock* __res
                     const u32 wi = (u32)((pos >> 5) - wbase);
                     if (wi - winBase >= 64) { winCur = winNext; winBase += 64; winNext = loadWin(winBase + 64); }
                     const u32 i = wi - winBase;
-                    const u32 a = range_rl(winCur, i);
-                    const u32 c = (i + 1 < 64) ? range_rl(winCur, (i + 1) & 63) : range_rl(winNext, 0);
+                    const u32 a = rl(winCur, i);
+                    const u32 c = (i + 1 < 64) ? rl(winCur, (i + 1) & 63) : rl(winNext, 0);
                     const u32 unit = (u32)(((((u64)a << 32) | c) << (pos & 31)) >> 36);
                     pos += 28;
                     code = (code << 28) | unit;

@@ -156,7 +156,7 @@ __global__ __launch_bounds__(64) void k_rlt_forward(XfStage st)
             const u64 m = __ballot(!cont);
             if (m == 0) { srcIdx += 256; run += 256; continue; }
             const int l = __ffsll((long long)m) - 1;
-            const u32 wl = (u32)__builtin_amdgcn_readlane((int)w, l);
+            const u32 wl = rl(w, l);
             const u32 diff = wl ^ v4;
             const int n = (diff == 0) ? 4 : ((__ffs((int)diff) - 1) >> 3);
             srcIdx += 4 * l + n;

@@ -52,20 +52,6 @@ constexpr size_t RX_BLOCK_BYTES = (size_t)RX_MATCH_WORDS * 4 + ((size_t)RX_LIT_P
 
 __host__ __device__ inline u32 rx_max_encoded(u32 n) { return n + (n < 32768 ? 1024u : n >> 5); }            // = knz_max_encoded_len(KNZ_T_ROLZX, n)
 
-// unaligned loads of block text through the global address space (see ldg in common.hpp)
-#ifdef KNZ_EMU
-__device__ __forceinline__ u64 rx_ld64(const u8* p) { u64 v; __builtin_memcpy(&v, p, 8); return v; }
-__device__ __forceinline__ u32 rx_ld32(const u8* p) { u32 v; __builtin_memcpy(&v, p, 4); return v; }
-#else
-typedef u64 __attribute__((aligned(1))) rx_u64_u;
-typedef u32 __attribute__((aligned(1))) rx_u32_u;
-__device__ __forceinline__ u64 rx_ld64(const u8* p) { return *(const __attribute__((address_space(1))) rx_u64_u*)(uintptr_t)p; }
-__device__ __forceinline__ u32 rx_ld32(const u8* p) { return *(const __attribute__((address_space(1))) rx_u32_u*)(uintptr_t)p; }
-#endif
-__device__ __forceinline__ void rx_st64(u8* p, u64 v) { __builtin_memcpy(p, &v, 8); }
-__device__ __forceinline__ void rx_st32(u8* p, u32 v) { __builtin_memcpy(p, &v, 4); }
-__device__ __forceinline__ void rx_wave_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
-
 struct RxTables { u32* matches; u16* lit; u16* idx; };
 
 __device__ __forceinline__ RxTables rx_tables(u8* base, int slot)
@@ -85,7 +71,7 @@ __device__ void rx_chunk_reset(const RxTables& t, int lane)
     for (u32 i = (u32)lane; i < RX_MATCH_WORDS / 4; i += 64) m[i] = make_uint4(0, 0, 0, 0);
     u32* p = reinterpret_cast<u32*>(t.lit);                                       // (the two probability sets are adjacent)
     for (u32 i = (u32)lane; i < (RX_LIT_PROBS + RX_IDX_PROBS) / 2; i += 64) p[i] = 0x7FFF7FFFu;
-    rx_wave_fence();
+    wave_fence();
 }
 
 // ROLZCodec::getKey1 / getKey2 of the bytes at p - delta, from the 8 bytes in front of p (w, little endian)
@@ -112,13 +98,13 @@ __device__ __forceinline__ void rx_encode(RxEnc& e, u16* probs, u32 val, int lan
     }
 #pragma unroll
     for (int i = 0; i < NB; i++) {
-        const u32 pi = (u32)__builtin_amdgcn_readlane((int)p, i);
+        const u32 pi = rl(p, i);
         const u64 split = (((e.high - e.low) >> 4) * (u64)(pi >> 4)) >> 8;
         if ((val >> (NB - 1 - i)) & 1) e.high = e.low + split;
         else e.low += split + 1;
         while (((e.low ^ e.high) >> 24) == 0) {
             if (e.full || e.idx + 4 >= e.lim) e.full = 1;                          // the bytes written reach `count`: refused
-            else { if (lane == 0) rx_st32(e.buf + e.idx, bswap32((u32)(e.high >> 32))); e.idx += 4; }
+            else { if (lane == 0) st_u<u32>(e.buf + e.idx, bswap32((u32)(e.high >> 32))); e.idx += 4; }
             e.low <<= 32;
             e.high = (e.high << 32) | 0xFFFFFFFFull;
         }
@@ -128,7 +114,7 @@ __device__ __forceinline__ void rx_encode(RxEnc& e, u16* probs, u32 val, int lan
 // ROLZCodec2::findMatch at `pos` of the chunk `s` (which ends at `end`): the reference's return value, -1 for no match. Registers `pos`.
 __device__ int rx_find_match(const RxTables& t, u8* counters, const u8* s, u32 pos, u32 end, u32 key, int minMatch, int lane)
 {
-    const u32 hash32 = rx_hash(rx_ld32(s + pos));
+    const u32 hash32 = rx_hash(ldg_u<u32>(s + pos));
     const int maxMatch = (int)(end - pos < (u32)RX_MAX_MATCH ? end - pos : (u32)RX_MAX_MATCH) - 8;
     const u32 counter = counters[key];
     u32* row = t.matches + ((size_t)key << RX_LOG_POS);
@@ -139,7 +125,7 @@ __device__ int rx_find_match(const RxTables& t, u8* counters, const u8* s, u32 p
             const u8* a = s + (e & ~RX_HASH_MASK);
             const u8* c = s + pos;
             while (n < maxMatch) {
-                const u64 x = rx_ld64(a + n) ^ rx_ld64(c + n);
+                const u64 x = ldg_u<u64>(a + n) ^ ldg_u<u64>(c + n);
                 if (x) { n += (__ffsll((long long)x) - 1) >> 3; break; }
                 n += 8;
             }
@@ -157,7 +143,7 @@ __device__ int rx_find_match(const RxTables& t, u8* counters, const u8* s, u32 p
     const int bestLen = (int)(best >> 8), bestIdx = (int)(RX_POS_MASK - (best & 0xFF));
     const u32 next = (counter + 1) & RX_POS_MASK;
     if (lane == 0) { counters[key] = (u8)next; row[next] = hash32 | pos; }
-    rx_wave_fence();
+    wave_fence();
     return bestLen < minMatch ? -1 : (bestIdx << 16) | (bestLen - minMatch);
 }
 
@@ -181,7 +167,7 @@ __global__ __launch_bounds__(64) void k_rolzx_forward(XfStage st, u8* __restrict
             __syncthreads();
             const u32 bulk = count & ~7u;
             for (u32 i = 8u * (u32)lane; i < bulk; i += 512) {
-                const u64 w = rx_ld64(src + i);
+                const u64 w = ldg_u<u64>(src + i);
 #pragma unroll
                 for (int k = 0; k < 8; k++) atomicAdd(&lds[(u32)(w >> (8 * k)) & 255], 1u);
             }
@@ -197,7 +183,7 @@ __global__ __launch_bounds__(64) void k_rolzx_forward(XfStage st, u8* __restrict
         else if (dt == DT_DNA) { delta = 8; minMatch = 7; flags = 4; }
         for (int i = lane; i < (int)(RX_KEYS / 4); i += 64) lds[i] = 0;
         __syncthreads();
-        if (lane == 0) { rx_st32(dst, bswap32(count)); dst[4] = (u8)flags; }
+        if (lane == 0) { st_u<u32>(dst, bswap32(count)); dst[4] = (u8)flags; }
         RxEnc e;
         e.low = 0; e.high = RX_TOP; e.idx = 5; e.lim = count; e.full = 0; e.buf = dst;
         const u32 srcEnd = count - 4;
@@ -212,7 +198,7 @@ __global__ __launch_bounds__(64) void k_rolzx_forward(XfStage st, u8* __restrict
             const u32 n = srcEnd - startChunk < 8u ? srcEnd - startChunk : 8u;
             for (u32 j = 0; j < n && !e.full; j++, srcIdx++) rx_encode<9>(e, t.lit, 0x100u | ldg<u8>(s + srcIdx), lane);
             while (srcIdx < sizeChunk && !e.full) {
-                const u64 w = rx_ld64(s + srcIdx - 8);                             // (srcIdx >= 8 here)
+                const u64 w = ldg_u<u64>(s + srcIdx - 8);                             // (srcIdx >= 8 here)
                 const u32 prev = (u32)(w >> 56);
                 const int match = rx_find_match(t, counters, s, srcIdx, sizeChunk, rx_key(w, delta), minMatch, lane);
                 if (match < 0) {
@@ -229,7 +215,7 @@ __global__ __launch_bounds__(64) void k_rolzx_forward(XfStage st, u8* __restrict
         for (int i = 0; i < 4 && !e.full; i++, srcIdx++)                            // the last literals: no reset, the chunk's contexts
             rx_encode<9>(e, t.lit + ((u32)ldg<u8>(s + srcIdx - 1) << 9), 0x100u | ldg<u8>(s + srcIdx), lane);
         if (!e.full && e.idx + 8 < count) {                                         // dispose(); the result is dstIdx < count
-            if (lane == 0) rx_st64(dst + e.idx, __builtin_bswap64(e.low));
+            if (lane == 0) st_u<u64>(dst + e.idx, __builtin_bswap64(e.low));
             d = e.idx + 8;
             ok = 1;
         }
@@ -257,7 +243,7 @@ __device__ __forceinline__ u32 rx_decode(RxDec& r, u16* probs, int lane)
         const u32 sub = c1 & 7;
         const int owner = (int)(c1 >> 3);
         const u32 word = (sub & 4) ? ((sub & 2) ? mine.w : mine.z) : ((sub & 2) ? mine.y : mine.x);
-        const u32 p = (u32)__builtin_amdgcn_readlane((int)((word >> (16 * (sub & 1))) & 0xFFFF), owner);
+        const u32 p = rl((word >> (16 * (sub & 1))) & 0xFFFF, owner);
         const u64 mid = r.low + ((((r.high - r.low) >> 4) * (u64)(p >> 4)) >> 8);
         u32 np;
         if (mid >= r.cur) { r.high = mid; np = (u32)((int)p - (((int)p - 0xFFFF + 32) >> 5)) & 0xFFFF; c1 += c1 + 1; }
@@ -273,7 +259,7 @@ __device__ __forceinline__ u32 rx_decode(RxDec& r, u16* probs, int lane)
             if (r.idx + 4 > r.count) { r.err = 1; break; }                         // 4 bytes that do not lie inside `count`: refused
             r.low = (r.low << 32) & RX_TOP;
             r.high = ((r.high << 32) | 0xFFFFFFFFull) & RX_TOP;
-            r.cur = ((r.cur << 32) | (u64)bswap32(rx_ld32(r.buf + r.idx))) & RX_TOP;
+            r.cur = ((r.cur << 32) | (u64)bswap32(ldg_u<u32>(r.buf + r.idx))) & RX_TOP;
             r.idx += 4;
         }
         if (r.err) break;
@@ -296,14 +282,14 @@ __global__ __launch_bounds__(64) void k_rolzx_inverse(XfStage st, u8* __restrict
     for (int i = lane; i < (int)(RX_KEYS / 4); i += 64) lds[i] = 0;
     __syncthreads();
     u32 ok = 0, out = 0;
-    const u32 dstEnd = count >= 5 ? bswap32(rx_ld32(src)) : 0u;
+    const u32 dstEnd = count >= 5 ? bswap32(ldg_u<u32>(src)) : 0u;
     if (count >= 13 && count <= RX_MAX_BLOCK && dstEnd != 0 && dstEnd <= 0x7FFFFFFFu && dstEnd <= st.cap[b]) {
         const u32 flags = ldg<u8>(src + 4);
         u32 delta = 2, minMatch = 3;
         if ((flags & 0x0E) == 8) delta = 3;
         else if ((flags & 0x0E) == 4) { delta = 8; minMatch = 7; }
         RxDec r;
-        r.low = 0; r.high = RX_TOP; r.cur = __builtin_bswap64(rx_ld64(src + 5)); r.idx = 13; r.count = count; r.err = 0; r.buf = src;
+        r.low = 0; r.high = RX_TOP; r.cur = __builtin_bswap64(ldg_u<u64>(src + 5)); r.idx = 13; r.count = count; r.err = 0; r.buf = src;
         u32 sizeChunk = dstEnd < RX_CHUNK ? dstEnd : RX_CHUNK, startChunk = 0;
         ok = 1;
         while (startChunk < dstEnd && ok) {
@@ -329,8 +315,8 @@ __global__ __launch_bounds__(64) void k_rolzx_inverse(XfStage st, u8* __restrict
                 if (dstIdx >= room) { ok = 0; break; }                             // (the reference would write behind the block)
                 const u32 savedIdx = dstIdx;
                 if (!haveW) {
-                    rx_wave_fence();                                               // the bytes lane 0 stored, the copy
-                    w = rx_ld64(o + dstIdx - 8);                                   // (dstIdx >= 8, or bytes of the chunk before)
+                    wave_fence();                                               // the bytes lane 0 stored, the copy
+                    w = ldg_u<u64>(o + dstIdx - 8);                                   // (dstIdx >= 8, or bytes of the chunk before)
                     haveW = true;
                 }
                 const u32 key = rx_key(w, delta);
@@ -348,21 +334,21 @@ __global__ __launch_bounds__(64) void k_rolzx_inverse(XfStage st, u8* __restrict
                     if (dstIdx + matchLen + minMatch > room) { ok = 0; break; }                    // (the reference would write behind the block)
                     const u32 matchIdx = rx_decode<RX_LOG_POS>(r, t.idx + (prev << RX_LOG_POS), lane);
                     if (r.err) { ok = 0; break; }
-                    rx_wave_fence();                                               // the ring and counter entries, and the literals, lane 0 stored
+                    wave_fence();                                               // the ring and counter entries, and the literals, lane 0 stored
                     const u32 ref = row[((u32)counters[key] - matchIdx) & RX_POS_MASK];
                     const u32 len = matchLen + minMatch;
                     // emitCopy: a byte-exact overlapping copy (ref < dstIdx: a position the decoder stored, or 0)
                     const u32 dist = dstIdx - ref;
                     if (dist >= len) {
                         const u32 bulk = len & ~7u;
-                        for (u32 i = 8u * (u32)lane; i < bulk; i += 512) rx_st64(o + dstIdx + i, rx_ld64(o + ref + i));
+                        for (u32 i = 8u * (u32)lane; i < bulk; i += 512) st_u<u64>(o + dstIdx + i, ldg_u<u64>(o + ref + i));
                         if ((u32)lane < len - bulk) o[dstIdx + bulk + lane] = o[ref + bulk + lane];
                     } else {
                         for (u32 i = (u32)lane; i < len; i += 64) o[dstIdx + i] = o[ref + i % dist];
                     }
                     dstIdx += len;
                     haveW = false;
-                    rx_wave_fence();                                               // every lane has read the ring before lane 0 stores into it
+                    wave_fence();                                               // every lane has read the ring before lane 0 stores into it
                 }
                 if (lane == 0) {
                     const u32 c = (u32)counters[key] + 1;

@@ -42,19 +42,19 @@ __global__ __launch_bounds__(64) void k_sbrt(XfStage st, int mode)
         u32 outb = 0;
         for (int t = 0; t < m; t++) {
             const u32 i = (u32)(i0 + t);
-            const u32 v = (u32)__builtin_amdgcn_readlane((int)inb, t);
+            const u32 v = rl(inb, t);
             u32 r, c;
             if (!INV) {
                 c = v;
                 const u32 hitk = (sym[0] == c) ? 1u : (sym[1] == c) ? 2u : (sym[2] == c) ? 3u : (sym[3] == c) ? 4u : 0u;
                 const u64 bal = __ballot(hitk != 0);
                 const int fl = __ffsll((long long)bal) - 1;
-                r = 4u * (u32)fl + (u32)__builtin_amdgcn_readlane((int)hitk, fl) - 1u;
+                r = 4u * (u32)fl + rl(hitk, fl) - 1u;
             } else {
                 r = v;
-                c = (u32)__builtin_amdgcn_readlane((int)pick4(sym, r & 3), (int)(r >> 2));
+                c = rl(pick4(sym, r & 3), (int)(r >> 2));
             }
-            const u32 pc = (u32)__builtin_amdgcn_readlane((int)pick4(last, c & 3), (int)(c >> 2));
+            const u32 pc = rl(pick4(last, c & 3), (int)(c >> 2));
             const u32 qc = ((useTime ? i : 0u) + (usePrev ? pc : 0u)) >> shift;
             if ((u32)lane == (c >> 2)) {
 #pragma unroll

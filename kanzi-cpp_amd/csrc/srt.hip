@@ -279,7 +279,7 @@ constexpr u64 SRT_END = 0ull;                                   // what a symbol
 #define KNZ_LDS_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
 #define KNZ_LDS_STORE(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
 #endif
-__device__ __forceinline__ u32 lds_peek(const u32* p) { return (u32)__builtin_amdgcn_readfirstlane((int)KNZ_LDS_LOAD(p)); }
+__device__ __forceinline__ u32 lds_peek(const u32* p) { return uni(KNZ_LDS_LOAD(p)); }
 __device__ __forceinline__ void lds_poke(u32* p, u32 v) { KNZ_LDS_STORE(p, v); }
 
 // Lane-level register edits with wave uniform operands. (This compiler has no writelane builtin; the lane select goes through m0,
@@ -295,21 +295,20 @@ __device__ __forceinline__ u32 srt_lane_merge(u32 w, u32 shifted, u32 n, bool in
 }
 #else
 // (an "s" operand the compiler believes divergent would come out as a VGPR: readfirstlane, which folds away for scalar values)
-__device__ __forceinline__ u32 srt_uni(u32 v) { return (u32)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ u32 srt_writelane(u32 val, u32 sel, u32 old)
 {
-    val = srt_uni(val); sel = srt_uni(sel);
+    val = uni(val); sel = uni(sel);
     asm("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(old) : "s"(val), "s"(sel) : "m0");
     return old;
 }
 __device__ __forceinline__ void srt_writelane2(u32& a, u32& b, u32 va, u32 vb, u32 sel)
 {
-    va = srt_uni(va); vb = srt_uni(vb); sel = srt_uni(sel);
+    va = uni(va); vb = uni(vb); sel = uni(sel);
     asm("s_mov_b32 m0, %4\n\tv_writelane_b32 %0, %2, m0\n\tv_writelane_b32 %1, %3, m0" : "+v"(a), "+v"(b) : "s"(va), "s"(vb), "s"(sel) : "m0");
 }
 __device__ __forceinline__ u32 srt_lane_merge(u32 w, u32 shifted, u32 n, bool insert, u32 ins)
 {
-    n = srt_uni(n); ins = srt_uni(ins);
+    n = uni(n); ins = uni(ins);
     const u64 below = (1ull << n) - 1ull;                        // (n < 64)
     if (insert) asm("s_mov_b32 m0, %4\n\tv_cndmask_b32 %0, %0, %1, %2\n\tv_writelane_b32 %0, %3, m0" : "+v"(w) : "v"(shifted), "s"(below), "s"(ins), "s"(n) : "m0");
     else asm("v_cndmask_b32 %0, %0, %1, %2" : "+v"(w) : "v"(shifted), "s"(below));
@@ -483,13 +482,13 @@ __device__ __forceinline__ void srt_list_drop(u32 (&a)[4], u32 rank, bool insert
     const u32 s0 = (u32)__builtin_amdgcn_update_dpp(0, (int)a[0], 0x130, 0xF, 0xF, true);   // wave_shl:1 (lane i <- lane i+1)
     if (__builtin_expect(j == 0, 1)) { a[0] = srt_lane_merge(a[0], s0, n, insert, ins); return; }
     // registers below the rank's move as a whole and take their last entry from the next one's first
-    a[0] = srt_writelane((u32)__builtin_amdgcn_readlane((int)a[1], 0), 63u, s0);
+    a[0] = srt_writelane(rl(a[1], 0), 63u, s0);
     const u32 s1 = (u32)__builtin_amdgcn_update_dpp(0, (int)a[1], 0x130, 0xF, 0xF, true);
     if (j == 1) { a[1] = srt_lane_merge(a[1], s1, n, insert, ins); return; }
-    a[1] = srt_writelane((u32)__builtin_amdgcn_readlane((int)a[2], 0), 63u, s1);
+    a[1] = srt_writelane(rl(a[2], 0), 63u, s1);
     const u32 s2 = (u32)__builtin_amdgcn_update_dpp(0, (int)a[2], 0x130, 0xF, 0xF, true);
     if (j == 2) { a[2] = srt_lane_merge(a[2], s2, n, insert, ins); return; }
-    a[2] = srt_writelane((u32)__builtin_amdgcn_readlane((int)a[3], 0), 63u, s2);
+    a[2] = srt_writelane(rl(a[3], 0), 63u, s2);
     const u32 s3 = (u32)__builtin_amdgcn_update_dpp(0, (int)a[3], 0x130, 0xF, 0xF, true);
     a[3] = srt_lane_merge(a[3], s3, n, insert, ins);
 }
@@ -564,7 +563,7 @@ __device__ __forceinline__ u32 srt_hot_runs(u32& a0, u32& outLen, u32& outSym, u
         const u32 full = z + 1;
         if (full >= remaining) return 1;
         if (term - 1u >= lim1) return 1;
-        const u32 e1 = (u32)__builtin_amdgcn_readlane((int)a0, 1);
+        const u32 e1 = rl(a0, 1);
         remaining -= full;
         const u64 rcn = *reinterpret_cast<const u64*>(reinterpret_cast<const char*>(q) + e1);
         const u32 en = e1 + 8u;
@@ -574,7 +573,7 @@ __device__ __forceinline__ u32 srt_hot_runs(u32& a0, u32& outLen, u32& outSym, u
         const u32 s0 = (u32)__builtin_amdgcn_update_dpp(0, (int)a0, 0x130, 0xF, 0xF, true);
         a0 = srt_lane_merge(a0, s0, term, true, ec);
         ec = en;
-        z = (u32)__builtin_amdgcn_readfirstlane((int)(u32)rcn); term = (u32)__builtin_amdgcn_readfirstlane((int)(u32)(rcn >> 32));
+        z = uni((u32)rcn); term = uni((u32)(rcn >> 32));
         if ((en & 0x7Fu) == 0 || (head & 63u) == 0) return 2;
     }
 }
@@ -619,8 +618,8 @@ __global__ __launch_bounds__(192) void k_srt_inverse(XfStage st, SrtInv w)
         return r;
     };
     u32 ec;                                                     // the front's entry (its record already taken)
-    const u64 rc0 = fetch((u32)__builtin_amdgcn_readlane((int)a[0], 0), ec);
-    u32 z = (u32)__builtin_amdgcn_readfirstlane((int)(u32)rc0), term = (u32)__builtin_amdgcn_readfirstlane((int)(u32)(rc0 >> 32));
+    const u64 rc0 = fetch(rl(a[0], 0), ec);
+    u32 z = uni((u32)rc0), term = uni((u32)(rc0 >> 32));
     u32 how = 1;
     bool open = true;                                           // (false: the block is complete, or given up)
     u32 lim1 = (nbSymbols < 64u ? nbSymbols : 64u) - 1u;        // the ranks the short way handles: 1 .. lim1
@@ -636,7 +635,7 @@ __global__ __launch_bounds__(192) void k_srt_inverse(XfStage st, SrtInv w)
         // (the long way, any run.) Whatever this run's record says (the front goes back to a rank >= 1, or leaves the list), the symbol
         // of the NEXT run is the one behind the front now: its record is read first and picked up at the bottom, behind the work on this run.
         u32 en;
-        const u64 rcn = fetch((u32)__builtin_amdgcn_readlane((int)a[0], 1), en);
+        const u64 rcn = fetch(rl(a[0], 1), en);
         a[0] = srt_writelane(en, 1u, a[0]);
         const u32 full = z + 1;
         const u32 emit = full < remaining ? full : remaining;
@@ -652,7 +651,7 @@ __global__ __launch_bounds__(192) void k_srt_inverse(XfStage st, SrtInv w)
             srt_list_drop(a, term, true, ec);
         }
         ec = en;
-        z = (u32)__builtin_amdgcn_readfirstlane((int)(u32)rcn); term = (u32)__builtin_amdgcn_readfirstlane((int)(u32)(rcn >> 32));
+        z = uni((u32)rcn); term = uni((u32)(rcn >> 32));
         if (nbSymbols < 2) break;
     }
     if (open) {
@@ -695,7 +694,7 @@ __global__ __launch_bounds__(192) void k_srt_inverse_general(XfStage st, SrtInv 
     // the symbol's next record; it counts as taken
     auto fetch = [&](u32 sym) -> u64 {
         const u32 sl = sym & 63u, sh = (sym >> 3) & 0x18u;
-        const u32 x = (u32)__builtin_amdgcn_readlane((int)qv, (int)sl);
+        const u32 x = rl(qv, sl);
         const u32 k8 = (x >> sh) & 0xFFu;
         const u64 r = *reinterpret_cast<const u64*>(reinterpret_cast<const char*>(L.q) + ((sym << 8) | k8));
         u32 nx = x + (8u << sh);
@@ -706,14 +705,14 @@ __global__ __launch_bounds__(192) void k_srt_inverse_general(XfStage st, SrtInv 
         qv = srt_writelane(nx, sl, qv);
         return r;
     };
-    u32 c = (u32)__builtin_amdgcn_readfirstlane((int)lw) & 0xFFu;
+    u32 c = uni(lw) & 0xFFu;
     const u64 rc0 = fetch(c);
-    u32 z = (u32)__builtin_amdgcn_readfirstlane((int)(u32)rc0), term = (u32)__builtin_amdgcn_readfirstlane((int)(u32)(rc0 >> 32));
+    u32 z = uni((u32)rc0), term = uni((u32)(rc0 >> 32));
     for (;;) {
         // Whatever this run's record says (c goes back to a rank >= 1, or leaves the list), the symbol of the NEXT run is the one
         // behind the front now -- a stale entry when the list is down to one symbol, read all the same (SRT.cpp:189-199 goes on
         // with r2s[1] whatever it holds): its record is read first and picked up at the bottom, behind the work on this run.
-        const u32 cn = ((u32)__builtin_amdgcn_readfirstlane((int)lw) >> 8) & 0xFFu;
+        const u32 cn = (uni(lw) >> 8) & 0xFFu;
         const u64 rcn = fetch(cn);
         const u32 full = z + 1;
         const u32 emit = full < remaining ? full : remaining;
@@ -728,7 +727,7 @@ __global__ __launch_bounds__(192) void k_srt_inverse_general(XfStage st, SrtInv 
             lw = srt_drop_front(lw, lane, term, 5u, c);
         }
         c = cn;
-        z = (u32)__builtin_amdgcn_readfirstlane((int)(u32)rcn); term = (u32)__builtin_amdgcn_readfirstlane((int)(u32)(rcn >> 32));
+        z = uni((u32)rcn); term = uni((u32)(rcn >> 32));
     }
     srt_chain_close(L, io, 1u, lane);
 }
@@ -880,7 +879,7 @@ __global__ __launch_bounds__(64) void k_srt_f_rank(XfStage st, SrtWs w)
     }
     __syncthreads();
     u32 lw = listw[lane];
-    u32 front = (u32)__builtin_amdgcn_readfirstlane((int)lw) & 0xFF;
+    u32 front = uni(lw) & 0xFF;
     u8* dst = st.dst[b];
     const u8* tb = reinterpret_cast<const u8*>(tile);
     u32 cur = 256, curCnt = 0;
@@ -898,7 +897,7 @@ __global__ __launch_bounds__(64) void k_srt_f_rank(XfStage st, SrtWs w)
             const u32 hz = (x - 0x01010101u) & ~x & 0x80808080u;
             const u64 m = __ballot(hz != 0);
             const int lane0 = __ffsll((long long)m) - 1;
-            const u32 hz0 = (u32)__builtin_amdgcn_readlane((int)hz, lane0);
+            const u32 hz0 = rl(hz, lane0);
             const int byteIdx = (__ffs((int)hz0) - 1) >> 3;
             if (lane == 0) dst[base[c] + curCnt] = (u8)(4 * lane0 + byteIdx);
             lw = srt_to_front(lw, lane, lane0, byteIdx, c);

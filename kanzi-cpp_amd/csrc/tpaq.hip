@@ -205,13 +205,11 @@ int tpaq_slice_blocks(size_t tableBytes, int nBlocks)
 // ------------------------------------------------------------------------------------------------
 // table accesses
 // ------------------------------------------------------------------------------------------------
+// loads are ld_agent (common.hpp); the store is relaxed at WORKGROUP scope, not agent scope like the loads: kept as found
+template <class T> __device__ __forceinline__ void st_wg(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 #ifdef KNZ_EMU
-template <class T> __device__ __forceinline__ T tq_ld(const T* p) { return *p; }
-template <class T> __device__ __forceinline__ void tq_st(T* p, T v) { *p = v; }
 __device__ __forceinline__ void tq_drain() { (void)__ballot(1); }
 #else
-template <class T> __device__ __forceinline__ T tq_ld(const T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <class T> __device__ __forceinline__ void tq_st(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void tq_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 #endif
 
@@ -288,7 +286,7 @@ struct TpaqPred {
 
     __device__ __forceinline__ u32 get() const { return pr; }
 
-    __device__ __forceinline__ u32 rl(u32 v, int l) const { return cm_rl(v, (u32)l); }
+    __device__ __forceinline__ u32 rl(u32 v, int l) const { return knz::rl(v, (u32)l); }
 
     static __device__ __forceinline__ u32 create_context(u32 ctxId, u32 cx)
     {
@@ -302,7 +300,7 @@ struct TpaqPred {
         return (u32)(h >> 1) ^ (u32)(h >> 9) ^ (x >> 2) ^ (y >> 3) ^ TPAQ_HASH;
     }
 
-    __device__ __forceinline__ u32 buf_at(u32 i) const { return (u32)tq_ld(buffer + (i & bufMask)); }
+    __device__ __forceinline__ u32 buf_at(u32 i) const { return (u32)ld_agent(buffer + (i & bufMask)); }
 
     // TPAQPredictor::findMatch (:545-602). The 8-byte big-endian compare: lane k < 8 holds byte k of both words; the lowest 16 bits of
     // the difference that are not zero belong to the highest k that differs.
@@ -313,7 +311,7 @@ struct TpaqPred {
             matchPos++;
             return;
         }
-        matchPos = (int)cm_uni((u32)tq_ld(hashes + hash));
+        matchPos = (int)uni((u32)ld_agent(hashes + hash));
         if (matchPos == 0 || (u32)(pos - matchPos) > bufMask) return;
         int r = matchLen + 2;
         while (r + 6 <= TPAQ_MAX_LENGTH) {
@@ -321,7 +319,7 @@ struct TpaqPred {
             const u32 p1 = (u32)(matchPos - r - 7) & bufMask;
             if (p0 > bufMask - 7 || p1 > bufMask - 7) break;
             bool ne = false;
-            if (lane < 8) ne = tq_ld(buffer + p0 + lane) != tq_ld(buffer + p1 + lane);
+            if (lane < 8) ne = ld_agent(buffer + p0 + lane) != ld_agent(buffer + p1 + lane);
             const u32 diff = (u32)__ballot(ne) & 0xFFu;
             if (diff != 0) {
                 const int hi = 31 - __builtin_clz(diff);          // bytes hi + 1 .. 7 agree: 8 * (7 - hi) trailing zero bits
@@ -346,7 +344,7 @@ struct TpaqPred {
 
     __device__ __forceinline__ void byte_done()
     {
-        if (lane == 0) tq_st(buffer + ((u32)pos & bufMask), (u8)c0);
+        if (lane == 0) st_wg(buffer + ((u32)pos & bufMask), (u8)c0);
         pos++;
         c8 = (c8 << 8) | ((c4 >> 24) & 0xFF);
         c4 = (c4 << 8) | (c0 & 0xFF);
@@ -361,8 +359,8 @@ struct TpaqPred {
             if (lane == 9) myW = lr;
             const int init = lane < 8 ? 32768 : lane == 8 ? 0 : TPAQ_BEGIN_LEARN_RATE;
             if (lane < 10) {
-                tq_st(mixers + (size_t)mixIdx * 10 + lane, myW - init);
-                myW = tq_ld(mixers + (size_t)newMix * 10 + lane) + init;          // (another mixer: no store of this byte is behind the load)
+                st_wg(mixers + (size_t)mixIdx * 10 + lane, myW - init);
+                myW = ld_agent(mixers + (size_t)newMix * 10 + lane) + init;          // (another mixer: no store of this byte is behind the load)
             }
             skew = (int)rl((u32)myW, 8);
             lr = (int)rl((u32)myW, 9);
@@ -392,8 +390,8 @@ struct TpaqPred {
         myCtx = lane == 0 ? ctx0 : lane == 1 ? ctx1 : lane == 2 ? ctx2 : lane == 3 ? ctx3 : lane == 4 ? ctx4 : lane == 5 ? ctx5 : (lane == 6 && set6) ? ctx6 : myCtx;
         tq_drain();                                     // the byte just stored may be read below
         find_match();
-        matchVal = (int)(cm_uni(buf_at((u32)matchPos)) | 0x100u);
-        if (lane == 0) tq_st(hashes + hash, pos);
+        matchVal = (int)(uni(buf_at((u32)matchPos)) | 0x100u);
+        if (lane == 0) st_wg(hashes + hash, pos);
     }
 
     // LogisticAdaptiveProbMap<false, RATE>::get on the map in LDS: every lane stores the same values
@@ -401,13 +399,13 @@ struct TpaqPred {
     __device__ __forceinline__ int apm0(int bit, int p, u32 ctx)
     {
         const int g = bit ? 65528 : 0;
-        const int a = (int)cm_uni(L.sse0[sse0Idx]), b = (int)cm_uni(L.sse0[sse0Idx + 1]);
+        const int a = (int)uni(L.sse0[sse0Idx]), b = (int)uni(L.sse0[sse0Idx + 1]);
         L.sse0[sse0Idx] = (u16)(a + ((g - a) >> RATE) + bit);
         L.sse0[sse0Idx + 1] = (u16)(b + ((g - b) >> RATE) + bit);
         const int s = L.stretch[p];
         sse0Idx = (u32)((s + 2048) >> 7) + 33 * ctx;
         const int w = s & 127;
-        const int ca = (int)cm_uni(L.sse0[sse0Idx]), cb = (int)cm_uni(L.sse0[sse0Idx + 1]);
+        const int ca = (int)uni(L.sse0[sse0Idx]), cb = (int)uni(L.sse0[sse0Idx + 1]);
         return ((ca << 7) + (cb - ca) * w) >> 11;
     }
 
@@ -417,15 +415,15 @@ struct TpaqPred {
     {
         const int g = bit ? 65528 : 0;
         const u32 i0 = sse1Idx, col0 = sse1Col;
-        const int a = (int)(u16)(cm_uni(tq_ld(sse1 + i0)) + L.sseRow[col0]), b = (int)(u16)(cm_uni(tq_ld(sse1 + i0 + 1)) + L.sseRow[col0 + 1]);
+        const int a = (int)(u16)(uni(ld_agent(sse1 + i0)) + L.sseRow[col0]), b = (int)(u16)(uni(ld_agent(sse1 + i0 + 1)) + L.sseRow[col0 + 1]);
         const int na = (int)(u16)(a + ((g - a) >> 7) + bit), nb = (int)(u16)(b + ((g - b) >> 7) + bit);
-        if (lane == 0) { tq_st(sse1 + i0, (u16)(na - L.sseRow[col0])); tq_st(sse1 + i0 + 1, (u16)(nb - L.sseRow[col0 + 1])); }
+        if (lane == 0) { st_wg(sse1 + i0, (u16)(na - L.sseRow[col0])); st_wg(sse1 + i0 + 1, (u16)(nb - L.sseRow[col0 + 1])); }
         const int s = L.stretch[p];
         const u32 col = (u32)((s + 2048) >> 7);
         const u32 i1 = col + 33 * ctx;
         sse1Idx = i1; sse1Col = col;
         const int w = s & 127;
-        const int la = (int)(u16)(cm_uni(tq_ld(sse1 + i1)) + L.sseRow[col]), lb = (int)(u16)(cm_uni(tq_ld(sse1 + i1 + 1)) + L.sseRow[col + 1]);
+        const int la = (int)(u16)(uni(ld_agent(sse1 + i1)) + L.sseRow[col]), lb = (int)(u16)(uni(ld_agent(sse1 + i1 + 1)) + L.sseRow[col + 1]);
         const int ca = i1 == i0 ? na : i1 == i0 + 1 ? nb : la;
         const int cb = i1 + 1 == i0 ? na : i1 == i0 ? nb : lb;
         return ((ca << 7) + (cb - ca) * w) >> 11;
@@ -464,7 +462,7 @@ struct TpaqPred {
             if (k == mBefore) pre = v;
             if (k < mTotal) v = row[v];
         }
-        if (active && mBefore == 0) tq_st(myPtr, (u8)v);
+        if (active && mBefore == 0) st_wg(myPtr, (u8)v);
         const u32 oldId6 = rl(myId, 6), pre6 = rl(pre, 6);
         // the new pointers
         u32 idx;
@@ -473,7 +471,7 @@ struct TpaqPred {
         else if (active) { idx = (lane == 5 ? (myCtx ^ c0) : (myCtx + c0)) & statesMask; myPtr = big + idx; myId = idx; }
         tq_drain();
         u32 seen = 0;
-        if (active) { myVal = (u32)tq_ld(myPtr); seen = (X && lane >= 2 && lane <= 5 && myId == oldId6) ? pre6 : myVal; }
+        if (active) { myVal = (u32)ld_agent(myPtr); seen = (X && lane >= 2 && lane <= 5 && myId == oldId6) ? pre6 : myVal; }
         // the match model's prediction (getMatchContextPred clears the match in the middle of a byte)
         int p7 = 0;
         if (matchLen != 0) {
@@ -489,7 +487,7 @@ struct TpaqPred {
         dot += __shfl_xor(dot, 1);
         dot += __shfl_xor(dot, 2);
         dot += __shfl_xor(dot, 4);
-        dot = (int)cm_uni((u32)dot) + skew + 65536;
+        dot = (int)uni((u32)dot) + skew + 65536;
         int p = mixPr = tpaq_squash(L, dot >> 17);
         // SSE
         if (!X) {

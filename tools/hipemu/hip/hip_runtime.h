@@ -190,6 +190,11 @@ static inline int __clzll(long long x) { return x == 0 ? 64 : __builtin_clzll((u
 template <class T> static inline T atomicAdd(T* p, T v) { const T o = *p; *p = o + v; return o; }
 template <class T> static inline T atomicOr(T* p, T v) { const T o = *p; *p = o | v; return o; }
 template <class T> static inline T atomicAnd(T* p, T v) { const T o = *p; *p = o & v; return o; }
+// scoped atomic accesses: fibers run one at a time, so a plain access is atomic at every scope
+#define __HIP_MEMORY_SCOPE_WORKGROUP 3
+#define __HIP_MEMORY_SCOPE_AGENT 4
+template <class T> static inline T __hip_atomic_load(const T* p, int, int) { return *p; }
+template <class T> static inline void __hip_atomic_store(T* p, T v, int, int) { *p = v; }
 static inline unsigned long long __ballot(int pred);
 static inline void __threadfence_block() { (void)__ballot(1); }      // (issued by the kernels in workgroup-uniform control flow)
 static inline void __threadfence() {}
