@@ -15,7 +15,8 @@
 //     * run groups (4 equal symbols) in one round by run length: the runs are sorted, the members follow their runs (k_bwt_f_run_*),
 //       and because that round rebuilds every member from the text, the members stay out of round 0's sort: the run groups are found in
 //       the text before the sort (FwdSort::run_scan), the first pass drops their members, the last pass leaves a gap per group where they
-//       belong, one key fills it (TextSrcKept, LastPassSrc, k_bwt_f_r0_fill; knob bwt_run_in_sort: through the sort as before),
+//       belong, one key fills its two ends and nobody reads its inside (TextSrcKept, LastPassSrc, k_bwt_f_r0_fill, R0_GAP_MARGIN; knob
+//       bwt_run_in_sort: through the sort as before),
 //   and the doubling rounds, h = 4, 8, 16, ..., refine what is left on the key ISA[p + h] (0 past the block end: "shorter sorts first"):
 //     * small groups (2..256 members) need no list at all: a kernel sweeps the bit map in windows of 2048 slots, finds the groups that
 //       start in its window and ranks every member by counting inside LDS (less / equal / equal-before),
@@ -104,7 +105,8 @@ enum FwdCounter : u32 {
     CNT_MED_LO = 9,              // medium descriptors of the lower size class, up to MED_LO_CAP members (k_bwt_f_med_compact)
     CNT_STAT_SMALL = 10,         // small members worked on (knob bwt_stats)
     CNT_STAT_SMALL_GROUPS = 11,  // small groups worked on (knob bwt_stats)
-    CNT_STAT_MED = 12,           // medium members worked on (knob bwt_stats)
+    CNT_STAT_MED = 12,           // in a doubling round: medium members worked on (knob bwt_stats)
+    CNT_STAT_R0_SKIPPED = 12,    // in round 0: workgroups of k_bwt_f_r0_flags that lay inside a gap and loaded no key (knob bwt_stats)
     CNT_TIED = 13,               // small members still tied after the round (the windows' counts summed)
     CNT_PROBE_CAND = 14,         // after round 0, owned by the probe: candidates of k_bwt_f_probe (k_bwt_f_probe_scan)
     CNT_LINKED = 14,             // in a doubling round, owned by the link step: members linked (k_bwt_f_link_payoff)
@@ -489,30 +491,65 @@ __global__ __launch_bounds__(256) void k_bwt_f_r0_bases(prims::RsLayout L, const
     if (last) gapStart[(size_t)sgm * 256 + tid] = b0 + incl - members[(size_t)sgm * 256 + tid];
 }
 
-// the gaps filled: the class's key with the position of its first member in every slot
+// The inside of a gap is left alone: only a gap's first slot is ever placed, every other slot of it starts no group, and what the flag
+// and the placing kernel would learn from its keys is known from the gap's bounds (gapStart, members). k_bwt_f_r0_fill writes the
+// class's key to the R0_GAP_MARGIN slots at either end of a gap (to all of a gap of up to two margins); a workgroup of k_bwt_f_r0_flags
+// whose slots, and a window of k_bwt_f_r0_place_text whose view, lie strictly behind the first slot of one gap and in front of its end
+// (r0_inside_gap) does its work without loading a key. What makes this safe: every slot a kernel reads without that test lies within
+// the margin of a gap end, and is therefore filled -- a workgroup that fails the test starts at or in front of the gap's first slot, or
+// ends behind the gap's last one, and reads no further than its 256 * R0F_ROWS slots (and the slot in front of them), or its SM_WIN.
+// The two kernels are the only readers of round 0's sorted keys (FwdSort::keysFree2, scratch of the rounds afterwards).
+constexpr u32 R0F_ROWS = 8;       // rows of 256 slots per workgroup of k_bwt_f_r0_flags
+constexpr u32 R0_GAP_MARGIN = 2048;
+static_assert(R0_GAP_MARGIN >= 256 * R0F_ROWS, "a workgroup of k_bwt_f_r0_flags that touches a gap's end must stay within the margin");
+static_assert(R0_GAP_MARGIN >= SM_WIN, "a window of k_bwt_f_r0_place_text that touches a gap's end must stay within the margin");
+
+// the n slots from a on lie strictly behind the first slot of the gap of (block b, byte c) and in front of its end
+__device__ __forceinline__ bool r0_inside_gap(const u32* __restrict__ members, const u32* __restrict__ gapStart, int b, u32 c, u32 a, u32 n)
+{
+    const u32 m = members[(u32)b * 256u + c];
+    if (m == 0u) return false;
+    const u32 g0 = gapStart[(u32)b * 256u + c];
+    return a > g0 && a - g0 < m && n <= m - (a - g0);
+}
+
+// the gaps filled: the class's key with the position of its first member in the slots at either end of the gap
 __global__ __launch_bounds__(256) void k_bwt_f_r0_fill(u64* __restrict__ keys, const u32* __restrict__ members, const u32* __restrict__ gapStart,
                                                        const u32* __restrict__ firstPos, int P, int pbits)
 {
-    const u32 sgm = blockIdx.y;
-    for (u32 c = 0; c < 256u; c++) {
-        const u32 m = members[sgm * 256u + c];
-        if (m == 0u) continue;
-        const u32 g0 = gapStart[sgm * 256u + c];
-        const u64 key = (rep_key(c, P) << pbits) | (u64)firstPos[sgm * 256u + c];
-        for (u32 i = blockIdx.x * 256u + threadIdx.x; i < m; i += gridDim.x * 256u) keys[g0 + i] = key;
-    }
+    const u32 sgm = blockIdx.y, c = blockIdx.x;                          // (a workgroup per class: at most two margins to write)
+    const u32 m = members[sgm * 256u + c];
+    if (m == 0u) return;
+    const u32 g0 = gapStart[sgm * 256u + c];
+    const u64 key = (rep_key(c, P) << pbits) | (u64)firstPos[sgm * 256u + c];
+    const bool whole = m <= 2u * R0_GAP_MARGIN;
+    const u32 cnt = whole ? m : 2u * R0_GAP_MARGIN;
+    for (u32 i = threadIdx.x; i < cnt; i += 256u) keys[g0 + ((whole || i < R0_GAP_MARGIN) ? i : m - 2u * R0_GAP_MARGIN + i)] = key;
 }
 
 // group-start flags of the sorted keys as a bit map (one ballot per wave): a slot starts a group when its key bytes differ from
-// its left neighbour's, when it is the first slot of a block, or when it or its left neighbour is a short suffix
-constexpr u32 R0F_ROWS = 8;       // rows of 256 slots per workgroup, all loads of a thread in flight at once (one row per workgroup ran at 2.5 TB/s)
+// its left neighbour's, when it is the first slot of a block, or when it or its left neighbour is a short suffix.
+// R0F_ROWS rows of 256 slots per workgroup, all loads of a thread in flight at once (one row per workgroup ran at 2.5 TB/s).
+// members (null: no gaps): a workgroup inside a gap (one class per thread looks) writes its zero words and loads no key; nSkipped (null
+// without the knob bwt_stats) counts those.
 __global__ __launch_bounds__(256) void k_bwt_f_r0_flags(const u64* __restrict__ keys, const u32* __restrict__ base, int nBlocks, u32 total, int P, int pbits,
-                                                        unsigned long long* __restrict__ gbits64)
+                                                        unsigned long long* __restrict__ gbits64, const u32* __restrict__ members, const u32* __restrict__ gapStart,
+                                                        u32* __restrict__ nSkipped)
 {
     __shared__ int sBlk;
+    __shared__ u32 sInside;
     const u32 a0 = blockIdx.x * (256u * R0F_ROWS);
-    if (threadIdx.x == 0) sBlk = find_block(base, nBlocks, a0 < total ? a0 : (total ? total - 1 : 0));
+    if (threadIdx.x == 0) { sBlk = find_block(base, nBlocks, a0 < total ? a0 : (total ? total - 1 : 0)); sInside = 0; }
     __syncthreads();
+    if (members != nullptr) {
+        if (r0_inside_gap(members, gapStart, sBlk, threadIdx.x, a0, 256u * R0F_ROWS)) sInside = 1;
+        __syncthreads();
+        if (sInside) {
+            if (threadIdx.x < 256u * R0F_ROWS / 64u) gbits64[(a0 >> 6) + threadIdx.x] = 0ull;
+            if (nSkipped != nullptr && threadIdx.x == 0) atomicAdd(nSkipped, 1u);
+            return;
+        }
+    }
     u64 kr[R0F_ROWS], kl[R0F_ROWS];
 #pragma unroll
     for (u32 r = 0; r < R0F_ROWS; r++) {
@@ -635,10 +672,11 @@ __device__ __forceinline__ bool sm_group_of(const SmWindow& W, u32 i, u32& s, u3
 // and the labels of every member that moved a second time).
 __global__ __launch_bounds__(256) void k_bwt_f_r0_place_text(BwtView bv, FwdView v, const u32* __restrict__ winLastIncl, const u32* __restrict__ winFirstInclRev, u32 nWin,
                                                              uint2* __restrict__ largeNext, const u64* __restrict__ keys, int nsym, int pbits, uint2* __restrict__ runList,
-                                                             const u32* __restrict__ gapTab)
+                                                             const u32* __restrict__ gapTab, const u32* __restrict__ gapMembers, const u32* __restrict__ gapStart)
 {
     // gapTab (null: the run members went through the sort): [block][256], != 0xFFFFFFFF where the byte's run group is a gap that
-    // k_bwt_f_r0_fill filled. Only its first slot is placed -- the run round writes position and label of every member
+    // k_bwt_f_r0_fill filled. Only its first slot is placed -- the run round writes position and label of every member. A window whose
+    // whole view lies inside a gap (r0_inside_gap; gapMembers, gapStart) has nothing to place, list or count, and its keys are not there
     __shared__ SmWindow W;
     __shared__ int sBlk;
     __shared__ ClassAgg A;
@@ -646,12 +684,19 @@ __global__ __launch_bounds__(256) void k_bwt_f_r0_place_text(BwtView bv, FwdView
     __shared__ u64 sK[SM_WIN];
     __shared__ u32 sNew[64];
     __shared__ u32 sAfterLocal;           // first group start in the owned part of the NEXT window behind what this one looks at
+    __shared__ u32 sInside;
     constexpr int E = (int)(SM_WIN / 256);
     constexpr u32 TSW = SM_TS / 32;       // words a window owns
     const int tid = (int)threadIdx.x;
     const u32 win = blockIdx.x;
     const u32 slot0 = win * SM_TS;
-    if (tid == 0) sBlk = find_block(v.base, v.nBlocks, slot0 < v.total ? slot0 : v.total - 1);
+    if (gapTab != nullptr) {
+        if (tid == 0) { sBlk = find_block(v.base, v.nBlocks, slot0 < v.total ? slot0 : v.total - 1); sInside = 0; }
+        __syncthreads();
+        if (r0_inside_gap(gapMembers, gapStart, sBlk, (u32)tid, slot0, SM_WIN)) sInside = 1;
+        __syncthreads();
+        if (sInside) return;
+    } else if (tid == 0) sBlk = find_block(v.base, v.nBlocks, slot0 < v.total ? slot0 : v.total - 1);
     agg_init(A);
     if (tid < 64) {
         sNew[tid] = 0;
@@ -2603,21 +2648,27 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_expand(const u64* __restrict_
 //   (members in front of the segment: moff of its first run) + (members of the columns in front of R) + #{earlier runs of the segment with L >= R},
 // three counts over the runs. A segment is cut into tiles of RUN_TILE consecutive runs (most segments are one partly filled tile; one
 // per block -- byte 0 of the stand-in -- has tens of thousands of runs), a tile into rows of 64 runs, one wave each:
-//   k_bwt_f_run_seg_marks, max scan      first run of the segment of every run
+//   k_bwt_f_run_seg_marks, max scans     first run of the segment of every run, and of its stretch of equal keys
+//   k_bwt_f_run_tie_marks, max scan      per run: the longest earlier run of its stretch (which of its members start a tie)
 //   k_bwt_f_run_tile_marks, sum scan,
 //   k_bwt_f_run_tile_starts              the tiles [tileStart[t], tileStart[t + 1]) in run order, their number in CNT_RUN_TILES
 //   k_bwt_f_run_tile_counts              tiles of segments of several tiles: colTab[tile][R] = #{runs of the tile with L >= R}
 //   k_bwt_f_run_tile_scan                per such segment and column: colTab[tile][R] = column offset of R + runs of the tiles in front
 //   k_bwt_f_run_emit                     per tile: the same counts per row in LDS, RUN_CH columns at a time; a wave then walks the columns
-//                                        of its row, ranks the runs that are still alive with a ballot and writes their records
+//                                        of its row, ranks the runs that are still alive with a ballot and writes their members:
+//                                        SA and R (ovr) to the member's slot, its tie flag as a byte
+//   k_bwt_f_run_tie_bits                 the tie flags as the bit map k_bwt_f_run_place reads
+// No record per member is written: what the member sort's kernels pass on as key, position and R per member is a function of the run
+// tables. k_bwt_f_run_place<true> then writes the labels and lists the ties.
 // Every loop is bounded by a count known when the kernel starts (runs of the tile, RUN_DIRECT_LMAX columns, tiles of the batch); nothing
 // waits for another workgroup. The host launches one workgroup per tile there CAN be (segments + runs / RUN_TILE), the ones past
 // CNT_RUN_TILES leave at once: no read-back. Runs longer than RUN_DIRECT_LMAX (a block of one byte: one run, one member per position)
 // send the batch through the member sort above: the tables are sized by that bound, and a column costs a wave one step however few of
-// its runs reach it.
+// its runs reach it. So does a batch with so many runs that a run's index and a length do not fit one word of k_bwt_f_run_tie_marks'
+// scan (idxBits + RUN_LBITS > 32: more than 4 M runs).
 constexpr u32 RUN_TILE = 1024;                       // runs per tile (16 rows of 64)
 constexpr u32 RUN_ROWS = RUN_TILE / 64;
-constexpr u32 RUN_DIRECT_LMAX = 1023;                // longest run the direct path takes
+constexpr u32 RUN_DIRECT_LMAX = 1023;                // longest run the direct path takes (RUN_LBITS bits: k_bwt_f_run_tie_marks)
 constexpr u32 RUN_COLS = RUN_DIRECT_LMAX + 1;        // columns of a tile's row in colTab (column R at index R)
 constexpr u32 RUN_CH = 256;                          // columns k_bwt_f_run_emit counts at a time
 static_assert(RUN_COLS == 4 * 256 && RUN_CH == 256 && RUN_ROWS % 4 == 0, "the kernels below map columns and rows to 256 threads");
@@ -2637,11 +2688,64 @@ __device__ __forceinline__ RunTile run_tile(const u32* __restrict__ tileStart, c
     return r;
 }
 
-__global__ __launch_bounds__(256) void k_bwt_f_run_seg_marks(const u64* __restrict__ sKey, u32 nRuns, int kbits, u32* __restrict__ segMark)
+// (strMark: the same for the stretches of equal (class, direction, T) inside the segments, see k_bwt_f_run_tie_marks)
+__global__ __launch_bounds__(256) void k_bwt_f_run_seg_marks(const u64* __restrict__ sKey, u32 nRuns, int kbits, u32* __restrict__ segMark, u32* __restrict__ strMark)
 {
     const u32 k = blockIdx.x * 256 + threadIdx.x;
     if (k >= nRuns) return;
-    segMark[k] = (k > 0 && (sKey[k] >> kbits) == (sKey[k - 1] >> kbits)) ? 0u : k;     // (a running maximum makes it the segment's first run)
+    const u64 key = sKey[k], prev = k > 0 ? sKey[k - 1] : 0ull;
+    segMark[k] = (k > 0 && (key >> kbits) == (prev >> kbits)) ? 0u : k;     // (a running maximum makes it the segment's first run)
+    strMark[k] = (k > 0 && key == prev) ? 0u : k;
+}
+
+// Ties among the members placed directly, from the runs alone. Two members of a column (class, direction, R) tie when their runs follow
+// the same text, i.e. lie in one STRETCH of equal sKey; such runs are adjacent. The member in front of (run k, R) in its column is the
+// nearest earlier run of the segment with L >= R, and that run lies in k's stretch exactly when some earlier run of the stretch has
+// L >= R. So (k, R) starts a tie exactly when R > P[k], P[k] = the largest L among the runs of k's stretch in front of k (0 for the
+// stretch's first run) -- the bit k_bwt_f_run_flags takes from keys[j] != keys[j - 1]. tie[k] = (first run of k's stretch) << RUN_LBITS | L
+// under a running maximum is (the same) << RUN_LBITS | max L of the stretch up to k, since the first runs do not decrease;
+// k_bwt_f_run_emit reads P[k] from tie[k - 1].
+constexpr int RUN_LBITS = 10;
+static_assert(RUN_DIRECT_LMAX < (1u << RUN_LBITS), "a run length of the direct path fits the low bits of tie[]");
+__global__ __launch_bounds__(256) void k_bwt_f_run_tie_marks(u32* __restrict__ tie, const u32* __restrict__ rcnt, u32 nRuns, u32 nsym)
+{
+    const u32 k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= nRuns) return;
+    const u32 L = rcnt[k] + nsym - 1u;
+    tie[k] = (tie[k] << RUN_LBITS) | (L < (1u << RUN_LBITS) ? L : (1u << RUN_LBITS) - 1u);
+}
+
+// The tie flags k_bwt_f_run_emit wrote, one byte per member, as the members' bit map (a word per thread); every bit from M up to the end
+// of the last window is set (the end of the last tie), as k_bwt_f_run_flags leaves them. (The first build had k_bwt_f_run_emit OR the
+// bits of every step into the map, up to three words by one lane: 1.14 ms for the kernel where the records took 0.63 -- a single-lane
+// atomic is one memory-side request, and a step holds only the runs of a row that reach the column; profiles/r12_run_tables.txt.)
+__global__ __launch_bounds__(256) void k_bwt_f_run_tie_bits(const u8* __restrict__ flags, u32 M, u32 nWords, u32* __restrict__ mbits)
+{
+    const u32 w = blockIdx.x * 256 + threadIdx.x;
+    if (w >= nWords) return;
+    const u32 j0 = 32u * w;
+    u32 bits = 0;
+    if (j0 + 32u <= M) {
+        const u32x4 a = ldg<u32x4>(flags + j0), b = ldg<u32x4>(flags + j0 + 16);
+        const u32 x[8] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w };
+#pragma unroll
+        for (u32 i = 0; i < 8; i++) bits |= ((x[i] * 0x00204081u) >> 21 & 0xFu) << (4 * i);      // (bytes of 0 / 1: bit 0 of byte q to bit q)
+    } else {
+        for (u32 i = 0; i < 32; i++) bits |= ((j0 + i >= M || flags[j0 + i] != 0) ? 1u : 0u) << i;
+    }
+    mbits[w] = bits;
+}
+
+// bit i of `mask` ORed into bit pos + i of a bit map, as at most three word-wide atomics
+__device__ __forceinline__ void or_mask64(u32* __restrict__ dst, u32 pos, unsigned long long mask)
+{
+    const u32 w0 = pos >> 5, sh = pos & 31;
+    const u32 p0 = (u32)(mask << sh);
+    const u32 p1 = sh ? (u32)(mask >> (32 - sh)) : (u32)(mask >> 32);
+    const u32 p2 = sh ? (u32)(mask >> (64 - sh)) : 0u;
+    if (p0) atomicOr(&dst[w0], p0);
+    if (p1) atomicOr(&dst[w0 + 1], p1);
+    if (p2) atomicOr(&dst[w0 + 2], p2);
 }
 
 __global__ __launch_bounds__(256) void k_bwt_f_run_tile_marks(const u32* __restrict__ segStart, u32 nRuns, u32* __restrict__ tileMark)
@@ -2725,11 +2829,14 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_tile_scan(const u32* __restri
     }
 }
 
-// one workgroup per tile, a wave per row of 64 runs: rk[j] = [class | hi(R) | T], rv[j] = position, Rout[j] = R for every member of the tile
+// one workgroup per tile, a wave per row of 64 runs. Member j of class di (the tile's: a tile lies in one segment) has the slot
+// desc[di].x + (j - loff[di]): SA and ovr (R, what the doubling rounds need to look behind the run) are written there, and the member's
+// tie flag (R > P, see k_bwt_f_run_tie_marks) is written as a byte, flags[j], which k_bwt_f_run_tie_bits packs into the members' bit map.
 __global__ __launch_bounds__(256) void k_bwt_f_run_emit(const u32* __restrict__ tileStart, const u32* __restrict__ segStart, const u32* __restrict__ rcnt,
                                                         const u32* __restrict__ moff, const u64* __restrict__ sKey, const u32* __restrict__ sE, u32 nRuns, u32 M,
-                                                        const u32* __restrict__ nTilesDev, const u32* __restrict__ colTab, u32 nsym, int kbits, int hbits,
-                                                        u64* __restrict__ keys, u32* __restrict__ vals, u32* __restrict__ Rout)
+                                                        const u32* __restrict__ nTilesDev, const u32* __restrict__ colTab, u32 nsym, int kbits,
+                                                        const uint2* __restrict__ desc, const u32* __restrict__ loff, const u32* __restrict__ tie,
+                                                        u32* __restrict__ SA, u32* __restrict__ ovr, u8* __restrict__ flags)
 {
     __shared__ u32 cnt[RUN_ROWS][RUN_CH];                                // runs of the row with L >= c0 + r, then the same of the rows in front
     __shared__ u32 colBase[RUN_CH];                                      // where column c0 + r of this tile starts in the segment
@@ -2741,25 +2848,25 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_emit(const u32* __restrict__ 
     const u32 wave = tid >> 6;
     const RunTile T = run_tile(tileStart, segStart, nRuns, t);
     const u32 nRows = (T.k1 - T.k0 + 63) / 64;
-    const u32 segBase = moff[T.a];
     const u32 tileMembers = (T.k1 < nRuns ? moff[T.k1] : M) - moff[T.k0];     // (the segment's, when the tile is all of it)
-    const bool above = ((sKey[T.k0] >> kbits) & 1ull) != 0;
-    const u64 hiAll = (1ull << hbits) - 1ull;
+    const u64 key0 = sKey[T.k0];
+    const bool above = ((key0 >> kbits) & 1ull) != 0;
+    const u32 di = (u32)(key0 >> (kbits + 1));
+    const u32 segBase = moff[T.a];
+    const u32 slotBase = desc[di].x - loff[di];                          // slot of member j: slotBase + j (mod 2^32)
     // my runs: wave w has the rows w, w + 4, ...
-    u32 Lr[RUN_ROWS / 4], rowMax[RUN_ROWS / 4], e[RUN_ROWS / 4];
-    u64 kb[RUN_ROWS / 4];
+    u32 Lr[RUN_ROWS / 4], rowMax[RUN_ROWS / 4], e[RUN_ROWS / 4], Pr[RUN_ROWS / 4];
     u32 lmax = 0;
     if (tid == 0) sLmax = 0;
 #pragma unroll
     for (u32 q = 0; q < RUN_ROWS / 4; q++) {
         const u32 k = T.k0 + (wave + 4 * q) * 64 + (u32)lane;
-        Lr[q] = 0; e[q] = 0; kb[q] = 0;
+        Lr[q] = 0; e[q] = 0; Pr[q] = 0;
         if (k < T.k1) {
-            const u64 key = sKey[k];
             Lr[q] = rcnt[k] + nsym - 1u;
             if (Lr[q] > RUN_DIRECT_LMAX) Lr[q] = RUN_DIRECT_LMAX;        // (the host sends no such batch here)
             e[q] = sE[k];
-            kb[q] = ((key >> (kbits + 1)) << (hbits + kbits)) | (key & ((1ull << kbits) - 1ull));
+            if ((tie[k] >> RUN_LBITS) != k) Pr[q] = tie[k - 1] & ((1u << RUN_LBITS) - 1u);     // (not the first run of its stretch: k > 0)
         }
         rowMax[q] = wave_max(Lr[q]);
         lmax = rowMax[q] > lmax ? rowMax[q] : lmax;
@@ -2813,9 +2920,10 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_emit(const u32* __restrict__ 
                 const unsigned long long m = __ballot(alive);
                 const u32 j = segBase + colBase[R - c0] + cnt[row][R - c0] + (u32)__popcll(m & __lanemask_lt());
                 if (alive && j < M) {
-                    keys[j] = kb[q] | ((above ? hiAll - (u64)R : (u64)R) << kbits);
-                    vals[j] = e[q] - R;
-                    Rout[j] = R;
+                    const u32 mySlot = slotBase + j;
+                    SA[mySlot] = e[q] - R;
+                    ovr[mySlot] = R;
+                    flags[j] = R > Pr[q] ? 1 : 0;
                 }
             }
         }
@@ -2827,6 +2935,9 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_emit(const u32* __restrict__ 
 // wave), the windows of 2048 members find their heads and sizes the way round 0 does (k_bwt_f_r0_winsum + two scans over the windows),
 // and the placing kernel reads keys, positions and 64 words of bits -- where k_bwt_f_large_flags wrote two index arrays of the members'
 // size and two device-wide scans ran over them.
+// k_bwt_f_run_flags makes the bits of the member-sort path (a run longer than RUN_DIRECT_LMAX, the knob bwt_run_sort) from the members'
+// sorted keys. The direct path has no keys: its bits come from the run tables (k_bwt_f_run_tie_marks, k_bwt_f_run_emit,
+// k_bwt_f_run_tie_bits), and k_bwt_f_run_place<true> reads no record either.
 __global__ __launch_bounds__(256) void k_bwt_f_run_flags(const u64* __restrict__ keys, u32 M, unsigned long long* __restrict__ bits64)
 {
     const u32 j = blockIdx.x * 256 + threadIdx.x;
@@ -2839,19 +2950,30 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_flags(const u64* __restrict__
     if ((threadIdx.x & 63) == 0) bits64[j >> 6] = m;
 }
 
-__global__ __launch_bounds__(256) void k_bwt_f_run_place(FwdView v, const uint2* __restrict__ desc, const u32* __restrict__ loff, u32 M, int kbits, const u64* __restrict__ keys,
-                                                         const u32* __restrict__ vals, const u32* __restrict__ bits, const u32* __restrict__ winLastIncl,
-                                                         const u32* __restrict__ winFirstInclRev, u32 nWin, uint2* __restrict__ largeNext, const u32* __restrict__ memberR,
-                                                         u32* __restrict__ ovr, u32* __restrict__ rtbits, const u32* __restrict__ lbase, int allLabels)
+// DIRECT: the members were placed by k_bwt_f_run_emit -- SA and ovr are written, the bits are the ties; what is left is the labels and the
+// descriptors. There are no member records then (keys, vals, memberR are null): the position is read from SA, and the class of a member
+// is found in loff (nDesc + 1 entries), once per workgroup by bisection and from there by stepping.
+template <bool DIRECT>
+__global__ __launch_bounds__(256) void k_bwt_f_run_place(FwdView v, const uint2* __restrict__ desc, const u32* __restrict__ loff, u32 nDesc, u32 M, int kbits,
+                                                         const u64* __restrict__ keys, const u32* __restrict__ vals, const u32* __restrict__ bits,
+                                                         const u32* __restrict__ winLastIncl, const u32* __restrict__ winFirstInclRev, u32 nWin,
+                                                         uint2* __restrict__ largeNext, const u32* __restrict__ memberR, u32* __restrict__ ovr,
+                                                         u32* __restrict__ rtbits, const u32* __restrict__ lbase, int allLabels)
 {
     // one member per thread (the kernel is a scatter of labels: occupancy is what hides its latency); the 64 words of the member's window of
     // 2048 are looked at by every one of the window's eight workgroups
     __shared__ SmWindow W;
     __shared__ ClassAgg A;
+    __shared__ u32 sDi;
     const int tid = (int)threadIdx.x;
     const u32 jb = blockIdx.x * 256u;
     const u32 win = jb / SM_WIN, j0 = win * SM_WIN;
     agg_init(A);
+    if (DIRECT && tid == 64) {
+        u32 lo = 0, hi = nDesc;                                          // last class with loff <= jb (jb < M = loff[nDesc])
+        while (hi - lo > 1) { const u32 mid = (lo + hi) >> 1; if (loff[mid] <= jb) lo = mid; else hi = mid; }
+        sDi = lo;
+    }
     if (tid < 64) {
         const u32 w = bits[(j0 >> 5) + (u32)tid];
         W.bw[tid] = w;
@@ -2883,14 +3005,16 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_place(FwdView v, const uint2*
         const u32 m = word & lowmask;
         const int si = m ? (int)(w * 32 + 31 - (u32)__clz((int)m)) : W.prevSet[w];
         const u32 nh = (si >= 0) ? j0 + (u32)si : (win ? winLastIncl[win - 1] : 0u);       // first member of my tie
-        const u32 di = (u32)(keys[j] >> kbits);
+        u32 di;
+        if (DIRECT) { di = sDi; while (di + 1 < nDesc && j >= loff[di + 1]) di++; }
+        else di = (u32)(keys[j] >> kbits);
         const u32 gs = desc[di].x, off = loff[di];
-        const u32 gp = vals[j];
         mySlot = gs + (j - off);
-        v.SA[mySlot] = gp;
+        const u32 gp = DIRECT ? v.SA[mySlot] : vals[j];
+        if (!DIRECT) v.SA[mySlot] = gp;
         // (the first tie of a group keeps the group's label, which round 0 wrote -- unless the members stayed out of its sort: allLabels)
         if (nh != off || allLabels) lab_set(v, gp, lbase[di], gs + (nh - off), gs);
-        ovr[mySlot] = memberR[j];                                            // what the doubling rounds need to look behind the run
+        if (!DIRECT) ovr[mySlot] = memberR[j];                               // what the doubling rounds need to look behind the run
         if (nh == j) {
             const u32 m2 = word & ~lowmask;
             const u32 ei = m2 ? (w * 32 + (u32)__ffs((int)m2) - 1) : W.nextSet[w];
@@ -2917,18 +3041,8 @@ __global__ __launch_bounds__(256) void k_bwt_f_run_place(FwdView v, const uint2*
         atomicOr(&rtbits[mySlot >> 5], 1u << (mySlot & 31));
     }
     if (lane == 0) {
-        const u32 w0 = s0 >> 5, sh = s0 & 31;
-        for (int which = 0; which < 2; which++) {
-            const unsigned long long mask = which ? rm : hm;
-            u32* dst = which ? rtbits : v.gnew;
-            if (mask == 0) continue;
-            const u32 p0 = (u32)(mask << sh);
-            const u32 p1 = sh ? (u32)(mask >> (32 - sh)) : (u32)(mask >> 32);
-            const u32 p2 = sh ? (u32)(mask >> (64 - sh)) : 0u;
-            if (p0) atomicOr(&dst[w0], p0);
-            if (p1) atomicOr(&dst[w0 + 1], p1);
-            if (p2) atomicOr(&dst[w0 + 2], p2);
-        }
+        if (hm) or_mask64(v.gnew, s0, hm);
+        if (rm) or_mask64(rtbits, s0, rm);
     }
 }
 
@@ -3199,6 +3313,7 @@ struct FwdSort {
     bool runDirect = false;                                // the run round placed its members directly (k_bwt_f_run_emit; knob bwt_run_sort)
     bool gaps = false;                                     // the run members stay out of round 0's sort (run_scan; knob bwt_run_in_sort)
     u32 gapClasses = 0, keptOut = 0, scanRuns = 0, scanLongest = 0;     // what run_scan found: run groups, their members, runs of their bytes, longest run
+    u32 r0Skipped = 0;                                     // workgroups of k_bwt_f_r0_flags that lay inside a gap (counted with the knob bwt_stats)
     u32 nMedLo = 0;                                        // descriptors of the lower size class among the nMed of the list
     u32 nRun, runElems, surv, nMed, nLarge, largeElems, survMembers;   // run groups of round 0 and their members; left: small groups (!= 0),
                                                                        // medium and large groups, large members, small members still tied
@@ -3327,7 +3442,7 @@ struct FwdSort {
             }
             std::swap(kin, kout);
         }
-        hipLaunchKernelGGL(k_bwt_f_r0_fill, dim3(128, (unsigned)st.nBlocks), dim3(256), 0, s, kin, w.gapMembers, w.gapStart, w.gapFirst, nsym, pbits);
+        hipLaunchKernelGGL(k_bwt_f_r0_fill, dim3(256, (unsigned)st.nBlocks), dim3(256), 0, s, kin, w.gapMembers, w.gapStart, w.gapFirst, nsym, pbits);
         keysFree = kout; keysFree2 = kin;
     }
     // Round 0: the suffixes of every block sorted by their first nsym symbols. Keys = [nsym bytes | position in the block]; one stable LSD
@@ -3364,7 +3479,8 @@ struct FwdSort {
         hipMemsetAsync(w.gbits, 0xFF, 4 * w.gbitsWords, s); hipMemsetAsync(w.gnew, 0, 4 * w.gbitsWords, s);
         hipMemsetAsync(w.counters, 0, 4 * CNT_ROUND_SLOTS, s);
         { KScope ks_("k_bwt_f_r0_flags"); hipLaunchKernelGGL(k_bwt_f_r0_flags, dim3((total + 256 * R0F_ROWS - 1) / (256 * R0F_ROWS)), dim3(256), 0, s, keysFree2, w.base, st.nBlocks, total, nsym, pbits,
-                                                             reinterpret_cast<unsigned long long*>(w.gbits)); }
+                                                             reinterpret_cast<unsigned long long*>(w.gbits), gaps ? w.gapMembers : (const u32*)nullptr, w.gapStart,
+                                                             tune.stats ? w.counters + CNT_STAT_R0_SKIPPED : (u32*)nullptr); }
         // group starts before / after every window of SM_TS slots (the windows of the placement): two scans over ~total/1792 values
         bounds(nTiles, true, w.gbits, total, SM_TS / 32);
         kbits = bits_for((u64)bv.VS + 2, 1);
@@ -3374,10 +3490,10 @@ struct FwdSort {
         const bool runRound = (2 * kbits + 1) < 64 && !tune.noRunRound;
         { KScope ks_("k_bwt_f_r0_place");
           hipLaunchKernelGGL(k_bwt_f_r0_place_text, dim3(nTiles), dim3(256), 0, s, bv, v, w.t1, w.t3, nTiles, w.large[cur], keysFree2, nsym, pbits, runRound ? w.runList : (uint2*)nullptr,
-                             gaps ? w.classTab : (const u32*)nullptr);
+                             gaps ? w.classTab : (const u32*)nullptr, w.gapMembers, w.gapStart);
           merge_bits(); }
         if (fetch(0, CNT_ROUND_SLOTS)) return -1;
-        nRun = hp[CNT_RUN]; runElems = hp[CNT_RUN_MEMBERS];
+        nRun = hp[CNT_RUN]; runElems = hp[CNT_RUN_MEMBERS]; r0Skipped = hp[CNT_STAT_R0_SKIPPED];
         return 0;
     }
     // the run groups go the ordinary way (the medium and large lists)
@@ -3430,17 +3546,22 @@ struct FwdSort {
           rkSorted = sort_one_segment<u64, false>(nRuns, w.runKeysA, w.runKeysB, nullptr, nullptr, idxBits, idxBits + kbits + 1 + rbits) ? w.runKeysB : w.runKeysA; }
         { KScope ks_("k_bwt_f_run_sorted"); hipLaunchKernelGGL(k_bwt_f_run_sorted, GRID1(nRuns), rkSorted, nRuns, idxBits, w.runE, w.runL, (u32)nsym, w.sE, w.sKey, w.rcnt); }
         { KScope ks_("k_bwt_f_scan_sum"); prims::launch_scan<prims::SCAN_SUM_EXCL>(s, w.rcnt, w.moff, nRuns, nullptr, w.scanTmp); }
-        u64* rk; u32* rv = w.valsA;
-        runDirect = !tune.runSort && longest <= RUN_DIRECT_LMAX;
+        u64* rk = nullptr; u32* rv = w.valsA;
+        u32* mbits = w.ebits; const u32 nWinM = (runElems + SM_WIN - 1) / SM_WIN;     // (the members' bit map reuses the run-end map, which nobody reads any more)
+        runDirect = !tune.runSort && longest <= RUN_DIRECT_LMAX && idxBits + RUN_LBITS <= 32;
         if (runDirect) {
             // the members placed without a sort (k_bwt_f_run_emit): segments and tiles of the sorted runs, the column tables of the segments
             // of several tiles, the records. The tables of the unsorted runs are free by now: runPos holds the segments' first runs, runE
             // the tiles' numbers. One workgroup per tile there can be: a segment's last tile may be short, and there are two segments per class.
             KScope ks_("k_bwt_f_run_direct");
-            u32* segStart = w.runPos; u32* tileIdx = w.runE;
+            u32* segStart = w.runPos; u32* tileIdx = w.runE; u32* tie = w.runL;
+            u8* flags = reinterpret_cast<u8*>(keysFree);                // (a byte per member; round 0's sorted keys, keysFree2, are placed by now, too)
             const u32 maxTiles = (u32)std::min<u64>((u64)nRuns, 2ull * nRun + nRuns / RUN_TILE + 1);
-            hipLaunchKernelGGL(k_bwt_f_run_seg_marks, GRID1(nRuns), w.sKey, nRuns, kbits, segStart);
+            hipLaunchKernelGGL(k_bwt_f_run_seg_marks, GRID1(nRuns), w.sKey, nRuns, kbits, segStart, tie);
             prims::launch_scan<prims::SCAN_MAX_INCL>(s, segStart, segStart, nRuns, nullptr, w.scanTmp);
+            prims::launch_scan<prims::SCAN_MAX_INCL>(s, tie, tie, nRuns, nullptr, w.scanTmp);
+            hipLaunchKernelGGL(k_bwt_f_run_tie_marks, GRID1(nRuns), tie, w.rcnt, nRuns, (u32)nsym);
+            prims::launch_scan<prims::SCAN_MAX_INCL>(s, tie, tie, nRuns, nullptr, w.scanTmp);
             hipLaunchKernelGGL(k_bwt_f_run_tile_marks, GRID1(nRuns), segStart, nRuns, tileIdx);
             prims::launch_scan<prims::SCAN_SUM_EXCL>(s, tileIdx, tileIdx, nRuns, nullptr, w.scanTmp, w.counters + CNT_RUN_TILES);
             hipLaunchKernelGGL(k_bwt_f_run_tile_starts, GRID1(nRuns), segStart, tileIdx, nRuns, w.runTileStart);
@@ -3448,26 +3569,30 @@ struct FwdSort {
                 hipLaunchKernelGGL(k_bwt_f_run_tile_counts, dim3(maxTiles), dim3(256), 0, s, w.runTileStart, segStart, w.rcnt, nRuns, w.counters + CNT_RUN_TILES, (u32)nsym, w.runColTab);
                 hipLaunchKernelGGL(k_bwt_f_run_tile_scan, dim3(maxTiles), dim3(256), 0, s, w.runTileStart, segStart, w.sKey, nRuns, w.counters + CNT_RUN_TILES, (u32)nsym, kbits, w.runColTab);
             }
-            rk = keysFree;
             hipLaunchKernelGGL(k_bwt_f_run_emit, dim3(maxTiles), dim3(256), 0, s, w.runTileStart, segStart, w.rcnt, w.moff, w.sKey, w.sE, nRuns, runElems, w.counters + CNT_RUN_TILES,
-                               w.runColTab, (u32)nsym, kbits, hbits, rk, rv, w.valsB);
+                               w.runColTab, (u32)nsym, kbits, w.runList, w.loff, tie, w.SA, w.ovr, flags);
+            hipLaunchKernelGGL(k_bwt_f_run_tie_bits, GRID1(nWinM * (SM_WIN / 32)), flags, runElems, nWinM * (SM_WIN / 32), mbits);
         } else {
             { KScope ks_("k_bwt_f_run_members"); hipLaunchKernelGGL(k_bwt_f_run_members, dim3((runElems + 2047) / 2048), dim3(256), 0, s, w.moff, nRuns, runElems, w.sKey, kbits, hbits,
                                                                     (u32)nsym, keysFree); }
-            KScope ks_("k_bwt_f_sort_members");
-            const int r = sort_one_segment<u64, false>(runElems, keysFree, keysFree2, nullptr, nullptr, 32, 32 + hbits + rbits);
-            rk = r ? keysFree : keysFree2;
-            hipLaunchKernelGGL(k_bwt_f_run_expand, GRID1(runElems), r ? keysFree2 : keysFree, runElems, w.sKey, w.sE, kbits, hbits, rk, rv, w.valsB);
+            { KScope ks_("k_bwt_f_sort_members");
+              const int r = sort_one_segment<u64, false>(runElems, keysFree, keysFree2, nullptr, nullptr, 32, 32 + hbits + rbits);
+              rk = r ? keysFree : keysFree2;
+              hipLaunchKernelGGL(k_bwt_f_run_expand, GRID1(runElems), r ? keysFree2 : keysFree, runElems, w.sKey, w.sE, kbits, hbits, rk, rv, w.valsB); }
+            // ties among the sorted members as a bit map (the direct path has written its own: k_bwt_f_run_tie_marks, k_bwt_f_run_emit)
+            KScope ks_("k_bwt_f_large_flags");
+            hipLaunchKernelGGL(k_bwt_f_run_flags, dim3(nWinM * (SM_WIN / 256)), dim3(256), 0, s, rk, runElems, reinterpret_cast<unsigned long long*>(mbits));
         }
-        // ties among the sorted members as a bit map, heads and sizes per window of 2048 members (the bit map reuses the run-end map, which
-        // nobody reads any more)
-        u32* mbits = w.ebits; const u32 nWinM = (runElems + SM_WIN - 1) / SM_WIN;
-        { KScope ks_("k_bwt_f_large_flags"); hipLaunchKernelGGL(k_bwt_f_run_flags, dim3(nWinM * (SM_WIN / 256)), dim3(256), 0, s, rk, runElems, reinterpret_cast<unsigned long long*>(mbits)); }
+        // heads and sizes per window of 2048 members
         bounds(nWinM, true, mbits, runElems, SM_WIN / 32);
         { KScope ks_("k_bwt_f_large_place");
           hipMemsetAsync(w.rtbits, 0, 4 * w.gbitsWords, s);
-          hipLaunchKernelGGL(k_bwt_f_run_place, dim3((runElems + 255) / 256), dim3(256), 0, s, v, w.runList, w.loff, runElems, hbits + kbits, rk, rv, mbits, w.t1, w.t3, nWinM, w.large[cur],
-                             w.valsB, w.ovr, w.rtbits, w.lbase, gaps ? 1 : 0);
+          if (runDirect)
+              hipLaunchKernelGGL(k_bwt_f_run_place<true>, dim3((runElems + 255) / 256), dim3(256), 0, s, v, w.runList, w.loff, nRun, runElems, hbits + kbits, (const u64*)nullptr,
+                                 (const u32*)nullptr, mbits, w.t1, w.t3, nWinM, w.large[cur], (const u32*)nullptr, w.ovr, w.rtbits, w.lbase, gaps ? 1 : 0);
+          else
+              hipLaunchKernelGGL(k_bwt_f_run_place<false>, dim3((runElems + 255) / 256), dim3(256), 0, s, v, w.runList, w.loff, nRun, runElems, hbits + kbits, rk, rv, mbits, w.t1, w.t3,
+                                 nWinM, w.large[cur], w.valsB, w.ovr, w.rtbits, w.lbase, gaps ? 1 : 0);
           v.ovr = w.ovr; v.rtbits = w.rtbits; }
         { KScope ks_("k_bwt_f_merge_bits"); merge_bits(); }
         return 0;
@@ -3492,8 +3617,9 @@ struct FwdSort {
             if (fetch(0, CNT_MED_LO + 1)) return -1;                    // (the probe's two slots, and the class count that goes with CNT_MED)
             surv |= hp[CNT_SMALL_LEFT]; nMed += hp[CNT_MED]; nMedLo += hp[CNT_MED_LO];
         }
-        if (tune.stats) fprintf(stderr, "after round 0 (nsym %d, total %u): run groups %u (%u members); small left %u, medium %u, large %u (%u members); run members placed directly %u, sorted %u, kept out of the round-0 sort %u\n",
-                                nsym, total, nRun, runElems, surv, nMed, nLarge, largeElems, (nRun && runDirect) ? runElems : 0u, (nRun && !runDirect) ? runElems : 0u, gaps ? keptOut : 0u);
+        if (tune.stats) fprintf(stderr, "after round 0 (nsym %d, total %u): run groups %u (%u members); small left %u, medium %u, large %u (%u members); run members placed directly %u, sorted %u, kept out of the round-0 sort %u; flag workgroups inside a gap %u\n",
+                                nsym, total, nRun, runElems, surv, nMed, nLarge, largeElems, (nRun && runDirect) ? runElems : 0u, (nRun && !runDirect) ? runElems : 0u, gaps ? keptOut : 0u,
+                                gaps ? r0Skipped : 0u);
         statT = std::chrono::steady_clock::now();
         return 0;
     }
