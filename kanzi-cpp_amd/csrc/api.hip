@@ -130,6 +130,29 @@ static std::string lane_ws(const char* base, int lane) { return lane <= 0 ? std:
 constexpr size_t PINNED_LANE_U32 = 32768;
 static u32* lane_pinned(Ctx* c, int lane) { return reinterpret_cast<u32*>(c->pinned) + PINNED_LANE_U32 * (lane < 0 ? 0 : lane); }
 
+// The fixed host words of the batch drivers (Encoder, Decoder) in the same area, all at the start of lane 0's slice:
+//   byte 0      total      the encoder's read-back of the output's size (bits of one stream, bytes of many)
+//   byte 8      marked     the blocks that did not fit a two-tier coder's first staging, read back with the total
+//   byte 0      walk       the decoder's read-back of the block walk (a call encodes or decodes, and the context is locked)
+//   byte 4096   hostedSum  a hosted block's checksum on its way to the device
+//   byte 0 ...  caps       the encoder's two capacity arrays of nBlocks words each on their way to the device, over as much of the
+//                          area as they need, all lanes' slices included
+// The capacity arrays are uploaded before the first stage runs, and the encoder synchronises its stream behind the upload
+// (Encoder::capacities): they are gone before a stage reads anything back into a lane's slice and before total and marked are
+// written. A hosted call has one block, so its capacities (bytes 0-7) stay clear of hostedSum, which is uploaded in front of them.
+// The stages synchronise behind their own read-backs; total, marked and walk are read behind a synchronisation of the context's
+// stream, at points where no stage runs.
+struct WalkResultHost { u64 endBit; int64_t nBlocks; int32_t ended; int32_t error; };
+struct PinnedWords {
+    u8* base;
+    explicit PinnedWords(Ctx* c) : base(static_cast<u8*>(c->pinned)) {}
+    u64* total() const { return reinterpret_cast<u64*>(base); }
+    u32* marked() const { return reinterpret_cast<u32*>(base + 8); }
+    WalkResultHost* walk() const { return reinterpret_cast<WalkResultHost*>(base); }
+    u64* hostedSum() const { return reinterpret_cast<u64*>(base + 4096); }
+    u32* caps() const { return reinterpret_cast<u32*>(base); }
+};
+
 thread_local ProfHook* g_prof = nullptr;
 
 struct CtxProf : ProfHook {
@@ -235,10 +258,17 @@ static std::atomic<int>& bwt_part_min_knob()
     return v;
 }
 
-// ranges of a batch that knz_hip_decode_blocks runs side by side on streams of their own (KNZ_DEC_PARTS / knob "dec_parts"; decode_impl)
+// ranges of a batch that knz_hip_decode_blocks runs side by side on streams of their own (KNZ_DEC_PARTS / knob "dec_parts"; Decoder::plan)
 static std::atomic<int>& dec_parts_knob()
 {
     static std::atomic<int> v([] { const char* e = getenv("KNZ_DEC_PARTS"); const int x = e ? atoi(e) : 3; return x < 1 ? 1 : (x > 3 ? 3 : x); }());
+    return v;
+}
+
+// fewest blocks such a range may have (KNZ_DEC_PART_MIN)
+static std::atomic<int>& dec_part_min_knob()
+{
+    static std::atomic<int> v([] { const char* e = getenv("KNZ_DEC_PART_MIN"); const int x = e ? atoi(e) : 2; return x < 1 ? 1 : x; }());
     return v;
 }
 
@@ -509,7 +539,7 @@ struct XfInfo {
     XfDir fwd, inv;
     bool setsType = false;       // reads and sets the per-block data type (XfStage::dtype)
     bool ignoresType = false;    // would have to read the data type and does not: refused behind a stage that sets it
-    bool lanes = true;           // the inverse may run in decode lanes (decode_impl)
+    bool lanes = true;           // the inverse may run in decode lanes (Decoder::plan)
 };
 
 static int lz_inverse(const StageCall& k)
@@ -579,14 +609,14 @@ static const XfInfo XF[] = {
                         .inv = { .launch = [](const StageCall& k) { launch_sbrt_inverse(k.s, k.st, 2); return 0; } } },
     { .id = KNZ_T_TIMESTAMP, .fwd = { .launch = [](const StageCall& k) { launch_sbrt_forward(k.s, k.st, 3); return 0; } },
                              .inv = { .launch = [](const StageCall& k) { launch_sbrt_inverse(k.s, k.st, 3); return 0; } } },
-    // (AliasCodec; the data type it starts from is preset from the block's magic or taken from the host stages, encode_impl)
+    // (AliasCodec; the data type it starts from is preset from the block's magic or taken from the host stages, Encoder::data_types)
     { .id = KNZ_T_PACK, .ws = "packScratch",
       .fwd = { .wsBytes = pack_scratch_bytes, .launch = [](const StageCall& k) { launch_pack_forward(k.s, k.st, k.ws); return 0; } },
       .inv = { .wsBytes = pack_scratch_bytes, .launch = [](const StageCall& k) { launch_pack_inverse(k.s, k.st, k.ws); return 0; } },
       .setsType = true },
     // (DNA, id 19: AliasCodec with the Context entry packOnlyDNA, TransformFactory.hpp:293-294. PACK's launchers; the forward refuses a
     // preset type other than UNDEFINED or DNA and a block whose detection does not say DNA, after it wrote what detection found. The
-    // inverse is PACK's. The Context entry outlives the stage: a PACK behind DNA in one chain is built with it too, encode_impl)
+    // inverse is PACK's. The Context entry outlives the stage: a PACK behind DNA in one chain is built with it too, Encoder::transforms)
     { .id = KNZ_T_DNA, .ws = "packScratch",
       .fwd = { .wsBytes = pack_scratch_bytes, .launch = [](const StageCall& k) { XfStage st = k.st; st.onlyDNA = 1; launch_pack_forward(k.s, st, k.ws); return 0; } },
       .inv = { .wsBytes = pack_scratch_bytes, .launch = [](const StageCall& k) { launch_pack_inverse(k.s, k.st, k.ws); return 0; } },
@@ -601,7 +631,7 @@ static const XfInfo XF[] = {
     { .id = KNZ_T_LZP, .ws = "lzpScratch",
       .fwd = { .wsBytes = lzp_scratch_bytes, .launch = [](const StageCall& k) { launch_lzp_forward(k.s, k.st, k.ws); return 0; } },
       .inv = { .wsBytes = lzp_scratch_bytes, .launch = [](const StageCall& k) { launch_lzp_inverse(k.s, k.st, k.ws); return 0; } } },
-    // (UTFCodec; it reads the data type -- preset from the block's magic, or what TEXT left on the host, encode_impl -- and writes UTF8,
+    // (UTFCodec; it reads the data type -- preset from the block's magic, or what TEXT left on the host, Encoder::data_types -- and writes UTF8,
     // which LZ and LZX treat like UNDEFINED (LZCodec.cpp:182-191). The refusal of LZ / LZX behind a stage that sets the type is kept for
     // UTF all the same: a block UTF refuses keeps its preset type, which the device LZ stages do not read. Scratch per lane like LZP's, so
     // the inverse runs in decode lanes. Behind the hosted prefix (TEXT) it is a device stage like any other, parse_chain)
@@ -866,7 +896,7 @@ static int seq_required(const Chain& ch, int n)
 
 // stride of a chain's two workspaces for blocks of n bytes. The chain's bound is what the reference gives the task's "buffer", and a
 // stage in even position may fill it: ZRLT in front writes up to requiredSize for a block without zeros, more than its own
-// getMaxEncodedLength. The stage behind it writes into the task's "data" (256 KiB or more, encode_impl) and asks for its own bound over
+// getMaxEncodedLength. The stage behind it writes into the task's "data" (256 KiB or more, model_capacities) and asks for its own bound over
 // that longer input (LZP: n + n / 64, ROLZX and SRT: n + 1024, MM: n + n / 16), so with two stages or more the stride is the chain's
 // bound of the chain's bound. A capacity is cut to the stride (k_seq_fwd_prepare); cut to the bound alone, ZRLT+LZP, ZRLT+ROLZX,
 // ZRLT+SRT and ZRLT+MM refused blocks in second position that the reference transforms (tests/test_gpu_pairs.py).
@@ -984,7 +1014,7 @@ static int run_stage(Ctx* c, hipStream_t s, const XfInfo& x, bool forward, const
 // blocks x longest block below 2 GiB (the documented limit, include/knz_hip.h) stays below this whatever the chain adds to the stride.
 constexpr u64 STREAMS_MAX_WORK = (u64)1 << 32;
 
-// A batch of many streams as encode_impl takes it (knz_hip_encode_streams builds it): the blocks of all streams in stream order, block b
+// A batch of many streams as the encoder takes it (knz_hip_encode_streams builds it): the blocks of all streams in stream order, block b
 // at d_in + inOff[b] with len[b] bytes, stream i owning the blocks [first[i], first[i + 1]). The d_* arrays are one upload.
 struct EncTab {
     int nItems = 0, nBlocks = 0;
@@ -995,218 +1025,239 @@ struct EncTab {
     std::vector<StreamOut> res;                // OUT: where the streams lie
 };
 
-// The output of a batch of many streams behind the framing scan: room check, the one clearing of the range (padding included), prologues
-static int streams_place(Ctx* c, hipStream_t s, const EncTab* tab, uint8_t* d_out, size_t outCap, u64 totalBytes)
+// What an entry point asks of the encoder. The defaults are a framed batch of one stream that starts with block 0, without a prologue.
+struct EncJob {
+    const knz_params* p = nullptr;
+    const uint8_t* d_in = nullptr; size_t n = 0;           // (many streams: all their bytes)
+    const uint8_t* prologue = nullptr; uint32_t prologueBits = 0;      // host bytes in front of the first block (many streams: unused, every stream has its own)
+    int framing = 1;                                       // 0: the bare entropy stage over one buffer (knz_hip_entropy_encode_bs)
+    int finish = 0;                                        // the end marker behind the blocks
+    int64_t firstBlock = 0;                                // the first block's id in its stream (many streams count from 0)
+    uint8_t* d_out = nullptr; size_t outCap = 0;
+    uint64_t* outBits = nullptr;                           // OUT: the bits written (many streams: 8 * the bytes of d_out in use); nullptr: no wait for the assembly
+    const knz_host_stages* hs = nullptr;                   // one block whose leading stages the host has run
+    u32 streamBlockSize = 0;                               // block size of the stream the buffer belongs to, where p->block_size is not it (per-stage calls)
+    EncTab* tab = nullptr;                                 // the batch holds many streams
+};
+
+// Destination capacities the reference would present (io/CompressedOutputStream.cpp:141,461-462,733-739): block i of a stream runs on
+// buffer slot i % jobs; "data" of slot 0 is max(bs + bs/8, 256 KiB), of the others max(bs + bs/64, 64 KiB); "buffer" grows to the largest
+// requiredSize seen on the slot. Host arithmetic only: bufCap[b] and dataCap[b] of the nBlocks blocks of one stream whose first has the id
+// firstBlock -- len[b] bytes each, or with len == nullptr n bytes cut into blocks of bs --, or with `first` (every stream's first block, and
+// one entry more) of many streams, each of which starts with fresh buffers and counts its blocks from 0.
+static void model_capacities(const Chain& ch, int jobs, u32 bs, int64_t firstBlock, int nBlocks, size_t n, const u32* len, const u32* first,
+                             u32* bufCap, u32* dataCap)
 {
-    if (totalBytes > outCap) return fail(c, KNZ_ERR_WRITE_FILE, "output buffer too small: need %zu have %zu", (size_t)totalBytes, outCap);
-    {
-        ProfScope ps(c, "memset_out");
-        if (totalBytes) HIPCHK(c, hipMemsetAsync(d_out, 0, (size_t)totalBytes, s));
-    }
-    launch_stream_prologues(s, reinterpret_cast<u32*>(d_out), tab->d_st, tab->d_res, tab->nItems, tab->d_pro);
-    return 0;
-}
-
-static int streams_results(Ctx* c, hipStream_t s, EncTab* tab)
-{
-    tab->res.resize((size_t)tab->nItems);
-    if (tab->nItems) HIPCHK(c, hipMemcpyAsync(tab->res.data(), tab->d_res, sizeof(StreamOut) * (size_t)tab->nItems, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    HIPCHK(c, hipGetLastError());
-    return 0;
-}
-
-// capsMode: 0 = reference stream buffers (jobs model), otherwise every destination capacity = capsMode (per-stage API)
-// tab: the batch holds many streams (n = all their bytes; prologue, prologueBits and firstBlock are unused: every stream has its own
-// prologue and counts its blocks from 0; *outBits = 8 * the bytes of d_out in use)
-static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t n, const uint8_t* prologue,
-                       uint32_t prologueBits, int framing, int finish, int64_t firstBlock, uint8_t* d_out, size_t outCap,
-                       uint64_t* outBits, const knz_host_stages* hs = nullptr, u32 streamBlockSize = 0, EncTab* tab = nullptr)
-{
-    ProfInstall pi_(c);
-    HIPCHK(c, hipSetDevice(c->device));
-    if ((reinterpret_cast<uintptr_t>(d_in) & 15) || (reinterpret_cast<uintptr_t>(d_out) & 15))
-        return fail(c, KNZ_ERR_INVALID_PARAM, "device buffers must be 16-byte aligned");
-    const u32 bs = (u32)p->block_size;
-    if (framing && (bs < 1024 || bs > (1u << 30) || (bs & 15))) return fail(c, KNZ_ERR_INVALID_PARAM, "invalid block size %u", bs);
-    Chain ch;
-    const int nHosted = hs ? hs->stages : 0;
-    if (int r = parse_chain(c, p, nHosted, true, &ch)) return r;
-    const int nTok = ch.n;
-    hipStream_t s = c->stream;
-
-    const int nBlocks = tab ? tab->nBlocks : (n == 0) ? 0 : (int)((n + bs - 1) / bs);
-    const u64* inOff = tab ? tab->d_inOff : nullptr;
-    const u32* lenTab = tab ? tab->d_len : nullptr;
-    if (hs) {
-        // one block, in the length the host stages left it (never longer than the block it came from)
-        if (nBlocks != 1 || hs->orig_len > bs || n > hs->orig_len + 8192u) return fail(c, KNZ_ERR_INVALID_PARAM, "a hosted call takes exactly one block");
-        if ((hs->orig_len <= 15) != (n <= 15) || (hs->orig_len <= 15 && hs->applied_mask)) return fail(c, KNZ_ERR_INVALID_PARAM, "copy blocks go through no stage");
-    }
-    // device-side positions of a batch are 32-bit (suffix array slots, bit offsets inside staging areas): a batch
-    // is limited to 2 GiB of input; the host layers split larger inputs into several calls
-    if (n > (size_t)0x7FFFFFFF - 8ull * (size_t)(nBlocks + 1) * 1056) return fail(c, KNZ_ERR_INVALID_PARAM, "batch of %zu bytes exceeds the 2 GiB per-call limit", n);
-    if ((prologueBits + 7) / 8 > 200) return fail(c, KNZ_ERR_INVALID_PARAM, "prologue too long");
-    const size_t needOut = ((size_t)prologueBits + 7) / 8 + 16;
-    if (outCap < needOut) return fail(c, KNZ_ERR_WRITE_FILE, "output buffer too small");
-    u64* d_total;
-    if (int r = ws_get(c, "total", 64, (void**)&d_total, s)) return r;
-
-    FrameParams fp;
-    fp.framing = framing; fp.nTransforms = nTok; fp.checksumBits = p->checksum_bits; fp.finish = finish; fp.prologueBits = prologueBits;
-    u64* h_total = reinterpret_cast<u64*>(c->pinned);
-    if (nBlocks == 0 && tab) {
-        // empty streams only: each is its prologue and the end marker
-        launch_stream_frame(s, nullptr, nullptr, nullptr, nullptr, 0, tab->d_st, tab->nItems, fp, tab->d_excl, tab->d_res, d_total);
-        HIPCHK(c, hipMemcpyAsync(h_total, d_total, sizeof(u64), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        if (int r = streams_place(c, s, tab, d_out, outCap, *h_total)) return r;
-        if (outBits) *outBits = 8 * *h_total;
-        return streams_results(c, s, tab);
-    }
-    if (nBlocks == 0) {
-        HIPCHK(c, hipMemsetAsync(d_out, 0, needOut, s));
-        if (prologueBits) {
-            u8* d_pro;
-            if (int r = ws_get(c, "prologue", 256, (void**)&d_pro, s)) return r;
-            HIPCHK(c, hipMemcpyAsync(d_pro, prologue, (prologueBits + 7) / 8, hipMemcpyHostToDevice, s));
-            launch_put_prologue(s, reinterpret_cast<u32*>(d_out), d_pro, prologueBits);
+    jobs = (jobs <= 0) ? 1 : (jobs > 64 ? 64 : jobs);
+    u32 slotBuf[64] = { 0 };
+    const u32 full = (u32)seq_required(ch, (int)bs);
+    for (int64_t b = 0, it = 0; b < nBlocks; b++) {
+        if (first) {
+            const int64_t was = it;
+            while ((int64_t)first[it + 1] <= b) it++;
+            if (it != was) std::fill(slotBuf, slotBuf + jobs, 0u);
         }
+        const int64_t gid = first ? b - (int64_t)first[it] : firstBlock + b;
+        const int slot = (int)(gid % jobs);
+        const u32 l = len ? len[b] : (u32)(((size_t)(b + 1) * bs <= n) ? bs : n - (size_t)b * bs);      // (the reference sizes its buffers by the block as read)
+        const u32 req = (u32)seq_required(ch, (int)l);
+        // a slot's buffer is at least what a full block needed earlier on that slot, and what this block needs
+        u32 bufc = slotBuf[slot];
+        if (gid >= jobs && bufc < full) bufc = full;
+        if (bufc < req) bufc = req;
+        slotBuf[slot] = bufc;
+        const u32 datac = (slot == 0) ? std::max(bs + (bs >> 3), 256u * 1024u) : std::max(bs + (bs >> 6), 65536u);
+        bufCap[b] = bufc;
+        dataCap[b] = std::max(datac, req);
+    }
+}
+
+// One batch through the transforms, the entropy coder and the bit assembly, phase by phase (run). Four kinds of request share it: a
+// framed batch, one hosted block (hs), many streams (tab), and the bare entropy stage of the per-stage calls (framing 0).
+struct Encoder {
+    Ctx* c; const EncJob& j;
+    ProfInstall prof;
+    const knz_params* p; const knz_host_stages* hs; EncTab* tab; hipStream_t s; u32 bs; PinnedWords pin;
+    Chain ch; int nHosted = 0, nBlocks = 0;
+    bool realStages = false, wantType = false, direct = false;      // a stage other than NONE; a device stage reads the per-block data type; NullTransforms only
+    FrameParams fp; u64* d_total = nullptr;
+    u64 S = 0; SeqWs w;
+    u32* d_origLen = nullptr; BlockInfo* d_info = nullptr; u64* d_sums = nullptr;
+    EcEnc enc; EcStaged staged; u32 slotMul = 1;
+
+    Encoder(Ctx* ctx, const EncJob& job) : c(ctx), j(job), prof(ctx), p(job.p), hs(job.hs), tab(job.tab), s(ctx->stream), bs((u32)job.p->block_size), pin(ctx) {}
+
+    const u64* in_off() const { return tab ? tab->d_inOff : nullptr; }
+    const u32* len_tab() const { return tab ? tab->d_len : nullptr; }
+    size_t min_out() const { return ((size_t)j.prologueBits + 7) / 8 + 16; }
+
+    // The request is one the phases can take: the chain, nBlocks and the frame parameters are set. Nothing is launched.
+    int check()
+    {
+        HIPCHK(c, hipSetDevice(c->device));
+        if ((reinterpret_cast<uintptr_t>(j.d_in) & 15) || (reinterpret_cast<uintptr_t>(j.d_out) & 15))
+            return fail(c, KNZ_ERR_INVALID_PARAM, "device buffers must be 16-byte aligned");
+        if (j.framing && (bs < 1024 || bs > (1u << 30) || (bs & 15))) return fail(c, KNZ_ERR_INVALID_PARAM, "invalid block size %u", bs);
+        nHosted = hs ? hs->stages : 0;
+        if (int r = parse_chain(c, p, nHosted, true, &ch)) return r;
+        for (int i = 0; i < ch.n; i++) { realStages |= ch.tok[i] != KNZ_T_NONE; wantType |= ch.xf[i] && ch.xf[i]->setsType; }
+        // (what the phases behind rely on. No public entry point builds such a request: the per-stage entropy calls have no transform, the
+        // per-stage transform calls go through transform_host and never come here)
+        if (!j.framing && realStages) return fail(c, KNZ_ERR_INVALID_PARAM, "a call without framing takes no transform");
+        nBlocks = tab ? tab->nBlocks : (j.n == 0) ? 0 : (int)((j.n + bs - 1) / bs);
+        if (hs) {
+            // one block, in the length the host stages left it (never longer than the block it came from)
+            if (nBlocks != 1 || hs->orig_len > bs || j.n > hs->orig_len + 8192u) return fail(c, KNZ_ERR_INVALID_PARAM, "a hosted call takes exactly one block");
+            if ((hs->orig_len <= 15) != (j.n <= 15) || (hs->orig_len <= 15 && hs->applied_mask)) return fail(c, KNZ_ERR_INVALID_PARAM, "copy blocks go through no stage");
+        }
+        // device-side positions of a batch are 32-bit (suffix array slots, bit offsets inside staging areas): a batch
+        // is limited to 2 GiB of input; the host layers split larger inputs into several calls
+        if (j.n > (size_t)0x7FFFFFFF - 8ull * (size_t)(nBlocks + 1) * 1056) return fail(c, KNZ_ERR_INVALID_PARAM, "batch of %zu bytes exceeds the 2 GiB per-call limit", j.n);
+        if ((j.prologueBits + 7) / 8 > 200) return fail(c, KNZ_ERR_INVALID_PARAM, "prologue too long");
+        if (j.outCap < min_out()) return fail(c, KNZ_ERR_WRITE_FILE, "output buffer too small");
+        fp.framing = j.framing; fp.nTransforms = ch.n; fp.checksumBits = p->checksum_bits; fp.finish = j.finish; fp.prologueBits = j.prologueBits;
+        return ws_get(c, "total", 64, (void**)&d_total, s);
+    }
+
+    // No block: the output is the prologue (every stream's own) and, where asked for, the end marker. Synchronises the stream.
+    int empty()
+    {
+        if (tab) {
+            launch_stream_frame(s, nullptr, nullptr, nullptr, nullptr, 0, tab->d_st, tab->nItems, fp, tab->d_excl, tab->d_res, d_total);
+            if (int r = read_total(false)) return r;
+            return place();
+        }
+        HIPCHK(c, hipMemsetAsync(j.d_out, 0, min_out(), s));
+        if (int r = prologues()) return r;
         HIPCHK(c, hipStreamSynchronize(s));
-        if (outBits) *outBits = (u64)prologueBits + ((framing && finish) ? 8 : 0);
+        if (j.outBits) *j.outBits = (u64)j.prologueBits + ((j.framing && j.finish) ? 8 : 0);
         return 0;
     }
 
-    // ---- block bookkeeping
-    u32 *d_origLen; BlockInfo* d_info;
-    if (int r = ws_get(c, "origLen", sizeof(u32) * nBlocks, (void**)&d_origLen, s)) return r;
-    if (int r = ws_get(c, "info", sizeof(BlockInfo) * nBlocks, (void**)&d_info, s)) return r;
-    const int maxIn = tab ? (int)tab->maxLen : (int)((n < bs) ? n : bs);
-    const int required = seq_stride(ch, maxIn);
-    const u64 S = ((u64)required + 255) & ~255ull;
-    bool realStages = false, wantType = false;              // (wantType: a device stage reads the per-block data type)
-    for (int i = 0; i < nTok; i++) { realStages |= ch.tok[i] != KNZ_T_NONE; wantType |= ch.xf[i] && ch.xf[i]->setsType; }
-    SeqWs w;
-    if (tab && (u64)nBlocks * S > STREAMS_MAX_WORK) return fail(c, KNZ_ERR_INVALID_PARAM, "%d blocks with a longest block of %d bytes exceed the workspace limit of a call (blocks x longest block <= 2 GiB): split the call", nBlocks, maxIn);
-    if (int r = seq_alloc(c, nBlocks, S, realStages, chain_scratch_u32(ch, true, nBlocks, (u32)S), &w, -1, s)) return r;
-    w.a.origLen = d_origLen;
-    const bool direct = !realStages && !p->checksum_bits;      // NullTransforms only: one bookkeeping launch
-    if (!direct) launch_init_blocks(s, n, bs, nBlocks, d_origLen, w.a.len, lenTab);
-    // block checksums of the ORIGINAL bytes (io/CompressedOutputStream.cpp:675-682)
-    u64* d_sums = nullptr;
-    if (p->checksum_bits) {
+    // The per-block arrays and the chain's workspaces of stride S. Queued: the blocks' lengths (the direct path sets them with its one
+    // launch, transforms) and the checksums of the ORIGINAL bytes (io/CompressedOutputStream.cpp:675-682).
+    int bookkeeping()
+    {
+        if (int r = ws_get(c, "origLen", sizeof(u32) * nBlocks, (void**)&d_origLen, s)) return r;
+        if (int r = ws_get(c, "info", sizeof(BlockInfo) * nBlocks, (void**)&d_info, s)) return r;
+        const int maxIn = tab ? (int)tab->maxLen : (int)((j.n < bs) ? j.n : bs);
+        S = ((u64)seq_stride(ch, maxIn) + 255) & ~255ull;
+        if (tab && (u64)nBlocks * S > STREAMS_MAX_WORK) return fail(c, KNZ_ERR_INVALID_PARAM, "%d blocks with a longest block of %d bytes exceed the workspace limit of a call (blocks x longest block <= 2 GiB): split the call", nBlocks, maxIn);
+        if (int r = seq_alloc(c, nBlocks, S, realStages, chain_scratch_u32(ch, true, nBlocks, (u32)S), &w, -1, s)) return r;
+        w.a.origLen = d_origLen;
+        direct = !realStages && !p->checksum_bits;
+        if (!direct) launch_init_blocks(s, j.n, bs, nBlocks, d_origLen, w.a.len, len_tab());
+        if (!p->checksum_bits) return 0;
         if (int r = ws_get(c, "sums", sizeof(u64) * nBlocks, (void**)&d_sums, s)) return r;
         if (hs) {
-            // (the checksum is the ORIGINAL block's: the host computed it before its stages ran)
-            u64* hsum = reinterpret_cast<u64*>(c->pinned) + 512;
-            *hsum = hs->checksum;
-            HIPCHK(c, hipMemcpyAsync(d_sums, hsum, sizeof(u64), hipMemcpyHostToDevice, s));
+            // (the host computed the checksum before its stages ran)
+            *pin.hostedSum() = hs->checksum;
+            HIPCHK(c, hipMemcpyAsync(d_sums, pin.hostedSum(), sizeof(u64), hipMemcpyHostToDevice, s));
         } else {
-            launch_block_ptrs(s, d_in, bs, nBlocks, w.d_viewPtr, inOff);
+            launch_block_ptrs(s, j.d_in, bs, nBlocks, w.d_viewPtr, in_off());
             launch_xxhash(s, w.d_viewPtr, d_origLen, nBlocks, p->checksum_bits, d_sums);
         }
+        return 0;
     }
 
-    // destination capacities the reference would present (io/CompressedOutputStream.cpp:141,461-462,733-739):
-    // block i runs on buffer slot i % jobs; "data" of slot 0 is max(bs + bs/8, 256 KiB), of the others
-    // max(bs + bs/64, 64 KiB); "buffer" grows to the largest requiredSize seen on the slot.
-    if (realStages) {
-        const int jobs = (p->jobs <= 0) ? 1 : (p->jobs > 64 ? 64 : p->jobs);
+    // The capacities of the reference's buffers (model_capacities) on the device, for chains with a stage. Synchronises the stream: the
+    // arrays leave through the pinned area, whose words the stages and the framing use from here on (PinnedWords).
+    int capacities()
+    {
+        if (!realStages) return 0;
         if ((size_t)nBlocks * 8 > c->pinnedCap) return fail(c, KNZ_ERR_INVALID_PARAM, "too many blocks in one batch (%d)", nBlocks);
-        u32* h = reinterpret_cast<u32*>(c->pinned);
-        u32* hEven = h; u32* hOdd = h + nBlocks;
-        std::vector<u32> slotBuf((size_t)jobs, 0);
-        // (a batch of many streams: every stream starts with fresh buffers and counts its blocks from 0)
-        for (int64_t b = 0, it = 0; b < nBlocks; b++) {
-            if (tab) {
-                const int64_t was = it;
-                while ((int64_t)tab->first[(size_t)it + 1] <= b) it++;
-                if (it != was) std::fill(slotBuf.begin(), slotBuf.end(), 0u);
-            }
-            const int64_t gid = tab ? b - (int64_t)tab->first[(size_t)it] : firstBlock + b;
-            const int slot = (int)(gid % jobs);
-            const u32 len = tab ? tab->len[(size_t)b] : hs ? hs->orig_len : (u32)(((size_t)(b + 1) * bs <= n) ? bs : n - (size_t)b * bs);      // (the reference sizes its buffers by the block as read)
-            const u32 req = (u32)seq_required(ch, (int)len);
-            // a slot's buffer is at least what a full block needed earlier on that slot
-            u32 bufc = slotBuf[slot];
-            if (gid >= jobs) { const u32 full = (u32)seq_required(ch, (int)bs); if (bufc < full) bufc = full; }
-            if (bufc < req) bufc = req;
-            slotBuf[slot] = bufc;
-            u32 datac = (slot == 0) ? std::max(bs + (bs >> 3), 256u * 1024u) : std::max(bs + (bs >> 6), 65536u);
-            if (!framing) { bufc = (u32)p->jobs; datac = (u32)p->jobs; }      // per-stage API: explicit capacity
-            hEven[b] = framing ? std::max(bufc, req) : bufc;
-            hOdd[b] = framing ? std::max(datac, req) : datac;
-        }
+        u32* hEven = pin.caps(); u32* hOdd = hEven + nBlocks;
+        model_capacities(ch, p->jobs, bs, j.firstBlock, nBlocks, j.n, tab ? tab->len.data() : hs ? &hs->orig_len : nullptr, tab ? tab->first.data() : nullptr,
+                         hEven, hOdd);
         HIPCHK(c, hipMemcpyAsync(w.d_capEven, hEven, sizeof(u32) * nBlocks, hipMemcpyHostToDevice, s));
         HIPCHK(c, hipMemcpyAsync(w.d_capOdd, hOdd, sizeof(u32) * nBlocks, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipStreamSynchronize(s));     // pinned scratch is reused below
+        HIPCHK(c, hipStreamSynchronize(s));
+        return 0;
     }
 
-    // ---- per-block data type: preset from the block's magic, or what the host stages left
-    if (wantType) {
+    // The per-block data type, where a device stage reads it: preset from the block's magic, or what the host stages left
+    int data_types()
+    {
+        if (!wantType) return 0;
         if (hs) HIPCHK(c, hipMemsetAsync(w.a.dtype, hs->reserved <= 9 ? (int)hs->reserved : 0, (size_t)nBlocks, s));
-        else launch_seq_fwd_dtype(s, w.a, nBlocks, d_in, bs, inOff);
+        else launch_seq_fwd_dtype(s, w.a, nBlocks, j.d_in, bs, in_off());
+        return 0;
     }
 
-    // ---- transform stages
-    if (direct) launch_seq_fwd_direct(s, w.a, d_origLen, n, bs, nBlocks, nTok, d_in, w.d_viewPtr, inOff, lenTab);
-    for (int i = 0; i < nTok && !direct; i++) {
-        launch_seq_fwd_prepare(s, w.a, nBlocks, i, d_in, bs, w.A, w.B, S, inOff);
-        if (i < nHosted) {
-            launch_seq_fwd_hosted(s, w.a, nBlocks, i, (hs->applied_mask >> i) & 1u);
-            continue;
+    // The chain over the batch: w.d_viewPtr and w.a.len are what the entropy coder reads, w.a.skip the stages that refused a block. The BWT
+    // and BWTS stages synchronise the stream between their rounds (XF).
+    int transforms()
+    {
+        if (direct) { launch_seq_fwd_direct(s, w.a, d_origLen, j.n, bs, nBlocks, ch.n, j.d_in, w.d_viewPtr, in_off(), len_tab()); return 0; }
+        for (int i = 0; i < ch.n; i++) {
+            launch_seq_fwd_prepare(s, w.a, nBlocks, i, j.d_in, bs, w.A, w.B, S, in_off());
+            if (i < nHosted) {
+                launch_seq_fwd_hosted(s, w.a, nBlocks, i, (hs->applied_mask >> i) & 1u);
+                continue;
+            }
+            if (ch.xf[i] == nullptr) {
+                launch_seq_fwd_null(s, w.a, nBlocks, i);
+                continue;
+            }
+            XfStage st = xf_stage(w, nBlocks, (u32)S, p->entropy_type);
+            st.dtype = wantType ? w.a.dtype : nullptr;
+            st.blockSize = j.streamBlockSize ? j.streamBlockSize : bs;
+            // (TransformFactory.hpp:290-295: the DNA transform leaves packOnlyDNA in the Context that the chain's later stages are built
+            // from, so a PACK anywhere behind it in the same chain refuses what is not DNA as well)
+            for (int k = 0; k < i; k++) if (ch.tok[k] == KNZ_T_DNA) st.onlyDNA = 1;
+            if (int r = run_stage(c, s, *ch.xf[i], true, st)) return r;
+            launch_seq_fwd_commit(s, w.a, nBlocks, i);
         }
-        if (ch.xf[i] == nullptr) {
-            launch_seq_fwd_null(s, w.a, nBlocks, i);
-            continue;
-        }
-        XfStage st = xf_stage(w, nBlocks, (u32)S, p->entropy_type);
-        st.dtype = wantType ? w.a.dtype : nullptr;
-        st.blockSize = streamBlockSize ? streamBlockSize : (framing ? bs : 0u);
-        // (TransformFactory.hpp:290-295: the DNA transform leaves packOnlyDNA in the Context that the chain's later stages are built
-        // from, so a PACK anywhere behind it in the same chain refuses what is not DNA as well)
-        for (int j = 0; j < i; j++) if (ch.tok[j] == KNZ_T_DNA) st.onlyDNA = 1;
-        if (int r = run_stage(c, s, *ch.xf[i], true, st)) return r;
-        launch_seq_fwd_commit(s, w.a, nBlocks, i);
+        launch_seq_fwd_finish(s, w.a, nBlocks, j.d_in, bs, w.A, w.B, S, w.d_viewPtr, in_off());
+        return 0;
     }
-    if (!direct) launch_seq_fwd_finish(s, w.a, nBlocks, d_in, bs, w.A, w.B, S, w.d_viewPtr, inOff);
-    BlockView view;
-    view.ptr = w.d_viewPtr; view.len = w.a.len;
-    u32* d_blockLen = w.a.len;
-    u8* d_skip = w.a.skip;
 
-    // ---- entropy stage
-    const EcInfo* ec = ch.ec;
-    const u32 entChunk = ec->entChunk;
-    const u32 slotMul = ec->slotsOf ? (u32)ec->slotsOf(S) : ec->slots;
-    const int chunksPerBlock = (int)((S + entChunk - 1) / entChunk);
-    const int maxChunks = chunksPerBlock * (int)slotMul;
-    const size_t nSlots = (size_t)nBlocks * maxChunks;
-    ChunkDesc* d_desc;
-    if (int r = ws_get(c, "desc", sizeof(ChunkDesc) * nSlots, (void**)&d_desc, s)) return r;
-    const EcEnc enc = { c, s, view, d_origLen, framing ? 15u : 0u, nBlocks, S, chunksPerBlock, maxChunks, nSlots, d_desc,
-                        streamBlockSize ? streamBlockSize : bs, ec->extra };
-    EcStaged staged;
-    if (int r = ec->encode(enc, &staged)) return r;
+    // The coder's launches over the batch (enc); `staged` is what it leaves for the framing, and for a second tier
+    int entropy()
+    {
+        const EcInfo* ec = ch.ec;
+        slotMul = ec->slotsOf ? (u32)ec->slotsOf(S) : ec->slots;
+        const int chunksPerBlock = (int)((S + ec->entChunk - 1) / ec->entChunk);
+        const int maxChunks = chunksPerBlock * (int)slotMul;
+        const size_t nSlots = (size_t)nBlocks * maxChunks;
+        ChunkDesc* d_desc;
+        if (int r = ws_get(c, "desc", sizeof(ChunkDesc) * nSlots, (void**)&d_desc, s)) return r;
+        BlockView view;
+        view.ptr = w.d_viewPtr; view.len = w.a.len;
+        enc = { c, s, view, d_origLen, j.framing ? 15u : 0u, nBlocks, S, chunksPerBlock, maxChunks, nSlots, d_desc,
+                j.streamBlockSize ? j.streamBlockSize : bs, ec->extra };
+        return ec->encode(enc, &staged);
+    }
 
-    // ---- framing + assembly
-    // (many streams: the blocks' places restart at every stream, and d_total holds the BYTES of output in use)
-    auto block_scan = [&] {
-        if (tab) launch_stream_frame(s, d_info, d_blockLen, d_origLen, tab->d_itemOf, nBlocks, tab->d_st, tab->nItems, fp, tab->d_excl, tab->d_res, d_total);
-        else launch_block_scan(s, d_info, d_blockLen, d_origLen, nBlocks, fp, d_total);
-    };
-    launch_block_sum(s, d_desc, d_info, d_blockLen, nBlocks, maxChunks, entChunk, slotMul);
-    block_scan();
-    // The output must be zero before the OR-assembly; its size is only known on the device, so the
-    // total is read back first (8 bytes) and only the used part is cleared.
-    u32* h_marked = reinterpret_cast<u32*>(h_total + 1);
-    *h_marked = 0;
-    HIPCHK(c, hipMemcpyAsync(h_total, d_total, sizeof(u64), hipMemcpyDeviceToHost, s));
-    if (staged.marked) HIPCHK(c, hipMemcpyAsync(h_marked, staged.marked, sizeof(u32), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (*h_marked) {
-        // the two-tier coders, the rare path: blocks that did not fit their staging are coded again into 32 n + 16 bytes each (workspace
-        // taken only now), then the lengths are summed again
+    // d_total, and with `marked` the count of the blocks that did not fit their staging, in the pinned words. Synchronises the stream.
+    int read_total(bool marked)
+    {
+        if (marked) *pin.marked() = 0;
+        HIPCHK(c, hipMemcpyAsync(pin.total(), d_total, sizeof(u64), hipMemcpyDeviceToHost, s));
+        if (marked && staged.marked) HIPCHK(c, hipMemcpyAsync(pin.marked(), staged.marked, sizeof(u32), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        return 0;
+    }
+
+    // The blocks' lengths summed and their places scanned (many streams: the places restart at every stream, and d_total holds the BYTES
+    // of output in use), the total read back. Synchronises the stream.
+    int sum_and_scan(bool marked)
+    {
+        launch_block_sum(s, enc.desc, d_info, w.a.len, nBlocks, enc.maxChunks, ch.ec->entChunk, slotMul);
+        if (tab) launch_stream_frame(s, d_info, w.a.len, d_origLen, tab->d_itemOf, nBlocks, tab->d_st, tab->nItems, fp, tab->d_excl, tab->d_res, d_total);
+        else launch_block_scan(s, d_info, w.a.len, d_origLen, nBlocks, fp, d_total);
+        return read_total(marked);
+    }
+
+    // Every block's place in the output and the output's size on the host: it must be zero before the OR-assembly and its size is only
+    // known on the device, so the total is read back first (8 bytes) and only the used part is cleared (place). Synchronises the stream
+    // once, or twice where blocks of a two-tier coder are coded again.
+    int frame()
+    {
+        if (int r = sum_and_scan(true)) return r;
+        if (*pin.marked() == 0) return 0;
+        // the rare path: blocks that did not fit their staging are coded again into 32 n + 16 bytes each (workspace taken only now),
+        // then the lengths are summed again
         struct Big { Ctx* c; hipStream_t s; int rc; } big = { c, s, 0 };
         auto bigAlloc = [](void* user, size_t bytes) -> void* {
             Big* g = static_cast<Big*>(user);
@@ -1214,43 +1265,68 @@ static int encode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, size_t 
             g->rc = ws_get(g->c, "cmBig", bytes, &m, g->s);
             return g->rc ? nullptr : m;
         };
-        const int r = ec->again(enc, staged, bigAlloc, &big);
+        const int r = ch.ec->again(enc, staged, bigAlloc, &big);
         if (r == -2) return big.rc;                               // (ws_get has said why)
         if (r < 0) return fail(c, -1, "binary coder: encode failed: %s", hipGetErrorString(hipGetLastError()));
-        launch_block_sum(s, d_desc, d_info, d_blockLen, nBlocks, maxChunks, entChunk, slotMul);
-        block_scan();
-        HIPCHK(c, hipMemcpyAsync(h_total, d_total, sizeof(u64), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
+        return sum_and_scan(false);
     }
-    if (tab) {
-        if (int r = streams_place(c, s, tab, d_out, outCap, *h_total)) return r;
-        launch_assemble(s, d_desc, d_info, d_blockLen, d_origLen, d_skip, d_sums, staged.hdr, nBlocks, maxChunks, entChunk, slotMul, staged.hdrStride, fp,
-                        reinterpret_cast<u32*>(d_out));
-        if (outBits) *outBits = 8 * *h_total;
-        return streams_results(c, s, tab);
-    }
-    const u64 totalBits = *h_total;
-    const size_t outBytes = (size_t)((totalBits + 7) >> 3);
-    if (((outBytes + 8 + 3) & ~(size_t)3) > outCap) return fail(c, KNZ_ERR_WRITE_FILE, "output buffer too small: need %zu have %zu", (outBytes + 8 + 3) & ~(size_t)3, outCap);
+
+    // The prologue, or every stream's own, into the cleared output
+    int prologues()
     {
-        ProfScope ps(c, "memset_out");
-        HIPCHK(c, hipMemsetAsync(d_out, 0, (outBytes + 8 + 3) & ~(size_t)3, s));
-    }
-    if (prologueBits) {
+        if (tab) { launch_stream_prologues(s, reinterpret_cast<u32*>(j.d_out), tab->d_st, tab->d_res, tab->nItems, tab->d_pro); return 0; }
+        if (!j.prologueBits) return 0;
         u8* d_pro;
         if (int r = ws_get(c, "prologue", 256, (void**)&d_pro, s)) return r;
-        HIPCHK(c, hipMemcpyAsync(d_pro, prologue, (prologueBits + 7) / 8, hipMemcpyHostToDevice, s));
-        launch_put_prologue(s, reinterpret_cast<u32*>(d_out), d_pro, prologueBits);
+        HIPCHK(c, hipMemcpyAsync(d_pro, j.prologue, (j.prologueBits + 7) / 8, hipMemcpyHostToDevice, s));
+        launch_put_prologue(s, reinterpret_cast<u32*>(j.d_out), d_pro, j.prologueBits);
+        return 0;
     }
-    launch_assemble(s, d_desc, d_info, d_blockLen, d_origLen, d_skip, d_sums, staged.hdr, nBlocks, maxChunks, entChunk, slotMul, staged.hdrStride, fp,
-                    reinterpret_cast<u32*>(d_out));
-    HIPCHK(c, hipGetLastError());
-    if (outBits) {
+
+    // The output behind the framing: room check, the one clearing of what is used (many streams: the padding between them included),
+    // prologues, assembly, and what the caller gets back. Many streams: synchronises the stream (where the streams lie is read back);
+    // one stream: only where the caller asks for the bit count.
+    int place()
+    {
+        const u64 total = *pin.total();                           // bits of the one stream, or bytes of all streams
+        const size_t used = tab ? (size_t)total : ((size_t)((total + 7) >> 3) + 8 + 3) & ~(size_t)3;
+        if (used > j.outCap) return fail(c, KNZ_ERR_WRITE_FILE, "output buffer too small: need %zu have %zu", used, j.outCap);
+        {
+            ProfScope ps(c, "memset_out");
+            if (used) HIPCHK(c, hipMemsetAsync(j.d_out, 0, used, s));
+        }
+        if (int r = prologues()) return r;
+        if (nBlocks) launch_assemble(s, enc.desc, d_info, w.a.len, d_origLen, w.a.skip, d_sums, staged.hdr, nBlocks, enc.maxChunks, ch.ec->entChunk, slotMul, staged.hdrStride, fp,
+                                     reinterpret_cast<u32*>(j.d_out));
+        if (!tab) {
+            HIPCHK(c, hipGetLastError());
+            if (j.outBits) {
+                HIPCHK(c, hipStreamSynchronize(s));
+                *j.outBits = total;
+            }
+            return 0;
+        }
+        if (j.outBits) *j.outBits = 8 * total;
+        tab->res.resize((size_t)tab->nItems);
+        if (tab->nItems) HIPCHK(c, hipMemcpyAsync(tab->res.data(), tab->d_res, sizeof(StreamOut) * (size_t)tab->nItems, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
-        *outBits = totalBits;
+        HIPCHK(c, hipGetLastError());
+        return 0;
     }
-    return 0;
-}
+
+    int run()
+    {
+        if (int r = check()) return r;
+        if (nBlocks == 0) return empty();
+        if (int r = bookkeeping()) return r;
+        if (int r = capacities()) return r;
+        if (int r = data_types()) return r;
+        if (int r = transforms()) return r;
+        if (int r = entropy()) return r;
+        if (int r = frame()) return r;
+        return place();
+    }
+};
 
 int knz_hip_encode_blocks(knz_ctx* ctx, const knz_params* p, const uint8_t* d_in, size_t n, const uint8_t* prologue,
                           uint32_t prologue_bits, int64_t first_block_id, int finish, uint8_t* d_out, size_t out_cap,
@@ -1258,7 +1334,10 @@ int knz_hip_encode_blocks(knz_ctx* ctx, const knz_params* p, const uint8_t* d_in
 {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     CTX_LOCK(c);
-    return encode_impl(c, p, d_in, n, prologue, prologue_bits, 1, finish, first_block_id, d_out, out_cap, out_bits);
+    EncJob j;
+    j.p = p; j.d_in = d_in; j.n = n; j.prologue = prologue; j.prologueBits = prologue_bits; j.firstBlock = first_block_id; j.finish = finish;
+    j.d_out = d_out; j.outCap = out_cap; j.outBits = out_bits;
+    return Encoder(c, j).run();
 }
 
 int knz_hip_encode_block_hosted(knz_ctx* ctx, const knz_params* p, const knz_host_stages* hs, const uint8_t* d_in, size_t n, const uint8_t* prologue,
@@ -1267,15 +1346,16 @@ int knz_hip_encode_block_hosted(knz_ctx* ctx, const knz_params* p, const knz_hos
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     CTX_LOCK(c);
     if (!hs) return fail(c, KNZ_ERR_INVALID_PARAM, "no host stage record");
-    return encode_impl(c, p, d_in, n, prologue, prologue_bits, 1, finish, first_block_id, d_out, out_cap, out_bits, hs);
+    EncJob j;
+    j.p = p; j.d_in = d_in; j.n = n; j.prologue = prologue; j.prologueBits = prologue_bits; j.firstBlock = first_block_id; j.finish = finish;
+    j.d_out = d_out; j.outCap = out_cap; j.outBits = out_bits; j.hs = hs;
+    return Encoder(c, j).run();
 }
 
 // ------------------------------------------------------------------------------------------------
 // decode
 // ------------------------------------------------------------------------------------------------
-struct WalkResultHost { u64 endBit; int64_t nBlocks; int32_t ended; int32_t error; };
-
-// A batch of many streams as decode_impl takes it (knz_hip_decode_streams builds it): d_sd is the upload of the items, d_walk room for
+// A batch of many streams as the decoder takes it (knz_hip_decode_streams builds it): d_sd is the upload of the items, d_walk room for
 // one StreamWalk per stream and one more. The per-stream verdicts go back into `items`.
 struct DecTab {
     int nItems = 0;
@@ -1284,43 +1364,74 @@ struct DecTab {
     const StreamDec* d_sd = nullptr; StreamWalk* d_walk = nullptr;
 };
 
-// tab: the batch holds many streams (inBits = the bits of d_in that any stream reaches; startBit, maxBlocks and the OUT arguments are
-// unused: every stream has its own start and gets its own verdict, and a stream's failure is no failure of the call)
-static int decode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, uint64_t inBits, uint64_t startBit, int64_t maxBlocks,
-                       int framing, u32 rawLen, uint8_t* d_out, size_t outCap, uint64_t* outBytes, uint64_t* endBit,
-                       int64_t* blocksDone, int32_t* rawDecoded, uint64_t* usedBits, int nHosted = 0, uint32_t* skipOut = nullptr, uint64_t* sumOut = nullptr, u32 streamBlockSize = 0,
-                       DecTab* tab = nullptr)
-{
-    ProfInstall pi_(c);
-    HIPCHK(c, hipSetDevice(c->device));
-    if ((reinterpret_cast<uintptr_t>(d_in) & 15) || (reinterpret_cast<uintptr_t>(d_out) & 15))
-        return fail(c, KNZ_ERR_INVALID_PARAM, "device buffers must be 16-byte aligned");
-    const u32 bs = (u32)p->block_size;
-    if (framing && (bs < 1024 || bs > (1u << 30) || (bs & 15))) return fail(c, KNZ_ERR_INVALID_PARAM, "invalid block size %u", bs);
-    // (the host stages in front are undone by the caller after the call: for the device they are stages that leave the data alone)
-    Chain ch;
-    if (int r = parse_chain(c, p, nHosted, false, &ch)) return r;
-    const int nTok = ch.n;
-    // bitstream version of the blocks (0 = current). Below 6 the Huffman chunks, the BWT block header and the LZ blocks have their
-    // old layouts (HuffmanDecoder.cpp:349-459, BWTBlockCodec.cpp:140-164, LZCodec.cpp:614-760)
-    const int bsVersion = (p->bs_version == 0) ? 6 : p->bs_version;
-    if (bsVersion < 0 || bsVersion > 6) return fail(c, KNZ_ERR_STREAM_VERSION, "cannot read bitstream version %d", bsVersion);
-    hipStream_t s = c->stream;
+// What an entry point asks of the decoder. The defaults are the framed blocks of one stream from bit 0, as many as the output holds.
+struct DecJob {
+    const knz_params* p = nullptr;
+    const uint8_t* d_in = nullptr; uint64_t inBits = 0;    // (many streams: the bits of d_in that any stream reaches)
+    uint64_t startBit = 0; int64_t maxBlocks = 0;          // (many streams: unused, every stream has its own start)
+    int framing = 1; u32 rawLen = 0;                       // 0: the bare entropy stage of one buffer of rawLen bytes (knz_hip_entropy_decode_bs)
+    uint8_t* d_out = nullptr; size_t outCap = 0;
+    int nHosted = 0;                                       // leading stages the caller undoes on the host after the call
+    u32 streamBlockSize = 0;                               // as EncJob's
+    DecTab* tab = nullptr;                                 // the batch holds many streams: each gets its own verdict, and a stream's failure is no failure of the call
+};
 
-    BitSrc src;
-    src.words = reinterpret_cast<const u32*>(d_in);
-    src.nBytes = (inBits + 7) >> 3;
-    src.nWords = src.nBytes >> 2;
-    src.limitBits = inBits;
+// What the decoder reports of one stream (of many streams nothing: DecTab::items). An entry point copies out what its ABI has.
+struct DecResult {
+    bool walked = false;                                   // endBit and blocksDone hold: the walk has passed, whatever failed behind it
+    u64 endBit = 0; int64_t blocksDone = 0;
+    u64 outBytes = 0;                                      // of a call that succeeds
+    int32_t rawDecoded = 0; u64 usedBits = 0;              // the first block's bytes, or -1 where a call without framing cannot decode it; the bits its decoder used
+    u32 skipOut = 0xFF; u64 sumOut = 0;                    // the first block's skip flags (0xFF: a copy block, or none) and stored checksum
+};
 
-    DecBlock* d_blocks;
-    int nBlocks = 0;
+// One batch through the walk, the entropy decoder and the inverse chain, phase by phase (run)
+struct Decoder {
+    Ctx* c; const DecJob& j; DecResult& res;
+    ProfInstall prof;
+    const knz_params* p; DecTab* tab; hipStream_t s; u32 bs; PinnedWords pin;
+    Chain ch; int bsVersion = 6; BitSrc src;
+    u32 realMask = 0; bool lanesOk = true;                   // the device's stages; every one of them may run in lanes
+    DecBlock* d_blocks = nullptr; int nBlocks = 0;
     std::vector<StreamWalk> sw;                              // many streams: every stream's first slot, block count and verdict of the walk
     u64 *d_outOff = nullptr, *d_room = nullptr;              // many streams: every block's place in d_out and the room behind it
-    if (tab) {
-        // the walk in two passes (streams.hip): count, scan the counts -- the total sizes the block table --, then fill
+    u32 unit = 0; u64 S = 0, outStride = 0; int maxChunks = 0, lanes = 1;
+    std::vector<DecBlock> hb;                                // the blocks as the device left them
+
+    Decoder(Ctx* ctx, const DecJob& job, DecResult& out) : c(ctx), j(job), res(out), prof(ctx), p(job.p), tab(job.tab), s(ctx->stream), bs((u32)job.p->block_size), pin(ctx) {}
+
+    // The request is one the phases can take: the chain, the bitstream version and the source are set. Nothing is launched.
+    int check()
+    {
+        HIPCHK(c, hipSetDevice(c->device));
+        if ((reinterpret_cast<uintptr_t>(j.d_in) & 15) || (reinterpret_cast<uintptr_t>(j.d_out) & 15))
+            return fail(c, KNZ_ERR_INVALID_PARAM, "device buffers must be 16-byte aligned");
+        if (j.framing && (bs < 1024 || bs > (1u << 30) || (bs & 15))) return fail(c, KNZ_ERR_INVALID_PARAM, "invalid block size %u", bs);
+        // (the host stages in front are undone by the caller after the call: for the device they are stages that leave the data alone)
+        if (int r = parse_chain(c, p, j.nHosted, false, &ch)) return r;
+        for (int i = 0; i < ch.n; i++) if (ch.xf[i]) { realMask |= 1u << (7 - i); lanesOk &= ch.xf[i]->lanes; }
+        // (what range() relies on; no public entry point builds such a request, see Encoder::check)
+        if (!j.framing && realMask) return fail(c, KNZ_ERR_INVALID_PARAM, "a call without framing takes no transform");
+        // bitstream version of the blocks (0 = current). Below 6 the Huffman chunks, the BWT block header and the LZ blocks have their
+        // old layouts (HuffmanDecoder.cpp:349-459, BWTBlockCodec.cpp:140-164, LZCodec.cpp:614-760)
+        bsVersion = (p->bs_version == 0) ? 6 : p->bs_version;
+        if (bsVersion < 0 || bsVersion > 6) return fail(c, KNZ_ERR_STREAM_VERSION, "cannot read bitstream version %d", bsVersion);
+        src.words = reinterpret_cast<const u32*>(j.d_in);
+        src.nBytes = (j.inBits + 7) >> 3;
+        src.nWords = src.nBytes >> 2;
+        src.limitBits = j.inBits;
+        return 0;
+    }
+
+    // nBlocks and every block's place in its stream (d_blocks); many streams: also every block's place and room in the output (d_outOff,
+    // d_room) and every item's verdict of the walk; one stream: endBit and blocksDone. Synchronises the stream.
+    int walk() { return tab ? walk_streams() : walk_blocks(); }
+
+    // (in two passes, streams.hip: count, scan the counts -- the total sizes the block table --, then fill)
+    int walk_streams()
+    {
         sw.resize((size_t)tab->nItems + 1);
-        launch_walk_streams_count(s, d_in, tab->d_sd, tab->nItems, p->checksum_bits, bs, tab->d_walk);
+        launch_walk_streams_count(s, j.d_in, tab->d_sd, tab->nItems, p->checksum_bits, bs, tab->d_walk);
         HIPCHK(c, hipMemcpyAsync(sw.data(), tab->d_walk, sizeof(StreamWalk) * sw.size(), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
         HIPCHK(c, hipGetLastError());
@@ -1335,76 +1446,82 @@ static int decode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, uint64_
         if (int r = ws_get(c, "decBlocks", sizeof(DecBlock) * (size_t)nBlocks, (void**)&d_blocks, s)) return r;
         if (int r = ws_get(c, "decOutOff", sizeof(u64) * (size_t)nBlocks, (void**)&d_outOff, s)) return r;
         if (int r = ws_get(c, "decRoom", sizeof(u64) * (size_t)nBlocks, (void**)&d_room, s)) return r;
-        launch_walk_streams_fill(s, d_in, tab->d_sd, tab->nItems, p->checksum_bits, bs, tab->d_walk, d_blocks, d_outOff, d_room);
-    } else {
-        int64_t bound = framing ? (int64_t)(outCap / bs) + 2 : 1;
-        if (maxBlocks > 0 && maxBlocks < bound) bound = maxBlocks;
+        launch_walk_streams_fill(s, j.d_in, tab->d_sd, tab->nItems, p->checksum_bits, bs, tab->d_walk, d_blocks, d_outOff, d_room);
+        return 0;
+    }
+
+    int walk_blocks()
+    {
+        int64_t bound = j.framing ? (int64_t)(j.outCap / bs) + 2 : 1;
+        if (j.maxBlocks > 0 && j.maxBlocks < bound) bound = j.maxBlocks;
         void* d_walk;
         if (int r = ws_get(c, "decBlocks", sizeof(DecBlock) * (size_t)bound, (void**)&d_blocks, s)) return r;
         if (int r = ws_get(c, "walk", 64, &d_walk, s)) return r;
-        launch_walk_blocks(s, src, startBit, bound, framing, rawLen, p->checksum_bits, bs, d_blocks, d_walk);
-        WalkResultHost* h_walk = reinterpret_cast<WalkResultHost*>(c->pinned);
-        HIPCHK(c, hipMemcpyAsync(h_walk, d_walk, sizeof(WalkResultHost), hipMemcpyDeviceToHost, s));
+        launch_walk_blocks(s, src, j.startBit, bound, j.framing, j.rawLen, p->checksum_bits, bs, d_blocks, d_walk);
+        HIPCHK(c, hipMemcpyAsync(pin.walk(), d_walk, sizeof(WalkResultHost), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
-        const WalkResultHost walk = *h_walk;
-        if (walk.error) return fail(c, walk.error, "invalid block framing");
-        nBlocks = (int)walk.nBlocks;
-        if (endBit) *endBit = walk.endBit;
-        if (blocksDone) *blocksDone = nBlocks;
-        if (nBlocks == 0) { if (outBytes) *outBytes = 0; return 0; }
-        if (framing && (size_t)nBlocks * bs > outCap + bs) return fail(c, KNZ_ERR_WRITE_FILE, "output buffer too small");
+        const WalkResultHost found = *pin.walk();
+        if (found.error) return fail(c, found.error, "invalid block framing");
+        nBlocks = (int)found.nBlocks;
+        res.walked = true; res.endBit = found.endBit; res.blocksDone = nBlocks;
+        if (nBlocks && j.framing && (size_t)nBlocks * bs > j.outCap + bs) return fail(c, KNZ_ERR_WRITE_FILE, "output buffer too small");
+        return 0;
     }
-    if (!tab && framing && (size_t)nBlocks * bs > (size_t)0x7FFFFFFF) return fail(c, KNZ_ERR_INVALID_PARAM, "batch of %d blocks exceeds the 2 GiB per-call limit (pass max_blocks)", nBlocks);
-    if (tab) {
-        // the same limit by what the items can hold: a stream of k blocks decodes to at most min(out_cap, k block sizes) bytes
+
+    // The 2 GiB of a call, by the blocks of one stream or by what the items of many can hold
+    int limits()
+    {
+        if (!tab) {
+            if (j.framing && (size_t)nBlocks * bs > (size_t)0x7FFFFFFF) return fail(c, KNZ_ERR_INVALID_PARAM, "batch of %d blocks exceeds the 2 GiB per-call limit (pass max_blocks)", nBlocks);
+            return 0;
+        }
+        // a stream of k blocks decodes to at most min(out_cap, k block sizes) bytes
         u64 most = 0;
         for (int i = 0; i < tab->nItems; i++) most += std::min<u64>(tab->items[i].out_cap, (u64)sw[(size_t)i].count * bs);
         if (most > (u64)0x7FFFFFFF) return fail(c, KNZ_ERR_INVALID_PARAM, "the streams of this call decode to up to %llu bytes, more than the 2 GiB per-call limit: split the call", (unsigned long long)most);
+        return 0;
     }
 
-    // workspace stride: large enough for every valid preTransformLength of this chain
-    // (many streams: no block can be longer than the largest room, so the workspaces are sized by that and not by the block size -- a
-    // thousand files of 1 KiB in a stream format of 4 MiB blocks take megabytes, not gigabytes; a longer block fails either way, with
-    // the code it gets below where its room is too small)
-    const u32 unit = tab ? std::max(tab->maxUnit, 1u) : framing ? bs : rawLen;
-    const int required = seq_stride(ch, (int)unit);       // (the whole chain sizes the buffers, as in the encoder: a UTF stage adds 8 KiB of room)
-    const u64 S = ((u64)required + 255) & ~255ull;
-    if (tab && (u64)nBlocks * S > STREAMS_MAX_WORK) return fail(c, KNZ_ERR_INVALID_PARAM, "%d blocks with a longest block of %u bytes exceed the workspace limit of a call (blocks x longest block <= 2 GiB): split the call", nBlocks, unit);
-    const u32 maxPre = (u32)S;
-    const int maxChunks = (int)((S + ENT_CHUNK - 1) / ENT_CHUNK);
-    const u64 outStride = framing ? bs : 0;
-    u32 realMask = 0;                                        // the device's stages
-    bool lanesOk = true;
-    for (int i = 0; i < nTok; i++) if (ch.xf[i]) { realMask |= 1u << (7 - i); lanesOk &= ch.xf[i]->lanes; }
-    const bool realStages = realMask != 0;
-
-    // Up to three ranges side by side (knob dec_parts / KNZ_DEC_PARTS, default 3, at least KNZ_DEC_PART_MIN = 2 blocks per range -- 7 blocks: decode
-    // 4.42 -> 4.04 ms; 4 blocks: no difference --; chains with inverse stages only; not
-    // while per-kernel timing is on, not for chains with a stage that has no lanes): the entropy decoders are chains with a few
-    // waves per CU and the row ranking of the BWT inverse is latency as well -- they run under the other ranges' bandwidth-bound kernels instead
-    // of in front of them. Measured (26 blocks of 8 MiB, 1 / 2 / 3 ranges): decode 9.96 / 9.76 / 9.63 ms on the stand-in, 10.49 / 10.17 / 9.86 on the
-    // real files; entropy-only chains (configs 1, 2) lose 2-5 % to the extra launches and stay one range.
-    int lanes = 1;
+    // The workspace stride S and the ranges the batch is decoded in
+    int plan()
     {
-        const int want = dec_parts_knob().load();
-        static const int least = [] { const char* e = getenv("KNZ_DEC_PART_MIN"); const int x = e ? atoi(e) : 2; return x < 1 ? 1 : x; }();      // fewest blocks per range
-        if (framing && realStages && !c->profiling && lanesOk && nHosted == 0 && want > 1) {
+        // large enough for every valid preTransformLength of this chain
+        // (many streams: no block can be longer than the largest room, so the workspaces are sized by that and not by the block size -- a
+        // thousand files of 1 KiB in a stream format of 4 MiB blocks take megabytes, not gigabytes; a longer block fails either way, with
+        // the code it gets below where its room is too small)
+        unit = tab ? std::max(tab->maxUnit, 1u) : j.framing ? bs : j.rawLen;
+        S = ((u64)seq_stride(ch, (int)unit) + 255) & ~255ull;      // (the whole chain sizes the buffers, as in the encoder: a UTF stage adds 8 KiB of room)
+        if (tab && (u64)nBlocks * S > STREAMS_MAX_WORK) return fail(c, KNZ_ERR_INVALID_PARAM, "%d blocks with a longest block of %u bytes exceed the workspace limit of a call (blocks x longest block <= 2 GiB): split the call", nBlocks, unit);
+        maxChunks = (int)((S + ENT_CHUNK - 1) / ENT_CHUNK);
+        outStride = j.framing ? bs : 0;
+        // Up to three ranges side by side (knob dec_parts / KNZ_DEC_PARTS, default 3, at least KNZ_DEC_PART_MIN = 2 blocks per range -- 7 blocks: decode
+        // 4.42 -> 4.04 ms; 4 blocks: no difference --; chains with inverse stages only; not
+        // while per-kernel timing is on, not for chains with a stage that has no lanes): the entropy decoders are chains with a few
+        // waves per CU and the row ranking of the BWT inverse is latency as well -- they run under the other ranges' bandwidth-bound kernels instead
+        // of in front of them. Measured (26 blocks of 8 MiB, 1 / 2 / 3 ranges): decode 9.96 / 9.76 / 9.63 ms on the stand-in, 10.49 / 10.17 / 9.86 on the
+        // real files; entropy-only chains (configs 1, 2) lose 2-5 % to the extra launches and stay one range.
+        const int want = dec_parts_knob().load(), least = dec_part_min_knob().load();
+        if (realMask && !c->profiling && lanesOk && j.nHosted == 0 && want > 1) {
             lanes = want > 3 ? 3 : want;
             while (lanes > 1 && nBlocks < least * lanes) lanes--;
         }
+        return 0;
     }
 
     // Range k of the batch's blocks through entropy decoder and inverse chain, on stream `sp` with the workspaces of lane k (one range: lane
-    // -1, the whole batch, whose BWT inverse may be split into parts). The blocks are independent and the walk above has left every block's
+    // -1, the whole batch, whose BWT inverse may be split into parts). The blocks are independent and the walk has left every block's
     // place in the stream in d_blocks, so a range is a smaller decode of its own: its entries of d_blocks, its part of the caller's output.
-    auto range = [&](int k, hipStream_t sp) -> int {
+    // It leaves every block's verdict, length and checksum verdict in its entries of d_blocks. The BWTS inverse synchronises `sp` (XF).
+    int range(int k, hipStream_t sp)
+    {
+        const bool realStages = realMask != 0;
         const int lane = lanes > 1 ? k : -1;
         int b0, nb;
         cut(nBlocks, lanes, k, &b0, &nb);
         DecBlock* blk = d_blocks + b0;
         // (many streams: the blocks' places and rooms come from the tables, `room` only has to differ from ~0)
-        uint8_t* out = tab ? d_out : d_out + (size_t)b0 * outStride;
-        const u64 room = tab ? 0 : (u64)outCap - (u64)b0 * outStride;
+        uint8_t* out = tab ? j.d_out : j.d_out + (size_t)b0 * outStride;
+        const u64 room = tab ? 0 : (u64)j.outCap - (u64)b0 * outStride;
         const u64* offT = tab ? d_outOff + b0 : nullptr;
         const u64* roomT = tab ? d_room + b0 : nullptr;
         SeqWs w;
@@ -1413,86 +1530,115 @@ static int decode_impl(Ctx* c, const knz_params* p, const uint8_t* d_in, uint64_
         // entropy stage decodes into workspace A (or straight into the output when no transform applies)
         // with inverse stages the entropy decoder writes into the workspace (any valid preTransformLength fits);
         // the room in the caller's buffer is enforced where the last inverse stage gets its capacity
-        launch_check_prelen(sp, blk, nb, realStages ? maxPre : unit, realStages ? ~0ull : room, outStride, roomT);
+        launch_check_prelen(sp, blk, nb, realStages ? (u32)S : unit, realStages ? ~0ull : room, outStride, roomT);
         launch_seq_inv_entropy_dst(sp, w.a, blk, nb, out, outStride, w.A, S, w.d_entDst, realMask, unit, room, offT, roomT);
-        if (int r = ch.ec->decode({ c, sp, lane, src, blk, nb, S, maxChunks, nSlots, framing, bsVersion, streamBlockSize ? streamBlockSize : bs,
+        if (int r = ch.ec->decode({ c, sp, lane, src, blk, nb, S, maxChunks, nSlots, j.framing, bsVersion, j.streamBlockSize ? j.streamBlockSize : bs,
                                     ch.ec->extra, w.d_entDst })) return r;
         // inverse transforms, last stage first (TransformSequence.hpp:197-224)
         if (realStages) {
-            const u32 capFinal = framing ? std::min(bs, unit) : (u32)p->jobs;           // per-stage API passes its capacity in p->jobs
+            const u32 capFinal = std::min(bs, unit);
             const u32 blkLenModel = std::max(bs + 512u, bs + (bs >> 4));
-            const u32 capMid = framing ? (u32)std::min<u64>(S, blkLenModel) : (u32)p->jobs;
+            const u32 capMid = (u32)std::min<u64>(S, blkLenModel);
             // (the reference's buffer, which the stages that judge by capacity go by, is sized by the stream's block size whatever the workspaces here are)
-            const u32 capModel = framing ? (u32)std::min<u64>(((u64)seq_stride(ch, (int)bs) + 255) & ~255ull, blkLenModel) : 0u;
-            for (int i = nTok - 1; i >= 0; i--) {
+            const u32 capModel = (u32)std::min<u64>(((u64)seq_stride(ch, (int)bs) + 255) & ~255ull, blkLenModel);
+            for (int i = ch.n - 1; i >= 0; i--) {
                 if (ch.xf[i] == nullptr) continue;
-                launch_seq_inv_prepare(sp, w.a, blk, nb, i, out, outStride, w.A, w.B, S, capMid, capFinal, realMask, framing ? room : ~0ull, offT, roomT);
+                launch_seq_inv_prepare(sp, w.a, blk, nb, i, out, outStride, w.A, w.B, S, capMid, capFinal, realMask, room, offT, roomT);
                 XfStage st = xf_stage(w, nb, (u32)S, p->entropy_type);
                 st.bsVersion = bsVersion;
                 st.maxCap = std::max(capMid, capFinal);
                 st.capModel = capModel;
-                st.blockSize = streamBlockSize ? streamBlockSize : (framing ? bs : 0u);
+                st.blockSize = j.streamBlockSize ? j.streamBlockSize : bs;
                 if (int r = run_stage(c, sp, *ch.xf[i], false, st, lane)) return r;
                 launch_seq_inv_commit(sp, w.a, blk, nb, i, ch.tok[i]);
             }
         }
-        if (p->checksum_bits && framing && nHosted == 0) {
+        if (p->checksum_bits && j.framing && j.nHosted == 0) {
             u64* d_sums;
             if (int r = ws_get(c, lane_ws("sums", lane), sizeof(u64) * nb, (void**)&d_sums, sp)) return r;
             launch_verify_checksums(sp, blk, nb, p->checksum_bits, out, outStride, w.d_viewPtr, w.a.alen, d_sums, offT);
         }
         return 0;
-    };
+    }
 
-    if (int r = fork_join(c, s, lanes, false, range)) return r;
-    HIPCHK(c, hipGetLastError());
-    // results
-    std::vector<DecBlock> hb((size_t)nBlocks);
-    HIPCHK(c, hipMemcpyAsync(hb.data(), d_blocks, sizeof(DecBlock) * (size_t)nBlocks, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (tab) {
-        // every stream by itself, by the rules below: the first failing block's code, the refusal of a short block that is not the last
-        for (int i = 0; i < tab->nItems; i++) {
-            knz_item& it = tab->items[i];
-            if (it.error) continue;
-            const size_t b0 = (size_t)sw[(size_t)i].first, b1 = b0 + sw[(size_t)i].count;
-            u64 bytes = 0;
-            for (size_t b = b0; b < b1 && !it.error; b++) {
-                if (hb[b].error) it.error = hb[b].error;
-                else if (b + 1 < b1 && hb[b].preLen != bs) it.error = KNZ_ERR_PROCESS_BLOCK;
-                bytes += hb[b].preLen;
-            }
-            it.out_len = it.error ? 0 : bytes;
+    // The verdict on the blocks [b0, b1) of one stream, by the rules of DecodingTask::run: 0 and their bytes, or the first block that fails
+    // (*bad) with its code, or with KNZ_ERR_PROCESS_BLOCK where it is short and not the last
+    int judge(size_t b0, size_t b1, u64* bytes, size_t* bad) const
+    {
+        *bytes = 0;
+        for (size_t b = b0; b < b1; b++) {
+            *bad = b;
+            if (hb[b].error) return hb[b].error;
+            if (j.framing && b + 1 < b1 && hb[b].preLen != bs) return KNZ_ERR_PROCESS_BLOCK;
+            *bytes += hb[b].preLen;
         }
         return 0;
     }
-    u64 total = 0;
-    for (int b = 0; b < nBlocks; b++) {
-        if (hb[b].error) {
-            if (getenv("KNZ_DEBUG_ERR")) fprintf(stderr, "DBG block %d error %d used %llu\n", b, hb[b].error, (unsigned long long)hb[b].usedBits);
-            if (rawDecoded) { *rawDecoded = -1; if (usedBits) *usedBits = hb[b].usedBits; return 0; }
-            return fail(c, hb[b].error, "block %d: decoding failed (code %d)", b + 1, hb[b].error);
-        }
-        if (framing && b + 1 < nBlocks && hb[b].preLen != bs)
-            return fail(c, KNZ_ERR_PROCESS_BLOCK, "block %d: short non-final block (%u bytes) not supported", b + 1, hb[b].preLen);
-        total += hb[b].preLen;
-    }
-    if (outBytes) *outBytes = total;
-    if (skipOut) *skipOut = hb[0].copyBlock ? 0xFFu : hb[0].skipFlags;
-    if (sumOut) *sumOut = hb[0].checksum;
-    if (rawDecoded) *rawDecoded = (int32_t)hb[0].preLen;
-    if (usedBits) *usedBits = hb[0].usedBits;
-    return 0;
-}
 
+    // The blocks read back and judged: every item by itself, or the one stream for the call. Synchronises the stream.
+    int results()
+    {
+        hb.resize((size_t)nBlocks);
+        HIPCHK(c, hipMemcpyAsync(hb.data(), d_blocks, sizeof(DecBlock) * (size_t)nBlocks, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        u64 bytes;
+        size_t bad = 0;
+        if (tab) {
+            for (int i = 0; i < tab->nItems; i++) {
+                knz_item& it = tab->items[i];
+                if (it.error) continue;
+                const size_t b0 = (size_t)sw[(size_t)i].first;
+                it.error = judge(b0, b0 + sw[(size_t)i].count, &bytes, &bad);
+                it.out_len = it.error ? 0 : bytes;
+            }
+            return 0;
+        }
+        if (judge(0, (size_t)nBlocks, &bytes, &bad)) {
+            const DecBlock& k = hb[bad];
+            const int no = (int)bad + 1;
+            if (!k.error) return fail(c, KNZ_ERR_PROCESS_BLOCK, "block %d: short non-final block (%u bytes) not supported", no, k.preLen);
+            // (the first failing block ends the call, so the variable is read once)
+            if (getenv("KNZ_DEBUG_ERR")) fprintf(stderr, "DBG block %d error %d used %llu\n", (int)bad, k.error, (unsigned long long)k.usedBits);
+            // (a call without framing reports a block that does not decode as a result, not as a failure)
+            if (!j.framing) { res.rawDecoded = -1; res.usedBits = k.usedBits; return 0; }
+            return fail(c, k.error, "block %d: decoding failed (code %d)", no, k.error);
+        }
+        res.outBytes = bytes;
+        res.skipOut = hb[0].copyBlock ? 0xFFu : hb[0].skipFlags;
+        res.sumOut = hb[0].checksum;
+        res.rawDecoded = (int32_t)hb[0].preLen;
+        res.usedBits = hb[0].usedBits;
+        return 0;
+    }
+
+    int run()
+    {
+        if (int r = check()) return r;
+        if (int r = walk()) return r;
+        if (nBlocks == 0) return 0;
+        if (int r = limits()) return r;
+        if (int r = plan()) return r;
+        if (int r = fork_join(c, s, lanes, false, [this](int k, hipStream_t sp) { return range(k, sp); })) return r;
+        HIPCHK(c, hipGetLastError());
+        return results();
+    }
+};
+
+// (end_bit and blocks_done also of a batch that fails behind its walk)
 int knz_hip_decode_blocks(knz_ctx* ctx, const knz_params* p, const uint8_t* d_in, uint64_t in_bits, uint64_t start_bit,
                           int64_t max_blocks, uint8_t* d_out, size_t out_cap, uint64_t* out_bytes, uint64_t* end_bit,
                           int64_t* blocks_done)
 {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     CTX_LOCK(c);
-    return decode_impl(c, p, d_in, in_bits, start_bit, max_blocks, 1, 0, d_out, out_cap, out_bytes, end_bit, blocks_done,
-                       nullptr, nullptr);
+    DecJob j;
+    j.p = p; j.d_in = d_in; j.inBits = in_bits; j.startBit = start_bit; j.maxBlocks = max_blocks; j.d_out = d_out; j.outCap = out_cap;
+    DecResult res;
+    const int r = Decoder(c, j, res).run();
+    if (res.walked && end_bit) *end_bit = res.endBit;
+    if (res.walked && blocks_done) *blocks_done = res.blocksDone;
+    if (r == 0 && out_bytes) *out_bytes = res.outBytes;
+    return r;
 }
 
 int knz_hip_decode_block_hosted(knz_ctx* ctx, const knz_params* p, int32_t host_stages, const uint8_t* d_in, uint64_t in_bits, uint64_t start_bit,
@@ -1500,11 +1646,15 @@ int knz_hip_decode_block_hosted(knz_ctx* ctx, const knz_params* p, int32_t host_
 {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     CTX_LOCK(c);
-    int64_t nb = 0;
-    if (skip_flags) *skip_flags = 0xFF;
-    if (checksum) *checksum = 0;
-    const int r = decode_impl(c, p, d_in, in_bits, start_bit, 1, 1, 0, d_out, out_cap, out_bytes, end_bit, &nb, nullptr, nullptr, host_stages, skip_flags, checksum);
-    if (done) *done = (int32_t)nb;
+    DecJob j;
+    j.p = p; j.d_in = d_in; j.inBits = in_bits; j.startBit = start_bit; j.maxBlocks = 1; j.d_out = d_out; j.outCap = out_cap; j.nHosted = host_stages;
+    DecResult res;
+    const int r = Decoder(c, j, res).run();
+    if (res.walked && end_bit) *end_bit = res.endBit;
+    if (r == 0 && out_bytes) *out_bytes = res.outBytes;
+    if (skip_flags) *skip_flags = res.skipOut;
+    if (checksum) *checksum = res.sumOut;
+    if (done) *done = (int32_t)res.blocksDone;
     return r;
 }
 
@@ -1592,7 +1742,9 @@ int knz_hip_encode_streams(knz_ctx* ctx, const knz_params* p, const uint8_t* d_i
     tab.d_len = reinterpret_cast<const u32*>(d_tab + oLen); tab.d_itemOf = reinterpret_cast<const u32*>(d_tab + oItem);
     tab.d_pro = d_tab + oPro; tab.d_res = reinterpret_cast<StreamOut*>(d_tab + oRes); tab.d_excl = reinterpret_cast<u64*>(d_tab + oExcl);
     u64 bits = 0;
-    const int r = encode_impl(c, p, d_in, total, nullptr, 0, 1, finish, 0, d_out, out_cap, &bits, nullptr, 0, &tab);
+    EncJob j;
+    j.p = p; j.d_in = d_in; j.n = total; j.finish = finish; j.d_out = d_out; j.outCap = out_cap; j.outBits = &bits; j.tab = &tab;
+    const int r = Encoder(c, j).run();
     if (r) { hipStreamSynchronize(s); return r; }          // (`host` may still be on its way)
     for (size_t i = 0; i < n_items; i++) {
         items[i].out_off = tab.res[i].base;
@@ -1633,7 +1785,10 @@ int knz_hip_decode_streams(knz_ctx* ctx, const knz_params* p, const uint8_t* d_i
     DecTab tab;
     tab.nItems = (int)n_items; tab.items = items; tab.maxUnit = maxUnit;
     tab.d_sd = reinterpret_cast<const StreamDec*>(d_tab); tab.d_walk = reinterpret_cast<StreamWalk*>(d_tab + oWalk);
-    const int r = decode_impl(c, p, d_in, reach, 0, 0, 1, 0, d_out, out_cap, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, &tab);
+    DecJob j;
+    j.p = p; j.d_in = d_in; j.inBits = reach; j.d_out = d_out; j.outCap = out_cap; j.tab = &tab;
+    DecResult res;
+    const int r = Decoder(c, j, res).run();
     if (r) hipStreamSynchronize(s);
     return r;
 }
@@ -1766,12 +1921,15 @@ int knz_hip_entropy_encode_bs(knz_ctx* ctx, int entropy_type, uint32_t stream_bl
     if (int r = ws_get(c, "stageOut", cap, (void**)&d_out, c->stream)) return r;
     HIPCHK(c, hipMemcpyAsync(d_in, in, n, hipMemcpyHostToDevice, c->stream));
     u64 bits = 0;
-    int r = encode_impl(c, &p, d_in, n, nullptr, 0, 0, 0, 0, d_out, cap, &bits, nullptr, stream_block_size);
+    EncJob j;
+    j.p = &p; j.d_in = d_in; j.n = n; j.framing = 0; j.d_out = d_out; j.outCap = cap; j.outBits = &bits; j.streamBlockSize = stream_block_size;
+    int r = Encoder(c, j).run();
     if (r == KNZ_ERR_WRITE_FILE && ec_info(entropy_type)->twoTier) {         // (an id without a row has failed in parse_chain, with another code)
         // the bound of the binary coders is their first tier (knz_hip_encode_bound): the second holds whatever the format can write
         const size_t cap2 = cap + 32 * (size_t)n;
         if (int r2 = ws_get(c, "stageOut", cap2, (void**)&d_out, c->stream)) return r2;
-        r = encode_impl(c, &p, d_in, n, nullptr, 0, 0, 0, 0, d_out, cap2, &bits, nullptr, stream_block_size);
+        j.d_out = d_out; j.outCap = cap2;
+        r = Encoder(c, j).run();
     }
     if (r) return r;
     const size_t bytes = (size_t)((bits + 7) >> 3);
@@ -1809,8 +1967,13 @@ int knz_hip_entropy_decode_bs(knz_ctx* ctx, int entropy_type, int bs_version, ui
     if (int r = ws_get(c, "stageIn", inBytes + 64, (void**)&d_in, c->stream)) return r;
     if (int r = ws_get(c, "stageOut", (size_t)n + 64, (void**)&d_out, c->stream)) return r;
     HIPCHK(c, hipMemcpyAsync(d_in, in, inBytes, hipMemcpyHostToDevice, c->stream));
-    u64 ob = 0;
-    if (int r = decode_impl(c, &p, d_in, in_bits, start_bit, 1, 0, n, d_out, n, &ob, nullptr, nullptr, decoded, used_bits, 0, nullptr, nullptr, stream_block_size)) return r;
+    DecJob j;
+    j.p = &p; j.d_in = d_in; j.inBits = in_bits; j.startBit = start_bit; j.maxBlocks = 1; j.framing = 0; j.rawLen = n; j.d_out = d_out; j.outCap = n;
+    j.streamBlockSize = stream_block_size;
+    DecResult res;
+    if (int r = Decoder(c, j, res).run()) return r;
+    *decoded = res.rawDecoded;
+    if (used_bits) *used_bits = res.usedBits;
     if (*decoded == (int32_t)n) {
         HIPCHK(c, hipMemcpyAsync(out, d_out, n, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -216,7 +216,7 @@ def _fits_one_call(n, block_size, hipapi):
 
 def _calls(sizes, block_size, hipapi):
     """Cuts the item numbers into runs that one device call takes: its item and block counts, its bytes (every item at a multiple
-    of 16; the 2 GiB limit of a call leaves room for the blocks' slack, csrc/api.hip encode_impl) and its workspaces (blocks x longest
+    of 16; the 2 GiB limit of a call leaves room for the blocks' slack, csrc/api.hip Encoder::check) and its workspaces (blocks x longest
     block). On the way back the sizes are the stored ones, which are the rooms the call is given. An item that is too large for any
     call is a ValueError: such a buffer belongs to the stream classes."""
     runs, cur, nbytes, nblocks, longest = [], [], 0, 0, 0
