@@ -119,7 +119,8 @@ __global__ __launch_bounds__(64) void k_ans1_ctx(BlockView view, int chunksPerBl
 constexpr u32 A1E_ST = 64;                     // steps per stretch (= lanes: one step per lane when the emissions are placed)
 
 __global__ __launch_bounds__(64) void k_ans1_encode(BlockView view, int chunksPerBlock, ChunkDesc* __restrict__ desc,
-                                                    const uint2* __restrict__ encTab, u8* __restrict__ payBase, u64 payStride)
+                                                    const uint2* __restrict__ encTab, const u32* __restrict__ hist,
+                                                    u8* __restrict__ payBase, u64 payStride)
 {
     const int gc = blockIdx.x;
     const int b = gc / chunksPerBlock;
@@ -226,6 +227,18 @@ __global__ __launch_bounds__(64) void k_ans1_encode(BlockView view, int chunksPe
             }
             __syncthreads();
         }
+    } else if (ci > 0) {
+        // ANSRangeEncoder.cpp:216-245 on a chunk of fewer than 4 bytes: the loop takes no step, and the "last symbols" of all four
+        // states are block[-1], the byte in front of the chunk, coded in context 0 with the record the encoder object holds for that
+        // pair -- the one of the latest chunk of this block that had it (its own included). A record's xMax is above TOP, so the step
+        // emits nothing. Where no chunk had the pair the reference reads a record it never wrote; the states stay at TOP then.
+        const u32 sym = ldg<u8>(blk - 1);
+        for (int c = gc; c >= gc - ci; c--) {
+            if (hist[(size_t)c * 65536 + sym] == 0) continue;
+            const uint4 e = operands(encTab[(size_t)c * 65536 + sym]);
+            st = st + (e.w & 0xFFFFu) + (__umulhi(st, e.x) >> (e.w >> 16)) * e.z;
+            break;
+        }
     }
     const u32 q = itemsTop - 2 * nOut;
     // varint(size) + 4 states -> mid ; payload piece
@@ -264,7 +277,7 @@ void launch_ans1_encode(hipStream_t s, BlockView view, int nBlocks, int chunksPe
     (void)hipMemsetAsync(desc, 0, sizeof(ChunkDesc) * (size_t)nCh * ANS1_SLOTS, s);
     { KScope ks_("k_ans1_hist"); hipLaunchKernelGGL(k_ans1_hist, dim3(64, nCh), dim3(256), 0, s, view, chunksPerBlock, ws.hist); }
     { KScope ks_("k_ans1_ctx"); hipLaunchKernelGGL(k_ans1_ctx, dim3(nCh * 256), dim3(64), 0, s, view, chunksPerBlock, ws.hist, desc, ws.encTab, ws.hdr); }
-    { KScope ks_("k_ans1_encode"); hipLaunchKernelGGL(k_ans1_encode, dim3(nCh), dim3(64), 0, s, view, chunksPerBlock, desc, ws.encTab, ws.pay, ws.payStride); }
+    { KScope ks_("k_ans1_encode"); hipLaunchKernelGGL(k_ans1_encode, dim3(nCh), dim3(64), 0, s, view, chunksPerBlock, desc, ws.encTab, ws.hist, ws.pay, ws.payStride); }
 }
 
 }  // namespace knz
