@@ -348,7 +348,7 @@ KNZ_API int knz_hip_get_kernel_times(knz_ctx* ctx, knz_kernel_time* out, int cap
  * "bwt_no_run_round", "bwt_run_fallback" (1: force the general path for runs), "bwt_plain_labels" (32-bit labels, as blocks above
  * 256 MiB), "bwt_no_pack", "bwt_no_unsplit_skip" (medium groups whose keys are all equal stored and sorted like any other),
  * "bwt_no_group_sleep" (such groups gathered in every round, also where the round before already tells that no key will differ),
- * "bwt_no_medium_fuse" (medium groups' keys gathered by a kernel of their own, as with the 32-bit labels), "bwt_chain_list" (1: the fused medium kernel lists the groups of the chain round for a kernel of their own, as the other paths do, instead of finishing them in place; also KNZ_BWT_CHAIN_LIST), "bwt_run_sort" (1: the run round's members generated and sorted instead of placed directly; also KNZ_BWT_RUN_SORT), "bwt_run_in_sort" (1: the run members go through round 0's sort instead of staying out of it; also KNZ_BWT_RUN_IN_SORT), "bwt_link" (0: the suffix sort's link step for groups inside long repeats off), "bwt_stats", "bwt_split" (parts of a batch the BWT stages run in, 1..4), "bwt_part_min" (fewest blocks per such part, default 2), "dec_parts" (block ranges a decode call runs side by side, 1..3), "rs_onesweep" (0: radix passes with a
+ * "bwt_no_medium_fuse" (medium groups' keys gathered by a kernel of their own, as with the 32-bit labels), "bwt_run_sort" (1: the run round's members generated and sorted instead of placed directly; also KNZ_BWT_RUN_SORT), "bwt_run_in_sort" (1: the run members go through round 0's sort instead of staying out of it; also KNZ_BWT_RUN_IN_SORT), "bwt_link" (0: the suffix sort's link step for groups inside long repeats off), "bwt_stats", "bwt_split" (parts of a batch the BWT stages run in, 1..4), "bwt_part_min" (fewest blocks per such part, default 2), "dec_parts" (block ranges a decode call runs side by side, 1..3), "rs_onesweep" (0: radix passes with a
  * counting kernel of their own), "lz_serial_decode" (1: LZ / LZX blocks decoded by one wave each), "mtf_tile" (0: MTFT tile size by
  * batch size, 1024 / 4096 force it), "mtf_chain" (1: MTFT forward ranks by the byte-serial kernel of rounds 2-4),
  * "bwt_inv_jump_all" (1: the inverse BWT ranks its rows by pointer jumping over all of them instead of the ruler walk: decodes the

@@ -23,7 +23,7 @@
 //     * medium groups (257..8192) are (start, length) descriptors (found through staging slots, no atomics); one workgroup sorts a
 //       group in LDS: majority-key split or a stable LSD radix sort (8-bit digits, ranking by ballot matching inside a wave),
 //     * a group whose majority key is its OWN label (a periodic stretch whose period divides h) is finished in one round by pointer
-//       jumping along its chains (med_chain_round inside k_bwt_f_medium_fused; k_bwt_f_super where the groups are listed),
+//       jumping along its chains (med_chain_round, inside the workgroup that holds the group in LDS anyway),
 //     * large groups go through one global radix sort of (descriptor index, key) pairs.
 //   A round sorts on the labels as they stood when it began (a refined head read beside an unrefined one would order two suffixes that
 //   are still equal): the keys of medium and large groups are gathered by kernels of their own before anything moves; the small groups
@@ -51,7 +51,7 @@ constexpr u32 SM_G = 256;          // largest "small" group
 // size the global sort of (descriptor, key) pairs is no slower than one workgroup per CU. Stays 8,192.
 constexpr u32 MED_CAP = 8192;
 constexpr u32 MED_LO_CAP = 2048;   // medium groups up to here are sorted by workgroups of 256 threads x 8 members, larger ones by 512 x 16
-constexpr u32 SUPER_CAP = 8192;    // largest group the chain round and the periodic-stretch probe take
+constexpr u32 CHAIN_CAP = 8192;   // largest group the chain round and the periodic-stretch probe take
 constexpr int GATHER_THREADS = 512;        // workgroup of k_bwt_f_gather_desc
 constexpr u32 GATHER_ROWS = 16;            // members it holds per thread: a medium group whole
 static_assert(MED_CAP <= GATHER_ROWS * GATHER_THREADS, "k_bwt_f_gather_desc judges a medium group from one batch of loads");
@@ -100,7 +100,7 @@ enum FwdCounter : u32 {
     CNT_RUN = 4,                 // run groups (round 0)
     CNT_RUN_MEMBERS = 5,         // their members
     CNT_RUN_LONGEST = 6,         // longest run (run round)
-    CNT_SUPER = 7,               // groups that take the chain round (listed: k_bwt_f_super reads it)
+    CNT_CHAINED = 7,             // groups that took the chain round (med_chain_round)
     CNT_RUNS = 8,                // runs of run-group bytes (run round)
     CNT_MED_LO = 9,              // medium descriptors of the lower size class, up to MED_LO_CAP members (k_bwt_f_med_compact)
     CNT_STAT_SMALL = 10,         // small members worked on (knob bwt_stats)
@@ -173,6 +173,27 @@ __device__ __forceinline__ u32 gather_key(const FwdView& v, u32 gp, u32 h, u32 b
 {
     const u32 q = gp + h;
     return (q < blkEnd) ? lab_old(v, q, blkBase) - blkBase + 1u : 0u;
+}
+
+// Is the slot in a group the run round, the probe or the link step left with a shared length of its own (FwdView::rtbits, ovr)?
+__device__ __forceinline__ bool look_marked(const FwdView& v, u32 slot) { return v.rtbits && ((v.rtbits[slot >> 5] >> (slot & 31)) & 1u); }
+// The offset a group (by its first slot) or a slot looks at in the round of offset h: h, or max(ovr, h) where the slot is marked. A group is
+// marked whole, so its first slot answers for all members. (marked: where the caller holds the bit already, as the small-group windows do.)
+__device__ __forceinline__ u32 look_offset(const FwdView& v, u32 slot, u32 h, bool marked)
+{
+    if (!marked) return h;
+    const u32 r = v.ovr[slot];
+    return r > h ? r : h;
+}
+__device__ __forceinline__ u32 look_offset(const FwdView& v, u32 slot, u32 h) { return look_offset(v, slot, h, look_marked(v, slot)); }
+
+// A medium group d all of whose members found key0, looking off positions on, is left whole: staged for the next round's list as
+// med_write_back would have, the verdict recorded for k_bwt_f_med_sleep, counted (stats: knob bwt_stats). By one thread.
+__device__ __forceinline__ void med_leave_whole(const FwdView& v, uint2 d, u32 key0, u32 off, u32 h, bool stats)
+{
+    v.medStage[d.x >> 8] = d;
+    if (v.verdictNow) v.verdictNow[d.x >> 8] = make_uint2(key0, verdict_word(v.round, (off == h && key0 != 0u) ? VERDICT_PLAIN : VERDICT_WHOLE, d.y));
+    if (stats) { atomicAdd(&v.counters[CNT_STAT_UNSPLIT], 1u); atomicAdd(&v.counters[CNT_STAT_UNSPLIT_MEMBERS], d.y); }
 }
 
 __device__ __forceinline__ void classify_child(const FwdView& v, uint2* __restrict__ medNext, uint2* __restrict__ largeNext, u32 start, u32 size, u32& surv)
@@ -838,138 +859,38 @@ __global__ __launch_bounds__(256) void k_bwt_f_r0_place_text(BwtView bv, FwdView
     if (tid < 64 && sNew[tid]) atomicOr(&v.gnew[(slot0 >> 5) + (u32)tid], sNew[tid]);
 }
 
-__global__ __launch_bounds__(256) void k_bwt_f_gather_small(FwdView v, u32 h, int stats)
+constexpr int SM_ROWS = (int)(SM_WIN / 256);       // window elements per thread: i = threadIdx.x + 256 k
+
+// Fetch of one member of a small group: window element i (slot slot0 + i) of the group that starts at element s. b0 = block of the
+// window's first slot, sRt = the window's words of rtbits. Gives the position gp, the block's first slot bb and the key of the round of
+// offset h (gather_key at look_offset); counts the developer statistics (knob bwt_stats).
+__device__ __forceinline__ u32 sm_fetch_key(const FwdView& v, u32 h, int b0, const u32* sRt, u32 slot0, u32 i, u32 s, int stats, u32& gp, u32& bb)
 {
-    __shared__ SmWindow W;
-    __shared__ int sAny;
-    __shared__ int sBlk;
-    __shared__ u32 sRt[64];
-    const u32 slot0 = blockIdx.x * SM_TS;
-    if (threadIdx.x >= 64 && threadIdx.x < 128) sRt[threadIdx.x - 64] = v.rtbits ? v.rtbits[(slot0 >> 5) + threadIdx.x - 64] : 0u;
-    if (!sm_load_window(v, slot0, W, &sAny)) return;
-    if (threadIdx.x == 0) sBlk = find_block(v.base, v.nBlocks, slot0 < v.total ? slot0 : v.total - 1);
-    __syncthreads();
-    const int b0 = sBlk;
-#pragma unroll
-    for (int k = 0; k < (int)(SM_WIN / 256); k++) {
-        const u32 i = threadIdx.x + 256u * k;
-        u32 s, e;
-        if (!sm_group_of(W, i, s, e)) continue;
-        const u32 slot = slot0 + i;
-        int b = b0;
-        while (slot >= v.base[b + 1]) b++;
-        u32 off = h;
-        if ((sRt[i >> 5] >> (i & 31)) & 1u) { const u32 r = v.ovr[slot]; off = r > h ? r : h; }
-        v.K[slot] = gather_key(v, v.SA[slot], off, v.base[b], v.base[b + 1]);
-        if (stats) { atomicAdd(&v.counters[CNT_STAT_SMALL], 1u); if (i == s) atomicAdd(&v.counters[CNT_STAT_SMALL_GROUPS], 1u); }      // (developer statistics, knob bwt_stats)
-    }
+    const u32 slot = slot0 + i;
+    int b = b0;
+    while (slot >= v.base[b + 1]) b++;
+    bb = v.base[b];
+    const u32 off = look_offset(v, slot, h, (sRt[i >> 5] >> (i & 31)) & 1u);
+    gp = v.SA[slot];
+    const u32 key = gather_key(v, gp, off, bb, v.base[b + 1]);
+    if (stats) { atomicAdd(&v.counters[CNT_STAT_SMALL], 1u); if (i == s) atomicAdd(&v.counters[CNT_STAT_SMALL_GROUPS], 1u); }
+    return key;
 }
 
-// (plain labels only: versioned ones take k_bwt_f_small_fused)
-__global__ __launch_bounds__(256) void k_bwt_f_sort_small(FwdView v, u32* __restrict__ survTile)
-{
-    __shared__ SmWindow W;
-    __shared__ int sAny;
-    __shared__ u32 sSA[SM_WIN];
-    __shared__ u32 sK[SM_WIN];
-    __shared__ u32 sNew[64];
-    __shared__ u32 sWs[4];
-    const u32 slot0 = blockIdx.x * SM_TS;
-    if (!sm_load_window(v, slot0, W, &sAny)) { if (threadIdx.x == 0 && survTile) survTile[blockIdx.x] = 0; return; }
-    if (threadIdx.x < 64) sNew[threadIdx.x] = 0;
-    u32 gs[SM_WIN / 256], ge[SM_WIN / 256];
-    bool act[SM_WIN / 256];
-#pragma unroll
-    for (int k = 0; k < (int)(SM_WIN / 256); k++) {
-        const u32 i = threadIdx.x + 256u * k;
-        act[k] = sm_group_of(W, i, gs[k], ge[k]);
-        if (act[k]) { sSA[i] = v.SA[slot0 + i]; sK[i] = v.K[slot0 + i]; }
-    }
-    __syncthreads();
-    u32 surv = 0;
-#pragma unroll
-    for (int k = 0; k < (int)(SM_WIN / 256); k++) {
-        if (!act[k]) continue;
-        const u32 i = threadIdx.x + 256u * k;
-        const u32 ki = sK[i];
-        u32 less = 0, eq = 0, eqBefore = 0;
-        for (u32 j = gs[k]; j < ge[k]; j++) {
-            const u32 kj = sK[j];
-            less += (kj < ki) ? 1u : 0u;
-            const u32 same = (kj == ki) ? 1u : 0u;
-            eq += same;
-            eqBefore += (j < i) ? same : 0u;
-        }
-        const u32 gp = sSA[i];
-        const u32 headIdx = gs[k] + less;
-        v.SA[slot0 + headIdx + eqBefore] = gp;
-        if (less != 0) {
-            lab_set(v, gp, 0u, slot0 + headIdx, slot0 + gs[k]);                // (a small group's label is its first slot; plain labels need no block base)
-            if (eqBefore == 0) atomicOr(&sNew[headIdx >> 5], 1u << (headIdx & 31));
-        }
-        if (eq > 1) surv++;
-    }
-    {
-        // members that are still tied, per window (summed by a scan: the host decides by their number whether the next round looks for
-        // links first; one counter for all windows would be an atomic per wave on one address)
-        const u32 ws = wave_sum(surv);
-        if ((threadIdx.x & 63) == 0) { sWs[threadIdx.x >> 6] = ws; if (ws) v.counters[CNT_SMALL_LEFT] = 1; }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && survTile) survTile[blockIdx.x] = sWs[0] + sWs[1] + sWs[2] + sWs[3];
-    if (threadIdx.x < 64 && sNew[threadIdx.x]) atomicOr(&v.gnew[(slot0 >> 5) + threadIdx.x], sNew[threadIdx.x]);
-}
-
-// Keys and refinement of the small groups in ONE sweep (versioned labels, see lab_old): k_bwt_f_gather_small + k_bwt_f_sort_small without the
-// key array in between -- a window's bit-map words, positions and keys are read once and stay in LDS (the two kernels read the bit map and
-// SA twice and wrote and read K: 24 of the 40 KiB a dense window moved per round).
-// PACKED (blocks of up to 8 MiB: a key -- a label inside the block + 1 -- has 24 bits): the key in LDS is (key << 8 | place in the group), unique
-// inside the group, so that ONE compare per pair gives a member its stable rank (smaller keys + equal keys in front of it) and a second one
-// against (key << 8) the smaller keys alone; the plain form needs "smaller", "equal" and "equal and in front" -- 9.4 vector instructions
-// per pair against 4, and a member of a group of g compares with all g (round 6: groups of 33..256 members are a third of the small-group
-// visits of the first rounds on real files).
+// Rank and place of a window's small groups, positions in sSA and keys in sK (behind a barrier): every member act[k] of group
+// [gs[k], ge[k]) counts the members with a smaller key and the equal ones in front of it, and goes to that place; a member that leaves the
+// group's head gets the label of its subgroup's first slot (bb[k] = its block's first slot), the subgroup's first member sets the new
+// group start. Members still tied are summed per wave (CNT_SMALL_LEFT) and per window (survTile, when not null).
+// PACKED: a key in sK is (key << 8 | place in the group), unique inside the group, so that ONE compare per pair gives a member its stable
+// rank (smaller keys + equal keys in front of it) and a second one against (key << 8) the smaller keys alone; the plain form needs
+// "smaller", "equal" and "equal and in front" -- 9.4 vector instructions per pair against 4.
 template <bool PACKED>
-__global__ __launch_bounds__(256) void k_bwt_f_small_fused(FwdView v, u32 h, u32* __restrict__ survTile, int stats)
+__device__ __forceinline__ void sm_rank_place(const FwdView& v, u32 slot0, const bool* act, const u32* gs, const u32* ge, const u32* bb,
+                                              const u32* sSA, const u32* sK, u32* sNew, u32* sWs, u32* __restrict__ survTile)
 {
-    __shared__ SmWindow W;
-    __shared__ int sAny;
-    __shared__ int sBlk;
-    __shared__ u32 sRt[64];
-    __shared__ u32 sSA[SM_WIN];
-    __shared__ u32 sK[SM_WIN];
-    __shared__ u32 sNew[64];
-    __shared__ u32 sWs[4];
-    const u32 slot0 = blockIdx.x * SM_TS;
-    if (threadIdx.x >= 64 && threadIdx.x < 128) sRt[threadIdx.x - 64] = v.rtbits ? v.rtbits[(slot0 >> 5) + threadIdx.x - 64] : 0u;
-    if (!sm_load_window(v, slot0, W, &sAny)) { if (threadIdx.x == 0 && survTile) survTile[blockIdx.x] = 0; return; }
-    if (threadIdx.x < 64) sNew[threadIdx.x] = 0;
-    if (threadIdx.x == 64) sBlk = find_block(v.base, v.nBlocks, slot0 < v.total ? slot0 : v.total - 1);
-    __syncthreads();
-    const int b0 = sBlk;
-    u32 gs[SM_WIN / 256], ge[SM_WIN / 256], bb[SM_WIN / 256];
-    bool act[SM_WIN / 256];
-#pragma unroll
-    for (int k = 0; k < (int)(SM_WIN / 256); k++) {
-        const u32 i = threadIdx.x + 256u * k;
-        act[k] = sm_group_of(W, i, gs[k], ge[k]);
-        bb[k] = 0;
-        if (!act[k]) continue;
-        const u32 slot = slot0 + i;
-        int b = b0;
-        while (slot >= v.base[b + 1]) b++;
-        bb[k] = v.base[b];
-        u32 off = h;
-        if ((sRt[i >> 5] >> (i & 31)) & 1u) { const u32 r = v.ovr[slot]; off = r > h ? r : h; }
-        const u32 gp = v.SA[slot];
-        sSA[i] = gp;
-        const u32 key = gather_key(v, gp, off, bb[k], v.base[b + 1]);
-        sK[i] = PACKED ? ((key << 8) | (i - gs[k])) : key;
-        if (stats) { atomicAdd(&v.counters[CNT_STAT_SMALL], 1u); if (i == gs[k]) atomicAdd(&v.counters[CNT_STAT_SMALL_GROUPS], 1u); }      // (developer statistics, knob bwt_stats)
-    }
-    __syncthreads();
     u32 surv = 0;
 #pragma unroll
-    for (int k = 0; k < (int)(SM_WIN / 256); k++) {
+    for (int k = 0; k < SM_ROWS; k++) {
         if (!act[k]) continue;
         const u32 i = threadIdx.x + 256u * k;
         const u32 ki = sK[i];
@@ -1007,12 +928,101 @@ __global__ __launch_bounds__(256) void k_bwt_f_small_fused(FwdView v, u32 h, u32
         surv += tied;
     }
     {
+        // members that are still tied, per window (summed by a scan: the host decides by their number whether the next round looks for
+        // links first; one counter for all windows would be an atomic per wave on one address)
         const u32 ws = wave_sum(surv);
         if ((threadIdx.x & 63) == 0) { sWs[threadIdx.x >> 6] = ws; if (ws) v.counters[CNT_SMALL_LEFT] = 1; }
     }
     __syncthreads();
     if (threadIdx.x == 0 && survTile) survTile[blockIdx.x] = sWs[0] + sWs[1] + sWs[2] + sWs[3];
     if (threadIdx.x < 64 && sNew[threadIdx.x]) atomicOr(&v.gnew[(slot0 >> 5) + threadIdx.x], sNew[threadIdx.x]);
+}
+
+__global__ __launch_bounds__(256) void k_bwt_f_gather_small(FwdView v, u32 h, int stats)
+{
+    __shared__ SmWindow W;
+    __shared__ int sAny;
+    __shared__ int sBlk;
+    __shared__ u32 sRt[64];
+    const u32 slot0 = blockIdx.x * SM_TS;
+    if (threadIdx.x >= 64 && threadIdx.x < 128) sRt[threadIdx.x - 64] = v.rtbits ? v.rtbits[(slot0 >> 5) + threadIdx.x - 64] : 0u;
+    if (!sm_load_window(v, slot0, W, &sAny)) return;
+    if (threadIdx.x == 0) sBlk = find_block(v.base, v.nBlocks, slot0 < v.total ? slot0 : v.total - 1);
+    __syncthreads();
+    const int b0 = sBlk;
+#pragma unroll
+    for (int k = 0; k < SM_ROWS; k++) {
+        const u32 i = threadIdx.x + 256u * k;
+        u32 s, e, gp, bb;
+        if (!sm_group_of(W, i, s, e)) continue;
+        v.K[slot0 + i] = sm_fetch_key(v, h, b0, sRt, slot0, i, s, stats, gp, bb);
+    }
+}
+
+// (plain labels only, keys from k_bwt_f_gather_small: versioned ones take k_bwt_f_small_fused)
+__global__ __launch_bounds__(256) void k_bwt_f_sort_small(FwdView v, u32* __restrict__ survTile)
+{
+    __shared__ SmWindow W;
+    __shared__ int sAny;
+    __shared__ u32 sSA[SM_WIN];
+    __shared__ u32 sK[SM_WIN];
+    __shared__ u32 sNew[64];
+    __shared__ u32 sWs[4];
+    const u32 slot0 = blockIdx.x * SM_TS;
+    if (!sm_load_window(v, slot0, W, &sAny)) { if (threadIdx.x == 0 && survTile) survTile[blockIdx.x] = 0; return; }
+    if (threadIdx.x < 64) sNew[threadIdx.x] = 0;
+    u32 gs[SM_ROWS], ge[SM_ROWS], bb[SM_ROWS];
+    bool act[SM_ROWS];
+#pragma unroll
+    for (int k = 0; k < SM_ROWS; k++) {
+        const u32 i = threadIdx.x + 256u * k;
+        act[k] = sm_group_of(W, i, gs[k], ge[k]);
+        bb[k] = 0;                                          // (plain labels need no block base)
+        if (act[k]) { sSA[i] = v.SA[slot0 + i]; sK[i] = v.K[slot0 + i]; }
+    }
+    __syncthreads();
+    sm_rank_place<false>(v, slot0, act, gs, ge, bb, sSA, sK, sNew, sWs, survTile);
+}
+
+// Keys and refinement of the small groups in ONE sweep (versioned labels, see lab_old): k_bwt_f_gather_small + k_bwt_f_sort_small without the
+// key array in between -- a window's bit-map words, positions and keys are read once and stay in LDS (the two kernels read the bit map and
+// SA twice and wrote and read K: 24 of the 40 KiB a dense window moved per round).
+// PACKED (blocks of up to 8 MiB: a key -- a label inside the block + 1 -- has 24 bits): the keys are ranked in sm_rank_place's packed form; a
+// member of a group of g compares with all g (round 6: groups of 33..256 members are a third of the small-group visits of the first rounds
+// on real files).
+template <bool PACKED>
+__global__ __launch_bounds__(256) void k_bwt_f_small_fused(FwdView v, u32 h, u32* __restrict__ survTile, int stats)
+{
+    __shared__ SmWindow W;
+    __shared__ int sAny;
+    __shared__ int sBlk;
+    __shared__ u32 sRt[64];
+    __shared__ u32 sSA[SM_WIN];
+    __shared__ u32 sK[SM_WIN];
+    __shared__ u32 sNew[64];
+    __shared__ u32 sWs[4];
+    const u32 slot0 = blockIdx.x * SM_TS;
+    if (threadIdx.x >= 64 && threadIdx.x < 128) sRt[threadIdx.x - 64] = v.rtbits ? v.rtbits[(slot0 >> 5) + threadIdx.x - 64] : 0u;
+    if (!sm_load_window(v, slot0, W, &sAny)) { if (threadIdx.x == 0 && survTile) survTile[blockIdx.x] = 0; return; }
+    if (threadIdx.x < 64) sNew[threadIdx.x] = 0;
+    if (threadIdx.x == 64) sBlk = find_block(v.base, v.nBlocks, slot0 < v.total ? slot0 : v.total - 1);
+    __syncthreads();
+    const int b0 = sBlk;
+    u32 gs[SM_ROWS], ge[SM_ROWS], bb[SM_ROWS];
+    bool act[SM_ROWS];
+#pragma unroll
+    for (int k = 0; k < SM_ROWS; k++) {
+        const u32 i = threadIdx.x + 256u * k;
+        act[k] = sm_group_of(W, i, gs[k], ge[k]);
+        bb[k] = 0;
+        if (!act[k]) continue;
+        u32 gp;
+        const u32 key = sm_fetch_key(v, h, b0, sRt, slot0, i, gs[k], stats, gp, bb[k]);
+        sSA[i] = gp;
+        sK[i] = PACKED ? ((key << 8) | (i - gs[k])) : key;
+    }
+    __syncthreads();
+    sm_rank_place<PACKED>(v, slot0, act, gs, ge, bb, sSA, sK, sNew, sWs, survTile);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1246,8 +1256,7 @@ __global__ __launch_bounds__(GATHER_THREADS) void k_bwt_f_gather_desc(FwdView v,
         if (threadIdx.x == 0) { sBlk = find_block(v.base, v.nBlocks, d.x); sDiff = 0; }
         __syncthreads();
         const u32 bb = v.base[sBlk], be = v.base[sBlk + 1];
-        u32 off = h;                                        // (uniform for the group)
-        if (v.rtbits && ((v.rtbits[d.x >> 5] >> (d.x & 31)) & 1u)) { const u32 r = v.ovr[d.x]; off = r > h ? r : h; }
+        const u32 off = look_offset(v, d.x, h);             // (uniform for the group)
         // the first member's label and key, by every thread for itself (one address for the workgroup, in flight beside the loads below)
         const u32 gp0 = v.SA[d.x];
         const u32 lab = lab_old(v, gp0, bb), key0 = gather_key(v, gp0, off, bb, be);
@@ -1264,14 +1273,8 @@ __global__ __launch_bounds__(GATHER_THREADS) void k_bwt_f_gather_desc(FwdView v,
         // (block base, label the members carry): what the sorting kernel needs per group without a chain of dependent loads of its own
         if (threadIdx.x == 0) {
             descInfo[g] = make_uint2(bb, lab);
-            if (unsplit) {                                  // (every thread has read desc[g] in front of the verdict's barrier)
-                v.medStage[d.x >> 8] = d; desc[g] = make_uint2(d.x, 0u);
-                if (v.verdictNow) v.verdictNow[d.x >> 8] = make_uint2(key0, verdict_word(v.round, (off == h && key0 != 0u) ? VERDICT_PLAIN : VERDICT_WHOLE, d.y));
-            }
-            if (stats) {
-                atomicAdd(&v.counters[CNT_STAT_MED], d.y); atomicAdd(&v.counters[CNT_STAT_MED_GROUPS], 1u);
-                if (unsplit) { atomicAdd(&v.counters[CNT_STAT_UNSPLIT], 1u); atomicAdd(&v.counters[CNT_STAT_UNSPLIT_MEMBERS], d.y); }
-            }
+            if (stats) { atomicAdd(&v.counters[CNT_STAT_MED], d.y); atomicAdd(&v.counters[CNT_STAT_MED_GROUPS], 1u); }
+            if (unsplit) { desc[g] = make_uint2(d.x, 0u); med_leave_whole(v, d, key0, off, h, stats); }       // (every thread has read desc[g] in front of the verdict's barrier)
         }
         __syncthreads();
     }
@@ -1311,7 +1314,7 @@ __global__ __launch_bounds__(256) void k_bwt_f_med_sleep(FwdView v, uint2* __res
     if (d.y <= SM_G || d.y > MED_CAP) return;
     const uint2 was = v.verdictWas[d.x >> 8];
     if (was.y != verdict_word(v.round - 1u, VERDICT_PLAIN, d.y)) return;
-    if (v.rtbits && ((v.rtbits[d.x >> 5] >> (d.x & 31)) & 1u)) return;
+    if (look_marked(v, d.x)) return;                        // (an offset of its own, not the plain h)
     const u32 bb = v.base[find_block(v.base, v.nBlocks, d.x)];
     u32 s1, k1, s2, k2;
     if (!sleep_target(v, desc, nDesc, bb + was.x - 1u, bb, true, s1, k1) || s1 == d.x) return;
@@ -1583,8 +1586,18 @@ __device__ __forceinline__ void med_majority_write_back(MedLds<THREADS, ROWS>& L
     if (__ballot(surv != 0) != 0 && (tid & 63) == 0) v.counters[CNT_SMALL_LEFT] = 1;
 }
 
-// The chain round (see k_bwt_f_super, whose sort this is, key for key) on a group that is in LDS already: oK / oV [0, n) = keys and
-// positions in position order, m = the group's own label as a key, link = the offset the keys were gathered at. It needs no LDS beyond
+// The chain round. A group whose majority key is the group's OWN label: for most members p the suffix p + h is a member too, i.e. the
+// members form chains p, p + h, p + 2h, ... inside the group (a periodic stretch whose period divides h) that end in a member e whose key is
+// another label. With c(p) = steps from p to the end e(p) of its chain, two members compare like this: all of them start with the group's
+// h symbols B, so suffix p = B^(c+1) followed by what the key of e(p) stands for. The one with the shorter chain meets its foreign
+// key while the other still shows B (label = the group's own): it is the smaller one when that key is below the own label,
+// the larger one when above; equal chain lengths leave the two foreign keys to decide. One sort on
+//     hi = key(e) < own ? c : 2 cmax + 1 - c (cmax = the longest chain),   lo = rank of key(e) among the chain ends
+// therefore does what log2(longest chain) doubling rounds would do; ties share (c + 1) h symbols and the depth of the end's label
+// (at least 2h altogether) and go on as ordinary groups. The members are in position order (every sort of the pipeline is stable),
+// so p + h is found by binary search in the group itself and c, e come from pointer jumping in LDS.
+// It runs on a group that is in LDS already: oK / oV [0, n) = keys and positions in position order, m = the group's own label as a key,
+// link = the offset the keys were gathered at (look_offset: h, or what the group is known to share beyond it). It needs no LDS beyond
 // the group's own, because what it adds is never live together with what it replaces:
 //   - a member's link and chain length are one word, (successor's index | steps << 16), and take the place of its position in oV once every
 //     binary search has read the positions (the links wait in registers for that); the final re-gather reads the positions from SA, which
@@ -1737,14 +1750,12 @@ __device__ __forceinline__ bool med_chain_round(MedLds<THREADS, ROWS>& L, const 
 }
 
 // The refinement of one group whose keys and positions are in LDS (oK / oV [0, n), position order; the workgroup in step behind the
-// stores): chain round, majority split or radix sort, write-back. info = (block base, the members' label). A group whose majority looks at
-// the group itself takes the chain round: in place (med_chain_round; chainLink = the offset its keys were gathered at, from
-// k_bwt_f_medium_fused) or, chainLink == 0, listed for k_bwt_f_super. storeKeys: the keys are nowhere but in LDS (k_bwt_f_medium_fused), so
-// a group listed for the chain round, which reads them from K, stores them there first.
+// stores): chain round, majority split or radix sort, write-back. info = (block base, the members' label), off = the offset the keys
+// were gathered at. A group whose majority looks at the group itself takes the chain round, in place (med_chain_round).
 // Left with the workgroup in step.
 template <int THREADS, int ROWS, bool STATS>
-__device__ __forceinline__ void med_sort_group(MedLds<THREADS, ROWS>& L, const FwdView& v, u32 gs, u32 n, uint2 info, int npass, bool storeKeys, u32 chainLink,
-                                               uint2* __restrict__ medNext, uint2* __restrict__ largeNext, uint4* __restrict__ superList)
+__device__ __forceinline__ void med_sort_group(MedLds<THREADS, ROWS>& L, const FwdView& v, u32 gs, u32 n, uint2 info, int npass, u32 off,
+                                               uint2* __restrict__ medNext, uint2* __restrict__ largeNext)
 {
     constexpr int WAVES = THREADS / 64;
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1757,16 +1768,10 @@ __device__ __forceinline__ void med_sort_group(MedLds<THREADS, ROWS>& L, const F
     for (u32 i = (u32)tid; i < n; i += THREADS) c += (L.oK[i] == m) ? 1u : 0u;
     c = med_block_sum(L, c);
     bool chained = false;
-    if (c < n && 2 * c >= n && n <= SUPER_CAP && m == info.y - info.x + 1u) {
+    if (c < n && 2 * c >= n && n <= CHAIN_CAP && m == info.y - info.x + 1u) {
         // the majority looks at the group itself (a periodic stretch whose period divides h): the chain round finishes it in one round
-        if (chainLink == 0u) {
-            if (tid == 0) { const u32 at = atomicAdd(&v.counters[CNT_SUPER], 1u); superList[at] = make_uint4(gs, n, info.x, info.y); }
-            if (storeKeys) for (u32 i = (u32)tid; i < n; i += THREADS) v.K[gs + i] = L.oK[i];
-            __syncthreads();
-            return;
-        }
-        chained = med_chain_round<THREADS, ROWS>(L, v, gs, n, m, chainLink, npass);
-        if (chained && tid == 0) atomicAdd(&v.counters[CNT_SUPER], 1u);
+        chained = med_chain_round<THREADS, ROWS>(L, v, gs, n, m, off, npass);
+        if (chained && tid == 0) atomicAdd(&v.counters[CNT_CHAINED], 1u);
     }
     if (STATS && tid == 0 && c == n) { atomicAdd(&v.counters[CNT_STAT_UNSPLIT], 1u); atomicAdd(&v.counters[CNT_STAT_UNSPLIT_MEMBERS], n); }
     if (c < n && !chained) {
@@ -1865,11 +1870,12 @@ __device__ __forceinline__ void med_sort_group(MedLds<THREADS, ROWS>& L, const F
 // (Round 6 measured the keys fetched inside this kernel, versioned labels as in k_bwt_f_small_fused: gather + sort of the medium groups
 // 9.1 -> 11.0 ms on the real files, 5.5 -> 6.9 on the stand-in -- a sorting workgroup waits for its own three dependent loads, the gather kernel
 // keeps eight groups per CU in flight and walks the list XCD by XCD. The keys stay a kernel of their own.)
+// The chain round runs here on plain labels as well: the round's keys sit in K before any label moves, med_chain_round works on the group's
+// own LDS and re-reads positions only from the group's own range of SA, which no other workgroup writes.
 // (STATS: the instantiation the knob bwt_stats launches; it counts the groups that come out unsplit and the ones of the majority path.)
 template <int THREADS, int ROWS, bool STATS>
-__global__ __launch_bounds__(THREADS, (THREADS >= 1024 ? 4 : THREADS / 128)) void k_bwt_f_sort_medium(FwdView v, const uint2* __restrict__ desc, u32 nDesc, int npass, u32 minLen,
-                                                               uint2* __restrict__ medNext, uint2* __restrict__ largeNext, const uint2* __restrict__ descInfo,
-                                                               uint4* __restrict__ superList)
+__global__ __launch_bounds__(THREADS, (THREADS >= 1024 ? 4 : THREADS / 128)) void k_bwt_f_sort_medium(FwdView v, const uint2* __restrict__ desc, u32 nDesc, u32 h, int npass, u32 minLen,
+                                                               uint2* __restrict__ medNext, uint2* __restrict__ largeNext, const uint2* __restrict__ descInfo)
 {
     constexpr u32 CAP = (u32)ROWS * THREADS;
     __shared__ MedLds<THREADS, ROWS> L;
@@ -1889,7 +1895,7 @@ __global__ __launch_bounds__(THREADS, (THREADS >= 1024 ? 4 : THREADS / 128)) voi
             for (int r = 0; r < ROWS; r++) { const u32 i = (u32)tid + (u32)r * THREADS; if (i < n) { L.oK[i] = k[r]; L.oV[i] = p[r]; } }
         }
         __syncthreads();
-        med_sort_group<THREADS, ROWS, STATS>(L, v, gs, n, info, npass, false, 0u, medNext, largeNext, superList);
+        med_sort_group<THREADS, ROWS, STATS>(L, v, gs, n, info, npass, look_offset(v, gs, h), medNext, largeNext);     // (the offset k_bwt_f_gather_desc gathered at)
     }
 }
 
@@ -1898,11 +1904,11 @@ __global__ __launch_bounds__(THREADS, (THREADS >= 1024 ? 4 : THREADS / 128)) voi
 // XCDs walk contiguous eighths of the class side by side, as k_bwt_f_gather_desc does with the list. The members' positions and keys
 // (gather_key: lab_old answers with the label a position had when the round began, whatever the round has written since) stay in
 // registers until the verdict: all keys equal -> the group is staged again and its verdict recorded, as k_bwt_f_gather_desc does, and
-// nothing else is written; else they go to LDS and through med_sort_group. No key passes through K (but the ones of a group listed for
-// the chain round) and nothing through descInfo. skip == 0 (knob bwt_no_unsplit_skip): every group is sorted.
+// nothing else is written; else they go to LDS and through med_sort_group. No key passes through K and nothing through descInfo.
+// skip == 0 (knob bwt_no_unsplit_skip): every group is sorted.
 template <int THREADS, int ROWS, bool STATS>
 __global__ __launch_bounds__(THREADS, 4) void k_bwt_f_medium_fused(FwdView v, const uint2* __restrict__ desc, const u32* __restrict__ classIdx, u32 nClass, u32 h, int npass,
-                                                               int skip, int chainList, uint2* __restrict__ medNext, uint2* __restrict__ largeNext, uint4* __restrict__ superList)
+                                                               int skip, uint2* __restrict__ medNext, uint2* __restrict__ largeNext)
 {
     constexpr u32 CAP = (u32)ROWS * THREADS;
     __shared__ MedLds<THREADS, ROWS> L;
@@ -1919,8 +1925,7 @@ __global__ __launch_bounds__(THREADS, 4) void k_bwt_f_medium_fused(FwdView v, co
         if (n <= SM_G || n > CAP) continue;                 // (uniform) void: taken apart by the probe, or asleep (k_bwt_f_med_sleep)
         const int blk = find_block(v.base, v.nBlocks, gs);  // (uniform)
         const u32 bb = v.base[blk], be = v.base[blk + 1];
-        u32 off = h;                                        // (uniform for the group)
-        if (v.rtbits && ((v.rtbits[gs >> 5] >> (gs & 31)) & 1u)) { const u32 r = v.ovr[gs]; off = r > h ? r : h; }
+        const u32 off = look_offset(v, gs, h);              // (uniform for the group)
         // the first member's label and key, by every thread for itself (one address for the workgroup, in flight beside the loads below)
         const u32 gp0 = v.SA[gs];
         const u32 lab = lab_old(v, gp0, bb), key0 = gather_key(v, gp0, off, bb, be);
@@ -1940,172 +1945,15 @@ __global__ __launch_bounds__(THREADS, 4) void k_bwt_f_medium_fused(FwdView v, co
             unsplit = sDiff == 0;
         }
         if (tid == 0) {
-            if (unsplit) {
-                v.medStage[gs >> 8] = d;
-                if (v.verdictNow) v.verdictNow[gs >> 8] = make_uint2(key0, verdict_word(v.round, (off == h && key0 != 0u) ? VERDICT_PLAIN : VERDICT_WHOLE, n));
-            }
-            if (STATS) {
-                atomicAdd(&v.counters[CNT_STAT_MED], n); atomicAdd(&v.counters[CNT_STAT_MED_GROUPS], 1u);
-                if (unsplit) { atomicAdd(&v.counters[CNT_STAT_UNSPLIT], 1u); atomicAdd(&v.counters[CNT_STAT_UNSPLIT_MEMBERS], n); }
-            }
+            if (STATS) { atomicAdd(&v.counters[CNT_STAT_MED], n); atomicAdd(&v.counters[CNT_STAT_MED_GROUPS], 1u); }
+            if (unsplit) med_leave_whole(v, d, key0, off, h, STATS);
         }
         if (unsplit) { __syncthreads(); continue; }         // (uniform; sDiff stays 0, and every thread has read it before the next group's verdict)
 #pragma unroll
         for (int r = 0; r < ROWS; r++) { const u32 i = (u32)tid + (u32)r * THREADS; if (i < n) { L.oK[i] = key[r]; L.oV[i] = gp[r]; } }
         __syncthreads();
         if (tid == 0) sDiff = 0;                            // (every thread has read it; the barriers of the sort lie in front of the next group's verdict)
-        med_sort_group<THREADS, ROWS, STATS>(L, v, gs, n, make_uint2(bb, lab), npass, true, chainList ? 0u : off, medNext, largeNext, superList);
-    }
-}
-
-// A group whose majority key is the group's OWN label: for most members p the suffix p + h is a member too, i.e. the members form
-// chains p, p + h, p + 2h, ... inside the group (a periodic stretch whose period divides h) that end in a member e whose key is another
-// label. With c(p) = steps from p to the end e(p) of its chain, two members compare like this: all of them start with the group's
-// h symbols B, so suffix p = B^(c+1) followed by what the key of e(p) stands for. The one with the shorter chain meets its foreign
-// key while the other still shows B (label = the group's own): it is the smaller one when that key is below the own label,
-// the larger one when above; equal chain lengths leave the two foreign keys to decide. One sort on
-//     hi = key(e) < own ? c : 2 CAP - c,   lo = rank of key(e) among the chain ends
-// therefore does what log2(longest chain) doubling rounds would do; ties share (c + 1) h symbols and the depth of the end's label
-// (at least 2h altogether) and go on as ordinary groups. The members are in position order (every sort of the pipeline is stable),
-// so p + h is found by binary search in the group itself and c, e come from pointer jumping in LDS.
-__global__ __launch_bounds__(1024) void k_bwt_f_super(FwdView v, const uint4* __restrict__ superList, u32 h, int npass, uint2* __restrict__ medNext, uint2* __restrict__ largeNext)
-{
-    constexpr int THREADS = 1024, ROWS = 8;                // (126 KB of LDS: one workgroup per CU, so as many waves in it as a workgroup can have)
-    constexpr u32 CAP = (u32)ROWS * THREADS;
-    __shared__ MedLds<THREADS, ROWS> L;
-    __shared__ u16 nxt[CAP];
-    __shared__ u16 cn[CAP];
-    __shared__ u16 trEnd[CAP];
-    __shared__ u32 sEnds;
-    __shared__ u32 sMoved[2];
-    __shared__ u32 sCmax;
-    const int tid = (int)threadIdx.x, lane = tid & 63;
-    const unsigned long long ltMask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    const u32 nList = v.counters[CNT_SUPER];
-    for (u32 g = blockIdx.x; g < nList; g += gridDim.x) {
-        const uint4 d = superList[g];
-        const u32 gs = d.x, n = d.y;                       // 256 < n <= CAP
-        {
-            u32 k[ROWS], p[ROWS];
-#pragma unroll
-            for (int r = 0; r < ROWS; r++) { const u32 i = (u32)tid + (u32)r * THREADS; k[r] = 0; p[r] = 0; if (i < n) { k[r] = v.K[gs + i]; p[r] = v.SA[gs + i]; } }
-#pragma unroll
-            for (int r = 0; r < ROWS; r++) { const u32 i = (u32)tid + (u32)r * THREADS; if (i < n) { L.oK[i] = k[r]; L.oV[i] = p[r]; } }
-        }
-        if (tid == 0) { sEnds = 0; sCmax = 0; L.oldLab = d.w; L.blkBase = d.z; }
-        __syncthreads();
-        const u32 m = d.w - d.z + 1u;
-        // the offset the group's keys were gathered at (k_bwt_f_gather_desc): h, or what the group is known to share beyond it
-        u32 link = h;
-        if (v.rtbits && ((v.rtbits[gs >> 5] >> (gs & 31)) & 1u)) { const u32 r = v.ovr[gs]; link = r > h ? r : h; }
-        // ---- chain links: the member `link` further on
-#pragma unroll 4
-        for (int r = 0; r < ROWS; r++) {
-            const u32 i = (u32)tid + (u32)r * THREADS;
-            if (i >= n) continue;
-            u32 to = i, one = 0;
-            if (L.oK[i] == m) {
-                const u32 target = L.oV[i] + link;
-                u32 lo = i + 1, hi = n;                     // first index with position >= target
-                while (lo < hi) { const u32 mid = (lo + hi) >> 1; if (L.oV[mid] < target) lo = mid + 1; else hi = mid; }
-                if (lo < n && L.oV[lo] == target) { to = lo; one = 1; }
-            }
-            nxt[i] = (u16)to; cn[i] = (u16)one;
-        }
-        __syncthreads();
-        // ---- pointer jumping: chain end and chain length of every member (until no link moves any more)
-        for (u32 span = 1, it = 0; span < n; span <<= 1, it ^= 1) {
-            u32 a[ROWS], b[ROWS];
-            bool moved = false;
-#pragma unroll
-            for (int r = 0; r < ROWS; r++) {
-                const u32 i = (u32)tid + (u32)r * THREADS;
-                a[r] = 0; b[r] = 0;
-                if (i < n) { const u32 j = nxt[i]; a[r] = nxt[j]; b[r] = (u32)cn[i] + (u32)cn[j]; moved = moved || (a[r] != j); }
-            }
-            if (tid == 0) sMoved[it] = 0;                          // (two flags in turn: the other one may still be read by a slow thread)
-            __syncthreads();
-            if (moved) sMoved[it] = 1;
-#pragma unroll
-            for (int r = 0; r < ROWS; r++) { const u32 i = (u32)tid + (u32)r * THREADS; if (i < n) { nxt[i] = (u16)a[r]; cn[i] = (u16)b[r]; } }
-            __syncthreads();
-            if (!sMoved[it]) break;
-        }
-        u32 e[ROWS], cc[ROWS], tail[ROWS];
-#pragma unroll
-        for (int r = 0; r < ROWS; r++) {
-            const u32 i = (u32)tid + (u32)r * THREADS;
-            e[r] = 0; cc[r] = 0; tail[r] = 0;
-            if (i < n) { e[r] = nxt[i]; cc[r] = cn[i]; tail[r] = L.oK[e[r]]; }
-        }
-        __syncthreads();
-        // ---- the chain ends, compacted (any order) and sorted by key
-#pragma unroll
-        for (int r = 0; r < ROWS; r++) {
-            const u32 i = (u32)tid + (u32)r * THREADS;
-            const bool isEnd = (i < n) && cc[r] == 0;
-            const unsigned long long bal = __ballot(isEnd);
-            u32 base0 = 0;
-            if (lane == 0 && bal) base0 = atomicAdd(&sEnds, (u32)__popcll(bal));
-            base0 = (u32)__shfl((int)base0, 0, 64);
-            if (isEnd) { const u32 at = base0 + (u32)__popcll(bal & ltMask); L.oK[at] = tail[r]; L.oV[at] = i; }
-        }
-        __syncthreads();
-        const u32 nEnds = sEnds;
-        if (nEnds <= (u32)THREADS) {
-            u32 kk = 0, vv = 0, at = 0;
-            if ((u32)tid < nEnds) {
-                kk = L.oK[tid]; vv = L.oV[tid];
-                for (u32 j = 0; j < nEnds; j++) { const u32 kj = L.oK[j]; at += (kj < kk || (kj == kk && j < (u32)tid)) ? 1u : 0u; }
-            }
-            __syncthreads();
-            if ((u32)tid < nEnds) { L.oK[at] = kk; L.oV[at] = vv; }
-            __syncthreads();
-        } else {
-            med_radix_sort<THREADS, ROWS>(L, nEnds, npass);
-        }
-        // rank of an end's key = first index with that key
-        for (u32 j = (u32)tid; j < nEnds; j += THREADS) {
-            const u32 key = L.oK[j];
-            u32 lo = 0, hi = j;
-            while (lo < hi) { const u32 mid = (lo + hi) >> 1; if (L.oK[mid] < key) lo = mid + 1; else hi = mid; }
-            trEnd[L.oV[j]] = (u16)lo;
-        }
-        __syncthreads();
-        // ---- one sort of all members on (hi, rank of the end's key); the key is as wide as the longest chain and the number of ends ask for
-        {
-            u32 cm = 0;
-#pragma unroll
-            for (int r = 0; r < ROWS; r++) cm = cc[r] > cm ? cc[r] : cm;
-            cm = wave_max(cm);
-            if (lane == 0 && cm) atomicMax(&sCmax, cm);
-        }
-        __syncthreads();
-        const u32 cmax = sCmax;
-        const u32 trBits = bitlen_u32(nEnds ? nEnds - 1 : 0), hiBits = bitlen_u32(2u * cmax + 1u);
-        u32 fk[ROWS];
-#pragma unroll
-        for (int r = 0; r < ROWS; r++) {
-            const u32 i = (u32)tid + (u32)r * THREADS;
-            fk[r] = 0;
-            if (i < n) { const u32 hiKey = (tail[r] < m) ? cc[r] : (2u * cmax + 1u - cc[r]); fk[r] = (hiKey << trBits) | (u32)trEnd[e[r]]; }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < ROWS; r++) { const u32 i = (u32)tid + (u32)r * THREADS; if (i < n) { L.oK[i] = fk[r]; L.oV[i] = i; } }
-        __syncthreads();
-        med_radix_sort<THREADS, ROWS>(L, n, (int)((hiBits + trBits + 7) / 8));
-        {
-            u32 p[ROWS];
-#pragma unroll
-            for (int r = 0; r < ROWS; r++) { const u32 i = (u32)tid + (u32)r * THREADS; p[r] = 0; if (i < n) p[r] = v.SA[gs + L.oV[i]]; }
-            __syncthreads();
-#pragma unroll
-            for (int r = 0; r < ROWS; r++) { const u32 i = (u32)tid + (u32)r * THREADS; if (i < n) L.oV[i] = p[r]; }
-        }
-        __syncthreads();
-        med_write_back<THREADS, ROWS>(L, v, gs, n, medNext, largeNext);
-        __syncthreads();
+        med_sort_group<THREADS, ROWS, STATS>(L, v, gs, n, make_uint2(bb, lab), npass, off, medNext, largeNext);
     }
 }
 
@@ -2130,7 +1978,7 @@ __global__ __launch_bounds__(256) void k_bwt_f_probe_scan(FwdView v, const uint2
     for (u32 g = blockIdx.x * 256 + threadIdx.x; g < nDesc; g += gridDim.x * 256) {
         const uint2 d = desc[g];
         const u32 gs = d.x, n = d.y;
-        if (n <= SM_G || n > SUPER_CAP) continue;
+        if (n <= SM_G || n > CHAIN_CAP) continue;
         if (rtbits != nullptr && ((rtbits[gs >> 5] >> (gs & 31)) & 1u)) continue;         // (groups of the run round know their offset already)
         const u32 a0 = v.SA[gs + (n >> 1) - 2], a1 = v.SA[gs + (n >> 1) - 1], a2 = v.SA[gs + (n >> 1)], a3 = v.SA[gs + (n >> 1) + 1];
         const u32 pd = a2 - a1;
@@ -2265,9 +2113,7 @@ __global__ __launch_bounds__(256) void k_bwt_f_large_keys(FwdView v, const uint2
     const u32 slot = d.x + (j - loff[lo]);
     const int b = find_block(v.base, v.nBlocks, d.x);
     const u32 gp = v.SA[slot];
-    u32 off = h;
-    if (v.rtbits && ((v.rtbits[d.x >> 5] >> (d.x & 31)) & 1u)) { const u32 r = v.ovr[d.x]; off = r > h ? r : h; }
-    const u32 key = gather_key(v, gp, off, v.base[b], v.base[b + 1]);
+    const u32 key = gather_key(v, gp, look_offset(v, d.x, h), v.base[b], v.base[b + 1]);
     keys[j] = (KEY)(((u64)lo << kbits) | (u64)key);
     vals[j] = gp;
 }
@@ -3139,18 +2985,17 @@ __global__ __launch_bounds__(256) void k_bwt_f_med_compact(uint2* __restrict__ s
 // knobs (tests, diagnostics): read from the environment once per process, or set through knz_hip_tune(). Each one forces, at test
 // sizes, a path that some inputs take by themselves (round-0 key length, no run round, the run groups' fall-back, the plain labels of
 // blocks above 256 MiB, the plain keys of blocks above 8 MiB, where the link step starts), or reports (stats).
-struct FwdTuning { int nsym; int noRunRound; int runFallback; int stats; int link; int plainLabels; int noPack; int noUnsplitSkip; int noGroupSleep; int noMediumFuse; int runSort; int chainList; int runInSort; };
+struct FwdTuning { int nsym; int noRunRound; int runFallback; int stats; int link; int plainLabels; int noPack; int noUnsplitSkip; int noGroupSleep; int noMediumFuse; int runSort; int runInSort; };
 static FwdTuning& fwd_tuning()
 {
     static FwdTuning t = [] {
-        FwdTuning x; x.nsym = 0; x.noRunRound = 0; x.runFallback = 0; x.stats = 0; x.link = 1; x.plainLabels = 0; x.noPack = 0; x.noUnsplitSkip = 0; x.noGroupSleep = 0; x.noMediumFuse = 0; x.runSort = 0; x.chainList = 0; x.runInSort = 0;     // link: 0 off, 1 on (from h = 32), n > 1: from h = n
+        FwdTuning x; x.nsym = 0; x.noRunRound = 0; x.runFallback = 0; x.stats = 0; x.link = 1; x.plainLabels = 0; x.noPack = 0; x.noUnsplitSkip = 0; x.noGroupSleep = 0; x.noMediumFuse = 0; x.runSort = 0; x.runInSort = 0;     // link: 0 off, 1 on (from h = 32), n > 1: from h = n
         if (getenv("KNZ_BWT_PLAIN_LABELS")) x.plainLabels = 1;
         if (getenv("KNZ_BWT_NO_PACK")) x.noPack = 1;
         if (getenv("KNZ_BWT_NO_UNSPLIT_SKIP")) x.noUnsplitSkip = 1;
         if (getenv("KNZ_BWT_NO_GROUP_SLEEP")) x.noGroupSleep = 1;
         if (getenv("KNZ_BWT_NO_MEDIUM_FUSE")) x.noMediumFuse = 1;
         if (const char* e = getenv("KNZ_BWT_RUN_SORT")) x.runSort = atoi(e);
-        if (const char* e = getenv("KNZ_BWT_CHAIN_LIST")) x.chainList = atoi(e);
         if (const char* e = getenv("KNZ_BWT_RUN_IN_SORT")) x.runInSort = atoi(e);
         if (const char* e = getenv("KNZ_BWT_LINK")) x.link = atoi(e);
         if (getenv("KNZ_BWT_STATS")) x.stats = 1;
@@ -3176,7 +3021,6 @@ int bwt_forward_tune(const char* key, int value)
     else if (!strcmp(key, "bwt_no_group_sleep")) t.noGroupSleep = value;        // every such group gathered in every round (no k_bwt_f_med_sleep, no records)
     else if (!strcmp(key, "bwt_no_medium_fuse")) t.noMediumFuse = value;        // medium groups through k_bwt_f_gather_desc and k_bwt_f_sort_medium on versioned labels too
     else if (!strcmp(key, "bwt_run_sort")) t.runSort = value;                   // 1: the run round's members generated and sorted (k_bwt_f_run_members, _expand), not placed directly
-    else if (!strcmp(key, "bwt_chain_list")) t.chainList = value;               // 1: k_bwt_f_medium_fused lists the chain round's groups for k_bwt_f_super (keys through K), not in place
     else if (!strcmp(key, "bwt_run_in_sort")) t.runInSort = value;              // 1: the run members go through round 0's sort (no FwdSort::run_scan, no gaps)
     else return -1;
     return 0;
@@ -3188,7 +3032,7 @@ struct FwdScratch {
     u32* SA; u32* ISA; u32* K; u64* ISA2;
     u32* t0; u32* t1; u32* t2; u32* t3;
     u32* gbits; u32* gnew; u32* rtbits; u32* ovr; size_t gbitsWords;
-    uint2* med[2]; uint2* medStage; uint2* medVerdict[2]; u32* medFlags; u32* medPrefix; u32* medIdxLo; u32* medIdxHi; size_t medSlots; uint2* descInfo; uint2* large[2]; uint2* runList; uint4* superList; u32* ebits;
+    uint2* med[2]; uint2* medStage; uint2* medVerdict[2]; u32* medFlags; u32* medPrefix; u32* medIdxLo; u32* medIdxHi; size_t medSlots; uint2* descInfo; uint2* large[2]; uint2* runList; u32* ebits;
     u32* loff; u32* lbase;
     u32* survTile;       // members still tied after a round's small-group sort, per window
     u32* linkedTile;     // members the link step linked, per window
@@ -3232,7 +3076,6 @@ static size_t fwd_carve(u8* p, int nBlocks, size_t total, FwdScratch* w, u32 VS)
     w->medVerdict[0] = (uint2*)take(16 * w->medSlots); w->medVerdict[1] = w->medVerdict[0] + w->medSlots;
     w->large[0] = (uint2*)take(8 * maxLarge); w->large[1] = (uint2*)take(8 * maxLarge);
     w->runList = (uint2*)take(8 * maxMed);
-    w->superList = (uint4*)take(16 * maxMed);
     w->descInfo = (uint2*)take(8 * maxMed);
     w->ebits = (u32*)take(4 * w->gbitsWords);
     w->loff = (u32*)take(4 * (maxMed + 1));
@@ -3384,7 +3227,7 @@ struct FwdSort {
         if (nsym < 1) return -4;
         // The doubling starts at the largest power of two the round-0 depth covers (groups and labels of depth nsym >= h are what a round
         // with offset h needs): h = 4, 8, 16, ... meets the periods real data has (record and row sizes are powers of two more often than
-        // not), which is what lets the chain round (k_bwt_f_super) see a group look at itself.
+        // not), which is what lets the chain round (med_chain_round) see a group look at itself.
         while (2 * h <= (u32)nsym) h <<= 1;
         return 0;
     }
@@ -3655,8 +3498,9 @@ struct FwdSort {
         if (tune.link) prims::launch_scan<prims::SCAN_SUM_EXCL>(s, w.survTile, w.survTile, nTiles, nullptr, w.scanTmp, w.counters + CNT_TIED);
     }
     // medium groups: two workgroup shapes, each takes the groups of its size class: 256 threads x 8 elements (21 KB of LDS, groups up to
-    // MED_LO_CAP) and 512 threads x 16 elements (76 KB: two groups per CU in flight); then the chain round. Fused (versioned labels): a
-    // launch per class over that class's index, none for a class without groups; else both shapes walk the whole list.
+    // MED_LO_CAP) and 512 threads x 16 elements (76 KB: two groups per CU in flight); a group that takes the chain round is finished by the
+    // workgroup that holds it. Fused (versioned labels): a launch per class over that class's index, none for a class without groups;
+    // else both shapes walk the whole list.
     void sort_medium()
     {
         const int npass = (kbits + 7) / 8, nxt = cur ^ 1;
@@ -3665,16 +3509,13 @@ struct FwdSort {
             const auto fuse256 = tune.stats ? k_bwt_f_medium_fused<256, 8, true> : k_bwt_f_medium_fused<256, 8, false>;
             const auto fuse512 = tune.stats ? k_bwt_f_medium_fused<512, 16, true> : k_bwt_f_medium_fused<512, 16, false>;
             // (whole multiples of 8 workgroups, one eighth of a class per XCD; four and two workgroups per CU at once)
-            if (nMedLo) hipLaunchKernelGGL(fuse256, dim3(std::min<u32>((nMedLo + 7) / 8 * 8, 2048)), dim3(256), 0, s, v, w.med[cur], w.medIdxLo, nMedLo, h, npass, skip, tune.chainList ? 1 : 0, w.med[nxt], w.large[nxt], w.superList);
-            if (nMedHi) hipLaunchKernelGGL(fuse512, dim3(std::min<u32>((nMedHi + 7) / 8 * 8, 1024)), dim3(512), 0, s, v, w.med[cur], w.medIdxHi, nMedHi, h, npass, skip, tune.chainList ? 1 : 0, w.med[nxt], w.large[nxt], w.superList);
+            if (nMedLo) hipLaunchKernelGGL(fuse256, dim3(std::min<u32>((nMedLo + 7) / 8 * 8, 2048)), dim3(256), 0, s, v, w.med[cur], w.medIdxLo, nMedLo, h, npass, skip, w.med[nxt], w.large[nxt]);
+            if (nMedHi) hipLaunchKernelGGL(fuse512, dim3(std::min<u32>((nMedHi + 7) / 8 * 8, 1024)), dim3(512), 0, s, v, w.med[cur], w.medIdxHi, nMedHi, h, npass, skip, w.med[nxt], w.large[nxt]);
         } else { KScope ks_("k_bwt_f_sort_medium"); const dim3 gridM(std::min<u32>(nMed, 8192));
           const auto sort256 = tune.stats ? k_bwt_f_sort_medium<256, 8, true> : k_bwt_f_sort_medium<256, 8, false>;
           const auto sort512 = tune.stats ? k_bwt_f_sort_medium<512, 16, true> : k_bwt_f_sort_medium<512, 16, false>;
-          hipLaunchKernelGGL(sort256, gridM, dim3(256), 0, s, v, w.med[cur], nMed, npass, SM_G, w.med[nxt], w.large[nxt], w.descInfo, w.superList);
-          hipLaunchKernelGGL(sort512, gridM, dim3(512), 0, s, v, w.med[cur], nMed, npass, MED_LO_CAP, w.med[nxt], w.large[nxt], w.descInfo, w.superList); }
-        // groups whose majority looks at the group itself, where sort_medium has listed them (the kernel reads the count itself);
-        // k_bwt_f_medium_fused finishes them in place (knob bwt_chain_list: lists them)
-        if (!medFuse || tune.chainList) { KScope ks_("k_bwt_f_super"); hipLaunchKernelGGL(k_bwt_f_super, dim3(std::min<u32>(nMed, 512)), dim3(1024), 0, s, v, w.superList, h, npass, w.med[nxt], w.large[nxt]); }
+          hipLaunchKernelGGL(sort256, gridM, dim3(256), 0, s, v, w.med[cur], nMed, h, npass, SM_G, w.med[nxt], w.large[nxt], w.descInfo);
+          hipLaunchKernelGGL(sort512, gridM, dim3(512), 0, s, v, w.med[cur], nMed, h, npass, MED_LO_CAP, w.med[nxt], w.large[nxt], w.descInfo); }
     }
     // large groups: (descriptor index, key) pairs, KEY = u32 where kbits + lbits bits fit. The keys are gathered before any kernel of the
     // round changes a label; the sort and the placement come after the small and medium groups.
@@ -3716,7 +3557,7 @@ struct FwdSort {
             const std::chrono::steady_clock::time_point now = std::chrono::steady_clock::now();
             fprintf(stderr, "round h=%u (%.3f ms): small members worked on %u in %u groups, medium members %u; after it: small left %u, medium groups %u, large %u (%u members); %u groups took the chain round; %u small members still tied\n",
                     h, std::chrono::duration<double, std::milli>(now - statT).count(), hp[CNT_STAT_SMALL], hp[CNT_STAT_SMALL_GROUPS], hp[CNT_STAT_MED], surv, nMed, nLarge, largeElems,
-                    hp[CNT_SUPER], hp[CNT_TIED]);
+                    hp[CNT_CHAINED], hp[CNT_TIED]);
             fprintf(stderr, "  medium groups worked on %u (%u members): all keys equal in %u (%u members)%s, majority path %u (%u members), asleep %u (%u members)\n", hp[CNT_STAT_MED_GROUPS], hp[CNT_STAT_MED],
                     hp[CNT_STAT_UNSPLIT], hp[CNT_STAT_UNSPLIT_MEMBERS], tune.noUnsplitSkip ? "" : " -- left alone", hp[CNT_STAT_MAJ], hp[CNT_STAT_MAJ_MEMBERS], hp[CNT_STAT_ASLEEP], hp[CNT_STAT_ASLEEP_MEMBERS]);
             statT = now;
