@@ -22,10 +22,6 @@
 
 namespace knz {
 
-constexpr u32 ANS_TOP = 1u << 15;
-constexpr u32 ANS_LR = 12;
-constexpr u32 ANS_SCALE = 1u << ANS_LR;
-
 // ------------------------------------------------------------------------------------------------
 // stats + header
 // ------------------------------------------------------------------------------------------------
@@ -44,15 +40,12 @@ __global__ __launch_bounds__(64) void k_ans0_stats(BlockView view, int maxChunks
 
     if (len <= 32) {
         // ANSRangeEncoder.cpp:160-163 : tiny block stored raw (also the <= 15 byte copy-block mode)
-        if (lane == 0) {
-            cd->hdrBits = 0; cd->midLen = 0; cd->trailerLen = 0; cd->aux = 0;
-            cd->nPieces = 1; cd->pieceBits[0] = 8 * len; cd->piecePtr[0] = blk;
-        }
+        if (lane == 0) desc_raw(cd, blk, 8 * len);
         return;
     }
     const u32 n = (len - start < ENT_CHUNK) ? (len - start) : ENT_CHUNK;
 
-    __shared__ u32 hist[8][264];                 // 8 private histograms (ans_chunk_counts)
+    __shared__ u32 hist[8][264];                 // 8 private histograms (chunk_counts)
     __shared__ u32 hdrw[HDR_WORDS];
     __shared__ u32 grpMax[64];
     for (int i = lane; i < 8 * 264; i += 64) (&hist[0][0])[i] = 0;
@@ -62,25 +55,18 @@ __global__ __launch_bounds__(64) void k_ans0_stats(BlockView view, int maxChunks
 
     // lane owns symbols 4*lane .. 4*lane+3
     u32 f[4];
-    ans_chunk_counts(lane, blk, n, hist, f);
-    u32 present = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) present |= (f[k] != 0 ? 1u : 0u) << k;
-    const u32 myCount = __popc(present);
-    const u32 inclCount = wave_incl_scan(myCount);
-    const u32 asz = (u32)__shfl((int)inclCount, 63, 64);
-    const u32 rankBase = inclCount - myCount;      // alphabet index of my first present symbol
+    chunk_counts(lane, blk, n, hist, f);
+    const Alphabet al = alphabet_of(f);
+    const u32 asz = al.asz;
 
     if (n != ANS_SCALE) ans_normalize<ANS_LR>(lane, f, n, asz);
 
     __shared__ u32 grpOff[64];
-    const u32 pos = ans_header_bits<ANS_LR>(lane, f, present, asz, rankBase, true, hdrw, grpMax, grpOff, 0);
+    const u32 pos = ans_header_bits<ANS_LR>(lane, f, al.present, asz, al.rankBase, true, hdrw, grpMax, grpOff, 0);
     __syncthreads();
 
     // ---- write header buffer + encoder table
-    u32* hdrOut = reinterpret_cast<u32*>(tmp + (size_t)slot * TMP_STRIDE);
-    const u32 hdrWordsUsed = (pos + 31) >> 5;
-    for (u32 i = lane; i < hdrWordsUsed; i += 64) hdrOut[i] = bswap32(hdrw[i]);
+    header_flush(lane, hdrw, pos, tmp + (size_t)slot * TMP_STRIDE);
 
     if (asz > 1) ans_enc_table<ANS_LR>(lane, f, encTab + (size_t)slot * 256);
     if (lane == 0) {

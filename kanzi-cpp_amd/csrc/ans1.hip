@@ -18,10 +18,6 @@
 
 namespace knz {
 
-constexpr u32 A1_TOP = 1u << 15;
-constexpr u32 A1_LR = 11;
-constexpr u32 A1_SCALE = 1u << A1_LR;
-
 // ------------------------------------------------------------------------------------------------
 // encode
 // ------------------------------------------------------------------------------------------------
@@ -85,19 +81,12 @@ __global__ __launch_bounds__(64) void k_ans1_ctx(BlockView view, int chunksPerBl
     const uint4 row = reinterpret_cast<const uint4*>(hist + (size_t)gc * 65536 + ctx * 256)[lane];
     u32 f[4] = { row.x, row.y, row.z, row.w };
     const u32 n = wave_sum(f[0] + f[1] + f[2] + f[3]);
-    u32 present = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) present |= (f[k] != 0 ? 1u : 0u) << k;
-    const u32 myCount = __popc(present);
-    const u32 inclCount = wave_incl_scan(myCount);
-    const u32 asz = (u32)__shfl((int)inclCount, 63, 64);
-    const u32 rankBase = inclCount - myCount;
+    const Alphabet al = alphabet_of(f);
+    const u32 asz = al.asz;
     if (asz) ans_normalize<A1_LR>(lane, f, n, asz);
-    const u32 pos = ans_header_bits<A1_LR>(lane, f, present, asz, rankBase, ctx == 0, hdrw, grpMax, grpOff, 0);
+    const u32 pos = ans_header_bits<A1_LR>(lane, f, al.present, asz, al.rankBase, ctx == 0, hdrw, grpMax, grpOff, 0);
     __syncthreads();
-    u32* hdrOut = reinterpret_cast<u32*>(hdrBuf + slot * HDR_BYTES);
-    const u32 hdrWordsUsed = (pos + 31) >> 5;
-    for (u32 i = lane; i < hdrWordsUsed; i += 64) hdrOut[i] = bswap32(hdrw[i]);
+    header_flush(lane, hdrw, pos, hdrBuf + slot * HDR_BYTES);
     if (asz) ans_enc_table<A1_LR>(lane, f, encTab + ((size_t)gc * 256 + ctx) * 256);
     if (lane == 0) { desc[slot].hdrBits = pos; desc[slot].aux = asz; }
 }
@@ -149,7 +138,7 @@ __global__ __launch_bounds__(64) void k_ans1_encode(BlockView view, int chunksPe
     if (lane == 0) for (u32 t = 0; t < tail; t++) pay[top - tail + t] = blk[end4 + t];   // ANSRangeEncoder.cpp:204-205
     const u32 itemsTop = top - tail;                 // item i (in emission order) lies at itemsTop - 2 (i + 1)
     u32 nOut = 0;                                    // items emitted so far (the same in all lanes)
-    u32 st = A1_TOP;
+    u32 st = ANS_TOP;
     const uint2* tab = encTab + (size_t)gc * 65536;
 
     __shared__ uint4 ebuf[2][A1E_ST][4];             // per (step, state): reciprocal, xMax, 2^11 - freq, bias | shift << 16

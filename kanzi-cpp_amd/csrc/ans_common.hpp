@@ -1,47 +1,17 @@
-// rANS table construction shared by the order-0 (ans.hip) and order-1 (ans1.hip) encoders.
+// What the coders with normalised frequency tables share beyond the header language of ent_header.hpp: the rANS constants,
+// normalizeFrequencies, the writer of the alphabet + frequency groups of one table (rANS order 0 and 1, RANGE) and the rANS encoder table
+// (order 0 and 1).
 #pragma once
 #include "common.hpp"
+#include "ent_header.hpp"
 
 namespace knz {
 
-// ------------------------------------------------------------------------------------------------
-// Byte counts of one chunk by one wave (Global.cpp:170-221), shared by the order-0 rANS and the RANGE statistics kernels: 16 bytes per
-// lane per iteration into 8 private histograms chosen by lane -- one ds_add instruction never sends more than 8 lanes to the same copy,
-// which is what bounds the same-address serialisation on skewed data (text: 15 % spaces). Row stride 264: copy c of a symbol sits 8c
-// banks away, not in the same bank. `hist` must be zero; f[k] = count of symbol 4 * lane + k.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void ans_chunk_counts(int lane, const u8* blk, u32 n, u32 (*hist)[264], u32 f[4])
-{
-    u32* myHist = hist[lane & 7];
-    const u32 n16 = n & ~15u;
-    const bool aligned = ((reinterpret_cast<uintptr_t>(blk) & 15) == 0);
-    if (aligned) {
-        const uint4* p4 = reinterpret_cast<const uint4*>(blk);
-        for (u32 i = lane; i < (n16 >> 4); i += 64) {
-            const uint4 v = p4[i];
-            const u32 w[4] = { v.x, v.y, v.z, v.w };
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                atomicAdd(&myHist[w[k] & 0xFF], 1u);
-                atomicAdd(&myHist[(w[k] >> 8) & 0xFF], 1u);
-                atomicAdd(&myHist[(w[k] >> 16) & 0xFF], 1u);
-                atomicAdd(&myHist[w[k] >> 24], 1u);
-            }
-        }
-    } else {
-        for (u32 i = lane; i < n16; i += 64) atomicAdd(&myHist[blk[i]], 1u);
-    }
-    for (u32 i = n16 + lane; i < n; i += 64) atomicAdd(&myHist[blk[i]], 1u);
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int s = 4 * lane + k;
-        u32 acc = 0;
-#pragma unroll
-        for (int c = 0; c < 8; c++) acc += hist[c][s];
-        f[k] = acc;
-    }
-}
+constexpr u32 ANS_TOP = 1u << 15;            // the states' lower bound, both orders
+constexpr u32 ANS_LR = 12;                   // log range of order 0 (one table per 16 KiB chunk)
+constexpr u32 ANS_SCALE = 1u << ANS_LR;
+constexpr u32 A1_LR = 11;                    // log range of order 1 (256 tables per 4 MiB chunk)
+constexpr u32 A1_SCALE = 1u << A1_LR;
 
 // ------------------------------------------------------------------------------------------------
 // pieces shared by order 0 (one table per 16 KiB chunk) and order 1 (one table per context of a 4 MiB chunk);
@@ -155,29 +125,7 @@ __device__ __forceinline__ u32 ans_header_bits_lr(int lane, const u32 f[4], u32 
                                                   u32* hdrw, u32* grpMax, u32* grpOff, u32 pos)
 {
     if (lrWhere == 1) { if (lane == 0) or_bits_words(hdrw, pos, LR - 8, 3); pos += 3; }
-    if (asz == 0) {
-        if (lane == 0) or_bits_words(hdrw, pos, 1, 2);   // FULL_ALPHABET(0), ALPHABET_0(1)
-        pos += 2;
-    } else if (asz == 256) {
-        pos += 2;                                   // FULL_ALPHABET(0), ALPHABET_256(0)
-    } else {
-        // PARTIAL_ALPHABET(1), 5 bits lastMask, masks
-        const u64 anyMask = __ballot(present != 0);
-        const int lastLane = 63 - __clzll((long long)anyMask);
-        const u32 lastMask = (u32)lastLane >> 1;    // symbol >> 3 == lane >> 1
-        if (lane == 0) {
-            or_bits_words(hdrw, pos, 1, 1);
-            or_bits_words(hdrw, pos + 1, lastMask, 5);
-        }
-        pos += 6;
-        // mask byte m: low nibble from lane 2m, high nibble from lane 2m+1 ; bit (s&7) = symbol present
-        const u32 other = (u32)__shfl_xor((int)present, 1, 64);
-        if ((lane & 1) == 0 && ((u32)lane >> 1) <= lastMask) {
-            const u32 byte = present | (other << 4);
-            or_bits_words(hdrw, pos + 8 * ((u32)lane >> 1), byte, 8);
-        }
-        pos += 8 * (lastMask + 1);
-    }
+    pos = alphabet_put(lane, present, asz, hdrw, pos);
     if (lrWhere == 2 && asz != 0) { if (lane == 0) or_bits_words(hdrw, pos, LR - 8, 3); pos += 3; }
 
     if (asz > 1) {

@@ -22,11 +22,10 @@
 //   k_ans1_*       order 1: one wave per 4 MiB chunk, the chunk's cumulative frequencies in LDS, a wave-wide search per step (see below).
 #include "common.hpp"
 #include "stages.hpp"
+#include "ans_common.hpp"
 
 namespace knz {
 
-constexpr u32 ANS_TOP = 1u << 15;
-constexpr u32 ANS_LR = 12;
 constexpr u32 ANS_MAX_CHUNK = 1u << 27;
 
 struct AnsDecChunk {
@@ -43,10 +42,7 @@ struct AnsDecChunk {
     u16 grp[44];         // per frequency group: (bit offset relative to freqBit of the logMax field) | logMax << 12
 };
 
-// The scan stages a 1 KiB window of the stream (4 words per lane, byte-swapped to bit order) in LDS.  Everything
-// the header walk reads is wave-uniform: all lanes run the same short dependent chain (one LDS read + a
-// handful of VALU operations per field), with no cross-lane traffic.
-constexpr u32 SCAN_WIN_BITS = 8192;
+// what the scan asks of its header window (HeaderWindow, ent_header.hpp) per order-0 chunk
 constexpr u32 SCAN_NEED_BITS = 3498 + 40 + 128 + 64;   // longest header + var-int + 4 states + one spare dword pair
 
 // values the compiler must have in registers at this point (it would otherwise move an LDS read it thinks is optional behind the
@@ -57,14 +53,6 @@ constexpr u32 SCAN_NEED_BITS = 3498 + 40 + 128 + 64;   // longest header + var-i
 #define KNZ_KEEP3(a, b, c) asm volatile("" : "+v"(a), "+v"(b), "+v"(c))
 #endif
 
-// n in [1, 32]; rel = bit offset from the window start
-__device__ __forceinline__ u32 lds_bits(const u32* win, u32 rel, u32 n)
-{
-    const u32 i = rel >> 5;
-    const u64 v = ((u64)win[i] << 32) | (u64)win[i + 1];
-    return (u32)((v << (rel & 31)) >> (64 - n));
-}
-
 // ORDER 0: one table per 16 KiB chunk, meta slot ci.  ORDER 1: 256 tables per 4 MiB chunk, meta slots
 // ci*257 + ctx, the chunk record (payload, states) in slot ci*257 + 256.
 template <int ORDER>
@@ -73,14 +61,14 @@ __global__ __launch_bounds__(64) void k_ans_scan(BitSrc src, DecBlock* __restric
 {
     constexpr u32 CHUNK = ORDER ? ANS1_CHUNK : ENT_CHUNK;
     constexpr u32 DIM = ORDER ? 256u : 1u;
-    constexpr u32 MAX_LR = ORDER ? 11u : ANS_LR;       // kanzi encoders emit 12 (order 0) / 11 (order 1); larger tables are not provisioned
+    constexpr u32 MAX_LR = ORDER ? A1_LR : ANS_LR;       // kanzi encoders emit 12 (order 0) / 11 (order 1); larger tables are not provisioned
     const int b = blockIdx.x;
     const int lane = lane_id();
     DecBlock& db = blocks[b];
     AnsDecChunk* cs = chunks + (size_t)b * maxChunks;
     for (int i = lane; i < maxChunks; i += 64) cs[i].kind = 3;
     if (db.error) return;
-    __shared__ u32 win[256 + 8];
+    __shared__ u32 win[HDR_WIN_WORDS];
     const u64 limit = uni64(db.payloadBit + ((db.bits + 7) & ~7ull));
     u64 pos = uni64(db.entropyBit);
     const u64 entropyBit = pos;
@@ -97,89 +85,31 @@ __global__ __launch_bounds__(64) void k_ans_scan(BitSrc src, DecBlock* __restric
         return;
     }
     const u32 nChunks = (preLen + CHUNK - 1) / CHUNK;
-    const u64 lastWord = ((src.nBytes + 3) >> 2) - 1;
-    // words past the end of the buffer are clamped to its last word: positions past `limit` are rejected
-    // before anything read there is trusted
-    auto issue = [&](u64 bit0, u32x4& dstv) {
-        const u64 w = (bit0 >> 5) + 4ull * (u32)lane;
-        const u64 w1 = w + 1, w2 = w + 2, w3 = w + 3;
-        const u32* p = src.words;
-        dstv.x = p[w < lastWord ? w : lastWord];
-        dstv.y = p[w1 < lastWord ? w1 : lastWord];
-        dstv.z = p[w2 < lastWord ? w2 : lastWord];
-        dstv.w = p[w3 < lastWord ? w3 : lastWord];
-    };
-    u32x4 wr = { 0, 0, 0, 0 };
-    u64 winBit0 = 0;
-    bool winValid = false;
-    u32x4 guess = { 0, 0, 0, 0 };
-    u64 guessBit0 = 0;
-    bool guessValid = false;
-    // make stream bits [pos, pos + need) readable through `win`: keep the current window if it still covers
-    // them, else take the prefetched guess if it does, else load exactly (blocking)
-    auto ensure = [&](u32 need) {
-        if (winValid && winBit0 <= pos && pos + need <= winBit0 + SCAN_WIN_BITS) return;
-        if (guessValid && guessBit0 <= pos && pos + need <= guessBit0 + SCAN_WIN_BITS) {
-            wr = guess; winBit0 = guessBit0;
-        } else {
-            winBit0 = pos & ~31ull;
-            issue(winBit0, wr);
-        }
-        guessValid = false;
-        __syncthreads();
-        {
-            u32x4 sw = { bswap32(wr.x), bswap32(wr.y), bswap32(wr.z), bswap32(wr.w) };
-            *reinterpret_cast<u32x4*>(&win[4 * lane]) = sw;
-        }
-        __syncthreads();
-        winValid = true;
-    };
+    HeaderWindow hw(win, src, lane);
     u64 prevPos = pos;
     u32 myGrp = 0;
     int err = 0;
     for (u32 ci = 0; ci < nChunks && !err; ci++) {
-        ensure(ORDER ? 3498u + 64u : SCAN_NEED_BITS);
+        hw.ensure(pos, ORDER ? 3498u + 64u : SCAN_NEED_BITS);
         if (ORDER == 0) {
-            // prefetch for the next chunk: same compressed size as this one, window centred on the estimate
-            guessValid = false;
-            if (ci >= 1 && ci + 1 < nChunks) {
-                const u64 est = pos + (pos - prevPos);
-                guessBit0 = (est > 2304 ? est - 2304 : 0) & ~31ull;
-                issue(guessBit0, guess);
-                guessValid = true;
-            }
+            hw.forget();
+            if (ci >= 1 && ci + 1 < nChunks) hw.prefetch(HeaderWindow::guess_at(pos, prevPos));
             prevPos = pos;
         }
-        const u32 lr = 8 + lds_bits(win, (u32)(pos - winBit0), 3);
+        const u32 lr = 8 + hw.bits(pos, 3);
         pos += 3;
         if (lr > MAX_LR) { err = 1; break; }
         u32 aszSum = 0;
-        u32 firstSym = 0;
         for (u32 k = 0; k < DIM; k++) {
-            if (ORDER) ensure(3498u + 64u);
+            if (ORDER) hw.ensure(pos, 3498u + 64u);
+            const u64 winBit0 = hw.bit0;
             AnsDecChunk& c = cs[ORDER ? ci * 257 + k : ci];
-            u32 p = (u32)(pos - winBit0);                  // header positions are window-relative from here
-            u32 asz = 0;
-            u64 maskBit = 0;
-            const u32 hb = lds_bits(win, p, 7);            // flag bits and (partial alphabets) the mask count
-            if ((hb >> 6) == 0) { asz = ((hb >> 5) & 1) ? 0u : 256u; p += 2; }
-            else {
-                const u32 lastMask = (hb >> 1) & 31;
-                p += 6;
-                maskBit = winBit0 + p;
-                // one mask byte per lane
-                const u32 byte = ((u32)lane <= lastMask) ? lds_bits(win, p + 8u * (u32)lane, 8) : 0u;
-                const u32 pc = __popc(byte);
-                asz = wave_sum(pc);
-                const u64 nz = __ballot(byte != 0);
-                if (nz) {
-                    const int fl = __ffsll((long long)nz) - 1;
-                    const u32 fb = rl(byte, (u32)fl);
-                    firstSym = 8u * (u32)fl + (u32)(__ffs((int)fb) - 1);
-                }
-                p += 8u * (lastMask + 1);
-            }
-            asz = uni(asz);
+            // header positions are window-relative from here
+            const AlphabetIn<u32> ai = alphabet_get([&](u32 at, u32 nb) { return win_bits(win, at, nb); }, lane, (u32)(pos - winBit0));
+            const u64 maskBit = pos + 6;                   // (of a partial alphabet; not read otherwise)
+            const u32 p = ai.next;
+            const u32 asz = uni(ai.a.asz);
+            const u32 firstSym = ai.firstSym;
             if (asz == 0) {
                 if (ORDER == 0) { err = 2; break; }        // decode() returns a short count -> failure
                 pos = winBit0 + p;                         // order 1: unused context, no table
@@ -230,7 +160,7 @@ __global__ __launch_bounds__(64) void k_ans_scan(BitSrc src, DecBlock* __restric
                 q = p + rel;
             } else {
                 for (u32 g = 0; g < nGroups; g++) {
-                    const u32 logMax = lds_bits(win, q, llr);
+                    const u32 logMax = win_bits(win, q, llr);
                     tooBig |= (logMax > lr) ? 1u : 0u;          // checked after the walk; a bad value cannot fault:
                     if ((u32)lane == g) myGrp = (q - p) | (logMax << 12);   // LDS reads past the window just return
                     q += llr + ((g + 1 == nGroups) ? lastCnt : chk) * logMax;   // unrelated words
@@ -258,20 +188,13 @@ __global__ __launch_bounds__(64) void k_ans_scan(BitSrc src, DecBlock* __restric
         } else {
             if (ORDER && aszSum == 0) { err = 2; break; }   // ANSRangeDecoder.cpp:196-199: short count
             // var-int and the 4 states
-            if (ORDER) ensure(40u + 128u + 64u);
-            u32 q = (u32)(pos - winBit0);
-            u32 value = lds_bits(win, q, 8); q += 8;
-            u32 res = value & 0x7F;
-            for (int shift = 7; value >= 128; shift += 7) {
-                value = lds_bits(win, q, 8); q += 8;
-                if (shift == 28) { if (value >= 128 || (value & 0x70) != 0) err = 1; res |= (value & 0x0F) << shift; break; }
-                res |= (value & 0x7F) << shift;
-            }
-            sz = res;
+            if (ORDER) hw.ensure(pos, 40u + 128u + 64u);
+            u32 q = (u32)(pos - hw.bit0);
+            sz = win_varint(win, q, err);
             if (sz >= ANS_MAX_CHUNK || sz > 2 * CHUNK - 2) err = 1;
-            st0 = lds_bits(win, q, 32); st1 = lds_bits(win, q + 32, 32); st2 = lds_bits(win, q + 64, 32); st3 = lds_bits(win, q + 96, 32);
+            st0 = win_bits(win, q, 32); st1 = win_bits(win, q + 32, 32); st2 = win_bits(win, q + 64, 32); st3 = win_bits(win, q + 96, 32);
             q += 128;
-            payloadBit = winBit0 + q;
+            payloadBit = hw.bit0 + q;
             endPos = payloadBit + 8ull * sz;
             kind = 0;
         }
@@ -290,6 +213,28 @@ __global__ __launch_bounds__(64) void k_ans_scan(BitSrc src, DecBlock* __restric
         if (err) db.error = KNZ_ERR_PROCESS_BLOCK;
         db.usedBits = pos - entropyBit;
     }
+}
+
+// What the table builders of both orders read back through the record the scan left: this lane's part of the alphabet (the mask bytes
+// of a partial one end where the frequencies begin) and its frequencies from the recorded group offsets. true: a damaged table.
+__device__ __forceinline__ Alphabet ans_dec_alphabet(const BitSrc& src, const AnsDecChunk& c, int lane)
+{
+    u32 present = 0xF;
+    if (c.asz != 256) {
+        const u64 mb = c.maskBit + 8ull * ((u32)lane >> 1);
+        present = mask_nibble((mb + 8 <= c.freqBit) ? peek_bits(src, mb, 8) : 0u, lane);
+    }
+    Alphabet al = alphabet_of_present(present);
+    al.asz = c.asz;
+    return al;
+}
+
+__device__ __forceinline__ bool ans_dec_freqs(const BitSrc& src, const AnsDecChunk& c, const Alphabet& al, u32 f[4])
+{
+    const u32 llr = (u32)ilog2_u32(c.lr) + 1u;
+    return freqs_get(al, 1u << c.lr,
+                     [&](u32 g, u32& w) -> u64 { const u32 ge = c.grp[g]; w = ge >> 12; return c.freqBit + (ge & 0xFFF) + llr; },
+                     [&](u64 at, u32 nb) { return peek_bits(src, at, nb); }, f);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -362,48 +307,11 @@ __global__ __launch_bounds__(64) void k_ans0_decode(BitSrc src, DecBlock* __rest
         const u32 lr = c.lr;
         const u32 scale = 1u << lr;
         const u32 asz = c.asz;
-        u32 present;
-        if (asz == 256) present = 0xF;
-        else {
-            const u32 m = (u32)lane >> 1;
-            const u64 mb = c.maskBit + 8ull * m;
-            const u32 byte = (mb + 8 <= c.freqBit) ? peek_bits(src, mb, 8) : 0u;
-            present = (lane & 1) ? (byte >> 4) : (byte & 0xF);
-        }
-        const u32 myCount = __popc(present);
-        const u32 incl = wave_incl_scan(myCount);
-        const u32 rank0 = incl - myCount;
-        u32 r = rank0;
-        const u32 chk = (asz >= 64) ? 8u : 6u;
-        const u32 llr = (u32)ilog2_u32(lr) + 1u;
-        u32 f[4] = { 0, 0, 0, 0 };
-        u32 lsum = 0;
-        int bad = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if ((present >> k) & 1) {
-                if (r >= 1) {
-                    const u32 g = (r - 1) / chk;
-                    const u32 ge = c.grp[g];
-                    const u32 lm = ge >> 12;
-                    const u32 fv = lm ? peek_bits(src, c.freqBit + (ge & 0xFFF) + llr + (u64)((r - 1) - g * chk) * lm, lm) + 1u : 1u;
-                    if (fv >= scale) bad = 1;
-                    f[k] = fv;
-                    lsum += fv;
-                }
-                r++;
-            }
-        }
-        const u32 sumOthers = wave_sum(lsum);
-        if (scale <= sumOthers) bad = 1;
-        if (!bad) {
-            u32 rr = rank0;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                if ((present >> k) & 1) { if (rr == 0) f[k] = scale - sumOthers; rr++; }
-            }
-        }
-        if (__ballot(bad) != 0) { if (lane == 0) chunkErr[gg] = 1; continue; }
+        const Alphabet al = ans_dec_alphabet(src, c, lane);
+        const u32 rank0 = al.rankBase;
+        const u32 present = al.present;
+        u32 f[4];
+        if (ans_dec_freqs(src, c, al, f)) { if (lane == 0) chunkErr[gg] = 1; continue; }
         const u32 tot = f[0] + f[1] + f[2] + f[3];
         const u32 cincl = wave_incl_scan(tot);
         u32 cum = cincl - tot;
@@ -481,11 +389,11 @@ __global__ __launch_bounds__(64) void k_ans0_decode(BitSrc src, DecBlock* __rest
     // Refill loads are branch-free so that their latency is not waited for at the load: word indices are
     // clamped to the last (possibly partial) word of the buffer -- bytes past the stream end are never consumed,
     // and an aligned dword never straddles a page.  Raw words are converted when they are stored to LDS.
-    const u64 lastWord = ((src.nBytes + 3) >> 2) - 1;
+    const ClampedWords cw = clamped_words(src);
     auto load5 = [&](u32 streamOff, u32 raw[5]) {
         const u64 w0 = (payBit + 8ull * streamOff) >> 5;
 #pragma unroll
-        for (int k = 0; k < 5; k++) { const u64 w = w0 + k; raw[k] = src.words[w < lastWord ? w : lastWord]; }
+        for (int k = 0; k < 5; k++) raw[k] = cw.raw(w0 + k);
     };
     // item form of 4 stream bytes s0 s1 s2 s3 (big-endian word v): low half = s0<<8|s1, high half = s2<<8|s3
     auto store4 = [&](u32 streamOff, const u32 raw[5]) {
@@ -661,51 +569,9 @@ __global__ __launch_bounds__(64) void k_ans1_tables(BitSrc src, DecBlock* __rest
     const AnsDecChunk& c = cs[ctx];
     if (c.kind != 0) return;
     const int lane = lane_id();
-    const u32 lr = c.lr;
-    const u32 scale = 1u << lr;
-    const u32 asz = c.asz;
-    u32 present;
-    if (asz == 256) present = 0xF;
-    else {
-        const u32 m = (u32)lane >> 1;
-        const u64 mb = c.maskBit + 8ull * m;
-        const u32 byte = (mb + 8 <= c.freqBit) ? peek_bits(src, mb, 8) : 0u;
-        present = (lane & 1) ? (byte >> 4) : (byte & 0xF);
-    }
-    const u32 myCount = __popc(present);
-    const u32 incl = wave_incl_scan(myCount);
-    const u32 rank0 = incl - myCount;
-    u32 r = rank0;
-    const u32 chk = (asz >= 64) ? 8u : 6u;
-    const u32 llr = (u32)ilog2_u32(lr) + 1u;
-    u32 f[4] = { 0, 0, 0, 0 };
-    u32 lsum = 0;
-    int bad = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        if ((present >> k) & 1) {
-            if (r >= 1) {
-                const u32 g = (r - 1) / chk;
-                const u32 ge = c.grp[g];
-                const u32 lm = ge >> 12;
-                const u32 fv = lm ? peek_bits(src, c.freqBit + (ge & 0xFFF) + llr + (u64)((r - 1) - g * chk) * lm, lm) + 1u : 1u;
-                if (fv >= scale) bad = 1;
-                f[k] = fv;
-                lsum += fv;
-            }
-            r++;
-        }
-    }
-    const u32 sumOthers = wave_sum(lsum);
-    if (scale <= sumOthers) bad = 1;
-    if (__ballot(bad) != 0) { if (lane == 0) blocks[b].error = KNZ_ERR_PROCESS_BLOCK; return; }
-    {
-        u32 rr = rank0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if ((present >> k) & 1) { if (rr == 0) f[k] = scale - sumOthers; rr++; }
-        }
-    }
+    const u32 scale = 1u << c.lr;
+    u32 f[4];
+    if (ans_dec_freqs(src, c, ans_dec_alphabet(src, c, lane), f)) { if (lane == 0) blocks[b].error = KNZ_ERR_PROCESS_BLOCK; return; }
     const u32 tot = f[0] + f[1] + f[2] + f[3];
     const u32 cincl = wave_incl_scan(tot);
     const u32 c0 = cincl - tot, c1 = c0 + f[0], c2 = c1 + f[1], c3 = c2 + f[2];
@@ -757,7 +623,7 @@ __global__ __launch_bounds__(64) void k_ans1_decode(BitSrc src, DecBlock* __rest
     const u16* cum16 = reinterpret_cast<const u16*>(cumL);
 
     __shared__ u32 ring[A1_RN / 2 + 4];          // 16-bit items in value form, 2 per word, + 4 mirrored items (+ 2 words a read may touch)
-    const u64 lastWord = ((src.nBytes + 3) >> 2) - 1;
+    const ClampedWords cw = clamped_words(src);
     // lane loads stream bytes [off + 16*lane, +16) -> 8 items
     auto fill_half = [&](u32 streamOff) {
         const u32 off = streamOff + 16u * (u32)lane;
@@ -766,7 +632,7 @@ __global__ __launch_bounds__(64) void k_ans1_decode(BitSrc src, DecBlock* __rest
         const u32 sh = (u32)bit & 31;
         u32 raw[5];
 #pragma unroll
-        for (int k = 0; k < 5; k++) { const u64 w = w0 + k; raw[k] = bswap32(src.words[w < lastWord ? w : lastWord]); }
+        for (int k = 0; k < 5; k++) raw[k] = bswap32(cw.raw(w0 + k));
         const u32 wo = (off & (2 * A1_RN - 1)) >> 2;
 #pragma unroll
         for (int k = 0; k < 4; k++) {

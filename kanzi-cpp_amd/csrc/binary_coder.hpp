@@ -13,6 +13,7 @@
 #pragma once
 #include "common.hpp"
 #include "binary_tail.hpp"
+#include "ent_header.hpp"
 
 namespace knz {
 
@@ -107,7 +108,7 @@ template <class P>
 __device__ __forceinline__ bool binary_decode_block(P& pr, const BitSrc& src, const BitSrc& s, u64& pos, u32 count, u8* __restrict__ block, int lane)
 {
     const u64 limit = s.limitBits;
-    const u64 lastWord = ((src.nBytes + 3) >> 2) - 1;
+    const ClampedWords cw = clamped_words(src);
     const u32 length = cm_chunk_len(count);
     u64 low = 0, high = CM_TOP, current = 0;
     u32 startChunk = 0;
@@ -131,8 +132,7 @@ __device__ __forceinline__ bool binary_decode_block(P& pr, const BitSrc& src, co
         const u32 sh = (u32)(payBit & 31);
         auto loadWin = [&](u32 unit0) -> u32 {
             const u64 w = wbase + unit0 + (u32)lane;
-            const u32 a = bswap32(src.words[w < lastWord ? w : lastWord]);
-            const u32 c = bswap32(src.words[w + 1 < lastWord ? w + 1 : lastWord]);
+            const u32 a = bswap32(cw.raw(w)), c = bswap32(cw.raw(w + 1));
             return sh ? ((a << sh) | (c >> (32 - sh))) : a;
         };
         u32 winBase = 0;

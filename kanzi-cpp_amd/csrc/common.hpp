@@ -350,23 +350,6 @@ __device__ __forceinline__ u32 take_bits(const BitSrc& s, u64& pos, u32 n, int& 
     return v;
 }
 
-// EntropyUtils::readVarInt (entropy/EntropyUtils.cpp:261-285)
-__device__ __forceinline__ u32 take_varint(const BitSrc& s, u64& pos, int& err)
-{
-    u32 value = take_bits(s, pos, 8, err);
-    u32 res = value & 0x7F;
-    for (int shift = 7; value >= 128 && !err; shift += 7) {
-        value = take_bits(s, pos, 8, err);
-        if (shift == 28) {
-            if (value >= 128 || (value & 0x70) != 0) { err = 1; return 0; }
-            res |= (value & 0x0F) << shift;
-            return res;
-        }
-        res |= (value & 0x7F) << shift;
-    }
-    return res;
-}
-
 // Per-block decode bookkeeping
 struct DecBlock {
     u64 payloadBit;      // first bit of the block's private stream (mode byte)

@@ -26,6 +26,7 @@
 #include "common.hpp"
 #include "stages.hpp"
 #include "binary_tail.hpp"
+#include "ent_header.hpp"
 
 namespace knz {
 
@@ -265,7 +266,7 @@ __global__ __launch_bounds__(64) void k_fpaq_decode(BitSrc src, DecBlock* __rest
         if (lane == 0) { if (bad) db.error = KNZ_ERR_PROCESS_BLOCK; db.usedBits = bad ? (s.limitBits - db.entropyBit) : 8ull * count; }
         return;
     }
-    const u64 lastWord = ((src.nBytes + 3) >> 2) - 1;
+    const ClampedWords cw = clamped_words(src);
     u64 low = 0, high = FPAQ_TOP, current = 0;
     u32 startChunk = 0;
     bool fail = false;
@@ -283,8 +284,7 @@ __global__ __launch_bounds__(64) void k_fpaq_decode(BitSrc src, DecBlock* __rest
         const u32 sh = (u32)(payBit & 31);
         auto loadWin = [&](u32 unit0) -> u32 {
             const u64 w = wbase + unit0 + (u32)lane;
-            const u32 a = bswap32(src.words[w < lastWord ? w : lastWord]);
-            const u32 c = bswap32(src.words[w + 1 < lastWord ? w + 1 : lastWord]);
+            const u32 a = bswap32(cw.raw(w)), c = bswap32(cw.raw(w + 1));
             return sh ? ((a << sh) | (c >> (32 - sh))) : a;
         };
         u32 winBase = 0;

@@ -16,6 +16,7 @@
 //   k_huff_decode  8 chunks per wave: 4096-entry decode tables in LDS, one lane per fragment.
 #include "common.hpp"
 #include "stages.hpp"
+#include "ent_header.hpp"
 
 namespace knz {
 
@@ -140,19 +141,14 @@ __global__ __launch_bounds__(64) void k_huff_encode(BlockView view, int maxChunk
     const u8* blk = view.ptr[b] + start;
     ChunkDesc* cd = desc + slot;
     const u32 n = (len - start < ENT_CHUNK) ? (len - start) : ENT_CHUNK;
-    const bool copyBlock = false;
-    (void)copyBlock;
 
     if (n < 32) {
         // HuffmanEncoder.cpp:326-329 : small chunk stored raw
-        if (lane == 0) {
-            cd->hdrBits = 0; cd->midLen = 0; cd->trailerLen = 0; cd->aux = 0;
-            cd->nPieces = 1; cd->pieceBits[0] = 8 * n; cd->piecePtr[0] = blk;
-        }
+        if (lane == 0) desc_raw(cd, blk, 8 * n);
         return;
     }
 
-    __shared__ u32 hist[8][264];     // 8 lane-selected copies, rows 8 banks apart (see k_ans0_stats)
+    __shared__ u32 hist[8][264];     // 8 lane-selected copies, rows 8 banks apart (chunk_counts)
     __shared__ u32 hdrw[HDR_WORDS];
     __shared__ u32 keys[256];        // (freq << 8) | sym of present symbols, then sorted
     __shared__ u32 sorted[256];
@@ -168,61 +164,16 @@ __global__ __launch_bounds__(64) void k_huff_encode(BlockView view, int maxChunk
     __syncthreads();
 
     // ---- histogram
-    u32* myHist = hist[lane & 7];
-    const u32 n16 = n & ~15u;
-    const bool aligned = ((reinterpret_cast<uintptr_t>(blk) & 15) == 0);
-    if (aligned) {
-        const uint4* p4 = reinterpret_cast<const uint4*>(blk);
-        for (u32 i = lane; i < (n16 >> 4); i += 64) {
-            const uint4 v = p4[i];
-            const u32 w[4] = { v.x, v.y, v.z, v.w };
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                atomicAdd(&myHist[w[k] & 0xFF], 1u);
-                atomicAdd(&myHist[(w[k] >> 8) & 0xFF], 1u);
-                atomicAdd(&myHist[(w[k] >> 16) & 0xFF], 1u);
-                atomicAdd(&myHist[w[k] >> 24], 1u);
-            }
-        }
-    } else {
-        for (u32 i = lane; i < n16; i += 64) atomicAdd(&myHist[blk[i]], 1u);
-    }
-    for (u32 i = n16 + lane; i < n; i += 64) atomicAdd(&myHist[blk[i]], 1u);
-    __syncthreads();
-
     u32 f[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int s = 4 * lane + k;
-        u32 acc = 0;
-#pragma unroll
-        for (int c = 0; c < 8; c++) acc += hist[c][s];
-        f[k] = acc;
-    }
+    chunk_counts(lane, blk, n, hist, f);
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < 4; k++) hist[0][4 * lane + k] = f[k];      // keep totals for the fallback path
-    u32 present = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) present |= (f[k] != 0 ? 1u : 0u) << k;
-    const u32 myCount = __popc(present);
-    const u32 inclCount = wave_incl_scan(myCount);
-    const u32 asz = (u32)__shfl((int)inclCount, 63, 64);
-    const u32 rankBase = inclCount - myCount;
+    const Alphabet al = alphabet_of(f);
+    const u32 asz = al.asz, rankBase = al.rankBase;
 
     // ---- alphabet (EntropyUtils.cpp:57-89)
-    u32 pos = 0;
-    if (asz == 256) {
-        pos = 2;
-    } else {
-        const u64 anyMask = __ballot(present != 0);
-        const int lastLane = 63 - __clzll((long long)anyMask);
-        const u32 lastMask = (u32)lastLane >> 1;
-        if (lane == 0) { or_bits_words(hdrw, 0, 1, 1); or_bits_words(hdrw, 1, lastMask, 5); }
-        const u32 other = (u32)__shfl_xor((int)present, 1, 64);
-        if ((lane & 1) == 0 && ((u32)lane >> 1) <= lastMask) or_bits_words(hdrw, 6 + 8 * ((u32)lane >> 1), present | (other << 4), 8);
-        pos = 6 + 8 * (lastMask + 1);
-    }
+    const u32 pos = alphabet_put(lane, al.present, asz, hdrw, 0);
 
     // alphabet[] and keys in alphabet order
     {
@@ -389,8 +340,7 @@ __global__ __launch_bounds__(64) void k_huff_encode(BlockView view, int maxChunk
         hdrBits = pos + (u32)__shfl((int)incl, 63, 64);
     }
     __syncthreads();
-    u32* hdrOut = reinterpret_cast<u32*>(tmp + (size_t)slot * TMP_STRIDE);
-    for (u32 i = lane; i < ((hdrBits + 31) >> 5); i += 64) hdrOut[i] = bswap32(hdrw[i]);
+    header_flush(lane, hdrw, hdrBits, tmp + (size_t)slot * TMP_STRIDE);
 
     if (asz <= 1) {
         if (lane == 0) { cd->hdrBits = hdrBits; cd->midLen = 0; cd->trailerLen = 0; cd->nPieces = 0; cd->aux = asz; }
@@ -485,21 +435,11 @@ struct HufDecChunk {
     u8 sizes[256];
 };
 
-
-// n in [1, 32]; rel = bit offset from the start of the LDS window (words in bit order)
-__device__ __forceinline__ u32 hwin_bits(const u32* win, u32 rel, u32 n)
-{
-    const u32 i = rel >> 5;
-    const u64 v = ((u64)win[i] << 32) | (u64)win[i + 1];
-    return (u32)((v << (rel & 31)) >> (64 - n));
-}
-
-constexpr u32 HSCAN_WIN_BITS = 8192;
 constexpr u32 HSCAN_NEED_BITS = 6 + 256 + 256 * 8 + 4 * 40 + 64;     // alphabet + 256 deltas (|d| <= 11: 8 bits) + 4 var-ints
 
 // One wave per block walks the chunk headers (readLengths, HuffmanDecoder.cpp:65-108, and the 4 fragment sizes,
-// :204-246).  Same scheme as the rANS scan: a 1 KiB window of the stream in LDS, the next window prefetched at a
-// guessed position, presence masks counted in parallel; the Exp-Golomb deltas are a short uniform chain
+// :204-246).  Same scheme as the rANS scan (HeaderWindow, ent_header.hpp): a 1 KiB window of the stream in LDS, the next window
+// prefetched at a guessed position, presence masks counted in parallel; the Exp-Golomb deltas are a short uniform chain
 // (one LDS read + count-leading-zeros per code).
 // V5: the chunk layout of bitstream versions below 6 (HuffmanDecoder.cpp:349-459): no raw small chunks; behind the lengths a 2-bit
 // stream count (0 = one) and ONE var-int bit count, then one code stream for the whole chunk -- kept as "fragment 0" here.
@@ -513,7 +453,7 @@ __global__ __launch_bounds__(64) void k_huff_scan(BitSrc src, DecBlock* __restri
     HufDecChunk* cs = chunks + (size_t)b * maxChunks;
     for (int i = lane; i < maxChunks; i += 64) cs[i].kind = 3;
     if (db.error) return;
-    __shared__ u32 win[256 + 8];
+    __shared__ u32 win[HDR_WIN_WORDS];
     __shared__ u32 codeSizeW[64];                      // 256 code lengths, written four at a time
     u8* codeSize = reinterpret_cast<u8*>(codeSizeW);
     const u64 limit = db.payloadBit + ((db.bits + 7) & ~7ull);
@@ -529,32 +469,7 @@ __global__ __launch_bounds__(64) void k_huff_scan(BitSrc src, DecBlock* __restri
         }
         return;
     }
-    const u64 lastWord = ((src.nBytes + 3) >> 2) - 1;
-    auto issue = [&](u64 bit0, u32x4& dstv) {
-        const u64 w = (bit0 >> 5) + 4ull * (u32)lane;
-        const u64 w1 = w + 1, w2 = w + 2, w3 = w + 3;
-        const u32* p = src.words;
-        dstv.x = p[w < lastWord ? w : lastWord];
-        dstv.y = p[w1 < lastWord ? w1 : lastWord];
-        dstv.z = p[w2 < lastWord ? w2 : lastWord];
-        dstv.w = p[w3 < lastWord ? w3 : lastWord];
-    };
-    u32x4 wr = { 0, 0, 0, 0 }, guess = { 0, 0, 0, 0 };
-    u64 winBit0 = 0, guessBit0 = 0;
-    bool winValid = false, guessValid = false;
-    auto ensure = [&](u32 need) {
-        if (winValid && winBit0 <= pos && pos + need <= winBit0 + HSCAN_WIN_BITS) return;
-        if (guessValid && guessBit0 <= pos && pos + need <= guessBit0 + HSCAN_WIN_BITS) { wr = guess; winBit0 = guessBit0; }
-        else { winBit0 = pos & ~31ull; issue(winBit0, wr); }
-        guessValid = false;
-        __syncthreads();
-        {
-            u32x4 sw = { bswap32(wr.x), bswap32(wr.y), bswap32(wr.z), bswap32(wr.w) };
-            *reinterpret_cast<u32x4*>(&win[4 * lane]) = sw;
-        }
-        __syncthreads();
-        winValid = true;
-    };
+    HeaderWindow hw(win, src, lane);
     // Signed Exp-Golomb code of a length delta (ExpGolombDecoder.hpp:52-75) by its first 8 bits, for codes that start with a 0
     // (a leading 1 is the one-bit code of delta 0): bits 6-9 = code length (0: no valid code starts like this), bits 0-4 =
     // delta + 16. A valid delta has |d| <= 11, i.e. a code of at most 8 bits (a prefix of more than 3 zeros can only decode to an
@@ -586,36 +501,15 @@ __global__ __launch_bounds__(64) void k_huff_scan(BitSrc src, DecBlock* __restri
             if (pos > limit) err = 1;
             continue;
         }
-        ensure(HSCAN_NEED_BITS);
-        guessValid = false;
-        if (ci >= 1 && ci + 1 < nChunks) {
-            const u64 est = pos + (pos - prevPos);
-            guessBit0 = (est > 2304 ? est - 2304 : 0) & ~31ull;
-            issue(guessBit0, guess);
-            guessValid = true;
-        }
+        hw.ensure(pos, HSCAN_NEED_BITS);
+        hw.forget();
+        if (ci >= 1 && ci + 1 < nChunks) hw.prefetch(HeaderWindow::guess_at(pos, prevPos));
         prevPos = pos;
-        u32 p = (u32)(pos - winBit0);
+        const u64 winBit0 = hw.bit0;
         // ---- alphabet (EntropyUtils.cpp:91-123): which of my 4 symbols are present
-        u32 asz, present, firstSym = 0;
-        const u32 hb = hwin_bits(win, p, 7);
-        if ((hb >> 6) == 0) { asz = ((hb >> 5) & 1) ? 0u : 256u; present = asz ? 0xFu : 0u; p += 2; }
-        else {
-            const u32 lastMask = (hb >> 1) & 31;
-            p += 6;
-            const u32 m = (u32)lane >> 1;
-            const u32 byte = (m <= lastMask) ? hwin_bits(win, p + 8u * m, 8) : 0u;
-            present = (lane & 1) ? (byte >> 4) : (byte & 0xF);
-            p += 8u * (lastMask + 1);
-            asz = wave_sum(__popc(present));
-            const u64 nz = __ballot(present != 0);
-            if (nz) {
-                const int fl = __ffsll((long long)nz) - 1;
-                const u32 fp = rl(present, fl);
-                firstSym = 4u * (u32)fl + (u32)(__ffs((int)fp) - 1);
-            }
-        }
-        asz = uni(asz);
+        const AlphabetIn<u32> ai = alphabet_get([&](u32 at, u32 nb) { return win_bits(win, at, nb); }, lane, (u32)(pos - winBit0));
+        const u32 p = ai.next, present = ai.a.present, firstSym = ai.firstSym;
+        const u32 asz = uni(ai.a.asz);
         if (asz == 0) { err = 2; break; }
         // ---- code length deltas (ExpGolombDecoder.hpp:52-75)
         // A valid delta has |d| <= 11, i.e. a code of at most 8 bits (prefix of <= 3 zeros); a longer prefix can only decode to an
@@ -633,7 +527,7 @@ __global__ __launch_bounds__(64) void k_huff_scan(BitSrc src, DecBlock* __restri
         const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
         u32 k = 0;
         while (k < asz) {
-            if (q > HSCAN_WIN_BITS - 96) { bad = 1; break; }                 // longer than any valid header
+            if (q > HDR_WIN_BITS - 96) { bad = 1; break; }                 // longer than any valid header
             const u32 bp = q + (u32)lane;
             const u32 wi = bp >> 5;                                          // (<= 254: the window has 264 words)
             const u32 top = (u32)(((((u64)win[wi] << 32) | (u64)win[wi + 1]) << (bp & 31)) >> 56);
@@ -677,7 +571,7 @@ __global__ __launch_bounds__(64) void k_huff_scan(BitSrc src, DecBlock* __restri
         if (err) break;
         __syncthreads();
         {
-            u32 r = wave_incl_scan(__popc(present)) - __popc(present);
+            u32 r = ai.a.rankBase;
             u32 packed = 0;
 #pragma unroll
             for (int k = 0; k < 4; k++) if ((present >> k) & 1) { packed |= (u32)codeSize[r] << (8 * k); r++; }
@@ -691,15 +585,9 @@ __global__ __launch_bounds__(64) void k_huff_scan(BitSrc src, DecBlock* __restri
         }
         if (V5) {
             // ---- HuffmanDecoder.cpp:374-383: stream count, bit count
-            if (hwin_bits(win, q, 2) != 0) { err = 1; break; }
+            if (win_bits(win, q, 2) != 0) { err = 1; break; }
             q += 2;
-            u32 value = hwin_bits(win, q, 8); q += 8;
-            u32 res = value & 0x7F;
-            for (int shift = 7; value >= 128; shift += 7) {
-                value = hwin_bits(win, q, 8); q += 8;
-                if (shift == 28) { if (value >= 128 || (value & 0x70) != 0) err = 1; res |= (value & 0x0F) << shift; break; }
-                res |= (value & 0x7F) << shift;
-            }
+            const u32 res = win_varint(win, q, err);
             if ((int)res < 0 || res > n * (u32)HUF_MAX_LEN) err = 1;
             if (err) break;
             const u64 fp5 = winBit0 + q;
@@ -718,13 +606,7 @@ __global__ __launch_bounds__(64) void k_huff_scan(BitSrc src, DecBlock* __restri
         const u32 maxFragBits = 8192u << 3;
         u32 szb[4];
         for (int j = 0; j < 4; j++) {
-            u32 value = hwin_bits(win, q, 8); q += 8;
-            u32 res = value & 0x7F;
-            for (int shift = 7; value >= 128; shift += 7) {
-                value = hwin_bits(win, q, 8); q += 8;
-                if (shift == 28) { if (value >= 128 || (value & 0x70) != 0) err = 1; res |= (value & 0x0F) << shift; break; }
-                res |= (value & 0x7F) << shift;
-            }
+            const u32 res = win_varint(win, q, err);
             szb[j] = res;
             if ((int)res < 0 || res > maxFragBits) err = 1;
         }
@@ -873,7 +755,7 @@ __global__ __launch_bounds__(64) void k_huff_decode(BitSrc src, DecBlock* __rest
             }
         }
     }
-    const u64 lastWord = ((src.nBytes + 3) >> 2) - 1;
+    const ClampedWords cw = clamped_words(src);
     const u64 w0 = fbeg >> 5;
     const u32 sh = (u32)fbeg & 31;
     // Round 5. The stream of a fragment reaches its lane through a ring of 32 words in LDS, as in k_ans0_decode: every 16 steps the lane
@@ -888,7 +770,7 @@ __global__ __launch_bounds__(64) void k_huff_decode(BitSrc src, DecBlock* __rest
     // words [f, f + 8) of the fragment (32 stream bits each, bits past the fragment's end zero: the reference decodes from a zero-padded copy)
     auto load9 = [&](u32 f, u32 raw[9]) {
 #pragma unroll
-        for (int t = 0; t < 9; t++) { const u64 w = w0 + f + t; raw[t] = src.words[w < lastWord ? w : lastWord]; }
+        for (int t = 0; t < 9; t++) raw[t] = cw.raw(w0 + f + t);
     };
     auto store8 = [&](u32 f, const u32 raw[9]) {
 #pragma unroll

@@ -2,6 +2,7 @@
 // copied to / from the bit stream unchanged, at whatever bit offset the framing gives them.
 #include "common.hpp"
 #include "stages.hpp"
+#include "ent_header.hpp"
 
 namespace knz {
 
@@ -16,8 +17,7 @@ __global__ void k_none_encode(BlockView view, int nBlocks, int maxChunks, ChunkD
     if (start >= len) return;
     ChunkDesc* cd = desc + slot;
     const u32 n = (len - start < ENT_CHUNK) ? (len - start) : ENT_CHUNK;
-    cd->hdrBits = 0; cd->midLen = 0; cd->trailerLen = 0; cd->aux = 0;
-    cd->nPieces = 1; cd->pieceBits[0] = 8 * n; cd->piecePtr[0] = view.ptr[b] + start;
+    desc_raw(cd, view.ptr[b] + start, 8 * n);
 }
 
 __global__ __launch_bounds__(256) void k_none_decode(BitSrc src, DecBlock* blocks, u8* const* outPtr)

@@ -53,10 +53,7 @@ __global__ __launch_bounds__(64) void k_range_stats(BlockView view, const u32* _
     ChunkDesc* cd = desc + slot;
     if (origLen[b] <= copyThreshold) {
         // copy block: entropy type forced to NONE (io/CompressedOutputStream.cpp:691-695)
-        if (lane == 0) {
-            cd->hdrBits = 0; cd->midLen = 0; cd->trailerLen = 0; cd->aux = 0;
-            cd->nPieces = 1; cd->pieceBits[0] = 8 * len; cd->piecePtr[0] = blk;
-        }
+        if (lane == 0) desc_raw(cd, blk, 8 * len);
         return;
     }
     const u32 n = (len - start < RANGE_CHUNK) ? (len - start) : RANGE_CHUNK;
@@ -73,22 +70,15 @@ __global__ __launch_bounds__(64) void k_range_stats(BlockView view, const u32* _
     __syncthreads();
 
     u32 f[4];                                                     // lane owns symbols 4*lane .. 4*lane+3
-    ans_chunk_counts(lane, blk, n, hist, f);
-    u32 present = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) present |= (f[k] != 0 ? 1u : 0u) << k;
-    const u32 myCount = __popc(present);
-    const u32 inclCount = wave_incl_scan(myCount);
-    const u32 asz = (u32)__shfl((int)inclCount, 63, 64);
-    const u32 rankBase = inclCount - myCount;
+    chunk_counts(lane, blk, n, hist, f);
+    const Alphabet al = alphabet_of(f);
+    const u32 present = al.present, asz = al.asz, rankBase = al.rankBase;
 
     if (n != (1u << lr)) ans_normalize_lr(lane, f, n, asz, lr);
     const u32 pos = ans_header_bits_lr(lane, f, present, asz, rankBase, 2, lr, hdrw, grpMax, grpOff, 0);
     __syncthreads();
 
-    u32* hdrOut = reinterpret_cast<u32*>(tmp + (size_t)slot * RANGE_STRIDE);
-    const u32 hdrWordsUsed = (pos + 31) >> 5;
-    for (u32 i = lane; i < hdrWordsUsed; i += 64) hdrOut[i] = bswap32(hdrw[i]);
+    header_flush(lane, hdrw, pos, tmp + (size_t)slot * RANGE_STRIDE);
 
     // A frequency that does not fit 16 bits: the normalisation's last line wrapped below zero (EntropyUtils.cpp:243; a short chunk at a low
     // log range whose many rare symbols were raised to 1). Nobody can read such a chunk, the reference included, but it writes one, with
@@ -369,7 +359,7 @@ __global__ __launch_bounds__(64) void k_range_decode(BitSrc src, DecBlock* __res
         if (lane == 0) { if (bad) db.error = KNZ_ERR_PROCESS_BLOCK; db.usedBits = bad ? (limit - db.entropyBit) : 8ull * count; }
         return;
     }
-    const u64 lastWord = ((src.nBytes + 3) >> 2) - 1;
+    const ClampedWords cw = clamped_words(src);
     const bool wordStores = ((reinterpret_cast<uintptr_t>(block) & 3) == 0);
     const u8* f2s = reinterpret_cast<const u8*>(f2sw);
     u32 start = 0;
@@ -379,29 +369,18 @@ __global__ __launch_bounds__(64) void k_range_decode(BitSrc src, DecBlock* __res
         // ---- alphabet (EntropyUtils.cpp:91-123): lane owns symbols 4*lane .. 4*lane+3, the nibble (lane & 1) of mask byte lane >> 1
         if (pos + 2 > limit) { fail = true; break; }
         const u32 hb = peek_bits(s, pos, 7);
-        u32 present = 0;
-        if ((hb >> 6) == 0) { present = ((hb >> 5) & 1) ? 0u : 0xFu; pos += 2; }
-        else {
-            const u32 lastMask = (hb >> 1) & 31;
-            if (pos + 6 + 8ull * (lastMask + 1) > limit) { fail = true; break; }
-            pos += 6;
-            const u32 mb = (((u32)lane >> 1) <= lastMask) ? peek_bits(s, pos + 8ull * ((u32)lane >> 1), 8) : 0u;
-            present = (mb >> (4 * ((u32)lane & 1))) & 0xFu;
-            pos += 8ull * (lastMask + 1);
-        }
-        const u32 myCount = __popc(present);
-        const u32 inclCount = wave_incl_scan(myCount);
-        const u32 asz = (u32)__shfl((int)inclCount, 63, 64);
-        const u32 rankBase = inclCount - myCount;
+        if ((hb >> 6) != 0 && pos + 6 + 8ull * (((hb >> 1) & 31) + 1) > limit) { fail = true; break; }     // the mask bytes
+        const auto fetch = [&](u64 at, u32 nb) { return peek_bits(s, at, nb); };
+        const AlphabetIn<u64> ai = alphabet_get(fetch, lane, pos);
+        pos = ai.next;
+        const u32 asz = ai.a.asz;
         if (asz == 0) { ended = true; break; }                       // RangeDecoder.cpp:163-164: the count so far
         if (pos + 3 > limit) { fail = true; break; }
         const u32 lr = 8 + peek_bits(s, pos, 3);
         pos += 3;
         const u32 scale = 1u << lr;
         if (asz == 1) {
-            const u64 any = __ballot(present != 0);
-            const int fl = __ffsll((long long)any) - 1;
-            const u32 sym = 4u * (u32)fl + (u32)(__ffs((int)rl(present, (u32)fl)) - 1);
+            const u32 sym = ai.firstSym;
             for (u32 i = (u32)lane; i < n; i += 64) block[start + i] = (u8)sym;
             start += n;
             continue;
@@ -420,32 +399,8 @@ __global__ __launch_bounds__(64) void k_range_decode(BitSrc src, DecBlock* __res
         }
         if (fail || pos + q > limit) { fail = true; break; }
         __syncthreads();
-        u32 f[4] = { 0, 0, 0, 0 };
-        u32 sum = 0;
-        bool bad = false;
-        {
-            u32 r = rankBase;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                if ((present >> k) & 1) {
-                    if (r >= 1) {
-                        const u32 g = (r - 1) / chk;
-                        const u32 w = grpW[g];
-                        f[k] = w ? peek_bits(s, pos + grpPos[g] + ((r - 1) - g * chk) * w, w) + 1 : 1u;
-                        bad |= f[k] >= scale;
-                        sum += f[k];
-                    }
-                    r++;
-                }
-            }
-        }
-        const u32 total = wave_sum(sum);
-        if (__ballot(bad) != 0 || scale <= total) { fail = true; break; }
-        if (rankBase == 0 && present) {
-            const int k0 = __ffs((int)present) - 1;
-#pragma unroll
-            for (int k = 0; k < 4; k++) if (k == k0) f[k] = scale - total;
-        }
+        u32 f[4];
+        if (freqs_get(ai.a, scale, [&](u32 g, u32& w) -> u64 { w = grpW[g]; return pos + grpPos[g]; }, fetch, f)) { fail = true; break; }
         {
             const u32 lsum = f[0] + f[1] + f[2] + f[3];
             const u32 lincl = wave_incl_scan(lsum);
@@ -479,8 +434,7 @@ __global__ __launch_bounds__(64) void k_range_decode(BitSrc src, DecBlock* __res
         // payload words from word wbase on, one per lane: winCur = words [winBase, +64), winNext the 64 behind them
         const u64 wbase = pos >> 5;
         auto loadWin = [&](u32 w0) -> u32 {
-            const u64 w = wbase + w0 + (u32)lane;
-            return bswap32(src.words[w < lastWord ? w : lastWord]);
+            return bswap32(cw.raw(wbase + w0 + (u32)lane));
         };
         u32 winBase = 0;
         u32 winCur = loadWin(0), winNext = loadWin(64);
